@@ -2,13 +2,18 @@
 """Benchmark of the hot path (BASELINE.json metric): images/sec forward+backward of
 BEV ERFNet -> fused WLS lane fit -> Area loss, 256x512, 2 lanes, batch 32 per GPU, fp32.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     (N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, one rank per
-    GPU, or started plainly -- it then re-executes itself under torch.distributed.run on 127.0.0.1)
+    GPU, or started plainly -- it then starts itself under torch.distributed.run on 127.0.0.1, in a child process)
 
 A step = model(x, True) -> loss = criterion(beta0, gt0) + criterion(beta1, gt1) -> grads to zero ->
 loss.backward() [-> one flat RCCL all-reduce of the gradients when N > 1].  The optimizer is excluded
 (SURVEY.md 8d).  Inputs are synthetic and resident in HBM before the timed region.  Prints ONE JSON line.
+
+A plain run sets up, runs W warm-up steps, times exactly K steps (ms_per_step = their time / K), writes the outputs of the
+last timed step when --dump-outputs is given, and prints the line.  --full adds everything else, after the timed region:
+the roofline (extra profiled steps), the fp32x9 leg, the other BASELINE configs, the PyTorch-ROCm / MIOpen and CPU
+baselines, the parity check against the CPU oracle, and the gradient check across ranks.
 """
 import argparse
 import ctypes
@@ -41,8 +46,9 @@ PEAK_HBM = 8.0e12                   # MI355X_MICROARCH.md: HBM3E peak (6.3 TB/s 
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "traffic.json")
 TRAFFIC_STEP_FILE = os.path.join(ROOT, "profiles", "traffic_step.json")
 CALIBRATION_FILE = os.path.join(ROOT, "profiles", "cpu_port_calibration.json")
-TIMED_BLOCKS = 5                    # the timed region = at least TIMED_BLOCKS blocks of --steps steps each; the median block is reported
-TIMED_REGION_S = 6.5                # ... and enough blocks to span this many seconds (an outside sampler with a 5 s period sees the GPU busy)
+TIMED_BLOCKS = 5                    # with --min-seconds > 0: the timed region = at least TIMED_BLOCKS blocks of --steps steps each,
+                                    # and enough blocks to span that many seconds; the median block is reported
+DUMP_ELEMS = 1 << 22                # --dump-outputs: an output with more elements is written as a fixed, seeded sample of this many
 
 
 def make_args(batch):
@@ -144,7 +150,8 @@ def cpu_baseline_and_parity(precision):
     from lanedetection_end2end_amd.bev.Networks.LSQ_layer import Net
     import synthetic_inputs as inputs
     from oracle import e2e_oracle, erfnet_oracle, fit_oracle, vendor_baseline
-    threads = min(os.cpu_count() or 1, 64)
+    # the CPUs this process was given (OMP_NUM_THREADS where the host sets it: os.cpu_count() counts the whole machine)
+    threads = int(os.environ.get("OMP_NUM_THREADS") or 0) or min(os.cpu_count() or 1, 64)
     torch.set_num_threads(threads)
     R = 256
     P = erfnet_oracle.make_params(seed=4, out_channels=2)
@@ -526,12 +533,34 @@ KERNEL_TIME_FILE = os.path.join(ROOT, "profiles", "kernel_time.json")
 TG_FAMILY, WG_FAMILY = "conv forward + data gradient (tap-GEMM kernels)", "weight gradient (+ its reductions)"
 
 
-def measure(workload, precision, B, steps, warmup, min_seconds, rank, world, dist, no_dropout=False):
-    """The timed region of one workload in this process: build the model, `warmup` untimed steps, then >= TIMED_BLOCKS
-    barrier- and synchronize-bracketed blocks of exactly `steps` steps spanning >= `min_seconds` (MAX over ranks per block, the
-    MEDIAN block is reported), then -- rank 0 -- three extra steps with HIP events around every MFMA launch for the roofline.
-    Returns (line, handles): `line` = the JSON fields of this workload (None on ranks > 0), `handles` = what the extras of the
-    headline need (model, step function, sizes).  Imports nothing from oracle/."""
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the timed path handed its caller in its last step, one `path/<name>.npy` per array -- float64 where
+    the path computes in fp64, float32 otherwise.  An array of more than DUMP_ELEMS elements is written as the same seeded
+    sample of its flattened elements in every run (`<name>_sample.npy`), so that the files of a run stay under 64 MB."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
+# names of the tensors the step's forward returns, per workload (None entries are skipped)
+OUTPUT_NAMES = {"bev": ("beta0", "beta1", "beta2", "beta3", "masked", "M", "logits", "line", "horizon"),
+                "bp": ("beta0", "beta1", "beta2", "beta3", "masked", "logits", "line", "horizon", "logits_seg"),
+                "seg": ("logits",)}
+
+
+def measure(workload, precision, B, steps, warmup, min_seconds, rank, world, dist, no_dropout=False, full=True, dump_dir=None):
+    """The timed region of one workload in this process: build the model, `warmup` untimed steps, then exactly `steps` timed
+    steps (with `min_seconds` > 0: >= TIMED_BLOCKS barrier- and synchronize-bracketed blocks of exactly `steps` steps spanning
+    >= `min_seconds`, MAX over ranks per block, the MEDIAN block is reported); `dump_dir`: rank 0 writes the last step's outputs
+    there.  With `full`: then -- rank 0 -- three extra steps with HIP events around every MFMA launch for the roofline, and at
+    N > 1 the cross-rank gradient check.  Returns (line, handles): `line` = the JSON fields of this workload (None on ranks > 0),
+    `handles` = what the extras of the headline need (model, step function, sizes).  Imports nothing from oracle/."""
     import synthetic_inputs as inputs
     from lanedetection_end2end_amd import _lib
     wl = WORKLOADS[workload]
@@ -564,15 +593,23 @@ def measure(workload, precision, B, steps, warmup, min_seconds, rank, world, dis
         dp.broadcast_parameters(model, src=0)
         reducer = dp.FlatGradAllReduce(params, flat_provider=model.net.flat_grad)
 
+    last = {}                                # --dump-outputs: the forward's outputs and the loss of the latest step
+    keep = dump_dir is not None and rank == 0
+
     def step(reduce=True):
         if workload == "bev":
-            b0, b1, _, _, _, _, _, _, _ = model(x, True)
-            loss = crit(b0, gt[:, 0]) + crit(b1, gt[:, 1])
+            out = model(x, True)
+            loss = crit(out[0], gt[:, 0]) + crit(out[1], gt[:, 1])
         elif workload == "bp":
             out = model(x, gt_line, True)
             loss = sum(crit(out[k], lanes[:, k], valid[:, k])[0] for k in range(wl["K"])) / wl["K"]
         else:
-            loss = crit(model(x, gt_line, False, early_return=True), target)
+            out = (model(x, gt_line, False, early_return=True),)
+            loss = crit(out[0], target)
+        if keep:
+            last.clear()
+            last.update((n, t) for n, t in zip(OUTPUT_NAMES[workload], out) if t is not None)
+            last["loss"] = loss
         for p in params:
             p.grad = None
         loss.backward()
@@ -585,19 +622,20 @@ def measure(workload, precision, B, steps, warmup, min_seconds, rank, world, dis
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    step()                                   # one more untimed step, clocked: sizes the number of blocks
-    torch.cuda.synchronize()
-    est = max(time.perf_counter() - t0, 1e-4)
-    nblocks = max(TIMED_BLOCKS, min(200, int(np.ceil(min_seconds / (est * steps)))))
-    if world > 1:                            # every rank must run the same number of blocks (collectives inside)
-        nb = torch.tensor([nblocks], device="cuda")
-        dist.all_reduce(nb, op=dist.ReduceOp.MAX)
-        nblocks = int(nb)
+    nblocks = 1
+    if min_seconds > 0:
+        t0 = time.perf_counter()
+        step()                               # one more untimed step, clocked: sizes the number of blocks
+        torch.cuda.synchronize()
+        est = max(time.perf_counter() - t0, 1e-4)
+        nblocks = max(TIMED_BLOCKS, min(200, int(np.ceil(min_seconds / (est * steps)))))
+        if world > 1:                        # every rank must run the same number of blocks (collectives inside)
+            nb = torch.tensor([nblocks], device="cuda")
+            dist.all_reduce(nb, op=dist.ReduceOp.MAX)
+            nblocks = int(nb)
     statuses.clear()
-    # timed region: nblocks blocks of exactly `steps` steps, each bracketed by barrier + synchronize on both sides and reduced
-    # with MAX over the ranks; the MEDIAN block is the reported one (the region spans >= 6.5 s, so that clocks are settled and
-    # an outside sampler with a 5 s period sees the GPU busy)
+    # timed region: nblocks blocks of exactly `steps` steps (one block unless --min-seconds asks for more), each bracketed by
+    # barrier + synchronize on both sides and reduced with MAX over the ranks; the MEDIAN block is the reported one
     blocks = []
     for _ in range(nblocks):
         if world > 1:
@@ -616,9 +654,17 @@ def measure(workload, precision, B, steps, warmup, min_seconds, rank, world, dis
             dtb = float(t)
         blocks.append(dtb)
     dt = float(np.median(blocks))
-    grad_check = None
     if reducer is not None:
         reducer.check()                      # the signature of the last all-reduce (inspected lazily inside the loop)
+    bad = int(torch.stack(statuses).abs().sum()) if statuses else 0
+    if bad or not torch.isfinite(loss):
+        raise SystemExit("bench: singular normal matrix / non-finite loss inside the timed region (%s %s)" % (workload, precision))
+    if keep:
+        last["grad"] = torch.cat([p.grad.reshape(-1) for p in params if p.grad is not None])    # model.parameters() order
+        dump_outputs(dump_dir, last)
+        last.clear()
+    grad_check = None
+    if reducer is not None and full:
         # debug field: every rank must hold bit-identical reduced gradients (two integer checksums of the bucket's bits)
         bits = reducer.last_flat.view(torch.int32).to(torch.int64)
         chk = torch.stack([bits.sum(), (bits * (torch.arange(bits.numel(), device=bits.device) % 251 + 1)).sum()])
@@ -639,14 +685,24 @@ def measure(workload, precision, B, steps, warmup, min_seconds, rank, world, dis
                       "devices": sorted(set(int(v) for v in _gather_ints(dist, torch.cuda.current_device(), world))),
                       "bucket_elements": int(reducer.last_flat.numel()),
                       "bit_identical_across_ranks": bool(all(torch.equal(allc[0], c) for c in allc))}
-    bad = int(torch.stack(statuses).abs().sum()) if statuses else 0
-    if bad or not torch.isfinite(loss):
-        raise SystemExit("bench: singular normal matrix / non-finite loss inside the timed region (%s %s)" % (workload, precision))
     handles = dict(model=model, step=step, B=B, R=R, wl=wl)
     if rank != 0:
         return None, handles
 
     ips = world * B * steps / dt
+    metric = "images/sec fwd+bwd, 256x512 2-lane bs32" if workload == "bev" else "images/sec fwd+bwd, %s" % workload
+    out = {"metric": metric, "value": round(ips, 2), "unit": "images/sec",
+           "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(1e3 * dt / steps, 3),
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": DTYPE_NAMES[precision], "data": "synthetic",
+           "config": {"workload": "%s, batch %d per GPU, %s, train mode (BN batch stats, Dropout2d %s), fwd+bwd, optimizer excluded"
+                                  % (wl["desc"], B, precision, "off" if no_dropout else "on"),
+                      "global_batch": world * B, "parallelism": "dp%d" % world,
+                      "grad_allreduce": ("flat fp32 bucket, %s over %d ranks" % ("RCCL" if dist.get_backend() == "nccl" else dist.get_backend(), dist.get_world_size())) if world > 1 else "none"},
+           "timed_blocks_ms_per_step": [round(1e3 * t / steps, 3) for t in blocks[:12]],
+           "timed_blocks": len(blocks), "timed_region_s": round(float(sum(blocks)), 2)}
+    if not full:
+        return out, handles
     # ---- roofline of the dominant kernel family: extra steps with HIP events around every MFMA launch
     lib = _lib.load()
     plan = model.net._plan(B, R, 2 * R)
@@ -731,18 +787,7 @@ def measure(workload, precision, B, steps, warmup, min_seconds, rank, world, dis
                 # measured on this chip (tools/mfma_sustain.hip, profiles/r2_mfma_sustain.txt): a bare fp32 MFMA stream holds
                 # 156 TFLOP/s from 10 ms to 1.7 s, i.e. the datasheet peak above is the roof the kernels can be held to
                 "sustained_mfma_measured": 156.0}
-    metric = "images/sec fwd+bwd, 256x512 2-lane bs32" if workload == "bev" else "images/sec fwd+bwd, %s" % workload
-    out = {"metric": metric, "value": round(ips, 2), "unit": "images/sec",
-           "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(1e3 * dt / steps, 3),
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": DTYPE_NAMES[precision], "data": "synthetic",
-           "config": {"workload": "%s, batch %d per GPU, %s, train mode (BN batch stats, Dropout2d %s), fwd+bwd, optimizer excluded"
-                                  % (wl["desc"], B, precision, "off" if no_dropout else "on"),
-                      "global_batch": world * B, "parallelism": "dp%d" % world,
-                      "grad_allreduce": ("flat fp32 bucket, %s over %d ranks" % ("RCCL" if dist.get_backend() == "nccl" else dist.get_backend(), dist.get_world_size())) if world > 1 else "none"},
-           "timed_blocks_ms_per_step": [round(1e3 * t / steps, 3) for t in blocks[:12]],
-           "timed_blocks": len(blocks), "timed_region_s": round(float(sum(blocks)), 2),
-           "roofline": roofline}
+    out["roofline"] = roofline
     if grad_check is not None:
         out["grad_allreduce_check"] = grad_check
     if precision == "bf16":
@@ -814,22 +859,32 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true", help="skip the other BASELINE configs (other_configs) of the default run")
     ap.add_argument("--vendor-tune", action="store_true",
                     help="miopen_baseline with cudnn.benchmark=True (MIOpen find mode: ~9 minutes of kernel tuning on a fresh box)")
-    ap.add_argument("--min-seconds", type=float, default=TIMED_REGION_S,
-                    help="the timed region repeats its --steps-step block until it spans this many seconds (default 6.5: an outside "
-                         "sampler with a 5 s period then sees the GPU busy); the median block is reported")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="> 0: the timed region repeats its --steps-step block (>= %d times) until it spans this many seconds, and "
+                         "the median block is reported (6.5: an outside sampler with a 5 s period then sees the GPU busy); default 0: "
+                         "exactly --steps timed steps" % TIMED_BLOCKS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, everything besides the headline figure: the roofline (profiled extra steps), the "
+                         "fp32x9 leg, the other BASELINE configs, the MIOpen and CPU baselines, the parity check against the CPU "
+                         "oracle, the gradient check across ranks (the --no-* options below trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the forward's outputs, the loss, the parameter gradients) as "
+                         "DIR/<name>.npy, float32 / float64; outputs above %d elements as a fixed, seeded sample" % DUMP_ELEMS)
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rank plumbing check on a box without GPUs (tests/test_bench_contract_cpu.py): rendezvous over "
                          "gloo, the barrier-bracketed timing loop around a CPU stand-in step (the flat 8.25 MB gradient all-reduce; "
                          "with --workload epoch: config 4's sharded epoch plan, every rank walking its index batches), "
                          "one JSON line from rank 0; measures nothing")
     ap.add_argument("--no-dropout", action="store_true", help="disable Dropout2d (parity-style run)")
-    ap.add_argument("--no-extras", action="store_true", help="the timed region and the roofline steps only: no fp32x9 leg, no other "
-                    "configs, no baselines (counter passes: profiles/collect.sh, every launch of the run belongs to the measured step)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: the timed region and the roofline steps only: no fp32x9 "
+                    "leg, no other configs, no baselines")
     ap.add_argument("--precision", choices=["fp32", "bf16", "fp32x9"], default="fp32",
                     help="fp32 (default = the BASELINE headline); bf16 = bf16 matrix cores and bf16 activation/gradient tensors "
                          "(config 3; not a parity mode, the reference is fp32 only); fp32x9 = fp32 tensors and accumulation, "
                          "products from exact 3-way bf16 splits on the bf16 matrix cores")
     a = ap.parse_args()
+    if a.dump_outputs is not None and (a.dry_run or a.workload == "epoch"):
+        ap.error("--dump-outputs needs a bev / bp / seg run on the GPU")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -840,8 +895,9 @@ def main():
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus),
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        import subprocess
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus),
+                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
     if a.gpus != world:
         raise SystemExit("bench.py --gpus %d is running inside a %d-rank job" % (a.gpus, world))
     if a.dry_run:
@@ -867,10 +923,11 @@ def main():
         return
 
     B = a.batch or WORKLOADS[a.workload]["batch"]
-    out, h = measure(a.workload, a.precision, B, a.steps, a.warmup, a.min_seconds, rank, world, dist, a.no_dropout)
+    out, h = measure(a.workload, a.precision, B, a.steps, a.warmup, a.min_seconds, rank, world, dist, a.no_dropout,
+                     full=a.full, dump_dir=a.dump_outputs)
     if rank == 0:
         model, step, R = h["model"], h["step"], h["R"]
-        if world == 1 and a.precision == "fp32" and not a.no_extras:
+        if a.full and world == 1 and a.precision == "fp32" and not a.no_extras:
             # not the headline: the same step with the 64- / 128-channel conv products formed on the bf16 matrix cores
             # from exact 3-way splits of both fp32 operands (all 9 partial products, fp32 accumulation)
             model.net.precision = "fp32x9"
@@ -891,7 +948,7 @@ def main():
         ips = out["value"]
         del model, step, h
         torch.cuda.empty_cache()
-        headline = world == 1 and a.workload == "bev" and not a.no_extras
+        headline = a.full and world == 1 and a.workload == "bev" and not a.no_extras
         if headline and a.precision == "fp32" and a.batch is None and not a.no_other_configs:
             out["other_configs"] = other_configs(a)
         if headline and not a.no_vendor_baseline:

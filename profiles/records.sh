@@ -9,11 +9,11 @@ TAG=${1:-r5}
 cd "$(dirname "$0")/.."
 R=gpurun_out/rec
 mkdir -p $R
-python bench.py > $R/${TAG}_bench.json 2> $R/bench.err                                                  # the headline (all extras)
-python bench.py --workload bp --precision bf16 > $R/${TAG}_bench_bp_320x640_b64_bf16.json 2> $R/bp16.err   # BASELINE config 3: geometry and dtype
-python bench.py --workload bp > $R/${TAG}_bench_bp_320x640_b64.json 2> $R/bp.err
-python bench.py --precision bf16 > $R/${TAG}_bench_bev_bf16.json 2> $R/bev16.err
-python bench.py --workload seg > $R/${TAG}_bench_seg_512x1024_b16.json 2> $R/seg.err                      # config 5, one GPU's shard
+python bench.py --full > $R/${TAG}_bench.json 2> $R/bench.err                                                  # the headline (all extras)
+python bench.py --full --workload bp --precision bf16 > $R/${TAG}_bench_bp_320x640_b64_bf16.json 2> $R/bp16.err   # BASELINE config 3: geometry and dtype
+python bench.py --full --workload bp > $R/${TAG}_bench_bp_320x640_b64.json 2> $R/bp.err
+python bench.py --full --precision bf16 > $R/${TAG}_bench_bev_bf16.json 2> $R/bev16.err
+python bench.py --full --workload seg > $R/${TAG}_bench_seg_512x1024_b16.json 2> $R/seg.err                      # config 5, one GPU's shard
 python bench.py --workload epoch > $R/${TAG}_bench_epoch.json 2> $R/epoch.err                             # config 4
 for f in $R/${TAG}_bench*.json; do
   python -c "import json; d=json.load(open('$f')); r=d.get('roofline') or {}; print('$f', d['value'], d['unit'], d['ms_per_step'], 'traffic on these sources:', (r.get('traffic_step') or {}).get('measured_on_these_sources'), 'parity ok:', (d.get('parity') or {}).get('ok'))"

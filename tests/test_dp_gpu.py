@@ -19,7 +19,7 @@ def test_bench_two_ranks_one_device_real_kernels():
         env.pop(k, None)
     env.update(LF_BENCH_SINGLE_DEVICE="1", LF_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8",
-                        "--min-seconds", "0", "--no-cpu-baseline", "--no-vendor-baseline"],
+                        "--min-seconds", "0", "--full", "--no-cpu-baseline", "--no-vendor-baseline"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

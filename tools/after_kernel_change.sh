@@ -10,10 +10,10 @@ timeout 120 python tools/kbench.py --iters 300 > gpurun_out/${TAG}_kbench.txt 2>
 tail -14 gpurun_out/${TAG}_kbench.txt
 timeout 900 python -m pytest ${@:-tests/test_backbone_gpu.py} -m gpu -x -q > gpurun_out/${TAG}_pytest.txt 2>&1
 tail -5 gpurun_out/${TAG}_pytest.txt
-timeout 240 python bench.py --no-cpu-baseline --no-vendor-baseline > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
+timeout 240 python bench.py --full --no-cpu-baseline --no-vendor-baseline > $TMPDIR/${TAG}_bench.json 2> $TMPDIR/${TAG}_bench.err || tail -5 $TMPDIR/${TAG}_bench.err
 python - <<PY
 import json
-d = json.loads(open("gpurun_out/${TAG}_bench.json").read().strip().splitlines()[-1])
+d = json.loads(open("$TMPDIR/${TAG}_bench.json").read().strip().splitlines()[-1])
 print(d["value"], d["ms_per_step"], d["roofline"]["families"], d.get("fp32_split_x9", {}).get("value"))
 PY
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${TAG} -o bench -- python bench.py --steps 10 --warmup 3 --min-seconds 1 --no-cpu-baseline --no-vendor-baseline > gpurun_out/${TAG}_trace.json 2> gpurun_out/${TAG}_trace.err
