@@ -32,7 +32,10 @@ extern "C" {
 #endif
 
 #define LF_ABI_VERSION 5      /* 5 (round 6): lf_erfnet_workspace_bytes_for added; lf_erfnet_set_precision refuses the removed modes 1 and 4;
-                                 lf_erfnet_forward_range / _backward_range take precision mode 2 */
+                                 lf_erfnet_forward_range / _backward_range take precision mode 2.
+                                 Later ADDITIONS that leave every existing entry point's contract as it was keep the number:
+                                 lf_convchain_set_precision / _workspace_bytes_for, lf_poolflat_bf16_*, lf_pointwise_bf16_*, and
+                                 lf_erfnet_backward's grad_encoder in mode 2 (the --clas heads and only_encode in bf16) */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -179,7 +182,9 @@ int lf_erfnet_forward(const lf_erfnet_plan* plan, const float* img, const float*
                       int training, int head, float* logits, void* workspace, size_t workspace_bytes, void* stream);
 /* Gradients are written (not accumulated) into grads_host[i]; NULL entries are skipped.
  * grad_encoder: optional (N,H/8,W/8,128) NHWC gradient w.r.t. the encoder output (`shared_encoder`,
- * BP/Networks/LSQ_layer.py:275), added where the decoder's gradient reaches the encoder; NULL = none.
+ * BP/Networks/LSQ_layer.py:275), added where the decoder's gradient reaches the encoder; NULL = none.  It has the storage
+ * type of the encoder output: fp32, or bf16 elements in precision mode 2 (the --clas heads and only_encode in bf16); the
+ * encoder-only backward (head = -1) takes it in every mode.
  * training: the mode the matching forward ran in.  1 = batch statistics (autograd of nn.BatchNorm2d in train mode);
  * 0 = running statistics (net.eval() with gradients enabled, e.g. fine-tuning with frozen statistics): BatchNorm is then
  * a per-channel affine map and its data gradient is gamma * rstd * dy, as torch computes it. */
@@ -222,6 +227,13 @@ int lf_pointwise_fwd(const float* x, const float* w, const float* b, float* y, i
 long lf_pointwise_scratch_floats(int N, int h, int w_, int C, int K);
 int lf_pointwise_bwd(const float* x, const float* gy, const float* w, float* gx, float* gw, float* gb, int N, int h, int w_,
                      int C, int K, float* scratch, void* stream);
+/* The same on the bf16 encoder output of precision mode 2 (ERFNet.py:84,86-95,151-153 in Net(precision="bf16")): x (N,h,w,C) NHWC
+ * bf16 (bit patterns, read in place), C % 8 == 0; y, w, b, gy, gw, gb fp32 as above; gx (N,h,w,C) NHWC is written as bf16 -- the
+ * grad_encoder that the encoder-only lf_erfnet_backward takes in mode 2.  Scratch as lf_pointwise_scratch_floats(). */
+int lf_pointwise_bf16_fwd(const uint16_t* x, const float* w, const float* b, float* y, int N, int h, int w_, int C, int K,
+                          void* stream);
+int lf_pointwise_bf16_bwd(const uint16_t* x, const float* gy, const float* w, uint16_t* gx, float* gw, float* gb, int N, int h,
+                          int w_, int C, int K, float* scratch, void* stream);
 /* ------------------------------------------------------------------------------------
  * Cold-path arithmetic natively (round 4): the nn.Linear tails of the --clas heads and the segmentation-mode fit input.
  *
@@ -277,12 +289,21 @@ int lf_rmsprop_step(const void* tensors_dev, const void* work_dev, int nblocks, 
  * workspace (lf_erfnet_encoder_offset); y = last block's post-ReLU output, NHWC.  The workspace holds the
  * saved pre-BN tensors until lf_convchain_backward, which writes every parameter gradient and (if gx != NULL)
  * the NHWC input gradient to hand to lf_erfnet_backward(grad_encoder).
+ * Precision (lf_convchain_set_precision): mode 0 (default) = fp32 tensors on the fp32 matrix cores; mode 2 = the backbone's
+ * "bf16" mode for the same trunk (BP/Networks/LSQ_layer.py:150-181 in Net(precision="bf16")): x, y, gy, gx and the saved pre-BN
+ * tensors hold bf16 elements (the pointers keep their float* type, as in lf_erfnet_*), the convolutions, their data gradients
+ * and weight gradients run on the bf16 matrix cores; BatchNorm statistics come from the fp32 values before the bf16 store;
+ * parameters, running statistics and parameter gradients stay fp32.  lf_convchain_workspace_bytes follows the mode the plan
+ * is set to; lf_convchain_workspace_bytes_for(plan, mode) names it (0 bytes for a mode other than 0 and 2), and a workspace
+ * sized for mode 2 serves mode 0 too.
  * ---------------------------------------------------------------------------------- */
 typedef struct lf_convchain_plan lf_convchain_plan;
 lf_convchain_plan* lf_convchain_plan_create(int N, int H, int W, int nlayers, const int* channels_host,
                                             const int* ksize_host);
 void lf_convchain_plan_destroy(lf_convchain_plan* plan);
 size_t lf_convchain_workspace_bytes(const lf_convchain_plan* plan);
+size_t lf_convchain_workspace_bytes_for(const lf_convchain_plan* plan, int mode);
+int lf_convchain_set_precision(const lf_convchain_plan* plan, int mode);      /* 0 or 2; anything else is refused */
 int lf_convchain_forward(const lf_convchain_plan* plan, const float* x, const float* const* params_host,
                          const float* const* params_dev, float* const* running_host, int training, float momentum,
                          float eps, float* y, void* workspace, size_t workspace_bytes, void* stream);
@@ -296,6 +317,10 @@ int lf_convchain_backward(const lf_convchain_plan* plan, const float* x, const f
  * library GEMMs (rocBLAS through torch.nn.functional.linear). */
 int lf_poolflat_fwd(const float* y, int N, int H, int W, int C, int mode, float* out, void* stream);
 int lf_poolflat_bwd(const float* y, const float* gout, int N, int H, int W, int C, int mode, float* gy, void* stream);
+/* The same on the bf16 NHWC trunk output of precision mode 2 (bit patterns): features and gout stay fp32 (the nn.Linear tails are
+ * fp32 in every mode), gy is written as bf16; the max-pool backward keeps ATen's first-maximum rule on the bf16 values. */
+int lf_poolflat_bf16_fwd(const uint16_t* y, int N, int H, int W, int C, int mode, float* out, void* stream);
+int lf_poolflat_bf16_bwd(const uint16_t* y, const float* gout, int N, int H, int W, int C, int mode, uint16_t* gy, void* stream);
 
 /* Projections.compute_coordinates (BP/test.py:172-186) + the gating of test_model (:77-88) in one launch:
  * x = resize(M_inv . [poly(beta, y_eval), y_prime, 1]) per (image, lane, sample height); then

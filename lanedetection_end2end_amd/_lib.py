@@ -57,6 +57,10 @@ def _declare(lib):
         "lf_convchain_backward": (I, [P, P, P, P, P, P, P, I, P, c_size_t, P]),
         "lf_poolflat_fwd": (I, [P, I, I, I, I, I, P, P]),
         "lf_poolflat_bwd": (I, [P, P, I, I, I, I, I, P, P]),
+        "lf_convchain_workspace_bytes_for": (c_size_t, [P, I]),
+        "lf_convchain_set_precision": (I, [P, I]),
+        "lf_poolflat_bf16_fwd": (I, [P, I, I, I, I, I, P, P]),
+        "lf_poolflat_bf16_bwd": (I, [P, P, I, I, I, I, I, P, P]),
         "lf_lane_decode": (I, [P, P, P, P, D, P, P, D, D, D, I, I, I, I, P, P, P]),
         "lf_trapezoid": (I, [P, P, I, D, D, I, I, P, P]),
         "lf_pipeline_plan_create": (P, [I, I, I, I, I, I]),
@@ -72,6 +76,8 @@ def _declare(lib):
         "lf_pointwise_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
         "lf_pointwise_scratch_floats": (L, [I, I, I, I, I]),
         "lf_pointwise_bwd": (I, [P, P, P, P, P, P, I, I, I, I, I, P, P]),
+        "lf_pointwise_bf16_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
+        "lf_pointwise_bf16_bwd": (I, [P, P, P, P, P, P, I, I, I, I, I, P, P]),
         "lf_adam_chunk": (I, []),
         "lf_adam_step": (I, [P, P, I, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                              I, ctypes.c_float, P]),

@@ -6,7 +6,10 @@ the same horizon head but a DIFFERENT line head -- four ``fully_connected_line{1
 are concatenated to (N, 3, 4), consumed by ``nn.CrossEntropyLoss`` (BEV/main.py:88,252) -- ``ClassificationBEV`` below.
 The conv trunk runs as ONE C-ABI call per direction (``lf_convchain_forward`` / ``_backward``) directly on
 the NHWC encoder output inside the backbone's workspace; pooling + NCHW flatten is ``lf_poolflat_*``; the
-``nn.Linear`` layers are plain library GEMMs.
+``nn.Linear`` layers are plain library GEMMs.  The trunk follows the storage type of its input: on the bf16 encoder output of
+the backbone's ``precision = "bf16"`` it runs in the chain's precision mode 2 (bf16 tensors on the bf16 matrix cores,
+``lf_convchain_set_precision``) and pooling reads bf16 (``lf_poolflat_bf16_*``); the features, the ``nn.Linear`` tails and
+the head outputs are fp32 in every mode.
 
 ``Projections`` mirrors BP/test.py:128-186 and ``decode_lanes`` fuses ``compute_coordinates`` for all lanes
 with the gating of ``test_model`` (BP/test.py:72-88) into one launch (``lf_lane_decode``).
@@ -37,7 +40,12 @@ class _ChainPlan:
             raise _lib.LaneFitLibraryError("lf_convchain_plan_create failed: %s" % lib.lf_last_error().decode())
         self.shape = (N, H, W)
         self.channels = tuple(channels)
-        self.ws_bytes = lib.lf_convchain_workspace_bytes(self.handle)
+        # one plan serves both precision modes (0: fp32 tensors, 2: bf16 tensors); the mode is set per call
+        self.ws_bytes = lib.lf_convchain_workspace_bytes_for(self.handle, 0)
+        self.ws_bytes_bf16 = lib.lf_convchain_workspace_bytes_for(self.handle, 2)
+
+    def workspace_bytes(self, mode):
+        return self.ws_bytes_bf16 if mode == 2 else self.ws_bytes
 
     def __del__(self):
         try:
@@ -47,14 +55,19 @@ class _ChainPlan:
 
 
 class _ConvChainFn(torch.autograd.Function):
-    """x: (N,H,W,C0) NHWC fp32 -> relu(bn_L(conv_L(... relu(bn_1(conv_1(x)))))) NHWC."""
+    """x: (N,H,W,C0) NHWC -> relu(bn_L(conv_L(... relu(bn_1(conv_1(x)))))) NHWC, of x's dtype: fp32 (precision mode 0) or bf16
+    (mode 2)."""
 
     @staticmethod
     def forward(ctx, mod, plan, x, training, *params):
         lib = _lib.load()
         N, H, W = plan.shape
-        ws = torch.empty(plan.ws_bytes, dtype=torch.uint8, device=x.device)
-        y = torch.empty(N, H, W, plan.channels[-1], dtype=torch.float32, device=x.device)
+        mode = 2 if x.dtype == torch.bfloat16 else 0
+        assert x.dtype in (torch.float32, torch.bfloat16) and x.is_contiguous()
+        _lib.check(lib.lf_convchain_set_precision(plan.handle, mode), "lf_convchain_set_precision")
+        ws_bytes = plan.workspace_bytes(mode)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        y = torch.empty(N, H, W, plan.channels[-1], dtype=x.dtype, device=x.device)
         params = [p.detach() for p in params]
         for p in params:
             assert p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
@@ -62,8 +75,8 @@ class _ConvChainFn(torch.autograd.Function):
         running = _ptr_array([b for bn in bns for b in (bn.running_mean, bn.running_var)])
         _lib.check(lib.lf_convchain_forward(plan.handle, _lib.ptr(x), _ptr_array(params), _lib.ptr(mod._ptr_table(params)),
                                             running, int(training), float(bns[0].momentum), float(bns[0].eps), _lib.ptr(y),
-                                            _lib.ptr(ws), plan.ws_bytes, _lib.stream()), "lf_convchain_forward")
-        ctx.plan, ctx.ws, ctx.x, ctx.y, ctx.params = plan, ws, x, y, params
+                                            _lib.ptr(ws), ws_bytes, _lib.stream()), "lf_convchain_forward")
+        ctx.plan, ctx.ws, ctx.x, ctx.y, ctx.params, ctx.mode = plan, ws, x, y, params, mode
         ctx.training = int(training)
         return y
 
@@ -71,22 +84,23 @@ class _ConvChainFn(torch.autograd.Function):
     def backward(ctx, gy):
         lib = _lib.load()
         plan, params = ctx.plan, ctx.params
-        gy = gy.contiguous()
+        gy = gy.to(ctx.y.dtype).contiguous()
         flat = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=gy.device)
         grads, off = [], 0
         for p in params:
             grads.append(flat[off: off + p.numel()].view(p.shape))
             off += p.numel()
         gx = torch.empty_like(ctx.x) if ctx.needs_input_grad[2] else None
+        _lib.check(lib.lf_convchain_set_precision(plan.handle, ctx.mode), "lf_convchain_set_precision")      # (plans are shared)
         _lib.check(lib.lf_convchain_backward(plan.handle, _lib.ptr(ctx.x), _lib.ptr(ctx.y), _lib.ptr(gy), _ptr_array(params),
-                                             _ptr_array(grads), _lib.ptr(gx), ctx.training, _lib.ptr(ctx.ws), plan.ws_bytes,
-                                             _lib.stream()), "lf_convchain_backward")
+                                             _ptr_array(grads), _lib.ptr(gx), ctx.training, _lib.ptr(ctx.ws),
+                                             plan.workspace_bytes(ctx.mode), _lib.stream()), "lf_convchain_backward")
         ctx.ws = None
         return (None, None, gx, None) + tuple(grads)
 
 
 class _PoolFlatFn(torch.autograd.Function):
-    """NHWC (N,H,W,C) -> (N, features) in NCHW flatten order; mode 0 = MaxPool2d(2,2), 1 = AvgPool2d((1,W))."""
+    """NHWC (N,H,W,C) fp32 or bf16 -> (N, features) fp32 in NCHW flatten order; mode 0 = MaxPool2d(2,2), 1 = AvgPool2d((1,W))."""
 
     @staticmethod
     def forward(ctx, y, mode):
@@ -94,7 +108,8 @@ class _PoolFlatFn(torch.autograd.Function):
         N, H, W, C = y.shape
         feat = C * (H // 2) * (W // 2) if mode == 0 else C * H
         out = torch.empty(N, feat, dtype=torch.float32, device=y.device)
-        _lib.check(lib.lf_poolflat_fwd(_lib.ptr(y), N, H, W, C, mode, _lib.ptr(out), _lib.stream()), "lf_poolflat_fwd")
+        fwd = lib.lf_poolflat_bf16_fwd if y.dtype == torch.bfloat16 else lib.lf_poolflat_fwd
+        _lib.check(fwd(_lib.ptr(y), N, H, W, C, mode, _lib.ptr(out), _lib.stream()), "lf_poolflat_fwd")
         ctx.save_for_backward(y)
         ctx.mode = mode
         return out
@@ -105,8 +120,9 @@ class _PoolFlatFn(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         N, H, W, C = y.shape
         gy = torch.empty_like(y)
-        _lib.check(lib.lf_poolflat_bwd(_lib.ptr(y), _lib.ptr(g.contiguous()), N, H, W, C, ctx.mode, _lib.ptr(gy),
-                                       _lib.stream()), "lf_poolflat_bwd")
+        bwd = lib.lf_poolflat_bf16_bwd if y.dtype == torch.bfloat16 else lib.lf_poolflat_bwd
+        _lib.check(bwd(_lib.ptr(y), _lib.ptr(g.contiguous()), N, H, W, C, ctx.mode, _lib.ptr(gy), _lib.stream()),
+                   "lf_poolflat_bwd")
         return gy, None
 
 
@@ -161,13 +177,15 @@ class Classification(nn.Module):
         return self._ptr_cache[1]
 
     def trunk(self, x):
-        """conv1..conv4 (+BN+ReLU) on a logical-NCHW tensor; returns NHWC (N,H,W,64)."""
+        """conv1..conv4 (+BN+ReLU) on a logical-NCHW tensor; returns NHWC (N,H,W,64), bf16 on a bf16 input (the encoder output
+        of the backbone's bf16 mode, read in place), fp32 otherwise."""
         if not x.is_cuda:
             raise _lib.LaneFitLibraryError("lanefit Classification needs its input on the MI355X; there is no CPU path")
         xh = x.permute(0, 2, 3, 1)
         if not xh.is_contiguous():           # the backbone hands out channels-last memory: normally a no-op
             xh = xh.contiguous()
-        xh = xh.float()
+        if xh.dtype != torch.bfloat16:
+            xh = xh.float()
         N, H, W, C = xh.shape
         assert C == self._channels[0]
         key = (N, H, W)

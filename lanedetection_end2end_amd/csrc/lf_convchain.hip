@@ -1,5 +1,8 @@
-// Chain of [Conv2d(k x k, stride 1, pad k/2, bias) -> BatchNorm2d -> ReLU] blocks on an NHWC fp32 tensor,
-// forward and backward, on the tap-GEMM kernels of lf_conv.hip.
+// Chain of [Conv2d(k x k, stride 1, pad k/2, bias) -> BatchNorm2d -> ReLU] blocks on an NHWC tensor, forward and
+// backward, on the tap-GEMM kernels of lf_conv.hip.  Precision mode 0 (the default): fp32 tensors on the fp32 matrix cores;
+// mode 2 (lf_convchain_set_precision, the backbone's "bf16"): x, the pre-BN tensors, y, gy and gx hold bf16 elements and the
+// convolutions and their weight gradients run on the bf16 matrix cores, as the backbone's mode 2 does -- parameters,
+// BatchNorm vectors and statistics, and all gradients of parameters stay fp32.
 //
 // Replaces the convolutional trunk of `Classification` (BP/Networks/LSQ_layer.py:150-191: conv1..conv4 with
 // their BatchNorms, :178-181) that the `--clas` line-type / horizon heads run on the shared encoder output.
@@ -14,6 +17,7 @@
 #include "lf_conv.h"
 #include "lf_eltwise.h"
 #include "lf_plan.h"
+#include "lf_types.h"
 
 #define LF_CHAIN_MAX 8
 
@@ -28,6 +32,10 @@ struct lf_convchain_plan {
     long sc[LF_CHAIN_MAX], sh[LF_CHAIN_MAX], asc[LF_CHAIN_MAX], ash[LF_CHAIN_MAX], c1[LF_CHAIN_MAX], c2[LF_CHAIN_MAX];
     long off_entries, off_packed, off_stat, stat_floats, off_wpart, wpart_floats, off_bpart, bpart_floats;
     long off_gA, off_gB, gbuf_floats, total_floats;
+    // precision mode 2 only, laid out after everything mode 0 uses (the mode-0 workspace is unchanged): the bf16 operand copy of
+    // the packed weights and the partial-row regions of the bf16 weight gradients (the read-once kernel's row counts)
+    long packed16_elems, off_packed16, wpart16_floats, off_wpart16, bpart16_floats, off_bpart16, total16_floats;
+    mutable int precision = 0;                          // lf_convchain_set_precision
 };
 
 namespace {
@@ -38,8 +46,9 @@ int add_pack(lf_convchain_plan* P, int param, int Kc, int Nc, long sk, long sn, 
     e.param = param; e.Kc = Kc; e.Nc = Nc; e.ntaps = g.ntaps; e.sk = sk; e.sn = sn;
     for (int t = 0; t < g.ntaps; ++t) e.tapidx[t] = tapidx[t];
     e.dst_off = P->packed_floats;
-    e.dst16_off = 0;                       // the heads stay on the fp32 matrix-core path
+    e.dst16_off = P->packed16_elems;       // (read by the bf16 pack kernel in mode 2 only)
     P->packed_floats += (long)g.ntaps * Kc * Nc;
+    P->packed16_elems += lf_pack_bf16_elems(Kc, Nc, g.ntaps);
     P->packs.push_back(e);
     return (int)P->packs.size() - 1;
 }
@@ -48,7 +57,9 @@ int add_pack(lf_convchain_plan* P, int param, int Kc, int Nc, long sk, long sn, 
 // ---- pooling + flatten in front of the fully connected layers (LSQ_layer.py:183-187) ---------------------
 // mode 0 ('line'):    MaxPool2d(2, 2)        NHWC (N,H,W,C) -> NCHW-flat (N, C*(H/2)*(W/2))
 // mode 1 ('horizon'): AvgPool2d((1, W))      NHWC (N,H,W,C) -> NCHW-flat (N, C*H)
-__global__ __launch_bounds__(256) void poolflat_max_fwd_kernel(const float* __restrict__ y, int N, int H, int W, int C,
+// T = the storage type of the NHWC tensor (float, or lf_bf16 in precision mode 2); the flat features and their gradient are fp32
+template <typename T>
+__global__ __launch_bounds__(256) void poolflat_max_fwd_kernel(const T* __restrict__ y, int N, int H, int W, int C,
                                                               float* __restrict__ out) {
     const int Ho = H / 2, Wo = W / 2;
     const long total = (long)N * C * Ho * Wo;
@@ -58,12 +69,13 @@ __global__ __launch_bounds__(256) void poolflat_max_fwd_kernel(const float* __re
         const int i = (int)(r % Ho);
         r /= Ho;
         const int c = (int)(r % C), n = (int)(r / C);
-        const float* b = y + (((long)n * H + 2 * i) * W + 2 * j) * C + c;
-        out[u] = fmaxf(fmaxf(b[0], b[C]), fmaxf(b[(long)W * C], b[(long)W * C + C]));
+        const T* b = y + (((long)n * H + 2 * i) * W + 2 * j) * C + c;
+        out[u] = fmaxf(fmaxf(lf_ld1(b), lf_ld1(b + C)), fmaxf(lf_ld1(b + (long)W * C), lf_ld1(b + (long)W * C + C)));
     }
 }
-__global__ __launch_bounds__(256) void poolflat_max_bwd_kernel(const float* __restrict__ y, const float* __restrict__ g,
-                                                              int N, int H, int W, int C, float* __restrict__ gy) {
+template <typename T>
+__global__ __launch_bounds__(256) void poolflat_max_bwd_kernel(const T* __restrict__ y, const float* __restrict__ g,
+                                                              int N, int H, int W, int C, T* __restrict__ gy) {
     const int Ho = H / 2, Wo = W / 2;
     const long total = (long)N * Ho * Wo * C;
     for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < total; u += (long)gridDim.x * 256) {
@@ -75,39 +87,41 @@ __global__ __launch_bounds__(256) void poolflat_max_bwd_kernel(const float* __re
         const long base = (((long)n * H + 2 * i) * W + 2 * j) * C + c;
         const long o[4] = {0, C, (long)W * C, (long)W * C + C};
         int arg = 0;
-        float m = y[base];
+        float m = lf_ld1(y + base);
 #pragma unroll
         for (int e = 1; e < 4; ++e) {      // first maximum in window scan order wins, as ATen's max_pool2d
-            const float v = y[base + o[e]];
+            const float v = lf_ld1(y + base + o[e]);
             if (v > m) { m = v; arg = e; }
         }
         const float gv = g[(((long)n * C + c) * Ho + i) * Wo + j];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) gy[base + o[e]] = e == arg ? gv : 0.f;
+        for (int e = 0; e < 4; ++e) lf_st1(gy + base + o[e], e == arg ? gv : 0.f);
     }
 }
-__global__ __launch_bounds__(256) void poolflat_avg_fwd_kernel(const float* __restrict__ y, int N, int H, int W, int C,
+template <typename T>
+__global__ __launch_bounds__(256) void poolflat_avg_fwd_kernel(const T* __restrict__ y, int N, int H, int W, int C,
                                                               float* __restrict__ out) {
     const long total = (long)N * H * C;
     for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < total; u += (long)gridDim.x * 256) {
         const int c = (int)(u % C);
         const long r = u / C;
         const int i = (int)(r % H), n = (int)(r / H);
-        const float* b = y + ((long)n * H + i) * W * C + c;
+        const T* b = y + ((long)n * H + i) * W * C + c;
         float s = 0.f;
-        for (int j = 0; j < W; ++j) s += b[(long)j * C];
+        for (int j = 0; j < W; ++j) s += lf_ld1(b + (long)j * C);
         out[((long)n * C + c) * H + i] = s / (float)W;
     }
 }
+template <typename T>
 __global__ __launch_bounds__(256) void poolflat_avg_bwd_kernel(const float* __restrict__ g, int N, int H, int W, int C,
-                                                              float* __restrict__ gy) {
+                                                              T* __restrict__ gy) {
     const long total = (long)N * H * W * C;
     const float inv = 1.f / (float)W;
     for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < total; u += (long)gridDim.x * 256) {
         const int c = (int)(u % C);
         const long r = u / C / W;
         const int i = (int)(r % H), n = (int)(r / H);
-        gy[u] = g[((long)n * C + c) * H + i] * inv;
+        lf_st1(gy + u, g[((long)n * C + c) * H + i] * inv);
     }
 }
 
@@ -135,6 +149,7 @@ lf_convchain_plan* lf_convchain_plan_create(int N, int H, int W, int nlayers, co
     lf_convchain_plan* P = new lf_convchain_plan();
     P->N = N; P->H = H; P->W = W; P->L = nlayers; P->packed_floats = 0;
     P->stat_floats = 0; P->wpart_floats = 0; P->bpart_floats = 0;
+    P->packed16_elems = 0; P->wpart16_floats = 0; P->bpart16_floats = 0;
     LfBump ws;
     const long npix = (long)N * H * W;
     int cmax = 0;
@@ -164,7 +179,9 @@ lf_convchain_plan* lf_convchain_plan_create(int N, int H, int W, int nlayers, co
         P->stat_floats = lf_maxl(P->stat_floats, (long)lf_tapgemm_stat_rows(g) * 2 * Co);
         P->stat_floats = lf_maxl(P->stat_floats, (long)lf_tapgemm_stat_rows(d) * 2 * Ci);
         P->wpart_floats = lf_maxl(P->wpart_floats, (long)lf_tapwgrad_splits(g) * kk * Ci * Co);
-        P->bpart_floats = lf_maxl(P->bpart_floats, (long)lf_tapwgrad_splits_bound(g, 0) * Co);      // (fp32 tensors: the chain has no bf16 mode)
+        P->bpart_floats = lf_maxl(P->bpart_floats, (long)lf_tapwgrad_splits_bound(g, 0) * Co);      // (fp32 tensors)
+        P->wpart16_floats = lf_maxl(P->wpart16_floats, (long)lf_tapwgrad_splits_bound(g, 1) * kk * Ci * Co);
+        P->bpart16_floats = lf_maxl(P->bpart16_floats, (long)lf_tapwgrad_splits_bound(g, 1) * Co);   // (bf16 tensors, mode 2)
     }
     P->stat_floats = lf_maxl(P->stat_floats, (long)lf_bn_bwd_reduce_rows(npix) * 2 * cmax);
     P->off_entries = ws.take((long)(P->packs.size() * sizeof(LfPackEntry) + 3) / 4);
@@ -177,11 +194,31 @@ lf_convchain_plan* lf_convchain_plan_create(int N, int H, int W, int nlayers, co
     P->off_gA = ws.take(P->gbuf_floats);
     P->off_gB = ws.take(P->gbuf_floats);
     P->total_floats = ws.cur;
+    // mode 2 only (the activation / gradient regions above are sized in floats and hold bf16 elements at half their size there)
+    P->off_packed16 = ws.take((P->packed16_elems + 1) / 2);
+    P->off_wpart16 = ws.take(P->wpart16_floats);
+    P->off_bpart16 = ws.take(P->bpart16_floats);
+    P->total16_floats = ws.cur;
     return P;
 }
 
 void lf_convchain_plan_destroy(lf_convchain_plan* P) { delete P; }
-size_t lf_convchain_workspace_bytes(const lf_convchain_plan* P) { return (size_t)P->total_floats * sizeof(float); }
+// follows the precision mode: call it after lf_convchain_set_precision
+size_t lf_convchain_workspace_bytes(const lf_convchain_plan* P) {
+    return (size_t)(P->precision == 2 ? P->total16_floats : P->total_floats) * sizeof(float);
+}
+// ... or for a NAMED precision mode (0 or 2; 0 bytes for any other), independent of the plan's current setting
+size_t lf_convchain_workspace_bytes_for(const lf_convchain_plan* P, int mode) {
+    if (!P || !(mode == 0 || mode == 2)) return 0;
+    return (size_t)(mode == 2 ? P->total16_floats : P->total_floats) * sizeof(float);
+}
+// 0: fp32 tensors on the fp32 matrix cores (the default); 2: bf16 tensors on the bf16 matrix cores (the backbone's mode 2).
+// The fp32x9 mode of the backbone has no counterpart here: its heads run in mode 0.
+int lf_convchain_set_precision(const lf_convchain_plan* P, int mode) {
+    LF_REQUIRE(P && (mode == 0 || mode == 2), "lf_convchain_set_precision: mode must be 0 (fp32 tensors) or 2 (bf16 tensors), got %d", mode);
+    P->precision = mode;
+    return 0;
+}
 
 // x (N,H,W,C0) NHWC; params_host / params_dev: 4*L device pointers (host array / device array);
 // running_host: 2*L device pointers (running_mean, running_var per block); y (N,H,W,C_L) NHWC = the last
@@ -197,6 +234,9 @@ int lf_convchain_forward(const lf_convchain_plan* P, const float* x, const float
     if (hipMemcpyAsync(ent, P->packs.data(), P->packs.size() * sizeof(LfPackEntry), hipMemcpyHostToDevice, st) != hipSuccess)
         return lf_fail("lf_convchain_forward: upload of the pack table failed");
     LF_TRY(lf_pack_weights_launch(ent, (int)P->packs.size(), params_dev, ws + P->off_packed, st));
+    const int s16 = P->precision == 2;
+    const unsigned short* wp16 = reinterpret_cast<const unsigned short*>(ws + P->off_packed16);
+    if (s16) LF_TRY(lf_pack_weights_bf16_launch(ent, (int)P->packs.size(), params_dev, ws + P->off_packed16, st));
     const long npix = (long)P->N * P->H * P->W;
     float* stat = ws + P->off_stat;
     for (int i = 0; i < P->L; ++i) {
@@ -204,6 +244,7 @@ int lf_convchain_forward(const lf_convchain_plan* P, const float* x, const float
         a.src = i == 0 ? x : ws + P->z[i - 1];
         a.dst = ws + P->z[i];
         a.wp = ws + P->off_packed + P->packs[P->pk_fwd[i]].dst_off;
+        if (s16) { a.s16 = 1; a.wp16 = wp16 + P->packs[P->pk_fwd[i]].dst16_off; }     // (statistics from the fp32 values before the bf16 store)
         a.bias = params_host[4 * i + 1];
         a.stats = stat; a.stats_ld = lf_stat_ld(lf_tapgemm_stat_rows(P->fwd[i]));
         int pro = LF_PRO_NONE;
@@ -216,7 +257,7 @@ int lf_convchain_forward(const lf_convchain_plan* P, const float* x, const float
                                   ws + P->sh[i], ws + P->asc[i], ws + P->ash[i], st));
     }
     const int l = P->L - 1;
-    return lf_bn_act(ws + P->z[l], ws + P->sc[l], ws + P->sh[l], nullptr, nullptr, y, npix, P->C[P->L], (long)P->H * P->W, 0, st);
+    return lf_bn_act(ws + P->z[l], ws + P->sc[l], ws + P->sh[l], nullptr, nullptr, y, npix, P->C[P->L], (long)P->H * P->W, s16, st);
 }
 
 // Backward of the forward that last used `workspace`.  gy (N,H,W,C_L) NHWC; grads_host: 4*L device pointers
@@ -233,27 +274,29 @@ int lf_convchain_backward(const lf_convchain_plan* P, const float* x, const floa
     const long npix = (long)P->N * P->H * P->W, ppi = (long)P->H * P->W;
     float* stat = ws + P->off_stat;
     float *A = ws + P->off_gA, *B = ws + P->off_gB;
+    const int s16 = P->precision == 2;
+    const unsigned short* wp16 = reinterpret_cast<const unsigned short*>(ws + P->off_packed16);
     // last block: BatchNorm + ReLU backward from the saved output
     int l = P->L - 1;
     const int rrows = lf_bn_bwd_reduce_rows(npix);
-    LF_TRY(lf_bn_bwd_reduce(gy, y, ws + P->z[l], ws + P->asc[l], ws + P->ash[l], nullptr, stat, lf_stat_ld(rrows), npix, P->C[l + 1], ppi, 0, st));
+    LF_TRY(lf_bn_bwd_reduce(gy, y, ws + P->z[l], ws + P->asc[l], ws + P->ash[l], nullptr, stat, lf_stat_ld(rrows), npix, P->C[l + 1], ppi, s16, st));
     LfStatPart rp = {stat, rrows, P->C[l + 1], 0, lf_stat_ld(rrows)};
     LF_TRY(lf_bn_bwd_finalize(&rp, 1, P->C[l + 1], (double)npix, ws + P->asc[l], ws + P->ash[l], ws + P->c1[l], ws + P->c2[l],
                               grads_host[4 * l + 2], grads_host[4 * l + 3], training, st));
     LF_TRY(lf_bn_bwd_apply(gy, y, ws + P->z[l], ws + P->asc[l], ws + P->ash[l], params_host[4 * l + 2], ws + P->c1[l],
-                           ws + P->c2[l], nullptr, A, nullptr, npix, P->C[l + 1], ppi, 0, st));
+                           ws + P->c2[l], nullptr, A, nullptr, npix, P->C[l + 1], ppi, s16, st));
     float *gz = A, *other = B;      // gz = d loss / d z_i
     for (int i = l; i >= 0; --i) {
         // weight + bias gradient: input a_{i-1} = relu(bn_{i-1}(z_{i-1})) recomputed on the operand load
         LfWgradArgs wa;
         wa.x = i == 0 ? x : ws + P->z[i - 1];
         wa.g = gz;
-        wa.s16 = 0;
-        wa.split = 0;                   // the heads stay on the fp32 matrix cores
+        wa.s16 = s16;                   // (mode 2: the bf16 kernels -- read-once where lf_tapwgrad_ro_ok takes the geometry)
+        wa.split = 0;
         wa.pro_sc = i == 0 ? nullptr : ws + P->sc[i - 1];
         wa.pro_sh = i == 0 ? nullptr : ws + P->sh[i - 1];
-        wa.partial = ws + P->off_wpart;
-        wa.bias_partial = ws + P->off_bpart;
+        wa.partial = ws + (s16 ? P->off_wpart16 : P->off_wpart);
+        wa.bias_partial = ws + (s16 ? P->off_bpart16 : P->off_bpart);
         LF_TRY(lf_tapwgrad_launch(P->fwd[i], wa, i == 0 ? LF_PRO_NONE : LF_PRO_BNRELU, st));
         const LfPackEntry& e = P->packs[P->pk_fwd[i]];
         const int nsplit = lf_tapwgrad_splits_for(P->fwd[i], wa, i == 0 ? LF_PRO_NONE : LF_PRO_BNRELU);
@@ -264,6 +307,7 @@ int lf_convchain_backward(const lf_convchain_plan* P, const float* x, const floa
         LfTapArgs a = lf_no_args();
         a.src = gz;
         a.wp = ws + P->off_packed + P->packs[P->pk_dg[i]].dst_off;
+        if (s16) { a.s16 = 1; a.wp16 = wp16 + P->packs[P->pk_dg[i]].dst16_off; }
         if (i == 0) {
             if (gx) { a.dst = gx; LF_TRY(lf_tapgemm_launch(P->dg[i], a, LF_PRO_NONE, 0, st)); }
             break;
@@ -277,7 +321,7 @@ int lf_convchain_backward(const lf_convchain_plan* P, const float* x, const floa
         LF_TRY(lf_bn_bwd_finalize(&sp, 1, P->C[i], (double)npix, ws + P->asc[j], ws + P->ash[j], ws + P->c1[j], ws + P->c2[j],
                                   grads_host[4 * j + 2], grads_host[4 * j + 3], training, st));
         LF_TRY(lf_bn_bwd_apply(other, nullptr, ws + P->z[j], ws + P->asc[j], ws + P->ash[j], params_host[4 * j + 2],
-                               ws + P->c1[j], ws + P->c2[j], nullptr, gz, nullptr, npix, P->C[i], ppi, 0, st));
+                               ws + P->c1[j], ws + P->c2[j], nullptr, gz, nullptr, npix, P->C[i], ppi, s16, st));
         // gz now holds d loss / d z_{i-1} (written over the consumed gradient), `other` is scratch again
     }
     return 0;
@@ -288,9 +332,9 @@ int lf_poolflat_fwd(const float* y, int N, int H, int W, int C, int mode, float*
     hipStream_t st = (hipStream_t)stream;
     if (mode == 0) {
         LF_REQUIRE(H % 2 == 0 && W % 2 == 0, "lf_poolflat_fwd: max-pool needs even H, W");
-        hipLaunchKernelGGL(poolflat_max_fwd_kernel, dim3(poolflat_grid((long)N * C * (H / 2) * (W / 2))), dim3(256), 0, st, y, N, H, W, C, out);
+        hipLaunchKernelGGL(poolflat_max_fwd_kernel<float>, dim3(poolflat_grid((long)N * C * (H / 2) * (W / 2))), dim3(256), 0, st, y, N, H, W, C, out);
     } else {
-        hipLaunchKernelGGL(poolflat_avg_fwd_kernel, dim3(poolflat_grid((long)N * H * C)), dim3(256), 0, st, y, N, H, W, C, out);
+        hipLaunchKernelGGL(poolflat_avg_fwd_kernel<float>, dim3(poolflat_grid((long)N * H * C)), dim3(256), 0, st, y, N, H, W, C, out);
     }
     LF_CHECK_LAUNCH("lf_poolflat_fwd");
     return 0;
@@ -302,11 +346,41 @@ int lf_poolflat_bwd(const float* y, const float* g, int N, int H, int W, int C, 
     hipStream_t st = (hipStream_t)stream;
     if (mode == 0) {
         LF_REQUIRE(H % 2 == 0 && W % 2 == 0, "lf_poolflat_bwd: max-pool needs even H, W");
-        hipLaunchKernelGGL(poolflat_max_bwd_kernel, dim3(poolflat_grid((long)N * (H / 2) * (W / 2) * C)), dim3(256), 0, st, y, g, N, H, W, C, gy);
+        hipLaunchKernelGGL(poolflat_max_bwd_kernel<float>, dim3(poolflat_grid((long)N * (H / 2) * (W / 2) * C)), dim3(256), 0, st, y, g, N, H, W, C, gy);
     } else {
-        hipLaunchKernelGGL(poolflat_avg_bwd_kernel, dim3(poolflat_grid((long)N * H * W * C)), dim3(256), 0, st, g, N, H, W, C, gy);
+        hipLaunchKernelGGL(poolflat_avg_bwd_kernel<float>, dim3(poolflat_grid((long)N * H * W * C)), dim3(256), 0, st, g, N, H, W, C, gy);
     }
     LF_CHECK_LAUNCH("lf_poolflat_bwd");
+    return 0;
+}
+
+// The same on a bf16 NHWC tensor (the trunk's output in precision mode 2): fp32 features out; gy written as bf16
+int lf_poolflat_bf16_fwd(const uint16_t* y, int N, int H, int W, int C, int mode, float* out, void* stream) {
+    LF_REQUIRE(y && out && N > 0 && C > 0, "lf_poolflat_bf16_fwd: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const lf_bf16* yb = reinterpret_cast<const lf_bf16*>(y);
+    if (mode == 0) {
+        LF_REQUIRE(H % 2 == 0 && W % 2 == 0, "lf_poolflat_bf16_fwd: max-pool needs even H, W");
+        hipLaunchKernelGGL(poolflat_max_fwd_kernel<lf_bf16>, dim3(poolflat_grid((long)N * C * (H / 2) * (W / 2))), dim3(256), 0, st, yb, N, H, W, C, out);
+    } else {
+        hipLaunchKernelGGL(poolflat_avg_fwd_kernel<lf_bf16>, dim3(poolflat_grid((long)N * H * C)), dim3(256), 0, st, yb, N, H, W, C, out);
+    }
+    LF_CHECK_LAUNCH("lf_poolflat_bf16_fwd");
+    return 0;
+}
+
+int lf_poolflat_bf16_bwd(const uint16_t* y, const float* g, int N, int H, int W, int C, int mode, uint16_t* gy, void* stream) {
+    LF_REQUIRE(y && g && gy && N > 0 && C > 0, "lf_poolflat_bf16_bwd: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const lf_bf16* yb = reinterpret_cast<const lf_bf16*>(y);
+    lf_bf16* gyb = reinterpret_cast<lf_bf16*>(gy);
+    if (mode == 0) {
+        LF_REQUIRE(H % 2 == 0 && W % 2 == 0, "lf_poolflat_bf16_bwd: max-pool needs even H, W");
+        hipLaunchKernelGGL(poolflat_max_bwd_kernel<lf_bf16>, dim3(poolflat_grid((long)N * (H / 2) * (W / 2) * C)), dim3(256), 0, st, yb, g, N, H, W, C, gyb);
+    } else {
+        hipLaunchKernelGGL(poolflat_avg_bwd_kernel<lf_bf16>, dim3(poolflat_grid((long)N * H * W * C)), dim3(256), 0, st, g, N, H, W, C, gyb);
+    }
+    LF_CHECK_LAUNCH("lf_poolflat_bf16_bwd");
     return 0;
 }
 

@@ -587,13 +587,15 @@ int lf_head_bwd_data(const float* gout, const float* w, float* gx, int N, int h,
 
 // ---------------------------------------------------------------------------------------
 // encoder.output_conv: Conv2d(128, K, 1) on the encoder output -- the `predict=True` branch of Encoder.forward that
-// Net.forward(only_encode=True) returns (BEV/Networks/ERFNet.py:84,86-95,151-153).  NHWC (N,h,w,C) fp32 in, NCHW (N,K,h,w) out.
+// Net.forward(only_encode=True) returns (BEV/Networks/ERFNet.py:84,86-95,151-153).  NHWC (N,h,w,C) in -- fp32, or bf16 in precision
+// mode 2 (T = the storage type of x and gx) --, NCHW (N,K,h,w) fp32 out; arithmetic fp32 either way.
 // Bandwidth-bound (reads C floats, writes K <= 8 per pixel): one thread per pixel, weights broadcast from LDS.
 // ---------------------------------------------------------------------------------------
 namespace {
 constexpr int PW_MAXK = 8, PW_MAXC = 256;
 
-__global__ __launch_bounds__(256) void pointwise_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+template <typename T>
+__global__ __launch_bounds__(256) void pointwise_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ b, float* __restrict__ y, long npix,
                                                            long pix_per_image, int C, int K) {
     __shared__ float sw[PW_MAXK * PW_MAXC];
@@ -602,9 +604,9 @@ __global__ __launch_bounds__(256) void pointwise_fwd_kernel(const float* __restr
     for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
         float acc[PW_MAXK];
         for (int k = 0; k < K; ++k) acc[k] = b ? b[k] : 0.f;
-        const float* xp = x + p * C;
+        const T* xp = x + p * C;
         for (int c = 0; c < C; c += 4) {
-            const lf_f32x4 v = *reinterpret_cast<const lf_f32x4*>(xp + c);
+            const lf_f32x4 v = lf_ldv(xp + c);
             for (int k = 0; k < K; ++k) {
                 const float* wk = sw + k * C + c;
                 acc[k] = fmaf(v.x, wk[0], fmaf(v.y, wk[1], fmaf(v.z, wk[2], fmaf(v.w, wk[3], acc[k]))));
@@ -616,8 +618,9 @@ __global__ __launch_bounds__(256) void pointwise_fwd_kernel(const float* __restr
 }
 
 // gx[p][c] = sum_k gy[n][k][q] * w[k][c]
+template <typename T>
 __global__ __launch_bounds__(256) void pointwise_bwd_data_kernel(const float* __restrict__ gy, const float* __restrict__ w,
-                                                                float* __restrict__ gx, long npix, long pix_per_image, int C,
+                                                                T* __restrict__ gx, long npix, long pix_per_image, int C,
                                                                 int K) {
     __shared__ float sw[PW_MAXK * PW_MAXC];
     for (int i = threadIdx.x; i < K * C; i += 256) sw[i] = w[i];
@@ -626,21 +629,22 @@ __global__ __launch_bounds__(256) void pointwise_bwd_data_kernel(const float* __
         const long n = p / pix_per_image, q = p - n * pix_per_image;
         float g[PW_MAXK];
         for (int k = 0; k < K; ++k) g[k] = gy[(n * K + k) * pix_per_image + q];
-        float* gp = gx + p * C;
+        T* gp = gx + p * C;
         for (int c = 0; c < C; c += 4) {
             lf_f32x4 v = {0.f, 0.f, 0.f, 0.f};
             for (int k = 0; k < K; ++k) {
                 const float* wk = sw + k * C + c;
                 v.x = fmaf(g[k], wk[0], v.x); v.y = fmaf(g[k], wk[1], v.y); v.z = fmaf(g[k], wk[2], v.z); v.w = fmaf(g[k], wk[3], v.w);
             }
-            *reinterpret_cast<lf_f32x4*>(gp + c) = v;
+            lf_stv(gp + c, v);
         }
     }
 }
 
 // partial rows: wrows[block][k][c] = sum over the block's pixels of gy[k] * x[c]; brows[block][k] = sum gy[k].
 // thread = channel (C <= 256 threads active), pixels of the block in sequence: x loads coalesce over c, gy broadcasts.
-__global__ __launch_bounds__(256) void pointwise_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ gy,
+template <typename T>
+__global__ __launch_bounds__(256) void pointwise_wgrad_kernel(const T* __restrict__ x, const float* __restrict__ gy,
                                                              float* __restrict__ wrows, float* __restrict__ brows, long npix,
                                                              long pix_per_image, int C, int K, int pix_per_block) {
     const int c = threadIdx.x;
@@ -651,7 +655,7 @@ __global__ __launch_bounds__(256) void pointwise_wgrad_kernel(const float* __res
         const long p = p0 + i;
         if (p >= npix) break;
         const long n = p / pix_per_image, q = p - n * pix_per_image;
-        const float xv = c < C ? x[p * C + c] : 0.f;
+        const float xv = c < C ? lf_ld1(x + p * C + c) : 0.f;
         for (int k = 0; k < K; ++k) {
             const float g = gy[(n * K + k) * pix_per_image + q];
             acc[k] = fmaf(g, xv, acc[k]);
@@ -671,7 +675,7 @@ extern "C" {
 int lf_pointwise_fwd(const float* x, const float* w, const float* b, float* y, int N, int h, int w_, int C, int K, void* stream) {
     LF_REQUIRE(x && w && y && C % 4 == 0 && C <= PW_MAXC && K >= 1 && K <= PW_MAXK, "lf_pointwise_fwd: bad arguments (C=%d K=%d)", C, K);
     const long npix = (long)N * h * w_;
-    hipLaunchKernelGGL(pointwise_fwd_kernel, dim3(grid_for(npix, 4096)), dim3(256), 0, (hipStream_t)stream, x, w, b, y, npix,
+    hipLaunchKernelGGL(pointwise_fwd_kernel<float>, dim3(grid_for(npix, 4096)), dim3(256), 0, (hipStream_t)stream, x, w, b, y, npix,
                        (long)h * w_, C, K);
     LF_CHECK_LAUNCH("pointwise_fwd");
     return 0;
@@ -687,15 +691,48 @@ int lf_pointwise_bwd(const float* x, const float* gy, const float* w, float* gx,
     hipStream_t st = (hipStream_t)stream;
     const long npix = (long)N * h * w_;
     if (gx) {
-        hipLaunchKernelGGL(pointwise_bwd_data_kernel, dim3(grid_for(npix, 4096)), dim3(256), 0, st, gy, w, gx, npix, (long)h * w_, C, K);
+        hipLaunchKernelGGL(pointwise_bwd_data_kernel<float>, dim3(grid_for(npix, 4096)), dim3(256), 0, st, gy, w, gx, npix, (long)h * w_, C, K);
         LF_CHECK_LAUNCH("pointwise_bwd_data");
     }
     if (gw || gb) {       // weight and bias gradients are independent requests (a frozen weight with a trainable bias)
         LF_REQUIRE(scratch, "lf_pointwise_bwd: scratch missing");
         const int rows = lf_cdiv(npix, 256);
         float* brows = scratch + (long)rows * K * C;
-        hipLaunchKernelGGL(pointwise_wgrad_kernel, dim3(rows), dim3(256), 0, st, x, gy, scratch, brows, npix, (long)h * w_, C, K, 256);
+        hipLaunchKernelGGL(pointwise_wgrad_kernel<float>, dim3(rows), dim3(256), 0, st, x, gy, scratch, brows, npix, (long)h * w_, C, K, 256);
         LF_CHECK_LAUNCH("pointwise_wgrad");
+        if (gw) LF_TRY(lf_rows_reduce_launch(scratch, rows, K * C, gw, 0, st));
+        if (gb) LF_TRY(lf_rows_reduce_launch(brows, rows, K, gb, 0, st));
+    }
+    return 0;
+}
+
+// The same on the bf16 encoder output of precision mode 2: x (N,h,w,C) NHWC bf16 in place, y (N,K,h,w) NCHW fp32; backward writes
+// gx as bf16 (the gradient the backbone's encoder-only backward takes in mode 2), gw / gb fp32.  C % 8 == 0 (16-byte pixels).
+int lf_pointwise_bf16_fwd(const uint16_t* x, const float* w, const float* b, float* y, int N, int h, int w_, int C, int K, void* stream) {
+    LF_REQUIRE(x && w && y && C % 8 == 0 && C <= PW_MAXC && K >= 1 && K <= PW_MAXK, "lf_pointwise_bf16_fwd: bad arguments (C=%d K=%d)", C, K);
+    const long npix = (long)N * h * w_;
+    hipLaunchKernelGGL(pointwise_fwd_kernel<lf_bf16>, dim3(grid_for(npix, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const lf_bf16*>(x), w, b, y, npix, (long)h * w_, C, K);
+    LF_CHECK_LAUNCH("pointwise_bf16_fwd");
+    return 0;
+}
+int lf_pointwise_bf16_bwd(const uint16_t* x, const float* gy, const float* w, uint16_t* gx, float* gw, float* gb, int N, int h, int w_,
+                          int C, int K, float* scratch, void* stream) {
+    LF_REQUIRE(x && gy && w && C % 8 == 0 && C <= PW_MAXC && K >= 1 && K <= PW_MAXK, "lf_pointwise_bf16_bwd: bad arguments (C=%d K=%d)", C, K);
+    hipStream_t st = (hipStream_t)stream;
+    const long npix = (long)N * h * w_;
+    const lf_bf16* xb = reinterpret_cast<const lf_bf16*>(x);
+    if (gx) {
+        hipLaunchKernelGGL(pointwise_bwd_data_kernel<lf_bf16>, dim3(grid_for(npix, 4096)), dim3(256), 0, st, gy, w,
+                           reinterpret_cast<lf_bf16*>(gx), npix, (long)h * w_, C, K);
+        LF_CHECK_LAUNCH("pointwise_bf16_bwd_data");
+    }
+    if (gw || gb) {
+        LF_REQUIRE(scratch, "lf_pointwise_bf16_bwd: scratch missing");
+        const int rows = lf_cdiv(npix, 256);
+        float* brows = scratch + (long)rows * K * C;
+        hipLaunchKernelGGL(pointwise_wgrad_kernel<lf_bf16>, dim3(rows), dim3(256), 0, st, xb, gy, scratch, brows, npix, (long)h * w_, C, K, 256);
+        LF_CHECK_LAUNCH("pointwise_bf16_wgrad");
         if (gw) LF_TRY(lf_rows_reduce_launch(scratch, rows, K * C, gw, 0, st));
         if (gb) LF_TRY(lf_rows_reduce_launch(brows, rows, K, gb, 0, st));
     }

@@ -830,7 +830,9 @@ int lf_erfnet_forward(const lf_erfnet_plan* P, const float* img, const float* co
 }
 
 // Backward of the forward that last used `workspace`.  grad_logits (N,Cout,H,W) NCHW; grad_encoder: optional
-// (N,H/8,W/8,128) NHWC gradient w.r.t. the encoder output (the `shared_encoder` the --clas heads consume);
+// (N,H/8,W/8,128) NHWC gradient w.r.t. the encoder output (the `shared_encoder` the --clas heads consume; bf16 elements in
+// precision mode 2, fp32 otherwise -- the storage type of the encoder output itself), joined by the first decoder layer's data
+// gradient (LF_EPI_ADD);
 // training: the mode the forward ran in (0 = running statistics: BatchNorm backward is then the affine map's);
 // grads_host: n_params device pointers receiving d loss / d param (NULL entries are skipped:
 // encoder.output_conv, the unused head).  Gradients are WRITTEN, not accumulated.
@@ -844,14 +846,13 @@ int lf_erfnet_backward(const lf_erfnet_plan* P, const float* img, const float* g
     LF_REQUIRE(head >= -1 && head < P->n_heads, "lf_erfnet_backward: head %d out of range", head);
     Ctx c{P, (float*)workspace, params_host, grads_host, nullptr, dropmask, training, (hipStream_t)stream};
     c.g_enc = grad_encoder;
-    c.s16 = P->precision == 2;
-    LF_REQUIRE(!(c.s16 && grad_encoder), "lf_erfnet_backward: grad_encoder is not supported with bf16 tensors (mode 2)");
+    c.s16 = P->precision == 2;       // (mode 2: grad_encoder holds bf16 elements, as the encoder output it differentiates)
     float *gA = c.at(P->off_gA), *gB = c.at(P->off_gB), *gC = c.at(P->off_gC);
     if (head < 0) {       // encoder only: the incoming gradient IS d loss / d (encoder output); the pass overwrites its buffers
         LF_REQUIRE(grad_encoder, "lf_erfnet_backward: the encoder-only backward needs grad_encoder");
         const int ne = encoder_layers(P);
         const Layer& Le = P->layers[ne - 1];
-        const size_t bytes = (size_t)P->N * Le.Hout * Le.Wout * Le.Cout * sizeof(float);
+        const size_t bytes = (size_t)P->N * Le.Hout * Le.Wout * Le.Cout * (c.s16 ? 2 : sizeof(float));
         if (hipMemcpyAsync(gA, grad_encoder, bytes, hipMemcpyDeviceToDevice, c.st) != hipSuccess)
             return lf_fail("lf_erfnet_backward: copy of grad_encoder failed");
         c.g_enc = nullptr;

@@ -209,10 +209,10 @@ class _BackboneFn(torch.autograd.Function):
         if head < 0:
             ctx.mark_non_differentiable(logits)
         if net.export_encoder_output and ctx.precision == 2:
-            # bf16 tensors: the in-place view is bf16 and takes no gradient (the --clas heads are an fp32 path)
+            # bf16 tensors: the in-place view is bf16 and differentiable -- its gradient comes back as bf16 and joins the backward
+            # where fp32's does (the --clas heads and only_encode run in this mode too)
             nenc = N * (H // 8) * (W // 8) * 128
             enc = ws[4 * plan.enc_off: 4 * plan.enc_off + 2 * nenc].view(torch.bfloat16).view(N, H // 8, W // 8, 128)
-            ctx.mark_non_differentiable(enc)
         elif net.export_encoder_output:
             # the encoder output is handed out IN PLACE: an NHWC view of the workspace (no copy, no transpose);
             # Net.forward permutes it to the reference's logical (N,128,H/8,W/8)
@@ -230,14 +230,16 @@ class _BackboneFn(torch.autograd.Function):
     def backward(ctx, glogits, genc):
         lib = _lib.load()
         N, H, W = ctx.plan.shape
+        # the encoder output's storage type: bf16 in precision mode 2 (lf_erfnet_backward reads grad_encoder as such)
+        enc_dtype = torch.bfloat16 if ctx.precision == 2 else torch.float32
         if ctx.head < 0:         # encoder-only forward: the incoming gradient is the encoder output's
             glogits = None
             if genc is None:
-                genc = torch.zeros(N, H // 8, W // 8, 128, dtype=torch.float32, device=ctx.x.device)
+                genc = torch.zeros(N, H // 8, W // 8, 128, dtype=enc_dtype, device=ctx.x.device)
         elif glogits is None:    # only the encoder output was used downstream
             glogits = torch.zeros(N, ctx.net.out_channels + ctx.head, H, W, dtype=torch.float32, device=ctx.x.device)
         if genc is not None:
-            genc = genc.contiguous()
+            genc = genc.to(enc_dtype).contiguous()
         plan, params = ctx.plan, ctx.params
         needs = ctx.needs_input_grad[6:]
         used = ctx.net._used_param_mask(ctx.head)
@@ -274,7 +276,8 @@ class _BackboneFn(torch.autograd.Function):
 
 
 class _PointwiseFn(torch.autograd.Function):
-    """``encoder.output_conv`` (Conv2d(128, K, 1)) on the NHWC encoder output -> NCHW (lf_pointwise_fwd / _bwd)."""
+    """``encoder.output_conv`` (Conv2d(128, K, 1)) on the NHWC encoder output -> NCHW fp32 (lf_pointwise_fwd / _bwd; on a bf16
+    encoder output, precision mode 2: lf_pointwise_bf16_fwd / _bwd, whose input gradient is bf16)."""
 
     @staticmethod
     def forward(ctx, enc_nhwc, weight, bias):
@@ -284,8 +287,9 @@ class _PointwiseFn(torch.autograd.Function):
         x = enc_nhwc.contiguous()
         wt = weight.detach().reshape(K, C).contiguous()
         y = torch.empty(N, K, h, w, dtype=torch.float32, device=x.device)
-        _lib.check(lib.lf_pointwise_fwd(_lib.ptr(x), _lib.ptr(wt), _lib.ptr(bias.detach().contiguous()), _lib.ptr(y), N, h, w, C, K,
-                                        _lib.stream()), "lf_pointwise_fwd")
+        fwd = lib.lf_pointwise_bf16_fwd if x.dtype == torch.bfloat16 else lib.lf_pointwise_fwd
+        _lib.check(fwd(_lib.ptr(x), _lib.ptr(wt), _lib.ptr(bias.detach().contiguous()), _lib.ptr(y), N, h, w, C, K,
+                       _lib.stream()), "lf_pointwise_fwd")
         ctx.save_for_backward(x, wt)
         ctx.wshape = weight.shape
         return y
@@ -301,8 +305,9 @@ class _PointwiseFn(torch.autograd.Function):
         gw = torch.empty_like(wt) if ctx.needs_input_grad[1] else None
         gb = torch.empty(K, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[2] else None     # independent of gw
         scratch = torch.empty(lib.lf_pointwise_scratch_floats(N, h, w, C, K), dtype=torch.float32, device=x.device)
-        _lib.check(lib.lf_pointwise_bwd(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(wt), _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb), N, h, w,
-                                        C, K, _lib.ptr(scratch), _lib.stream()), "lf_pointwise_bwd")
+        bwd = lib.lf_pointwise_bf16_bwd if x.dtype == torch.bfloat16 else lib.lf_pointwise_bwd
+        _lib.check(bwd(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(wt), _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb), N, h, w,
+                       C, K, _lib.ptr(scratch), _lib.stream()), "lf_pointwise_bwd")
         return gx, (None if gw is None else gw.view(ctx.wshape)), gb
 
 
@@ -524,8 +529,6 @@ class Net(nn.Module):
         params = self._ordered_params()
         export = self.export_encoder_output
         if only_encode:
-            if self.precision == "bf16":
-                raise NotImplementedError("only_encode reads an fp32 encoder output: use precision 'fp32' or 'fp32x9'")
             self.export_encoder_output = True
             head = -1                                 # the engine stops after the encoder: decoder BN statistics untouched
         try:
