@@ -193,6 +193,21 @@ int lf_erfnet_backward(const lf_erfnet_plan* plan, const float* img, const float
                        const float* dropmask, int training, int head, void* workspace, size_t workspace_bytes, void* stream);
 int lf_nhwc_to_nchw(const float* src, float* dst, int N, int H, int W, int C, void* stream);
 
+/* Inference engine: the eval-mode forward of ERFNet.Net (model.eval() under torch.no_grad() in validate(),
+ * Birds_Eye_View_Loss/main.py:373-388 and Backprojection_Loss/main.py:429-452, and test_model, Backprojection_Loss/test.py:35-58)
+ * with nothing a backward reads: every BatchNorm is folded into the convolution that feeds it from its running statistics, per
+ * call (one fold-and-pack launch), so a call after a training step sees the new statistics; no statistics, dropout, saved
+ * activations or partial rows.  Precision mode as set by lf_erfnet_set_precision (0, 2, 3).
+ * lf_erfnet_infer_workspace_bytes(plan, mode): its workspace for a named mode (0 for an unknown mode), about 1/20 of
+ * lf_erfnet_workspace_bytes_for at the headline size.  lf_erfnet_infer_encoder_offset: float offset of the encoder output
+ * (N,H/8,W/8,128) NHWC in it -- fp32, or bf16 elements in mode 2, the layout lf_erfnet_forward leaves -- the same in every mode.
+ * lf_erfnet_infer: arguments as lf_erfnet_forward without dropout mask and training flag; head = -1 = encoder only (logits may
+ * be NULL); the running statistics are read, never written. */
+size_t lf_erfnet_infer_workspace_bytes(const lf_erfnet_plan* plan, int mode);
+long lf_erfnet_infer_encoder_offset(const lf_erfnet_plan* plan);
+int lf_erfnet_infer(const lf_erfnet_plan* plan, const float* img, const float* const* params_host, const float* const* params_dev,
+                    float* const* running_host, int head, float* logits, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Block-level surface (round 4): a contiguous range [first, last) of the plan's layers (module order: 0 =
  * encoder.initial_block, 1..15 = encoder.layers[0..14], 16..21 = decoder.layers[0..5]) as one call, inside the plan of the
  * whole network at the matching input size -- what makes the reference's sub-modules callable on their own:

@@ -7,4 +7,15 @@ so that its own main.py can import them unchanged.
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["bev", "bp", "fit", "losses", "erfnet", "lsq", "geometry", "ops"]
+__all__ = ["bev", "bp", "fit", "losses", "erfnet", "lsq", "geometry", "ops", "use_inference_engine"]
+
+
+def use_inference_engine(module, on=True):
+    """Set ``inference_engine`` on every lanefit ERFNet inside ``module`` (the module itself, or e.g. the LSQ ``Net``'s ``.net``):
+    its eval-mode forwards under ``torch.no_grad()`` / ``torch.inference_mode()`` then run the forward-only engine
+    (``lf_erfnet_infer``).  Returns ``module``."""
+    from .erfnet import Net
+    for m in module.modules():
+        if isinstance(m, Net):
+            m.inference_engine = bool(on)
+    return module

@@ -99,6 +99,9 @@ def _declare(lib):
         "lf_erfnet_set_precision": (I, [P, I]),
         "lf_erfnet_profile": (I, [P, I]),
         "lf_erfnet_profile_read": (I, [P, P, c_char_p]),
+        "lf_erfnet_infer_workspace_bytes": (c_size_t, [P, I]),
+        "lf_erfnet_infer_encoder_offset": (L, [P]),
+        "lf_erfnet_infer": (I, [P, P, P, P, P, I, P, P, c_size_t, P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {
@@ -112,6 +115,7 @@ def _declare(lib):
         "lf_debug_conv1d_bwd_data_epi3": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P, P]),
         "lf_debug_conv1d_epi": (I, [P, P, P, P, I, I, P, P, P, P, P, P, I, I, I, I, I, I, P, P]),
         "lf_debug_conv1d_wgrad_pro": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P, P]),
+        "lf_debug_bias_residual_launches": (L, []),
     }
     for table in (sig, dbg):
         for name, (res, args) in table.items():

@@ -30,7 +30,9 @@ enum {
     LF_EPI_ADD = 4,         // v += add_src                    (residual / accumulated gradient)
     LF_EPI_STATS_SQ = 8,    // per-channel sum v, sum v^2      (BatchNorm forward statistics)
     LF_EPI_MASKBN = 16,     // v = (aux*msc+msh) > 0 ? v : 0   (ReLU backward through a recomputed BN)
-    LF_EPI_STATS_XHAT = 32  // per-channel sum v, sum v*aux (RAW: lf_bn_bwd_finalize turns the pair into sum v*xhat, xhat = aux*rstd - mean*rstd, in fp64)
+    LF_EPI_STATS_XHAT = 32, // per-channel sum v, sum v*aux (RAW: lf_bn_bwd_finalize turns the pair into sum v*xhat, xhat = aux*rstd - mean*rstd, in fp64)
+    LF_EPI_BIAS = 64        // compile-time selector only (never passed to lf_tapgemm_launch): the compiled-in epilogue keeps its bias
+                            // vector beside ADD -- the inference engine's folded residual tail relu(conv + b' + x)
 };
 
 struct LfTapArgs {
@@ -129,5 +131,26 @@ long lf_pack_bf16_elems(int Kc, int Nc, int ntaps);
 int lf_pack_weights_split_launch(const LfPackEntry* entries_dev, int nentries, const float* const* params_dev, void* arena48,
                                  hipStream_t st);
 bool lf_tapgemm_split_ok(const LfTapGeom& g);
+// launches that took a compiled-in bias + residual + ReLU epilogue since the process started (kernel-level tests)
+long lf_tapgemm_bias_residual_launches();
+
+// Inference fold-and-pack (eval-mode BatchNorm folded into the convolution that feeds it), one entry per forward convolution and
+// one per per-channel affine (the max-pool channels of a down-sampler, the stem): with s = gamma / sqrt(var + eps) in fp64,
+// packed weights w' = fl(w * s[n]), bias b' = fl((b - mean) * s + beta); an entry without gamma copies w and b; a vector-only
+// entry (pk.ntaps == 0) writes sc = fl(s), sh = fl(beta - mean * s) for its C channels.  BatchNorm channel = ch_off + n.
+struct LfFoldEntry {
+    LfPackEntry pk;         // the pack entry (dst_off / dst16_off into the INFERENCE arenas); pk.ntaps = 0: vector-only
+    int ch_off, C;          // BatchNorm channels [ch_off, ch_off + C) (C = pk.Nc for a convolution)
+    const float* gamma;     // null: no BatchNorm after this convolution
+    const float* beta;
+    const float* mean;      // running statistics
+    const float* var;
+    const float* bias;      // conv bias [Nc]
+    long out_off;           // float offset into the launch's vector region: the folded bias [Nc] (convolutions), or the per-channel
+                            // scale [C] followed by the shift [C] (vector-only entries) -- relative, so the table holds no workspace address
+};
+// arenas: fp32 [pk.dst_off], bf16 [pk.dst16_off] and split [3 * pk.dst16_off]; a null arena is not written; vec: the vector region
+int lf_fold_pack_launch(const LfFoldEntry* entries_dev, int nentries, const float* const* params_dev, float eps, float* vec, float* arena,
+                        void* arena16, void* arena48, hipStream_t st);
 int lf_pack_weights_bf16_launch(const LfPackEntry* entries_dev, int nentries, const float* const* params_dev, void* arena16,
                                 hipStream_t st);

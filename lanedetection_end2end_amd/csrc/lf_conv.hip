@@ -30,6 +30,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -145,7 +146,7 @@ __device__ __forceinline__ float sum16(float v) {
      * loads in flight at once the three-tensor epilogues (ADD + MASK + BN-backward sums) needed 270+ registers and     \
      * spilled 13-29 of them to scratch.  NOBIAS: data-gradient epilogues (compiled-in flags) carry no bias vector. */  \
     const bool stats = (epi & (LF_EPI_STATS_SQ | LF_EPI_STATS_XHAT)) != 0; \
-    constexpr bool NOBIAS = EPIC >= 0 && (EPIC & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) != 0; \
+    constexpr bool NOBIAS = EPIC >= 0 && !(EPIC & LF_EPI_BIAS) && (EPIC & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) != 0; \
     constexpr int NC = (NT % 2 == 0 && !LF_EPI_ONE_TILE) ? 2 : 1; \
     /* MASKBN + STATS_XHAT: the mask's two per-channel vectors are re-read (L1) instead of held -- 32 registers, the difference \
      * between two and three waves per SIMD for that variant */ \
@@ -986,7 +987,7 @@ __global__ __launch_bounds__(256, 2) void tapgemm_bf16_wl_kernel(const LfTapGeom
     constexpr int NT = C::NT, KS = C::KS, NSTEP = C::NSTEP, S = C::STAGES, CD = C::CD, PIXB = C::PIXB, NCH = PIXB / 16;
     constexpr bool S16 = true;
     const int epi = EPIC >= 0 ? EPIC : epi_rt;
-    constexpr bool NOBIAS = EPIC >= 0 && (EPIC & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) != 0;
+    constexpr bool NOBIAS = EPIC >= 0 && !(EPIC & LF_EPI_BIAS) && (EPIC & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) != 0;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int pl = lane & 15, kq = lane >> 4;
     const int cobw = wave * 16 * NT;                        // this wave's output channels
@@ -1354,7 +1355,7 @@ __global__ __launch_bounds__(256, (EPIC >= 0 && WvCfg<EPIC>::NBUF < 2) ? 2 : 1) 
     constexpr int NT = 4, MW = 2, R = C::R, CD = 64;
     constexpr bool S16 = true;
     const int epi = EPIC >= 0 ? EPIC : epi_rt;
-    constexpr bool NOBIAS = EPIC >= 0 && (EPIC & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) != 0;
+    constexpr bool NOBIAS = EPIC >= 0 && !(EPIC & LF_EPI_BIAS) && (EPIC & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) != 0;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int pl = lane & 15, kq = lane >> 4;
     const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl), ngroups = npix >> 4, GR = (unsigned)g.Wl >> 4;
@@ -2117,6 +2118,7 @@ __global__ __launch_bounds__(256, 4) void tapgemm_lean_kernel(const LfTapGeom g,
 }
 
 int g_split_any_size = 0;      // kernel-level tests only: let the split kernel take launches below its shipped size rule
+std::atomic<long> g_bres_launches{0};   // compiled-in bias + residual + ReLU launches (lf_tapgemm_bias_residual_launches)
 int g_bf16_lds = 4;            // tools / A-B runs only: 4 = wave-private (64 ch) / whole-line (128 ch) + 16-channel kernels where they apply, else the ring (shipped);
                                // 3 = the whole-line kernel at 64 channels too (round 5's routing); 2 = the ring
                                // for every launch it takes; 0 = the streaming bf16 kernel only
@@ -2132,6 +2134,7 @@ int pick_nt(int Cd) {
 }  // namespace
 
 void lf_tapgemm_set_split_any_size(int v) { g_split_any_size = v; }
+long lf_tapgemm_bias_residual_launches() { return g_bres_launches.load(); }
 void lf_tapgemm_set_bf16_lds(int v) { g_bf16_lds = v; }
 
 // launches the split kernel takes: whole 32-channel K-steps, 64-channel output slabs (NT = 4), whole 512-pixel
@@ -2265,8 +2268,11 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
     } while (0)
     const size_t tap_lds = LF_TAP_LDS_PER_TAP * g.ntaps;
     // the compiled-in data-gradient epilogues (mask / residual / BN-backward sums) carry no bias vector (NOBIAS): a launch
-    // that combines one of them with a bias takes the run-time-flag kernel
-    const int epis = ((epi & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) && a.bias) ? -2 : epi;
+    // that combines one of them with a bias takes the run-time-flag kernel -- except the inference engine's residual tail
+    // (bias + ADD + ReLU: BRES, compiled into the kernels the forward convolutions route to; the split kernel keeps the run-time form)
+    constexpr int BRES = LF_EPI_ADD | LF_EPI_RELU | LF_EPI_BIAS;
+    const int epis = (epi == (LF_EPI_ADD | LF_EPI_RELU) && a.bias) ? BRES
+                   : ((epi & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) && a.bias) ? -2 : epi;
     LF_REQUIRE(!a.s16 || a.wp16, "tapgemm: bf16 tensors need the bf16 matrix-core kernel (wp16)");
     if (a.split && a.wp48 && !a.wp16 && lf_tapgemm_split_ok(g)) {
         LF_REQUIRE(a.split == 9, "tapgemm: split must be 9 (got %d; the 6-term form was removed in round 6)", a.split);
@@ -2320,6 +2326,7 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
                 case LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TGL(LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
                 case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TGL(LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
                 case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_TGL(LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
+                case BRES: LF_TGL(BRES); ++g_bres_launches; break;
                 default: LF_TGL(-1); break;
             }
 #undef LF_TGL
@@ -2359,10 +2366,12 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
                 // 3's step against 115.8 us on the whole-line kernel, which takes these launches: `launched` stays false)
                 case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: break;
                 case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_TGV(LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
+                case BRES: LF_TGV(BRES); break;
                 default: LF_TGV(-1); break;
             }
 #undef LF_TGV
             if (launched) {
+                if (epis == BRES) ++g_bres_launches;
                 LF_CHECK_LAUNCH("tapgemm_bf16_wv");
                 return 0;
             }
@@ -2385,10 +2394,12 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
                 case LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TGW(LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
                 case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TGW(LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
                 case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_TGW(LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
+                case BRES: LF_TGW(BRES); break;
                 default: LF_TGW(-1); break;
             }
 #undef LF_TGW
             if (launched) {
+                if (epis == BRES) ++g_bres_launches;
                 LF_CHECK_LAUNCH("tapgemm_bf16_wl");
                 return 0;
             }
@@ -2432,21 +2443,24 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
             // compiled-in form.  Lanes kq = 2, 3 read the 16 elements BEHIND the pixel's 16 channels -- the next pixel's (or, past the
             // tensor's end, the buffer bound's zeros): finite values against the zero-padded half of the packed weights
             if (epis == 0) LF_TG16F(0); else LF_TG16F(LF_EPI_MASK | LF_EPI_STATS_XHAT);
-        } else if (nt == 3 && a.s16 && pro != LF_PRO_BNRELU && g.Cs == 16 && (epis == LF_EPI_STATS_SQ || epis == 0) &&
+        } else if (nt == 3 && a.s16 && pro != LF_PRO_BNRELU && g.Cs == 16 && (epis == LF_EPI_STATS_SQ || epis == LF_EPI_RELU || epis == 0) &&
                    (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB) {
             // ... and the 16 -> 48 channel convolution of DownsamplerBlock(16, 64) (9 taps, stride 2, BN forward sums; 112 us on the run-time-flag form)
+            // (RELU: the inference engine's folded form of the same convolution)
             if (epis == 0) hipLaunchKernelGGL((tapgemm_bf16_kernel<3, 0, 0, true>), grid, dim3(256), 0, st, g, a, pro, epi);
+            else if (epis == LF_EPI_RELU) hipLaunchKernelGGL((tapgemm_bf16_kernel<3, 0, LF_EPI_RELU, true>), grid, dim3(256), 0, st, g, a, pro, epi);
             else hipLaunchKernelGGL((tapgemm_bf16_kernel<3, 0, LF_EPI_STATS_SQ, true>), grid, dim3(256), 0, st, g, a, pro, epi);
         } else if (nt == 4 && a.s16 && pro == LF_PRO_BNRELU && epi == LF_EPI_RELU) {
             hipLaunchKernelGGL((tapgemm_bf16_kernel<4, 1, LF_EPI_RELU, false>), grid, dim3(256), 0, st, g, a, pro, epi);
         } else if (nt == 1 && a.s16 && pro != LF_PRO_BNRELU && ((g.Cs + 31) / 32 * 32 + g.s_choff <= g.s_pix) && (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB &&
-                   (epis == 0 || epis == LF_EPI_STATS_SQ || epis == LF_EPI_ADD)) {
+                   (epis == 0 || epis == LF_EPI_STATS_SQ || epis == LF_EPI_ADD || epis == LF_EPI_RELU)) {
             // 16 output channels from whole 32-channel steps (round 6: the sub-pixel phases of UpsamplerBlock(64, 16) and the data gradient
             // of DownsamplerBlock(16, 64)'s convolution: 8 launches per step on the run-time-flag form before): padding as out-of-range
             // offsets, compiled-in epilogue.  A partial last step (48 source channels) reads the pixel's next channels -- they exist:
             // the condition above -- against zero-padded weights
             if (epis == 0) hipLaunchKernelGGL((tapgemm_bf16_kernel<1, 0, 0, true>), grid, dim3(256), 0, st, g, a, pro, epi);
             else if (epis == LF_EPI_STATS_SQ) hipLaunchKernelGGL((tapgemm_bf16_kernel<1, 0, LF_EPI_STATS_SQ, true>), grid, dim3(256), 0, st, g, a, pro, epi);
+            else if (epis == LF_EPI_RELU) hipLaunchKernelGGL((tapgemm_bf16_kernel<1, 0, LF_EPI_RELU, true>), grid, dim3(256), 0, st, g, a, pro, epi);   // (inference: folded phases)
             else hipLaunchKernelGGL((tapgemm_bf16_kernel<1, 0, LF_EPI_ADD, true>), grid, dim3(256), 0, st, g, a, pro, epi);
         } else
         switch (nt) {
@@ -2480,6 +2494,7 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
                 case LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TG4(0, LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
                 case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TG4(0, LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
                 case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_TG4(0, LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
+                case BRES: LF_TG4(0, BRES); ++g_bres_launches; break;
                 default: LF_TG4(0, -1); break;
             }
             break;
@@ -2499,6 +2514,7 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
                     case LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_LEAN(0, LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
                     case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_LEAN(0, LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
                     case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_LEAN(0, LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
+                    case BRES: LF_LEAN(0, BRES); ++g_bres_launches; break;
                     default: LF_LEAN(0, -1); break;
                 }
 #undef LF_LEAN
@@ -3565,7 +3581,82 @@ __global__ __launch_bounds__(256) void pack_weights_split_kernel(const LfPackEnt
     }
 }
 
+// Inference fold-and-pack (lf_conv.h, LfFoldEntry): one workgroup row per entry, the three operand orders of the pack kernels
+// above, every weight scaled by its output channel's BatchNorm factor in fp64 and rounded once to fp32 (the bf16 / split forms are
+// taken from that fp32 value, as the training packs take theirs from the fp32 parameter).  Row y = 0 also writes the entry's
+// per-channel vectors.
+__device__ __forceinline__ double fold_scale(const LfFoldEntry& f, int n, float eps) {
+    if (!f.gamma) return 1.0;
+    const int c = f.ch_off + n;
+    return (double)f.gamma[c] / sqrt((double)f.var[c] + (double)eps);
+}
+__device__ __forceinline__ float fold_w(const LfFoldEntry& f, const float* w, int k, int n, int t, float eps) {
+    const float v = w[(long)k * f.pk.sk + (long)n * f.pk.sn + f.pk.tapidx[t]];
+    return f.gamma ? (float)((double)v * fold_scale(f, n, eps)) : v;
+}
+__global__ __launch_bounds__(256) void fold_pack_kernel(const LfFoldEntry* __restrict__ entries, const float* const* __restrict__ params,
+                                                       float eps, float* __restrict__ vec, float* __restrict__ arena, __bf16* __restrict__ arena16,
+                                                       __bf16* __restrict__ arena48) {
+    const LfFoldEntry f = entries[blockIdx.x];
+    const LfPackEntry& e = f.pk;
+    if (blockIdx.y == 0) {
+        for (int n = threadIdx.x; n < f.C; n += 256) {
+            const double s = fold_scale(f, n, eps);
+            const int c = f.ch_off + n;
+            float* out = vec + f.out_off;
+            if (e.ntaps > 0) {
+                out[n] = f.gamma ? (float)(((double)f.bias[n] - (double)f.mean[c]) * s + (double)f.beta[c]) : f.bias[n];
+            } else {
+                out[n] = (float)s;
+                out[f.C + n] = (float)((double)f.beta[c] - (double)f.mean[c] * s);
+            }
+        }
+    }
+    if (e.ntaps == 0) return;
+    const float* w = params[e.param];
+    const unsigned Nc = (unsigned)e.Nc;
+    if (arena) {            // [tap][Kc/4][Nc][4] (pack_weights_kernel)
+        float* dst = arena + e.dst_off;
+        const unsigned total = (unsigned)(e.ntaps * e.Kc * e.Nc), kbn = (unsigned)(e.Kc >> 2);
+        for (unsigned i = blockIdx.y * 256u + threadIdx.x; i < total; i += gridDim.y * 256u) {
+            const unsigned k4 = i & 3u, r = i >> 2, r2 = r / Nc, n = r - r2 * Nc, t = r2 / kbn, kb = r2 - t * kbn;
+            dst[i] = fold_w(f, w, (int)(kb * 4u + k4), (int)n, (int)t, eps);
+        }
+    }
+    if (arena16) {          // [tap][ceil(Kc/32)*4][Nc][8], zero beyond Kc (pack_weights_bf16_kernel)
+        __bf16* dst = arena16 + e.dst16_off;
+        const unsigned kbn = (unsigned)(((e.Kc + 31) >> 5) * 4), total = (unsigned)e.ntaps * kbn * Nc * 8u;
+        for (unsigned i = blockIdx.y * 256u + threadIdx.x; i < total; i += gridDim.y * 256u) {
+            const unsigned k8 = i & 7u, r = i >> 3, r2 = r / Nc, n = r - r2 * Nc, t = r2 / kbn, kb = r2 - t * kbn;
+            const int k = (int)(kb * 8u + k8);
+            dst[i] = (__bf16)(k < e.Kc ? fold_w(f, w, k, (int)n, (int)t, eps) : 0.f);
+        }
+    }
+    if (arena48 && e.Kc % 32 == 0) {     // [tap][Kc/8][Nc][3][8], exact 3-way split (pack_weights_split_kernel)
+        __bf16* dst = arena48 + 3 * e.dst16_off;
+        const unsigned kbn = (unsigned)(e.Kc >> 3), total = (unsigned)e.ntaps * kbn * Nc * 8u;
+        for (unsigned i = blockIdx.y * 256u + threadIdx.x; i < total; i += gridDim.y * 256u) {
+            const unsigned k8 = i & 7u, row = i >> 3, r2 = row / Nc, n = row - r2 * Nc, t = r2 / kbn, kb = r2 - t * kbn;
+            const float v = fold_w(f, w, (int)(kb * 8u + k8), (int)n, (int)t, eps);
+            const __bf16 vh = (__bf16)v;
+            const float r1 = v - (float)vh;
+            const __bf16 vm = (__bf16)r1;
+            dst[row * 24u + k8] = vh; dst[row * 24u + 8u + k8] = vm; dst[row * 24u + 16u + k8] = (__bf16)(r1 - (float)vm);
+        }
+    }
+}
+
 }  // namespace
+
+int lf_fold_pack_launch(const LfFoldEntry* entries_dev, int nentries, const float* const* params_dev, float eps, float* vec, float* arena,
+                        void* arena16, void* arena48, hipStream_t st) {
+    if (nentries <= 0) return 0;
+    LF_REQUIRE(vec, "fold_pack: null vector region");
+    hipLaunchKernelGGL(fold_pack_kernel, dim3(nentries, 16), dim3(256), 0, st, entries_dev, params_dev, eps, vec, arena,
+                       reinterpret_cast<__bf16*>(arena16), reinterpret_cast<__bf16*>(arena48));
+    LF_CHECK_LAUNCH("fold_pack");
+    return 0;
+}
 
 int lf_wgrad_reduce_launch(const float* partial, int splits, int ntaps, int Cs, int Cd, float* grad, long sk, long sn,
                            const int* tapidx_host, const float* bias_rows, int n_bias_rows, float* bias_grad,

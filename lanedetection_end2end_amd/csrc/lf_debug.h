@@ -42,6 +42,9 @@ int lf_debug_conv1d_bwd_data_epi3(const float* gy, const float* w, const float* 
 int lf_debug_conv1d_epi(const float* src, const float* w, const float* bias, float* dst, int transposed, int epi, const float* mask_src,
                         const float* add_src, const float* aux, const float* msc, const float* msh, float* stats, int N, int H, int W, int C,
                         int axis, int dilation, float* scratch, void* stream);
+/* tap-GEMM launches that took a compiled-in bias + residual + ReLU epilogue (the inference engine's block tail) since the process
+ * started: which kernel form a launch selected (tests/test_infer_gpu.py) */
+long lf_debug_bias_residual_launches(void);
 int lf_debug_conv1d_wgrad_phases(const float* x, const float* gy, int N, int H, int W, int C, int axis, int dilation,
                                  float* scratch, unsigned long long* dbg, void* stream);
 #ifdef __cplusplus

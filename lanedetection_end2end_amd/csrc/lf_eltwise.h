@@ -52,6 +52,9 @@ int lf_bn_bwd_apply(const float* g, const float* y, const float* t, const float*
 int lf_pool_rows(long npix_out);
 int lf_pool_concat_fwd(const float* x, int N, int H, int W, int Cin, float* cat, int cat_pix, int choff, float* rows, int ld,
                        int s16, hipStream_t st);
+// inference form: cat[..., choff:choff+Cin] = relu(maxpool2x2(x) * sc + sh) (sc / sh: Cin channels), no statistics
+int lf_pool_affine_fwd(const float* x, int N, int H, int W, int Cin, float* cat, int cat_pix, int choff, const float* sc,
+                       const float* sh, int s16, hipStream_t st);
 int lf_pool_bwd(const float* x, const float* gcat, int N, int H, int W, int Cin, int cat_pix, int choff, float* gx,
                 int s16, hipStream_t st);
 
@@ -59,6 +62,9 @@ int lf_pool_bwd(const float* x, const float* gcat, int N, int H, int W, int Cin,
 int lf_stem_rows(int N, int H, int W);
 int lf_stem_fwd(const float* img, int N, int Cin, int H, int W, const float* w, const float* b, float* cat, float* rows, int ld,
                 int s16, hipStream_t st);
+// inference form: relu(v * sc + sh) per channel of the concat buffer (eval-mode BatchNorm + ReLU in the epilogue), no statistics
+int lf_stem_fwd_infer(const float* img, int N, int Cin, int H, int W, const float* w, const float* b, const float* sc, const float* sh,
+                      float* cat, int s16, hipStream_t st);
 int lf_stem_wgrad_rows(int N, int H, int W);
 int lf_stem_wgrad(const float* img, const float* gcat, int N, int Cin, int H, int W, float* wrows, float* brows,
                   int s16, hipStream_t st);

@@ -327,6 +327,36 @@ __global__ __launch_bounds__(256) void pool_concat_fwd_kernel(const T* __restric
     }
 }
 
+// inference form: cat[..., choff + c] = relu(maxpool2x2(x)[c] * sc[c] + sh[c]) (the block's eval-mode BatchNorm + ReLU, after the
+// max: a negative scale stays correct), no statistics rows
+template <typename T, int NQ>
+__global__ __launch_bounds__(256) void pool_affine_fwd_kernel(const T* __restrict__ x, int N, int H, int W, int U, T* __restrict__ cat,
+                                                             int cat_pix, int choff, const float* __restrict__ sc,
+                                                             const float* __restrict__ sh, long units) {
+    constexpr int V = 4 * NQ;
+    const int C = U * V, Ho = H / 2, Wo = W / 2;
+    for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < units; u += (long)gridDim.x * 256) {
+        const int c = (int)(u % U) * V;
+        const long p = u / U;
+        const int ow = (int)(p % Wo);
+        const long r = p / Wo;
+        const int oh = (int)(r % Ho), n = (int)(r / Ho);
+        const T* b = x + (((long)n * H + 2 * oh) * W + 2 * ow) * C + c;
+        f32x4 v[NQ], u1[NQ], u2[NQ], u3[NQ];
+        lf_ldq<T, NQ>(b, v);
+        lf_ldq<T, NQ>(b + C, u1);
+        lf_ldq<T, NQ>(b + (long)W * C, u2);
+        lf_ldq<T, NQ>(b + (long)W * C + C, u3);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[q][e] = fmaxf(fmaxf(fmaxf(v[q][e], u1[q][e]), u2[q][e]), u3[q][e]);
+            v[q] = relu4(v[q] * ld4(sc + c + 4 * q) + ld4(sh + c + 4 * q));
+        }
+        lf_stq<T, NQ>(cat + p * cat_pix + choff + c, v);
+    }
+}
+
 template <typename T, int NQ>
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const T* __restrict__ x, const T* __restrict__ gcat, int N,
                                                       int H, int W, int U, int cat_pix, int choff, T* __restrict__ gx) {
@@ -547,6 +577,22 @@ int lf_pool_concat_fwd(const float* x, int N, int H, int W, int Cin, float* cat,
         hipLaunchKernelGGL((pool_concat_fwd_kernel<lf_bf16, 1>), grid, dim3(256), 0, st, as<lf_bf16>(x), N, H, W, Cin / V, as<lf_bf16>(cat), cat_pix, choff, rows, ld),
         hipLaunchKernelGGL((pool_concat_fwd_kernel<float, 1>), grid, dim3(256), 0, st, x, N, H, W, Cin / V, cat, cat_pix, choff, rows, ld));
     LF_CHECK_LAUNCH("pool_concat_fwd");
+    return 0;
+}
+
+int lf_pool_affine_fwd(const float* x, int N, int H, int W, int Cin, float* cat, int cat_pix, int choff, const float* sc,
+                       const float* sh, int s16, hipStream_t st) {
+    LF_REQUIRE(quad_ok(Cin) && H % 2 == 0 && W % 2 == 0 && sc && sh, "pool_affine: unsupported shape");
+    const long npo = (long)N * (H / 2) * (W / 2);
+    const bool oct = oct_ok(s16, Cin) && cat_pix % 8 == 0 && choff % 8 == 0;
+    const int V = oct ? 8 : 4;
+    const long units = npo * (Cin / V);
+    const dim3 grid(grid_for(units, LF_STREAM_BLOCKS));
+    LF_BY_STORAGE3(s16, oct,
+        hipLaunchKernelGGL((pool_affine_fwd_kernel<lf_bf16, 2>), grid, dim3(256), 0, st, as<lf_bf16>(x), N, H, W, Cin / V, as<lf_bf16>(cat), cat_pix, choff, sc, sh, units),
+        hipLaunchKernelGGL((pool_affine_fwd_kernel<lf_bf16, 1>), grid, dim3(256), 0, st, as<lf_bf16>(x), N, H, W, Cin / V, as<lf_bf16>(cat), cat_pix, choff, sc, sh, units),
+        hipLaunchKernelGGL((pool_affine_fwd_kernel<float, 1>), grid, dim3(256), 0, st, x, N, H, W, Cin / V, cat, cat_pix, choff, sc, sh, units));
+    LF_CHECK_LAUNCH("pool_affine_fwd");
     return 0;
 }
 

@@ -47,6 +47,14 @@ struct Layer {
     long b[5];                   // down: cat,y | nb: t1,t2,t3,t4,out | up: c,y
     ConvRef cv[4];
     BNRef bn[2];
+    int fi[4];                   // inference engine: fold entries of the forward convolutions (up-samplers: the four phases)
+    int fv;                      //   ... and of the per-channel affine (stem: all 16 channels; down-sampler: the pooled ones), -1 none
+};
+// where an inference fold entry takes its inputs from (the pointers of LfFoldEntry are filled per call)
+struct FoldSrc {
+    int p_g, p_b, bn;            // BatchNorm parameters / running-statistics index (-1: no BatchNorm)
+    int p_bias;                  // conv bias parameter (-1: vector-only entry)
+    long out_off;                // float offset of the folded bias (or of sc, sh = out_off + C) in the vector region
 };
 
 }  // namespace
@@ -78,6 +86,14 @@ struct lf_erfnet_plan {
     struct ProfRec { hipEvent_t a, b; int family; double flops; int layer; int Cs, Cd, ntaps; long npix; int epi; };
     mutable int prof_layer = -1;
     mutable std::vector<ProfRec> prof;
+    // inference engine (lf_erfnet_infer): forward-only fold table, its own compact arenas and per-channel vectors
+    std::vector<LfFoldEntry> fold;
+    std::vector<FoldSrc> fold_src;
+    long infer_packed_floats = 0, infer_packed16_elems = 0, infer_vec_floats = 0;
+    long infer_enc_floats = 0;
+    mutable std::vector<LfFoldEntry> fold_call;  // the table with this call's parameter pointers (rebuilt when one of them moved; it
+                                                 // holds no workspace address: outputs are offsets into the vector region)
+    mutable std::vector<const void*> fold_key;
 };
 
 namespace {
@@ -190,6 +206,71 @@ void account_wgrad(lf_erfnet_plan* P, const LfTapGeom& g) {
     }
 }
 long wpart_all_end(const lf_erfnet_plan* P, int s16) { return P->off_wpart_all + P->wpart_all_floats[s16] + P->bpart_all_floats[s16]; }
+
+// ---- inference engine: the fold table (one entry per forward convolution, one per per-channel affine), laid out once per plan
+int add_fold(lf_erfnet_plan* P, int pack, int p_bias, const BNRef* bn, int ch_off, int C) {
+    LfFoldEntry f;
+    memset(&f, 0, sizeof(f));
+    if (pack >= 0) {
+        f.pk = P->packs[pack];
+        f.pk.dst_off = P->infer_packed_floats;
+        P->infer_packed_floats += (long)f.pk.ntaps * f.pk.Kc * f.pk.Nc;
+        f.pk.dst16_off = P->infer_packed16_elems;
+        P->infer_packed16_elems += lf_pack_bf16_elems(f.pk.Kc, f.pk.Nc, f.pk.ntaps);
+    }
+    f.ch_off = ch_off; f.C = C;
+    FoldSrc src;
+    src.p_g = bn ? bn->p_g : -1; src.p_b = bn ? bn->p_b : -1; src.bn = bn ? bn->idx : -1;
+    src.p_bias = pack >= 0 ? p_bias : -1;
+    src.out_off = P->infer_vec_floats;
+    f.out_off = src.out_off;
+    P->infer_vec_floats += ((pack >= 0 ? C : 2 * C) + 63) / 64 * 64;      // 256-byte aligned vectors
+    P->fold.push_back(f);
+    P->fold_src.push_back(src);
+    return (int)P->fold.size() - 1;
+}
+
+void build_infer(lf_erfnet_plan* P) {
+    for (Layer& L : P->layers) {
+        for (int i = 0; i < 4; ++i) L.fi[i] = -1;
+        L.fv = -1;
+        if (L.kind == K_DOWN && L.x < 0) {
+            L.fv = add_fold(P, -1, -1, &L.bn[0], 0, L.Cout);                      // stem: conv and pooled channels, in-kernel
+        } else if (L.kind == K_DOWN) {
+            const int Cc = L.Cout - L.Cin;
+            L.fi[0] = add_fold(P, L.cv[0].fwd.pack, L.cv[0].p_b, &L.bn[0], 0, Cc);  // conv channels [0, Cc)
+            L.fv = add_fold(P, -1, -1, &L.bn[0], Cc, L.Cin);                        // pooled channels [Cc, Cout)
+        } else if (L.kind == K_NB) {
+            for (int i = 0; i < 4; ++i)                                            // bn1 after conv1x3_1, bn2 after conv1x3_2
+                L.fi[i] = add_fold(P, L.cv[i].fwd.pack, L.cv[i].p_b, i == 1 ? &L.bn[0] : i == 3 ? &L.bn[1] : nullptr, 0, L.Cout);
+        } else {
+            for (int ph = 0; ph < 4; ++ph) L.fi[ph] = add_fold(P, L.cv[0].fph[ph].pack, L.cv[0].p_b, &L.bn[0], 0, L.Cout);
+        }
+    }
+    for (const Layer& L : P->layers)
+        if (L.kind == K_UP) { P->infer_enc_floats = (long)P->N * L.Hin * L.Win * L.Cin; break; }
+}
+
+// byte layout of the inference workspace in a precision mode: the encoder output first (offset 0 in every mode), three activation
+// buffers of the largest layer (a block's input stays live for its residual), the fold table, the folded vectors, the arenas the
+// mode's kernels read (fp32: fp32; bf16: bf16; fp32x9: split + the fp32 copy its fall-back launches take)
+struct InferLayout { long enc, buf[3], table, vec, a32, a16, a48, total; };
+InferLayout infer_layout(const lf_erfnet_plan* P, int mode) {
+    auto al = [](long b) { return (b + 255) / 256 * 256; };
+    const long esz = mode == 2 ? 2 : 4;
+    InferLayout L;
+    long cur = 0;
+    L.enc = cur; cur += al(P->infer_enc_floats * esz);
+    for (int i = 0; i < 3; ++i) { L.buf[i] = cur; cur += al(P->gbuf_floats * esz); }
+    L.table = cur; cur += al((long)(P->fold.size() * sizeof(LfFoldEntry)));
+    L.vec = cur; cur += al(P->infer_vec_floats * 4);
+    L.a32 = L.a16 = L.a48 = -1;
+    if (mode != 2) { L.a32 = cur; cur += al(P->infer_packed_floats * 4); }
+    if (mode == 2) { L.a16 = cur; cur += al(P->infer_packed16_elems * 2); }
+    if (mode == 3) { L.a48 = cur; cur += al(3 * P->infer_packed16_elems * 2); }
+    L.total = cur;
+    return L;
+}
 
 }  // namespace
 
@@ -317,6 +398,7 @@ lf_erfnet_plan* lf_erfnet_plan_create(int N, int H, int W, int in_channels, int 
     P->off_gC = ws.take(P->gbuf_floats);
     P->off_wpart_all = ws.cur;                                  // last: its size follows the precision mode
     P->total_floats = wpart_all_end(P, 1);                      // (the larger of the two)
+    build_infer(P);
     return P;
 }
 
@@ -1065,6 +1147,148 @@ int lf_erfnet_backward_range(const lf_erfnet_plan* P, int first, int last, int h
     const Layer& Lf = P->layers[first];
     if (gx && first > 0) LF_TRY(nhwc_to_nchw(gin, gx, P->N, Lf.Hin, Lf.Win, Lf.Cin, c.s16, c.st));
     return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// Inference engine: the eval-mode forward (Net.forward under model.eval() and torch.no_grad(): validate() in
+// Birds_Eye_View_Loss/main.py:373-388 and Backprojection_Loss/main.py:429-452, test_model in Backprojection_Loss/test.py:35-58)
+// without anything a backward reads.  BatchNorm uses its running statistics, so bn(conv(x)) is a convolution with other weights
+// and bias: ONE fold-and-pack launch per call folds every BatchNorm into the convolution that feeds it (the running statistics
+// change after every training step: nothing is cached across calls), the stem and the max-pool branches apply the affine + ReLU
+// in-kernel, and a block's tail relu(bn2(conv1x3_2(v)) + x) is one tap-GEMM launch with a compiled-in bias + residual + ReLU
+// epilogue.  Per non_bottleneck_1d 4 launches, per down-sampler 2 (the stem 1), per up-sampler its 4 phases; no statistics, no
+// dropout, no saved activations: three ping-pong buffers of the largest layer and the encoder output.
+// ---------------------------------------------------------------------------------------
+namespace {
+
+int infer_fold_table(const lf_erfnet_plan* P, char* ws, const InferLayout& L, const float* const* params_host,
+                     float* const* running_host, hipStream_t st) {
+    std::vector<const void*> key;
+    key.reserve(P->n_params + 2 * P->n_bn);
+    for (int i = 0; i < P->n_params; ++i) key.push_back(params_host[i]);
+    for (int i = 0; i < 2 * P->n_bn; ++i) key.push_back(running_host[i]);
+    if (key != P->fold_key) {
+        // (the table is uploaded from this vector: let an earlier upload of it finish before it is rewritten)
+        if (!P->fold_key.empty() && hipStreamSynchronize(st) != hipSuccess) return lf_fail("lf_erfnet_infer: stream synchronisation failed");
+        P->fold_call = P->fold;
+        for (size_t i = 0; i < P->fold.size(); ++i) {
+            LfFoldEntry& f = P->fold_call[i];
+            const FoldSrc& s = P->fold_src[i];
+            if (s.bn >= 0) {
+                f.gamma = params_host[s.p_g]; f.beta = params_host[s.p_b];
+                f.mean = running_host[2 * s.bn]; f.var = running_host[2 * s.bn + 1];
+            }
+            if (s.p_bias >= 0) f.bias = params_host[s.p_bias];
+        }
+        P->fold_key = key;
+    }
+    if (hipMemcpyAsync(ws + L.table, P->fold_call.data(), P->fold_call.size() * sizeof(LfFoldEntry), hipMemcpyHostToDevice, st) != hipSuccess)
+        return lf_fail("lf_erfnet_infer: upload of the fold table failed");
+    return 0;
+}
+
+struct InferCtx {
+    const lf_erfnet_plan* P;
+    char* ws;
+    InferLayout L;
+    int mode, s16;
+    hipStream_t st;
+    float* vec(int fi, int which = 0) const {     // folded bias (which = 0) / scale (0) and shift (1) of a vector-only entry
+        return reinterpret_cast<float*>(ws + L.vec) + P->fold_src[fi].out_off + (which ? P->fold[fi].C : 0);
+    }
+};
+
+int infer_gemm(const InferCtx& c, const GemmOp& op, int fi, const float* src, float* dst, int epi, const float* add) {
+    const LfPackEntry& e = c.P->fold[fi].pk;
+    LfTapArgs a = lf_no_args();
+    a.src = src; a.dst = dst; a.bias = c.vec(fi); a.add_src = add; a.s16 = c.s16;
+    if (c.L.a32 >= 0) a.wp = reinterpret_cast<const float*>(c.ws + c.L.a32) + e.dst_off;
+    if (c.L.a16 >= 0) a.wp16 = reinterpret_cast<const unsigned short*>(c.ws + c.L.a16) + e.dst16_off;
+    if (c.L.a48 >= 0) {
+        a.split = 9;
+        a.wp48 = reinterpret_cast<const unsigned short*>(c.ws + c.L.a48) + 3 * e.dst16_off;
+    }
+    return lf_tapgemm_launch(op.geom, a, LF_PRO_NONE, epi, c.st);
+}
+
+// layers [0, nlayers); the last encoder layer writes the encoder-output region; *out = the last layer's output
+int forward_infer(const InferCtx& c, const float* img, const float* const* params_host, int nlayers, float** out) {
+    const lf_erfnet_plan* P = c.P;
+    const int N = P->N, ne = encoder_layers(P);
+    float* bufs[3];
+    for (int i = 0; i < 3; ++i) bufs[i] = reinterpret_cast<float*>(c.ws + c.L.buf[i]);
+    float* enc = reinterpret_cast<float*>(c.ws + c.L.enc);
+    auto other = [&](const float* u, const float* v) {
+        for (float* b : bufs) if (b != u && b != v) return b;
+        return bufs[0];
+    };
+    float* x = nullptr;
+    for (int li = 0; li < nlayers; ++li) {
+        const Layer& L = P->layers[li];
+        if (L.kind == K_DOWN && L.x < 0) {
+            float* y = bufs[0];
+            LF_TRY(lf_stem_fwd_infer(img, N, L.Cin, L.Hin, L.Win, params_host[L.cv[0].p_w], params_host[L.cv[0].p_b], c.vec(L.fv, 0),
+                                     c.vec(L.fv, 1), y, c.s16, c.st));
+            x = y;
+        } else if (L.kind == K_DOWN) {
+            float* y = li == ne - 1 ? enc : other(x, nullptr);
+            LF_TRY(infer_gemm(c, L.cv[0].fwd, L.fi[0], x, y, LF_EPI_RELU, nullptr));
+            LF_TRY(lf_pool_affine_fwd(x, N, L.Hin, L.Win, L.Cin, y, L.Cout, L.Cout - L.Cin, c.vec(L.fv, 0), c.vec(L.fv, 1), c.s16, c.st));
+            x = y;
+        } else if (L.kind == K_NB) {
+            float* t1 = other(x, nullptr);
+            float* t2 = other(x, t1);
+            float* y = li == ne - 1 ? enc : t2;
+            LF_TRY(infer_gemm(c, L.cv[0].fwd, L.fi[0], x, t1, LF_EPI_RELU, nullptr));
+            LF_TRY(infer_gemm(c, L.cv[1].fwd, L.fi[1], t1, t2, LF_EPI_RELU, nullptr));      // folded bn1
+            LF_TRY(infer_gemm(c, L.cv[2].fwd, L.fi[2], t2, t1, LF_EPI_RELU, nullptr));
+            LF_TRY(infer_gemm(c, L.cv[3].fwd, L.fi[3], t1, y, LF_EPI_ADD | LF_EPI_RELU, x));     // folded bn2 + residual
+            x = y;
+        } else {
+            float* y = other(x, nullptr);
+            for (int ph = 0; ph < 4; ++ph) LF_TRY(infer_gemm(c, L.cv[0].fph[ph], L.fi[ph], x, y, LF_EPI_RELU, nullptr));
+            x = y;
+        }
+    }
+    *out = x;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Bytes of the inference workspace in a precision mode (0 fp32, 2 bf16, 3 fp32x9); 0 for an unknown mode.  About 1/20 of the
+// training workspace at the headline size: no saved activations, statistics or partial rows.
+size_t lf_erfnet_infer_workspace_bytes(const lf_erfnet_plan* P, int mode) {
+    if (!P || !(mode == 0 || mode == 2 || mode == 3)) return 0;
+    return (size_t)infer_layout(P, mode).total;
+}
+// float offset of the encoder output (N, H/8, W/8, 128) NHWC -- fp32, or bf16 elements in mode 2 -- in the inference workspace
+long lf_erfnet_infer_encoder_offset(const lf_erfnet_plan* P) { return P ? infer_layout(P, 0).enc / 4 : -1; }
+
+// Eval-mode forward (running statistics, no dropout) in the plan's precision mode (lf_erfnet_set_precision): the same results as
+// lf_erfnet_forward(training = 0) to rounding, nothing written that a backward could read.  Arguments as lf_erfnet_forward, minus
+// the dropout mask; head = -1: encoder only (logits may be NULL).  Running statistics are read, never written.
+int lf_erfnet_infer(const lf_erfnet_plan* P, const float* img, const float* const* params_host, const float* const* params_dev,
+                    float* const* running_host, int head, float* logits, void* workspace, size_t workspace_bytes, void* stream) {
+    LF_REQUIRE(P && img && params_host && params_dev && running_host && (logits || head < 0) && workspace, "lf_erfnet_infer: null pointer");
+    LF_REQUIRE(head >= -1 && head < P->n_heads, "lf_erfnet_infer: head %d out of range", head);
+    InferCtx c;
+    c.P = P; c.ws = (char*)workspace; c.mode = P->precision; c.s16 = P->precision == 2; c.st = (hipStream_t)stream;
+    c.L = infer_layout(P, c.mode);
+    LF_REQUIRE(workspace_bytes >= (size_t)c.L.total, "lf_erfnet_infer: workspace too small (%zu < %ld)", workspace_bytes, c.L.total);
+    LF_TRY(infer_fold_table(P, c.ws, c.L, (const float* const*)params_host, running_host, c.st));
+    LF_TRY(lf_fold_pack_launch(reinterpret_cast<const LfFoldEntry*>(c.ws + c.L.table), (int)P->fold.size(), params_dev, BN_EPS,
+                               reinterpret_cast<float*>(c.ws + c.L.vec), c.L.a32 >= 0 ? reinterpret_cast<float*>(c.ws + c.L.a32) : nullptr,
+                               c.L.a16 >= 0 ? c.ws + c.L.a16 : nullptr, c.L.a48 >= 0 ? c.ws + c.L.a48 : nullptr, c.st));
+    float* last = nullptr;
+    if (head < 0) return forward_infer(c, img, params_host, encoder_layers(P), &last);
+    LF_TRY(forward_infer(c, img, params_host, (int)P->layers.size(), &last));
+    return lf_head_fwd(last, params_host[P->p_head_w[head]], params_host[P->p_head_b[head]], logits, P->N, P->H / 2, P->W / 2,
+                       P->Cout + head, c.s16, c.st);
 }
 
 }  // extern "C"

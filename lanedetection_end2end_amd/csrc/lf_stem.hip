@@ -40,9 +40,12 @@ __device__ __forceinline__ float row_sum(float v) {
 // A lane ends with channels 4 (l >> 4) .. + 3 of its pixel: one 16-byte store, 1 KB contiguous per instruction.  The pooled
 // channels (Cc ..15: max over the 2x2 window of input channel co - Cc) take the place of the accumulator's padding rows.
 // Workgroup = 256 pixels (one BatchNorm partial row, as before).
-template <int CIN, typename T>
+// AFF (the inference engine): the eval-mode BatchNorm + ReLU of the block in the epilogue, relu(v * sc + sh) per channel -- after the
+// max for the pooled channels, so a negative scale stays correct -- and no statistics rows.
+template <int CIN, typename T, bool AFF = false>
 __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__ img, int N, int H, int W, const float* __restrict__ w,
-                                                      const float* __restrict__ b, T* __restrict__ cat, float* __restrict__ rows, int ld) {
+                                                      const float* __restrict__ b, T* __restrict__ cat, float* __restrict__ rows, int ld,
+                                                      const float* __restrict__ sc = nullptr, const float* __restrict__ sh = nullptr) {
     constexpr int Cc = 16 - CIN, KK = 9 * CIN, KS = (KK + 3) / 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, pl = lane & 15, kq = lane >> 4;
     const int Ho = H / 2, Wo = W / 2;
@@ -59,9 +62,12 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__
         toff[s] = ci * H * W + (kh - 1) * W + (kw - 1);
         tkh[s] = kh; tkw[s] = kw;
     }
-    float bv[4];
+    float bv[4], av[4], cv[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) bv[e] = 4 * kq + e < Cc ? b[4 * kq + e] : 0.f;
+    for (int e = 0; e < 4; ++e) {
+        bv[e] = 4 * kq + e < Cc ? b[4 * kq + e] : 0.f;
+        if constexpr (AFF) { av[e] = sc[4 * kq + e]; cv[e] = sh[4 * kq + e]; }
+    }
     f32x4 s1 = zero4(), s2 = zero4();
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
@@ -95,12 +101,14 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__
             float pooled = 0.f;
             if (e >= 4 - CIN) pooled = __shfl(pm, (e - (4 - CIN)) * 16 + pl, 64);      // (compile-time e: CIN permutes, every lane takes part)
             out[e] = co < Cc ? acc[e] + bv[e] : pooled;
+            if constexpr (AFF) out[e] = fmaxf(out[e] * av[e] + cv[e], 0.f);
         }
         if (valid) lf_stv(cat + (size_t)p * 16 + 4 * kq, out);
+        if (AFF) continue;
         if (!valid) out = zero4();
         s1 += out; s2 += out * out;
     }
-    if (rows) {
+    if (!AFF && rows) {
         __shared__ float red[4][2][16];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -280,6 +288,24 @@ int lf_stem_fwd(const float* img, int N, int Cin, int H, int W, const float* w, 
     switch (Cin) { case 1: LF_STEM(1); break; case 2: LF_STEM(2); break; case 3: LF_STEM(3); break; default: LF_STEM(4); break; }
 #undef LF_STEM
     LF_CHECK_LAUNCH("stem_fwd");
+    return 0;
+}
+
+int lf_stem_fwd_infer(const float* img, int N, int Cin, int H, int W, const float* w, const float* b, const float* sc, const float* sh,
+                      float* cat, int s16, hipStream_t st) {
+    LF_REQUIRE(Cin >= 1 && Cin <= 4, "stem: in_channels %d not in 1..4", Cin);
+    LF_REQUIRE(H % 2 == 0 && W % 2 == 0, "stem: odd image size");
+    LF_REQUIRE((long)N * Cin * H * W * 4 < (long)OOB, "stem: image too large for 32-bit byte offsets");
+    LF_REQUIRE(sc && sh, "stem_fwd_infer: null scale / shift");
+    const dim3 grid(lf_stem_rows(N, H, W));
+#define LF_STEM(CI)                                                                                                                  \
+    do {                                                                                                                             \
+        if (s16) hipLaunchKernelGGL((stem_fwd_kernel<CI, lf_bf16, true>), grid, dim3(256), 0, st, img, N, H, W, w, b, as<lf_bf16>(cat), nullptr, 0, sc, sh); \
+        else hipLaunchKernelGGL((stem_fwd_kernel<CI, float, true>), grid, dim3(256), 0, st, img, N, H, W, w, b, cat, nullptr, 0, sc, sh); \
+    } while (0)
+    switch (Cin) { case 1: LF_STEM(1); break; case 2: LF_STEM(2); break; case 3: LF_STEM(3); break; default: LF_STEM(4); break; }
+#undef LF_STEM
+    LF_CHECK_LAUNCH("stem_fwd_infer");
     return 0;
 }
 

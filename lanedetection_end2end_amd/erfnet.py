@@ -9,6 +9,7 @@ called.  One ``torch.autograd.Function`` spans the whole backbone: its forward a
 are single C-ABI calls (``lf_erfnet_forward`` / ``lf_erfnet_backward``).
 """
 import ctypes
+import os
 
 import torch
 import torch.nn as nn
@@ -397,6 +398,9 @@ class Net(nn.Module):
         # encoder_output (N,128,H/8,W/8) is part of the return tuple (zero-copy view); wrappers that never read it
         # may switch it off
         self.export_encoder_output = True
+        # forward-only engine for eval mode under no_grad / inference_mode (lf_erfnet_infer: BatchNorm folded into the convolutions,
+        # no training workspace): opt-in, or LANEFIT_INFERENCE_ENGINE=1 when the Net is built (the reference's unmodified scripts)
+        self.inference_engine = os.environ.get("LANEFIT_INFERENCE_ENGINE", "") == "1"
         self._bind_blocks()
 
     def _blocks(self):
@@ -514,6 +518,36 @@ class Net(nn.Module):
         u = torch.rand(plan.drop_floats, dtype=torch.float32, device=device)
         return torch.where(u >= pvec, scale, zero)      # (three launches per step, not five; p = 1 gives 0, not 0 * inf)
 
+    def _infer(self, plan, x, head):
+        """Eval-mode forward on the inference engine (lf_erfnet_infer): the same (logits, NHWC encoder output) as _BackboneFn
+        returns, nothing saved for a backward.  The encoder output is a view of the call's own (small) workspace."""
+        lib = _lib.load()
+        N, H, W = plan.shape
+        dev = x.device
+        mode = _PRECISIONS[self.precision]
+        _lib.check(lib.lf_erfnet_set_precision(plan.handle, mode), "lf_erfnet_set_precision")
+        nbytes = lib.lf_erfnet_infer_workspace_bytes(plan.handle, mode)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        logits = (torch.empty(N, self.out_channels + head, H, W, dtype=torch.float32, device=dev) if head >= 0 else
+                  torch.empty(0, dtype=torch.float32, device=dev))
+        params = [p.detach() for p in self._ordered_params()]
+        for p in params:
+            assert p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+        running = self._ptrs.get("running", self._running_buffers())
+        _lib.check(lib.lf_erfnet_infer(plan.handle, _lib.ptr(x), self._ptrs.get("params", params),
+                                       _lib.ptr(self._device_ptr_table(params)), running, head,
+                                       _lib.ptr(logits) if head >= 0 else None, _lib.ptr(ws), nbytes, _lib.stream()),
+                   "lf_erfnet_infer")
+        if not self.export_encoder_output:
+            return logits, torch.empty(0, dtype=torch.float32, device=dev)
+        off = 4 * lib.lf_erfnet_infer_encoder_offset(plan.handle)
+        nenc = N * (H // 8) * (W // 8) * 128
+        if mode == 2:
+            enc = ws[off: off + 2 * nenc].view(torch.bfloat16)
+        else:
+            enc = ws[off: off + 4 * nenc].view(torch.float32)
+        return logits, enc.view(N, H // 8, W // 8, 128)
+
     # ---- forward -----------------------------------------------------------------------
     def forward(self, input, flag, only_encode=False):
         if not input.is_cuda:
@@ -532,7 +566,10 @@ class Net(nn.Module):
             self.export_encoder_output = True
             head = -1                                 # the engine stops after the encoder: decoder BN statistics untouched
         try:
-            logits, enc = _BackboneFn.apply(self, plan, x, head, self.training, dropmask, *params)
+            if self.inference_engine and not self.training and not torch.is_grad_enabled():
+                logits, enc = self._infer(plan, x, head)
+            else:
+                logits, enc = _BackboneFn.apply(self, plan, x, head, self.training, dropmask, *params)
         finally:
             self.export_encoder_output = export
         if only_encode:
