@@ -35,7 +35,9 @@ extern "C" {
                                  lf_erfnet_forward_range / _backward_range take precision mode 2.
                                  Later ADDITIONS that leave every existing entry point's contract as it was keep the number:
                                  lf_convchain_set_precision / _workspace_bytes_for, lf_poolflat_bf16_*, lf_pointwise_bf16_*, and
-                                 lf_erfnet_backward's grad_encoder in mode 2 (the --clas heads and only_encode in bf16) */
+                                 lf_erfnet_backward's grad_encoder in mode 2 (the --clas heads and only_encode in bf16);
+                                 additions since 5 (inference engine): lf_erfnet_infer*, lf_erfnet_infer_range*, lf_convchain_infer*,
+                                 lf_head_fit, lf_lane_infer* */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -208,6 +210,40 @@ long lf_erfnet_infer_encoder_offset(const lf_erfnet_plan* plan);
 int lf_erfnet_infer(const lf_erfnet_plan* plan, const float* img, const float* const* params_host, const float* const* params_dev,
                     float* const* running_host, int head, float* logits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The inference engine for a layer range: lf_erfnet_forward_range (below) in eval mode without gradients -- DownsamplerBlock /
+ * non_bottleneck_1d / UpsamplerBlock.forward(input), Encoder.forward(input), Decoder.forward(input, flag) under model.eval() and
+ * torch.no_grad() (BEV/Networks/ERFNet.py:19-22,44-60,86-95,104-107,129-142).  Layers [first, last) (+ head when last = the layer
+ * count) on an NCHW fp32 input -> NCHW fp32 output, precision mode as set by lf_erfnet_set_precision (0, 2, 3); the contract of
+ * lf_erfnet_forward_range without dropout mask and training flag, the schedule, kernels and folded weights of lf_erfnet_infer: the
+ * encoder range followed by the decoder range gives lf_erfnet_infer's logits bit for bit.  Running statistics are read, never
+ * written.  The workspace equals lf_erfnet_infer_workspace_bytes of the mode (the fold-and-pack launch covers the whole plan; input
+ * and output are staged through the activation buffers); 0 for an unknown mode or an empty / reversed range. */
+size_t lf_erfnet_infer_range_workspace_bytes(const lf_erfnet_plan* plan, int first, int last, int mode);
+int lf_erfnet_infer_range(const lf_erfnet_plan* plan, int first, int last, int head, const float* x, const float* const* params_host,
+                          const float* const* params_dev, float* const* running_host, float* y, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* Fused head + fit (inference): decoder.output_conv = ConvTranspose2d(16, K, 2, stride 2) (BEV/Networks/ERFNet.py:123,139) and
+ * Net.forward steps 2-4 (activation, row mask, grid, WLS: BEV/Networks/LSQ_layer.py:310-325, BP/Networks/LSQ_layer.py:298-313) in
+ * one pass over the last decoder layer's tensor: the logits are written only on request, the masked weight maps never.
+ *   x (N,h,w,16) NHWC: fp32 (x_bf16 = 0) or bf16 bit patterns (1); head_w (16,K,2,2), head_b (K) fp32, K <= 8;
+ *   grid_xy ... solver, beta, zinv, partials (>= lf_wls_workspace_bytes(N,K,order)), status: as lf_wls_fwd on the (N,K,2h,2w) maps;
+ *   logits_or_null (N,K,2h,2w) fp32.  With logits NULL, input rows that feed only output rows < zero_rows are never read (nor
+ *   is the grid on those rows); with logits requested every row is computed for them, and the fit still skips the masked rows.
+ * lf_lane_infer: image -> lane polynomials in one call = lf_erfnet_infer's schedule up to the last decoder layer, lf_head_fit on
+ * head 0 (K = the plan's out_channels), the solve; validate() / test_model of the reference consume exactly these outputs
+ * (Backprojection_Loss/test.py:35-88).  beta (N,K,order+1) fp64 and status (N*K) as lf_wls_fwd; reg_ls is added to the diagonal
+ * for both solvers (pass 0 for BP's GELS).  The encoder output stays at lf_erfnet_infer_encoder_offset of the workspace for the
+ * --clas heads.  lf_lane_infer_workspace_bytes: 0 for an unknown mode, K != out_channels or order outside 0..3. */
+int lf_head_fit(const void* x, int x_bf16, const float* head_w, const float* head_b, const float* grid_xy, long grid_batch_stride,
+                int N, int h, int w, int K, int zero_rows, int order, double reg, double y_offset, int act_kind, int solver,
+                float* logits_or_null, double* beta, double* zinv, void* partials, int32_t* status, void* stream);
+size_t lf_lane_infer_workspace_bytes(const lf_erfnet_plan* plan, int mode, int K, int order);
+int lf_lane_infer(const lf_erfnet_plan* plan, const float* img, const float* const* params_host, const float* const* params_dev,
+                  float* const* running_host, const float* grid_xy, long grid_batch_stride, int zero_rows, int order, double reg_ls,
+                  double y_offset, int act_kind, int use_cholesky, float* logits_or_null, double* beta, int32_t* status,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* Block-level surface (round 4): a contiguous range [first, last) of the plan's layers (module order: 0 =
  * encoder.initial_block, 1..15 = encoder.layers[0..14], 16..21 = decoder.layers[0..5]) as one call, inside the plan of the
  * whole network at the matching input size -- what makes the reference's sub-modules callable on their own:
@@ -326,6 +362,15 @@ int lf_convchain_forward(const lf_convchain_plan* plan, const float* x, const fl
 int lf_convchain_backward(const lf_convchain_plan* plan, const float* x, const float* y, const float* gy,
                           const float* const* params_host, float* const* grads_host, float* gx, int training,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* The trunk in eval mode without gradients (Classification.forward under model.eval() and torch.no_grad(),
+ * BP/Networks/LSQ_layer.py:192-196 in validate() / test_model): every BatchNorm folded into its convolution from the running
+ * statistics, per call (one fold-and-pack launch), then one convolution launch per block with a bias + ReLU epilogue; nothing saved.
+ * Mode as lf_convchain_set_precision (0; 2 reads the bf16 encoder output in place and writes y as bf16).  x, y, params and running
+ * pointers as lf_convchain_forward; the running statistics are read, never written.  Workspace: 0 bytes for a mode other than 0, 2. */
+size_t lf_convchain_infer_workspace_bytes(const lf_convchain_plan* plan, int mode);
+int lf_convchain_infer(const lf_convchain_plan* plan, const float* x, const float* const* params_host,
+                       const float* const* params_dev, float* const* running_host, float eps, float* y, void* workspace,
+                       size_t workspace_bytes, void* stream);
 /* Pool + flatten in front of the heads' fully connected layers (LSQ_layer.py:183-187,197-201):
  * mode 0 = MaxPool2d(2,2) -> (N, C*(H/2)*(W/2)); mode 1 = AvgPool2d((1,W)) -> (N, C*H); input NHWC,
  * output in the NCHW flatten order nn.Linear's weights expect.  The Linear layers themselves are plain

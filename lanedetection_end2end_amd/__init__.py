@@ -11,11 +11,13 @@ __all__ = ["bev", "bp", "fit", "losses", "erfnet", "lsq", "geometry", "ops", "us
 
 
 def use_inference_engine(module, on=True):
-    """Set ``inference_engine`` on every lanefit ERFNet inside ``module`` (the module itself, or e.g. the LSQ ``Net``'s ``.net``):
-    its eval-mode forwards under ``torch.no_grad()`` / ``torch.inference_mode()`` then run the forward-only engine
-    (``lf_erfnet_infer``).  Returns ``module``."""
+    """Set ``inference_engine`` on every lanefit ERFNet and every ``--clas`` head inside ``module`` (the module itself, or e.g. the
+    LSQ ``Net`` with its ``.net``, ``.line_classification`` and ``.horizon_estimation``): their eval-mode forwards under
+    ``torch.no_grad()`` / ``torch.inference_mode()`` then run the forward-only engine -- the whole network (``lf_erfnet_infer``),
+    block-level calls (``lf_erfnet_infer_range``) and the heads' trunk (``lf_convchain_infer``).  Returns ``module``."""
+    from .clas import Classification
     from .erfnet import Net
     for m in module.modules():
-        if isinstance(m, Net):
+        if isinstance(m, (Net, Classification)):
             m.inference_engine = bool(on)
     return module

@@ -102,6 +102,13 @@ def _declare(lib):
         "lf_erfnet_infer_workspace_bytes": (c_size_t, [P, I]),
         "lf_erfnet_infer_encoder_offset": (L, [P]),
         "lf_erfnet_infer": (I, [P, P, P, P, P, I, P, P, c_size_t, P]),
+        "lf_erfnet_infer_range_workspace_bytes": (c_size_t, [P, I, I, I]),
+        "lf_erfnet_infer_range": (I, [P, I, I, I, P, P, P, P, P, P, c_size_t, P]),
+        "lf_convchain_infer_workspace_bytes": (c_size_t, [P, I]),
+        "lf_convchain_infer": (I, [P, P, P, P, P, ctypes.c_float, P, P, c_size_t, P]),
+        "lf_head_fit": (I, [P, I, P, P, P, L, I, I, I, I, I, I, D, D, I, I, P, P, P, P, P, P]),
+        "lf_lane_infer_workspace_bytes": (c_size_t, [P, I, I, I]),
+        "lf_lane_infer": (I, [P, P, P, P, P, P, L, I, I, D, D, I, I, P, P, P, P, c_size_t, P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {

@@ -15,6 +15,7 @@ the head outputs are fp32 in every mode.
 with the gating of ``test_model`` (BP/test.py:72-88) into one launch (``lf_lane_decode``).
 """
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -153,6 +154,9 @@ class Classification(nn.Module):
         self._channels = (channels_in, 128, 128, 64, 64)
         self._plans = {}
         self._ptr_cache = (None, None)
+        # eval mode under no_grad: the trunk with its BatchNorms folded in (lf_convchain_infer); opt-in like erfnet.Net's switch
+        # (use_inference_engine, or LANEFIT_INFERENCE_ENGINE=1 when the module is built)
+        self.inference_engine = os.environ.get("LANEFIT_INFERENCE_ENGINE", "") == "1"
 
     def _make_line_heads(self):
         """BP: one 4-way head (BP/Networks/LSQ_layer.py:186-187)."""
@@ -176,9 +180,28 @@ class Classification(nn.Module):
             self._ptr_cache = (key, torch.tensor(key, dtype=torch.int64, device=params[0].device))
         return self._ptr_cache[1]
 
-    def trunk(self, x):
+    def _trunk_infer(self, plan, xh):
+        """The eval-mode trunk with every BatchNorm folded into its convolution (lf_convchain_infer): nothing saved."""
+        lib = _lib.load()
+        N, H, W = plan.shape
+        mode = 2 if xh.dtype == torch.bfloat16 else 0
+        _lib.check(lib.lf_convchain_set_precision(plan.handle, mode), "lf_convchain_set_precision")
+        nbytes = lib.lf_convchain_infer_workspace_bytes(plan.handle, mode)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=xh.device)
+        y = torch.empty(N, H, W, plan.channels[-1], dtype=xh.dtype, device=xh.device)
+        params = [p.detach() for p in self._trunk_params()]
+        for p in params:
+            assert p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+        bns = self._batchnorms()
+        running = _ptr_array([b for bn in bns for b in (bn.running_mean, bn.running_var)])
+        _lib.check(lib.lf_convchain_infer(plan.handle, _lib.ptr(xh), _ptr_array(params), _lib.ptr(self._ptr_table(params)), running,
+                                          float(bns[0].eps), _lib.ptr(y), _lib.ptr(ws), nbytes, _lib.stream()), "lf_convchain_infer")
+        return y
+
+    def trunk(self, x, folded=None):
         """conv1..conv4 (+BN+ReLU) on a logical-NCHW tensor; returns NHWC (N,H,W,64), bf16 on a bf16 input (the encoder output
-        of the backbone's bf16 mode, read in place), fp32 otherwise."""
+        of the backbone's bf16 mode, read in place), fp32 otherwise.  In eval mode with gradients disabled the BatchNorm-folded
+        trunk runs when ``inference_engine`` is on (``folded``: override the switch for this call)."""
         if not x.is_cuda:
             raise _lib.LaneFitLibraryError("lanefit Classification needs its input on the MI355X; there is no CPU path")
         xh = x.permute(0, 2, 3, 1)
@@ -191,13 +214,15 @@ class Classification(nn.Module):
         key = (N, H, W)
         if key not in self._plans:
             self._plans[key] = _ChainPlan(N, H, W, self._channels, (1, 3, 3, 3))
+        if not self.training and not torch.is_grad_enabled() and (self.inference_engine if folded is None else folded):
+            return self._trunk_infer(self._plans[key], xh)
         y = _ConvChainFn.apply(self, self._plans[key], xh, self.training, *self._trunk_params())
         if self.training:
             torch._foreach_add_([m.num_batches_tracked for m in self._batchnorms()], 1)
         return y
 
-    def forward(self, x):
-        y = self.trunk(x)
+    def forward(self, x, folded=None):
+        y = self.trunk(x, folded)
         if self.class_type == 'line':
             f = _PoolFlatFn.apply(y, 0)
             f = ops.linear(f, self.fully_connected1.weight, self.fully_connected1.bias, relu=True)      # F.relu(fc1(f)), one launch

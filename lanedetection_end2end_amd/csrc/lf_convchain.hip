@@ -36,6 +36,11 @@ struct lf_convchain_plan {
     // the packed weights and the partial-row regions of the bf16 weight gradients (the read-once kernel's row counts)
     long packed16_elems, off_packed16, wpart16_floats, off_wpart16, bpart16_floats, off_bpart16, total16_floats;
     mutable int precision = 0;                          // lf_convchain_set_precision
+    // inference (lf_convchain_infer): one fold entry per block, compact arenas of the forward packs only
+    std::vector<LfFoldEntry> fold;
+    long infer_packed_floats = 0, infer_packed16_elems = 0, infer_vec_floats = 0;
+    mutable std::vector<LfFoldEntry> fold_call;         // the table with this call's pointers (rebuilt when one of them moved)
+    mutable std::vector<const void*> fold_key;
 };
 
 namespace {
@@ -199,6 +204,19 @@ lf_convchain_plan* lf_convchain_plan_create(int N, int H, int W, int nlayers, co
     P->off_wpart16 = ws.take(P->wpart16_floats);
     P->off_bpart16 = ws.take(P->bpart16_floats);
     P->total16_floats = ws.cur;
+    for (int i = 0; i < nlayers; ++i) {
+        LfFoldEntry f;
+        memset(&f, 0, sizeof(f));
+        f.pk = P->packs[P->pk_fwd[i]];
+        f.pk.dst_off = P->infer_packed_floats;
+        P->infer_packed_floats += (long)f.pk.ntaps * f.pk.Kc * f.pk.Nc;
+        f.pk.dst16_off = P->infer_packed16_elems;
+        P->infer_packed16_elems += lf_pack_bf16_elems(f.pk.Kc, f.pk.Nc, f.pk.ntaps);
+        f.ch_off = 0; f.C = channels[i + 1];
+        f.out_off = P->infer_vec_floats;
+        P->infer_vec_floats += (f.C + 63) / 64 * 64;
+        P->fold.push_back(f);
+    }
     return P;
 }
 
@@ -258,6 +276,75 @@ int lf_convchain_forward(const lf_convchain_plan* P, const float* x, const float
     }
     const int l = P->L - 1;
     return lf_bn_act(ws + P->z[l], ws + P->sc[l], ws + P->sh[l], nullptr, nullptr, y, npix, P->C[P->L], (long)P->H * P->W, s16, st);
+}
+
+// ---- inference: the eval-mode trunk with every BatchNorm folded into its convolution ------------------------------------------
+// (Classification.forward under model.eval() and torch.no_grad(): BP/Networks/LSQ_layer.py:192-196 in validate() / test_model.)
+// Per call one fold-and-pack launch from the running statistics (nothing cached: a training step changes them), then one tap-GEMM
+// launch per block with the folded bias + ReLU epilogue; two ping-pong buffers, the last block writes y.  Byte layout: fold table,
+// folded bias vectors, the packed arena of the mode (fp32, or bf16 in mode 2), buffers A and B.
+namespace {
+struct ChainInferLayout { long table, vec, arena, buf[2], total; };
+ChainInferLayout chain_infer_layout(const lf_convchain_plan* P, int mode) {
+    auto al = [](long b) { return (b + 255) / 256 * 256; };
+    ChainInferLayout L;
+    long cur = 0;
+    L.table = cur; cur += al((long)(P->fold.size() * sizeof(LfFoldEntry)));
+    L.vec = cur; cur += al(P->infer_vec_floats * 4);
+    L.arena = cur; cur += al(mode == 2 ? P->infer_packed16_elems * 2 : P->infer_packed_floats * 4);
+    for (int i = 0; i < 2; ++i) { L.buf[i] = cur; cur += al(P->gbuf_floats * (mode == 2 ? 2 : 4)); }
+    L.total = cur;
+    return L;
+}
+}  // namespace
+
+size_t lf_convchain_infer_workspace_bytes(const lf_convchain_plan* P, int mode) {
+    if (!P || !(mode == 0 || mode == 2)) return 0;
+    return (size_t)chain_infer_layout(P, mode).total;
+}
+
+// x, y as lf_convchain_forward (bf16 elements in mode 2, x read in place); running statistics are read, never written.
+int lf_convchain_infer(const lf_convchain_plan* P, const float* x, const float* const* params_host, const float* const* params_dev,
+                       float* const* running_host, float eps, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    LF_REQUIRE(P && x && params_host && params_dev && running_host && y && workspace, "lf_convchain_infer: null pointer");
+    const int mode = P->precision, s16 = mode == 2;
+    const ChainInferLayout L = chain_infer_layout(P, mode);
+    LF_REQUIRE(workspace_bytes >= (size_t)L.total, "lf_convchain_infer: workspace too small (%zu < %ld)", workspace_bytes, L.total);
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    std::vector<const void*> key;
+    for (int i = 0; i < 4 * P->L; ++i) key.push_back(params_host[i]);
+    for (int i = 0; i < 2 * P->L; ++i) key.push_back(running_host[i]);
+    if (key != P->fold_key) {
+        // (the table is uploaded from this vector: let an earlier upload of it finish before it is rewritten)
+        if (!P->fold_key.empty() && hipStreamSynchronize(st) != hipSuccess) return lf_fail("lf_convchain_infer: stream synchronisation failed");
+        P->fold_call = P->fold;
+        for (int i = 0; i < P->L; ++i) {
+            LfFoldEntry& f = P->fold_call[i];
+            f.bias = params_host[4 * i + 1]; f.gamma = params_host[4 * i + 2]; f.beta = params_host[4 * i + 3];
+            f.mean = running_host[2 * i]; f.var = running_host[2 * i + 1];
+        }
+        P->fold_key = key;
+    }
+    if (hipMemcpyAsync(ws + L.table, P->fold_call.data(), P->fold_call.size() * sizeof(LfFoldEntry), hipMemcpyHostToDevice, st) != hipSuccess)
+        return lf_fail("lf_convchain_infer: upload of the fold table failed");
+    float* vec = reinterpret_cast<float*>(ws + L.vec);
+    LF_TRY(lf_fold_pack_launch(reinterpret_cast<const LfFoldEntry*>(ws + L.table), P->L, params_dev, eps, vec,
+                               s16 ? nullptr : reinterpret_cast<float*>(ws + L.arena), s16 ? ws + L.arena : nullptr, nullptr, st));
+    const float* src = x;
+    for (int i = 0; i < P->L; ++i) {
+        const LfFoldEntry& f = P->fold[i];
+        LfTapArgs a = lf_no_args();
+        a.src = src;
+        a.dst = i == P->L - 1 ? y : reinterpret_cast<float*>(ws + L.buf[i & 1]);
+        a.bias = vec + f.out_off;
+        a.s16 = s16;
+        if (s16) a.wp16 = reinterpret_cast<const unsigned short*>(ws + L.arena) + f.pk.dst16_off;
+        else a.wp = reinterpret_cast<const float*>(ws + L.arena) + f.pk.dst_off;
+        LF_TRY(lf_tapgemm_launch(P->fwd[i], a, LF_PRO_NONE, LF_EPI_RELU, st));
+        src = a.dst;
+    }
+    return 0;
 }
 
 // Backward of the forward that last used `workspace`.  gy (N,H,W,C_L) NHWC; grads_host: 4*L device pointers

@@ -1213,8 +1213,10 @@ int infer_gemm(const InferCtx& c, const GemmOp& op, int fi, const float* src, fl
     return lf_tapgemm_launch(op.geom, a, LF_PRO_NONE, epi, c.st);
 }
 
-// layers [0, nlayers); the last encoder layer writes the encoder-output region; *out = the last layer's output
-int forward_infer(const InferCtx& c, const float* img, const float* const* params_host, int nlayers, float** out) {
+// layers [first, nlayers); the last encoder layer writes the encoder-output region; *out = the last layer's output.  xin: the NHWC
+// input of layer `first` when first > 0 (one of the three activation buffers, or the encoder-output region); unused for first = 0
+int forward_infer(const InferCtx& c, const float* img, const float* const* params_host, int nlayers, float** out, int first = 0,
+                  float* xin = nullptr) {
     const lf_erfnet_plan* P = c.P;
     const int N = P->N, ne = encoder_layers(P);
     float* bufs[3];
@@ -1224,8 +1226,8 @@ int forward_infer(const InferCtx& c, const float* img, const float* const* param
         for (float* b : bufs) if (b != u && b != v) return b;
         return bufs[0];
     };
-    float* x = nullptr;
-    for (int li = 0; li < nlayers; ++li) {
+    float* x = xin;
+    for (int li = first; li < nlayers; ++li) {
         const Layer& L = P->layers[li];
         if (L.kind == K_DOWN && L.x < 0) {
             float* y = bufs[0];
@@ -1289,6 +1291,103 @@ int lf_erfnet_infer(const lf_erfnet_plan* P, const float* img, const float* cons
     LF_TRY(forward_infer(c, img, params_host, (int)P->layers.size(), &last));
     return lf_head_fwd(last, params_host[P->p_head_w[head]], params_host[P->p_head_b[head]], logits, P->N, P->H / 2, P->W / 2,
                        P->Cout + head, c.s16, c.st);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// The inference engine on the rest of the surface: a RANGE of layers (the block-level calls of lf_erfnet_forward_range in eval mode
+// under no_grad) and the one-call image -> lane coefficients entry (lf_lane_infer).
+// ---------------------------------------------------------------------------------------
+namespace {
+
+int infer_begin(InferCtx& c, const lf_erfnet_plan* P, void* workspace, const float* const* params_host, const float* const* params_dev,
+                float* const* running_host, void* stream) {
+    c.P = P; c.ws = (char*)workspace; c.mode = P->precision; c.s16 = P->precision == 2; c.st = (hipStream_t)stream;
+    c.L = infer_layout(P, c.mode);
+    LF_TRY(infer_fold_table(P, c.ws, c.L, params_host, running_host, c.st));
+    return lf_fold_pack_launch(reinterpret_cast<const LfFoldEntry*>(c.ws + c.L.table), (int)P->fold.size(), params_dev, BN_EPS,
+                               reinterpret_cast<float*>(c.ws + c.L.vec), c.L.a32 >= 0 ? reinterpret_cast<float*>(c.ws + c.L.a32) : nullptr,
+                               c.L.a16 >= 0 ? c.ws + c.L.a16 : nullptr, c.L.a48 >= 0 ? c.ws + c.L.a48 : nullptr, c.st);
+}
+
+// the lane-fit tail of lf_lane_infer behind the inference workspace: chunk partials, then the saved inverse the solve kernel writes
+struct LaneLayout { long partials, zinv, total; };
+LaneLayout lane_layout(const lf_erfnet_plan* P, int mode, int K, int order) {
+    auto al = [](long b) { return (b + 255) / 256 * 256; };
+    LaneLayout L;
+    long cur = infer_layout(P, mode).total;
+    L.partials = cur; cur += al((long)lf_wls_workspace_bytes(P->N, K, order));
+    L.zinv = cur; cur += al((long)P->N * K * (order + 1) * (order + 1) * (long)sizeof(double));
+    L.total = cur;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Workspace of lf_erfnet_infer_range: the whole-network inference layout of the mode (the fold-and-pack launch covers every fold
+// entry, the range's input is staged NCHW -> NHWC into the first activation buffer, the output leaves the last one straight into y):
+// equal to lf_erfnet_infer_workspace_bytes for every valid range; 0 for an unknown mode or an empty / reversed range.
+size_t lf_erfnet_infer_range_workspace_bytes(const lf_erfnet_plan* P, int first, int last, int mode) {
+    if (!P || first < 0 || last <= first || last > (int)P->layers.size()) return 0;
+    return lf_erfnet_infer_workspace_bytes(P, mode);
+}
+
+// Layers [first, last) (+ head when last is the layer count) in eval mode on the inference engine: the contract of
+// lf_erfnet_forward_range without dropout mask and training flag, the schedule and kernels of lf_erfnet_infer (encoder range
+// followed by decoder range = lf_erfnet_infer bit for bit).  x / y NCHW fp32; in mode 2 the input is rounded to bf16 on its way in.
+int lf_erfnet_infer_range(const lf_erfnet_plan* P, int first, int last, int head, const float* x, const float* const* params_host,
+                          const float* const* params_dev, float* const* running_host, float* y, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    LF_TRY(check_range(P, first, last, head, "lf_erfnet_infer_range"));
+    LF_REQUIRE(x && y && params_host && params_dev && running_host && workspace, "lf_erfnet_infer_range: null pointer");
+    LF_REQUIRE(workspace_bytes >= lf_erfnet_infer_range_workspace_bytes(P, first, last, P->precision),
+               "lf_erfnet_infer_range: workspace too small");
+    InferCtx c;
+    LF_TRY(infer_begin(c, P, workspace, params_host, params_dev, running_host, stream));
+    const Layer& Lf = P->layers[first];
+    float* xin = nullptr;
+    if (first > 0) {
+        xin = reinterpret_cast<float*>(c.ws + c.L.buf[0]);
+        LF_TRY(nchw_to_nhwc(x, xin, P->N, Lf.Hin, Lf.Win, Lf.Cin, c.s16, c.st));
+    }
+    float* out = nullptr;
+    LF_TRY(forward_infer(c, x, params_host, last, &out, first, xin));
+    const Layer& Ll = P->layers[last - 1];
+    if (head >= 0)
+        return lf_head_fwd(out, params_host[P->p_head_w[head]], params_host[P->p_head_b[head]], y, P->N, P->H / 2, P->W / 2,
+                           P->Cout + head, c.s16, c.st);
+    return nhwc_to_nchw(out, y, P->N, Ll.Hout, Ll.Wout, Ll.Cout, c.s16, c.st);
+}
+
+// Image -> lane polynomials in one call: lf_erfnet_infer's schedule up to the last decoder layer, the fused head + activation + row
+// mask + moments kernel on its 16-channel output (head 0, decoder.output_conv), the solve kernel of lf_wls_fwd.  K = the plan's
+// out_channels.  The encoder output stays at lf_erfnet_infer_encoder_offset for the --clas heads.
+size_t lf_lane_infer_workspace_bytes(const lf_erfnet_plan* P, int mode, int K, int order) {
+    if (!P || !(mode == 0 || mode == 2 || mode == 3) || K != P->Cout || order < 0 || order > 3) return 0;
+    return (size_t)lane_layout(P, mode, K, order).total;
+}
+
+int lf_lane_infer(const lf_erfnet_plan* P, const float* img, const float* const* params_host, const float* const* params_dev,
+                  float* const* running_host, const float* grid_xy, long grid_batch_stride, int zero_rows, int order, double reg_ls,
+                  double y_offset, int act_kind, int use_cholesky, float* logits_or_null, double* beta, int32_t* status,
+                  void* workspace, size_t workspace_bytes, void* stream) {
+    LF_REQUIRE(P && img && params_host && params_dev && running_host && grid_xy && beta && status && workspace,
+               "lf_lane_infer: null pointer");
+    LF_REQUIRE(order >= 0 && order <= 3, "lf_lane_infer: order %d not in 0..3", order);
+    const int K = P->Cout;
+    const LaneLayout LL = lane_layout(P, P->precision, K, order);
+    LF_REQUIRE(workspace_bytes >= (size_t)LL.total, "lf_lane_infer: workspace too small (%zu < %ld)", workspace_bytes, LL.total);
+    InferCtx c;
+    LF_TRY(infer_begin(c, P, workspace, params_host, params_dev, running_host, stream));
+    float* last = nullptr;
+    LF_TRY(forward_infer(c, img, params_host, (int)P->layers.size(), &last));
+    return lf_head_fit(last, c.s16, params_host[P->p_head_w[0]], params_host[P->p_head_b[0]], grid_xy, grid_batch_stride, P->N,
+                       P->H / 2, P->W / 2, K, zero_rows, order, reg_ls, y_offset, act_kind,
+                       use_cholesky ? LF_SOLVE_CHOLESKY : LF_SOLVE_LU, logits_or_null, beta,
+                       reinterpret_cast<double*>(c.ws + LL.zinv), c.ws + LL.partials, status, stream);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 // masked rows are never read.  Accumulation is fp64 (the reference's fp32 bmm over 131k
 // pixels is the source of its 5e-5..1e-4 noise floor); HBM-bound.
 #include "lf_common.h"
+#include "lf_types.h"
 
 #include <stdarg.h>
 
@@ -516,6 +517,164 @@ extern "C" int lf_wls_fwd(const float* logits, const float* grid_xy, long grid_b
         case 1: return wls_fwd_launch<1>(logits, grid_xy, grid_batch_stride, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
         case 2: return wls_fwd_launch<2>(logits, grid_xy, grid_batch_stride, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
         default: return wls_fwd_launch<3>(logits, grid_xy, grid_batch_stride, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// Fused head + fit (inference): decoder.output_conv = ConvTranspose2d(16, K, 2, stride 2) (BEV/Networks/ERFNet.py:123,139), the
+// activation, the row mask and the moment pass of the fit (BEV/Networks/LSQ_layer.py:310-325) in ONE pass over the last decoder
+// layer's 16-channel NHWC tensor: the (N,K,H,W) logits and the masked weight map are never written (the logits only on request),
+// and input rows that feed masked output rows only are never read.  One input pixel per lane (64 contiguous bytes of fp32, 32 of
+// bf16) -> its 2 x 2 output pixels for HM_LANES fit lanes; products in head_fwd_kernel's order (bias first, channels ascending);
+// moments in fp64 through Moments<ORDER>::add into the partials layout wls_solve_kernel reads.
+// ---------------------------------------------------------------------------------------
+namespace {
+
+constexpr int HM_LANES = 2;      // fit lanes (head channels) per workgroup: 2 * (3 * ORDER + 2) fp64 accumulators per thread
+constexpr int HM_MAXK = 8;
+
+template <int ORDER, typename T>
+__global__ __launch_bounds__(WLS_THREADS) void head_moments_kernel(
+    const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ grid, long grid_bs,
+    int K, int h, int wd, int zero_rows, float y_off, int act_kind, float* __restrict__ logits, double* __restrict__ partials) {
+    using M = Moments<ORDER>;
+    const int groups = (K + HM_LANES - 1) / HM_LANES;
+    const int n = blockIdx.y / groups, k0 = (blockIdx.y % groups) * HM_LANES, chunk = blockIdx.x;
+    __shared__ float sw[HM_LANES][16][4];
+    __shared__ float sb[HM_LANES];
+    for (int i = threadIdx.x; i < HM_LANES * 64; i += WLS_THREADS) {
+        const int kk = i >> 6, ci = (i >> 2) & 15, ab = i & 3;
+        const int k = k0 + kk < K ? k0 + kk : K - 1;              // (a lane group's spare slot repeats lane K - 1 and is not stored)
+        sw[kk][ci][ab] = w[(ci * K + k) * 4 + ab];
+        if (ci == 0 && ab == 0) sb[kk] = b[k];
+    }
+    __syncthreads();
+    const int W = 2 * wd;
+    const long HW = (long)(2 * h) * W;
+    const float* g = grid + (long)n * grid_bs;
+    const T* xn = x + (long)n * h * wd * 16;
+    // first input row that is needed: with logits requested every row, else the first one with an unmasked output row
+    const long first = logits ? 0 : (long)(zero_rows / 2) * wd;
+    const long units = (long)h * wd - first;
+    const long u0 = units * chunk / WLS_CHUNKS, u1 = units * (chunk + 1) / WLS_CHUNKS;
+    M acc[HM_LANES];
+#pragma unroll
+    for (int kk = 0; kk < HM_LANES; ++kk) acc[kk].zero();
+    for (long u = u0 + threadIdx.x; u < u1; u += WLS_THREADS) {
+        const long p = first + u;
+        const int i = (int)(p / wd), j = (int)(p - (long)i * wd);
+        float xv[16];
+        if constexpr (sizeof(T) == 2) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                lf_f32x4 v[2];
+                lf_ldq<T, 2>(xn + p * 16 + q * 8, v);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { xv[q * 8 + e] = v[0][e]; xv[q * 8 + 4 + e] = v[1][e]; }
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const lf_f32x4 v = lf_ldv(xn + p * 16 + q * 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xv[q * 4 + e] = v[e];
+            }
+        }
+        // the 2 x 64 head weights are read from LDS per pixel (wave-uniform broadcasts): `lz` is an opaque zero that keeps the
+        // compiler from hoisting all 128 of them into registers across the loop (260 VGPRs at order 3: one wave per SIMD)
+        int lz = 0;
+        asm volatile("" : "+s"(lz));
+        const bool live0 = 2 * i >= zero_rows, live1 = 2 * i + 1 >= zero_rows;
+        const long q0 = (long)(2 * i) * W + 2 * j;                 // output pixel (2i, 2j); (2i+1, 2j) = q0 + W
+        float4 ga = make_float4(0.f, 0.f, 0.f, 0.f), gb = ga;
+        if (live0) ga = *reinterpret_cast<const float4*>(g + 2 * q0);
+        if (live1) gb = *reinterpret_cast<const float4*>(g + 2 * (q0 + W));
+#pragma unroll
+        for (int kk = 0; kk < HM_LANES; ++kk) {
+            float o[4];
+#pragma unroll
+            for (int ab = 0; ab < 4; ++ab) o[ab] = sb[kk];
+            const float (*swk)[4] = sw[kk] + lz;
+#pragma unroll
+            for (int ci = 0; ci < 16; ++ci)
+#pragma unroll
+                for (int ab = 0; ab < 4; ++ab) o[ab] = fmaf(xv[ci], swk[ci][ab], o[ab]);
+            if (live0) {
+                acc[kk].add(act_fwd(o[0], act_kind), ga.x, ga.y, y_off);
+                acc[kk].add(act_fwd(o[1], act_kind), ga.z, ga.w, y_off);
+            }
+            if (live1) {
+                acc[kk].add(act_fwd(o[2], act_kind), gb.x, gb.y, y_off);
+                acc[kk].add(act_fwd(o[3], act_kind), gb.z, gb.w, y_off);
+            }
+            if (logits && k0 + kk < K) {
+                float* op = logits + ((long)n * K + k0 + kk) * HW + q0;
+                *reinterpret_cast<float2*>(op) = make_float2(o[0], o[1]);
+                *reinterpret_cast<float2*>(op + W) = make_float2(o[2], o[3]);
+            }
+        }
+    }
+    __shared__ double red[WLS_THREADS / LF_WAVE][HM_LANES][M::N];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int kk = 0; kk < HM_LANES; ++kk)
+#pragma unroll
+        for (int t = 0; t < M::N; ++t) {
+            const double s = lf_wave_sum(acc[kk].v[t]);
+            if (lane == 0) red[wave][kk][t] = s;
+        }
+    __syncthreads();
+    if (threadIdx.x < HM_LANES * M::N) {
+        const int kk = threadIdx.x / M::N, t = threadIdx.x % M::N;
+        if (k0 + kk < K) {
+            double s = 0.0;
+#pragma unroll
+            for (int wv = 0; wv < WLS_THREADS / LF_WAVE; ++wv) s += red[wv][kk][t];
+            partials[(((long)n * K + k0 + kk) * WLS_CHUNKS + chunk) * M::N + t] = s;
+        }
+    }
+}
+
+template <int ORDER>
+int head_fit_launch(const void* x, int s16, const float* w, const float* b, const float* grid, long gbs, int N, int h, int wd, int K,
+                    int zr, double reg, double y_off, int act, int solver, float* logits, double* beta, double* zinv,
+                    double* partials, int32_t* status, hipStream_t st) {
+    const dim3 g1(WLS_CHUNKS, N * ((K + HM_LANES - 1) / HM_LANES));
+    if (s16)
+        hipLaunchKernelGGL((head_moments_kernel<ORDER, lf_bf16>), g1, dim3(WLS_THREADS), 0, st, reinterpret_cast<const lf_bf16*>(x), w, b,
+                           grid, gbs, K, h, wd, zr, (float)y_off, act, logits, partials);
+    else
+        hipLaunchKernelGGL((head_moments_kernel<ORDER, float>), g1, dim3(WLS_THREADS), 0, st, reinterpret_cast<const float*>(x), w, b,
+                           grid, gbs, K, h, wd, zr, (float)y_off, act, logits, partials);
+    LF_CHECK_LAUNCH("head_moments");
+    hipLaunchKernelGGL((wls_solve_kernel<ORDER>), dim3(lf_cdiv(N * K, 64)), dim3(64), 0, st, partials, N * K, reg, solver, beta, zinv,
+                       status);
+    LF_CHECK_LAUNCH("wls_solve");
+    return 0;
+}
+
+}  // namespace
+
+// x (N,h,w,16) NHWC fp32 (x_bf16 = 0) or bf16 bit patterns (1); head_w (16,K,2,2), head_b (K) fp32; the fit runs on the
+// (N,K,2h,2w) maps the head would write.  Arguments from grid_xy on as lf_wls_fwd; logits_or_null (N,K,2h,2w) fp32.
+extern "C" int lf_head_fit(const void* x, int x_bf16, const float* head_w, const float* head_b, const float* grid_xy,
+                           long grid_batch_stride, int N, int h, int w, int K, int zero_rows, int order, double reg, double y_offset,
+                           int act_kind, int solver, float* logits_or_null, double* beta, double* zinv, void* partials,
+                           int32_t* status, void* stream) {
+    LF_REQUIRE(x && head_w && head_b && grid_xy && beta && zinv && partials && status, "lf_head_fit: null pointer");
+    LF_REQUIRE(N > 0 && h > 0 && w > 0 && K >= 1 && K <= HM_MAXK, "lf_head_fit: bad shape %d %d %d %d", N, K, h, w);
+    LF_REQUIRE(zero_rows >= 0 && zero_rows < 2 * h, "lf_head_fit: zero_rows %d out of [0,%d)", zero_rows, 2 * h);
+    LF_REQUIRE(order >= 0 && order <= 3, "lf_head_fit: order %d not in 0..3", order);
+    LF_REQUIRE(act_kind >= 0 && act_kind <= LF_ACT_NONE, "lf_head_fit: bad activation %d", act_kind);
+    LF_REQUIRE(grid_batch_stride % 4 == 0 && ((size_t)grid_xy & 15) == 0 && ((size_t)x & 15) == 0 &&
+               (!logits_or_null || ((size_t)logits_or_null & 7) == 0), "lf_head_fit: grid / input / logits are read and written as vectors: misaligned");
+    hipStream_t st = (hipStream_t)stream;
+    double* p = (double*)partials;
+    switch (order) {
+        case 0: return head_fit_launch<0>(x, x_bf16, head_w, head_b, grid_xy, grid_batch_stride, N, h, w, K, zero_rows, reg, y_offset, act_kind, solver, logits_or_null, beta, zinv, p, status, st);
+        case 1: return head_fit_launch<1>(x, x_bf16, head_w, head_b, grid_xy, grid_batch_stride, N, h, w, K, zero_rows, reg, y_offset, act_kind, solver, logits_or_null, beta, zinv, p, status, st);
+        case 2: return head_fit_launch<2>(x, x_bf16, head_w, head_b, grid_xy, grid_batch_stride, N, h, w, K, zero_rows, reg, y_offset, act_kind, solver, logits_or_null, beta, zinv, p, status, st);
+        default: return head_fit_launch<3>(x, x_bf16, head_w, head_b, grid_xy, grid_batch_stride, N, h, w, K, zero_rows, reg, y_offset, act_kind, solver, logits_or_null, beta, zinv, p, status, st);
     }
 }
 

@@ -444,11 +444,35 @@ class Net(nn.Module):
         if (C, h, w) != (io[0], io[1], io[2]):
             raise RuntimeError("ERFNet block expects an input of (N, %d, H, W), got %s" % (io[0], tuple(x.shape)))
         training = self._blocks()[first].training
+        if self.inference_engine and not training and not torch.is_grad_enabled():
+            return self._infer_range(plan, x, first, last, head)
         dropmask = self._make_dropmask(plan, x.device) if training else None
         y = _RangeFn.apply(self, plan, x, first, last, head, training, dropmask, *self._ordered_params())
         if training:
             bns = [m for b in self._blocks()[first:last] for m in b.modules() if isinstance(m, nn.BatchNorm2d)]
             torch._foreach_add_([m.num_batches_tracked for m in bns], 1)
+        return y
+
+    def _infer_range(self, plan, x, first, last, head):
+        """Layers [first, last) (+ head) in eval mode on the inference engine (lf_erfnet_infer_range): the schedule and folded
+        weights of the whole-network call, the small inference workspace, nothing saved for a backward."""
+        lib = _lib.load()
+        N, H, W = plan.shape
+        io = (ctypes.c_int * 6)()
+        _lib.check(lib.lf_erfnet_layer_io(plan.handle, last - 1, io), "lf_erfnet_layer_io")
+        oshape = (N, self.out_channels + head, H, W) if head >= 0 else (N, io[3], io[4], io[5])
+        mode = _PRECISIONS[self.precision]
+        _lib.check(lib.lf_erfnet_set_precision(plan.handle, mode), "lf_erfnet_set_precision")
+        nbytes = lib.lf_erfnet_infer_range_workspace_bytes(plan.handle, first, last, mode)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        y = torch.empty(oshape, dtype=torch.float32, device=x.device)
+        params = [p.detach() for p in self._ordered_params()]
+        for p in params:
+            assert p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+        running = self._ptrs.get("running", self._running_buffers())
+        _lib.check(lib.lf_erfnet_infer_range(plan.handle, first, last, head, _lib.ptr(x), self._ptrs.get("params", params),
+                                             _lib.ptr(self._device_ptr_table(params)), running, _lib.ptr(y), _lib.ptr(ws), nbytes,
+                                             _lib.stream()), "lf_erfnet_infer_range")
         return y
 
     # ---- bookkeeping -------------------------------------------------------------------
@@ -540,13 +564,49 @@ class Net(nn.Module):
                    "lf_erfnet_infer")
         if not self.export_encoder_output:
             return logits, torch.empty(0, dtype=torch.float32, device=dev)
-        off = 4 * lib.lf_erfnet_infer_encoder_offset(plan.handle)
+        return logits, self._infer_encoder_view(plan, ws, mode)
+
+    def _infer_encoder_view(self, plan, ws, mode):
+        """The NHWC encoder output inside an inference workspace (fp32, or bf16 in mode 2): a view, no copy."""
+        N, H, W = plan.shape
+        off = 4 * _lib.load().lf_erfnet_infer_encoder_offset(plan.handle)
         nenc = N * (H // 8) * (W // 8) * 128
         if mode == 2:
             enc = ws[off: off + 2 * nenc].view(torch.bfloat16)
         else:
             enc = ws[off: off + 4 * nenc].view(torch.float32)
-        return logits, enc.view(N, H // 8, W // 8, 128)
+        return enc.view(N, H // 8, W // 8, 128)
+
+    def _lane_infer(self, x, grid, zero_rows, order, reg_ls, y_offset, act_kind, use_cholesky, want_encoder):
+        """Image -> (beta (N,K,order+1) fp64, status (N*K) int32, NHWC encoder output or None) in one C call (lf_lane_infer:
+        the inference engine up to the last decoder layer, the fused head + activation + row mask + moments kernel, the solve);
+        head 0.  Neither logits nor weight maps are written."""
+        lib = _lib.load()
+        x = x.contiguous().float()
+        N, C, H, W = x.shape
+        assert C == self.in_channels, "expected %d input channels, got %d" % (self.in_channels, C)
+        plan = self._plan(N, H, W)
+        K = self.out_channels
+        mode = _PRECISIONS[self.precision]
+        _lib.check(lib.lf_erfnet_set_precision(plan.handle, mode), "lf_erfnet_set_precision")
+        nbytes = lib.lf_lane_infer_workspace_bytes(plan.handle, mode, K, order)
+        if nbytes == 0:
+            raise _lib.LaneFitLibraryError("lf_lane_infer_workspace_bytes: unsupported mode / order (%s, %d)" % (self.precision, order))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        beta = torch.empty(N, K, order + 1, dtype=torch.float64, device=x.device)
+        status = torch.empty(N * K, dtype=torch.int32, device=x.device)
+        params = [p.detach() for p in self._ordered_params()]
+        for p in params:
+            assert p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+        running = self._ptrs.get("running", self._running_buffers())
+        grid = grid.contiguous()
+        assert grid.dtype == torch.float32 and grid.shape[-2:] == (H * W, 2), (grid.shape, H, W)
+        gstride = H * W * 2 if grid.dim() == 3 and grid.shape[0] > 1 else 0      # (as ops.WLSFit)
+        _lib.check(lib.lf_lane_infer(plan.handle, _lib.ptr(x), self._ptrs.get("params", params),
+                                     _lib.ptr(self._device_ptr_table(params)), running, _lib.ptr(grid), gstride, int(zero_rows),
+                                     int(order), float(reg_ls), float(y_offset), int(act_kind), int(bool(use_cholesky)), None,
+                                     _lib.ptr(beta), _lib.ptr(status), _lib.ptr(ws), nbytes, _lib.stream()), "lf_lane_infer")
+        return beta, status, (self._infer_encoder_view(plan, ws, mode) if want_encoder else None)
 
     # ---- forward -----------------------------------------------------------------------
     def forward(self, input, flag, only_encode=False):

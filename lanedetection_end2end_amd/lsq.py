@@ -103,6 +103,51 @@ class _LaneFitNet(nn.Module):
         return fit.split_lanes(beta, self.nclasses, self.beta_dtype), masked
 
 
+    @torch.no_grad()
+    def detect(self, input, gt_line=None):
+        """Image -> ``(beta0, beta1, beta2, beta3, line, horizon)``: the fields of ``forward`` that test time consumes
+        (``validate()``, BP/test.py:35-88), with ``forward``'s dtypes, shapes and ``None``s, on the inference engine whatever the
+        ``inference_engine`` switches say and whatever the caller's grad state.  Eval mode only (the wrapper, its backbone and its heads).
+
+        End-to-end models run ONE C call from the image to the lane coefficients (``lf_lane_infer``: the backbone's inference
+        schedule, then head + activation + row mask + moments fused -- neither the logits nor the weight maps are written) and the
+        ``--clas`` heads with their BatchNorms folded in, on the encoder output inside that call's workspace.  A segmentation-mode
+        model (``end_to_end=False``) runs the inference-engine forward, ``lf_seg_maps`` and the existing fit; ``gt_line`` is what
+        BP's ``forward`` takes for its "prevent singular matrix" borrow (lanes flagged in it fit map [0, 0]): pass the same tensor
+        to get ``forward``'s coefficients for such lanes; the default ``None`` borrows nothing, as test time has no labels.
+        ``last_status`` is set; a singular system raises ``RuntimeError`` under ``check_singular`` as in ``forward``."""
+        # (the wrapper, the backbone and the heads: four flags, not a walk over ~300 modules on every call)
+        parts = (self, self.net) + ((self.line_classification, self.horizon_estimation) if self.classification_branch else ())
+        if any(m.training for m in parts):
+            raise RuntimeError("lanefit detect() needs the model, its backbone and its heads in eval mode (model.eval()): it folds "
+                               "the BatchNorm running statistics into the convolutions")
+        if not input.is_cuda:
+            raise erfnet._lib.LaneFitLibraryError("lanefit detect needs its input on the MI355X; there is no CPU path")
+        reg = 0.0 if (self.use_cholesky and self.cholesky_drops_reg) else self.reg_ls
+        if not self.end_to_end:
+            was = self.net.inference_engine
+            self.net.inference_engine = True
+            try:
+                output = self.net(input, False)[1]       # forward's flag: end_to_end * pretrained = 0 (the segmentation head)
+            finally:
+                self.net.inference_engine = was
+            maps = self._seg_maps(output, gt_line)
+            beta, _, status = fit.fit_lanes(maps, self.grid_on(output.device), self.zero_rows, self.order, reg, self.y_offset,
+                                            "none", self.use_cholesky, False, self.check_singular)
+            self.last_status = status
+            return fit.split_lanes(beta, self.nclasses, self.beta_dtype) + (None, None)
+        beta, status, enc = self.net._lane_infer(input, self.grid_on(input.device), self.zero_rows, self.order, reg, self.y_offset,
+                                                 ops.ACT_KINDS[self.activation_name], self.use_cholesky, self.classification_branch)
+        self.last_status = status
+        if self.check_singular:
+            ops._raise_if_singular(status, 1 if self.use_cholesky else 0)
+        line = horizon = None
+        if self.classification_branch:
+            enc = enc.permute(0, 3, 1, 2)             # logical NCHW, channels-last memory (as Net.forward hands it out)
+            line, horizon = self.line_classification(enc, folded=True), self.horizon_estimation(enc, folded=True)
+        return fit.split_lanes(beta, self.nclasses, self.beta_dtype) + (line, horizon)
+
+
 class BEVNet(_LaneFitNet):
     """``Net(args)``; ``forward(input, end_to_end) ->
     (beta0, beta1, beta2, beta3, masked, M, output, line, horizon)`` (BEV/Networks/LSQ_layer.py:290-326);
