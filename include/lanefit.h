@@ -37,7 +37,9 @@ extern "C" {
                                  lf_convchain_set_precision / _workspace_bytes_for, lf_poolflat_bf16_*, lf_pointwise_bf16_*, and
                                  lf_erfnet_backward's grad_encoder in mode 2 (the --clas heads and only_encode in bf16);
                                  additions since 5 (inference engine): lf_erfnet_infer*, lf_erfnet_infer_range*, lf_convchain_infer*,
-                                 lf_head_fit, lf_lane_infer* */
+                                 lf_head_fit, lf_lane_infer*;
+                                 additions since 5 (homography through the fit): lf_theta_grid, lf_theta_grid_bwd*, lf_wls_fwd_theta,
+                                 lf_wls_bwd_theta*, lf_wls_bwd_grid */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -243,6 +245,37 @@ int lf_lane_infer(const lf_erfnet_plan* plan, const float* img, const float* con
                   float* const* running_host, const float* grid_xy, long grid_batch_stride, int zero_rows, int order, double reg_ls,
                   double y_offset, int act_kind, int use_cholesky, float* logits_or_null, double* beta, int32_t* status,
                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* additions since 5 -- homography through the fit (BEV/Networks/LSQ_layer.py:84-87 ProjectiveGridGenerator.forward as a kernel, and
+ * the gradients the reference's autograd carries to the grid and to theta):
+ *   theta  (3,3) fp32 shared by all images (theta_batch_stride = 0) or (N,3,3) per image (theta_batch_stride = 9)
+ *   xs (W), ys (H)  fp32 base coordinates, made on the host with the reference's torch.linspace calls (xs 16-byte aligned)
+ *   (a, b, c) = theta [xs[j], ys[i], 1];  grid = (a / c, b / c) in fp32
+ * lf_theta_grid       grid_xy out (N | 1, H*W, 2) fp32.
+ * lf_theta_grid_bwd   grad_grid (same shape) -> grad_theta (N | 1, 3, 3) fp64; pixels whose grad_grid is exactly (0, 0) are
+ *                     skipped (masked rows: a pole there contributes nothing); workspace >= lf_theta_grid_bwd_workspace_bytes(N).
+ * lf_wls_fwd_theta    lf_wls_fwd with the grid computed inline: same outputs, same bits as lf_wls_fwd on lf_theta_grid's grid.
+ * lf_wls_bwd_theta    lf_wls_bwd's grad_logits plus grad_theta (N | 1, 3, 3) fp64 in the same pass: fp64 per-workgroup partials
+ *                     in workspace (>= lf_wls_bwd_theta_workspace_bytes(N,K)), added in a fixed order by a second launch; no
+ *                     atomics, no (N,H*W,2) gradient tensor.
+ * lf_wls_bwd_grid     d loss / d grid_xy of lf_wls_fwd (arguments as lf_wls_bwd): grad_grid (N,H*W,2) fp32, or (H*W,2) summed
+ *                     over images and lanes in a fixed order when grid_batch_stride = 0; masked rows are written as 0. */
+int lf_theta_grid(const float* theta, long theta_batch_stride, const float* xs, const float* ys, int N, int H, int W,
+                  float* grid_xy, void* stream);
+size_t lf_theta_grid_bwd_workspace_bytes(int N);
+int lf_theta_grid_bwd(const float* theta, long theta_batch_stride, const float* xs, const float* ys, const float* grad_grid,
+                      int N, int H, int W, double* grad_theta, void* workspace, void* stream);
+int lf_wls_fwd_theta(const float* logits, const float* theta, long theta_batch_stride, const float* xs, const float* ys,
+                     int N, int K, int H, int W, int zero_rows, int order, double reg, double y_offset, int act_kind, int solver,
+                     double* beta, double* zinv, float* masked, void* partials, int32_t* status, void* stream);
+size_t lf_wls_bwd_theta_workspace_bytes(int N, int K);
+int lf_wls_bwd_theta(const float* logits, const float* theta, long theta_batch_stride, const float* xs, const float* ys,
+                     int N, int K, int H, int W, int zero_rows, int order, double y_offset, int act_kind, const double* beta,
+                     const double* zinv, const double* grad_beta, float* grad_logits, double* grad_theta, void* workspace,
+                     void* stream);
+int lf_wls_bwd_grid(const float* logits, const float* grid_xy, long grid_batch_stride, int N, int K, int H, int W,
+                    int zero_rows, int order, double y_offset, int act_kind, const double* beta, const double* zinv,
+                    const double* grad_beta, float* grad_grid, void* stream);
 
 /* Block-level surface (round 4): a contiguous range [first, last) of the plan's layers (module order: 0 =
  * encoder.initial_block, 1..15 = encoder.layers[0..14], 16..21 = decoder.layers[0..5]) as one call, inside the plan of the

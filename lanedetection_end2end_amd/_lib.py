@@ -109,6 +109,13 @@ def _declare(lib):
         "lf_head_fit": (I, [P, I, P, P, P, L, I, I, I, I, I, I, D, D, I, I, P, P, P, P, P, P]),
         "lf_lane_infer_workspace_bytes": (c_size_t, [P, I, I, I]),
         "lf_lane_infer": (I, [P, P, P, P, P, P, L, I, I, D, D, I, I, P, P, P, P, c_size_t, P]),
+        "lf_theta_grid": (I, [P, L, P, P, I, I, I, P, P]),
+        "lf_theta_grid_bwd_workspace_bytes": (c_size_t, [I]),
+        "lf_theta_grid_bwd": (I, [P, L, P, P, P, I, I, I, P, P, P]),
+        "lf_wls_fwd_theta": (I, [P, P, L, P, P, I, I, I, I, I, I, D, D, I, I, P, P, P, P, P, P]),
+        "lf_wls_bwd_theta_workspace_bytes": (c_size_t, [I, I]),
+        "lf_wls_bwd_theta": (I, [P, P, L, P, P, I, I, I, I, I, I, D, I, P, P, P, P, P, P, P]),
+        "lf_wls_bwd_grid": (I, [P, P, L, I, I, I, I, I, I, D, I, P, P, P, P, P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {

@@ -694,6 +694,465 @@ extern "C" int lf_wls_bwd(const float* logits, const float* grid_xy, long grid_b
 }
 
 // ---------------------------------------------------------------------------------------
+// Homography through the fit (BEV/Networks/LSQ_layer.py:84-87 ProjectiveGridGenerator.forward + autograd of the fit w.r.t. its
+// grid): theta (3,3) shared or (N,3,3) per image, the base coordinates from two host-made tables xs (W) / ys (H).
+//   (a, b, c) = theta [px, py, 1],  gx = a / c,  gy = b / c          (fp32, one fixed contraction: every kernel here agrees bit for bit)
+// With v = Z^-1 gbeta, q = Y.v, r = x - Y.beta, s = w^2, y = y_off - gy (wls_bwd_kernel's notation), per pixel and lane
+//   dL/dgx = s q,   dL/dgy = -sum_k s (r v_k - q beta_k) (d - k) y^(d-k-1)
+//   dL/dtheta_0 = sum (dgx / c) p,  dL/dtheta_1 = sum (dgy / c) p,  dL/dtheta_2 = sum -((dgx gx + dgy gy) / c) p,   p = [px, py, 1]
+// The nine sums run in fp64 as per-workgroup partials in a caller-owned workspace, added in a fixed order by a second small
+// launch: no atomics, two runs are bit-identical.  Masked rows are neither read nor evaluated (a pole there stays harmless).
+// ---------------------------------------------------------------------------------------
+namespace {
+
+constexpr int TH_CHUNKS = 64;    // workgroups per (image, lane) of the backward launches = partial rows per (image, lane)
+
+struct Theta { float t[9]; };
+__device__ __forceinline__ Theta theta_load(const float* __restrict__ theta, long theta_bs, int n) {
+    Theta h;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) h.t[i] = theta[(long)n * theta_bs + i];
+    return h;
+}
+__device__ __forceinline__ void theta_point(const Theta& h, float px, float py, float& gx, float& gy, float& c) {
+    const float a = fmaf(py, h.t[1], fmaf(px, h.t[0], h.t[2]));
+    const float b = fmaf(py, h.t[4], fmaf(px, h.t[3], h.t[5]));
+    c = fmaf(py, h.t[7], fmaf(px, h.t[6], h.t[8]));
+    gx = a / c;
+    gy = b / c;
+}
+
+// nine fp64 sums of one thread: rows (dgx / c, dgy / c, -(dgx gx + dgy gy) / c) times (px, py, 1)
+struct ThetaAcc {
+    double v[9];
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) v[i] = 0.0;
+    }
+    __device__ __forceinline__ void add(double dgx, double dgy, float gx, float gy, float c, float px, float py) {
+        const double ic = 1.0 / (double)c;
+        const double t0 = dgx * ic, t1 = dgy * ic, t2 = -(dgx * (double)gx + dgy * (double)gy) * ic;
+        const double x = (double)px, y = (double)py;
+        v[0] = fma(t0, x, v[0]); v[1] = fma(t0, y, v[1]); v[2] += t0;
+        v[3] = fma(t1, x, v[3]); v[4] = fma(t1, y, v[4]); v[5] += t1;
+        v[6] = fma(t2, x, v[6]); v[7] = fma(t2, y, v[7]); v[8] += t2;
+    }
+    // workgroup sum (wave butterflies, then the waves in order) -> out[0..9)
+    __device__ __forceinline__ void store(double* __restrict__ out) {
+        __shared__ double red[WLS_THREADS / LF_WAVE][9];
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            const double s = lf_wave_sum(v[j]);
+            if (lane == 0) red[wave][j] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < 9) {
+            double s = 0.0;
+#pragma unroll
+            for (int w = 0; w < WLS_THREADS / LF_WAVE; ++w) s += red[w][threadIdx.x];
+            out[threadIdx.x] = s;
+        }
+    }
+};
+
+// Grid from theta: one thread per pixel; grid (N | 1, H*W, 2).
+__global__ __launch_bounds__(WLS_THREADS) void theta_grid_kernel(const float* __restrict__ theta, long theta_bs,
+                                                                const float* __restrict__ xs, const float* __restrict__ ys,
+                                                                int H, int W, float* __restrict__ grid) {
+    const long P = (long)H * W, p = (long)blockIdx.x * WLS_THREADS + threadIdx.x;
+    if (p >= P) return;
+    const int n = blockIdx.y, i = (int)(p / W), j = (int)(p - (long)i * W);
+    const Theta h = theta_load(theta, theta_bs, n);
+    float gx, gy, c;
+    theta_point(h, xs[j], ys[i], gx, gy, c);
+    *reinterpret_cast<float2*>(grid + ((long)n * P + p) * 2) = make_float2(gx, gy);
+}
+
+// Backward of theta_grid_kernel: grad_grid (N | 1, H*W, 2) fp32 -> per-chunk partials of the nine sums per image.  A pixel whose
+// incoming gradient is exactly (0, 0) -- a masked row -- contributes nothing and is not evaluated.
+__global__ __launch_bounds__(WLS_THREADS) void theta_grid_bwd_kernel(const float* __restrict__ theta, long theta_bs,
+                                                                    const float* __restrict__ xs, const float* __restrict__ ys,
+                                                                    const float* __restrict__ ggrid, int H, int W,
+                                                                    double* __restrict__ partials) {
+    const long P = (long)H * W;
+    const int n = blockIdx.y;
+    const Theta h = theta_load(theta, theta_bs, n);
+    ThetaAcc acc;
+    acc.zero();
+    for (long p = (long)blockIdx.x * WLS_THREADS + threadIdx.x; p < P; p += (long)gridDim.x * WLS_THREADS) {
+        const float2 g = *reinterpret_cast<const float2*>(ggrid + ((long)n * P + p) * 2);
+        if (g.x == 0.f && g.y == 0.f) continue;
+        const int i = (int)(p / W), j = (int)(p - (long)i * W);
+        const float px = xs[j], py = ys[i];
+        float gx, gy, c;
+        theta_point(h, px, py, gx, gy, c);
+        acc.add((double)g.x, (double)g.y, gx, gy, c, px, py);
+    }
+    acc.store(partials + ((long)n * gridDim.x + blockIdx.x) * 9);
+}
+
+// grad_theta[o] = sum of `rows` consecutive partial rows of nine, one wave per output matrix: each lane adds its rows in
+// ascending order, then one butterfly.
+__global__ __launch_bounds__(LF_WAVE) void theta_finish_kernel(const double* __restrict__ partials, int rows,
+                                                              double* __restrict__ grad_theta) {
+    const double* p = partials + (long)blockIdx.x * rows * 9;
+    double s[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) s[j] = 0.0;
+    for (int r = threadIdx.x; r < rows; r += LF_WAVE)
+#pragma unroll
+        for (int j = 0; j < 9; ++j) s[j] += p[(long)r * 9 + j];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        const double t = lf_wave_sum(s[j]);
+        if (threadIdx.x == 0) grad_theta[(long)blockIdx.x * 9 + j] = t;
+    }
+}
+
+// wls_moments_kernel with the grid computed inline from theta and the two tables: the 8 B/pixel grid read is gone.
+template <int ORDER, int VEC>
+__global__ __launch_bounds__(WLS_THREADS) void wls_moments_theta_kernel(
+    const float* __restrict__ logits, const float* __restrict__ theta, long theta_bs, const float* __restrict__ xs,
+    const float* __restrict__ ys, int K, int H, int W, int zero_rows, float y_off, int act_kind, float* __restrict__ masked,
+    double* __restrict__ partials) {
+    using M = Moments<ORDER>;
+    const int nk = blockIdx.y, chunk = blockIdx.x;
+    const long P = (long)H * W;
+    const float* o = logits + (long)nk * P;
+    const Theta h = theta_load(theta, theta_bs, nk / K);
+    float* mo = masked ? masked + (long)nk * P : nullptr;
+    const long first = (long)zero_rows * W;
+    const long units = (P - first) / VEC;
+    const long u0 = units * chunk / WLS_CHUNKS, u1 = units * (chunk + 1) / WLS_CHUNKS;
+    M acc;
+    acc.zero();
+    for (long u = u0 + threadIdx.x; u < u1; u += WLS_THREADS) {
+        const long p = first + u * VEC;
+        const int i = (int)(p / W), j = (int)(p - (long)i * W);
+        const float py = ys[i];
+        float gx, gy, c;
+        if constexpr (VEC == 4) {                       // W % 4 == 0: the four pixels share a row
+            const float4 ov = *reinterpret_cast<const float4*>(o + p);
+            const float4 px = *reinterpret_cast<const float4*>(xs + j);
+            float4 w;
+            w.x = act_fwd(ov.x, act_kind); w.y = act_fwd(ov.y, act_kind);
+            w.z = act_fwd(ov.z, act_kind); w.w = act_fwd(ov.w, act_kind);
+            theta_point(h, px.x, py, gx, gy, c); acc.add(w.x, gx, gy, y_off);
+            theta_point(h, px.y, py, gx, gy, c); acc.add(w.y, gx, gy, y_off);
+            theta_point(h, px.z, py, gx, gy, c); acc.add(w.z, gx, gy, y_off);
+            theta_point(h, px.w, py, gx, gy, c); acc.add(w.w, gx, gy, y_off);
+            if (mo) *reinterpret_cast<float4*>(mo + p) = w;
+        } else {
+            const float w = act_fwd(o[p], act_kind);
+            theta_point(h, xs[j], py, gx, gy, c);
+            acc.add(w, gx, gy, y_off);
+            if (mo) mo[p] = w;
+        }
+    }
+    if (mo) {
+        const long zu = first / VEC, z0 = zu * chunk / WLS_CHUNKS, z1 = zu * (chunk + 1) / WLS_CHUNKS;
+        for (long u = z0 + threadIdx.x; u < z1; u += WLS_THREADS) {
+            if constexpr (VEC == 4) *reinterpret_cast<float4*>(mo + u * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+            else mo[u] = 0.f;
+        }
+    }
+    __shared__ double red[WLS_THREADS / LF_WAVE][M::N];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < M::N; ++j) {
+        const double s = lf_wave_sum(acc.v[j]);
+        if (lane == 0) red[wave][j] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < M::N) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < WLS_THREADS / LF_WAVE; ++w) s += red[w][threadIdx.x];
+        partials[((long)nk * WLS_CHUNKS + chunk) * M::N + threadIdx.x] = s;
+    }
+}
+
+// The per-pixel terms of one lane: grad_logits as wls_bwd_kernel's `one`, and (dL/dgx, dL/dgy) of that lane.
+template <int D>
+__device__ __forceinline__ float fit_pixel_bwd(const double (&b)[D], const double (&v)[D], float ov, float gx, float gy, float y_off,
+                                               int act_kind, double& dgx, double& dgy) {
+    const double y = (double)(y_off - gy);
+    double yv = v[0], yb = b[0];
+#pragma unroll
+    for (int i = 1; i < D; ++i) { yv = fma(yv, y, v[i]); yb = fma(yb, y, b[i]); }
+    const double w = (double)act_fwd(ov, act_kind);
+    const double r = (double)gx - yb, s = w * w;
+    double dy = 0.0;                                      // sum_k (r v_k - q beta_k) (d - k) y^(d-k-1), Horner
+#pragma unroll
+    for (int k = 0; k < D - 1; ++k) dy = fma(dy, y, (double)(D - 1 - k) * (r * v[k] - yv * b[k]));
+    dgx = s * yv;
+    dgy = -s * dy;
+    return (float)(2.0 * w * yv * r * (double)act_bwd(ov, act_kind));
+}
+
+template <int D>
+__device__ __forceinline__ void fit_lane_consts(const double* __restrict__ beta, const double* __restrict__ zinv,
+                                                const double* __restrict__ gbeta, long nk, double (&b)[D], double (&v)[D]) {
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        b[i] = beta[nk * D + i];
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) s = fma(zinv[(nk * D + i) * D + j], gbeta[nk * D + j], s);
+        v[i] = s;
+    }
+}
+
+// wls_bwd_kernel with the grid inline, plus the nine theta sums of this workgroup's pixels -> partials[(nk, blockIdx.x)].
+template <int ORDER, int VEC>
+__global__ __launch_bounds__(WLS_THREADS) void wls_bwd_theta_kernel(
+    const float* __restrict__ logits, const float* __restrict__ theta, long theta_bs, const float* __restrict__ xs,
+    const float* __restrict__ ys, int K, int H, int W, int zero_rows, float y_off, int act_kind, const double* __restrict__ beta,
+    const double* __restrict__ zinv, const double* __restrict__ gbeta, float* __restrict__ gout, double* __restrict__ partials) {
+    constexpr int D = ORDER + 1;
+    const int nk = blockIdx.y;
+    const long P = (long)H * W;
+    const float* o = logits + (long)nk * P;
+    float* go = gout + (long)nk * P;
+    const Theta h = theta_load(theta, theta_bs, nk / K);
+    double b[D], v[D];
+    fit_lane_consts<D>(beta, zinv, gbeta, nk, b, v);
+    const long first = (long)zero_rows * W;
+    ThetaAcc acc;
+    acc.zero();
+    auto one = [&](float ov, float px, float py) -> float {
+        float gx, gy, c;
+        double dgx, dgy;
+        theta_point(h, px, py, gx, gy, c);
+        const float g = fit_pixel_bwd<D>(b, v, ov, gx, gy, y_off, act_kind, dgx, dgy);
+        acc.add(dgx, dgy, gx, gy, c, px, py);
+        return g;
+    };
+    const long units = P / VEC;
+    for (long u = (long)blockIdx.x * WLS_THREADS + threadIdx.x; u < units; u += (long)gridDim.x * WLS_THREADS) {
+        const long p = u * VEC;
+        if constexpr (VEC == 4) {
+            float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (p >= first) {
+                const int i = (int)(p / W), j = (int)(p - (long)i * W);
+                const float py = ys[i];
+                const float4 ov = *reinterpret_cast<const float4*>(o + p);
+                const float4 px = *reinterpret_cast<const float4*>(xs + j);
+                r.x = one(ov.x, px.x, py); r.y = one(ov.y, px.y, py);
+                r.z = one(ov.z, px.z, py); r.w = one(ov.w, px.w, py);
+            }
+            *reinterpret_cast<float4*>(go + p) = r;
+        } else {
+            float r = 0.f;
+            if (p >= first) {
+                const int i = (int)(p / W), j = (int)(p - (long)i * W);
+                r = one(o[p], xs[j], ys[i]);
+            }
+            go[p] = r;
+        }
+    }
+    acc.store(partials + ((long)nk * gridDim.x + blockIdx.x) * 9);
+}
+
+// d loss / d grid of an explicit grid: the thread that owns a pixel adds the lanes (and, for a shared grid, the images) in
+// ascending order in fp64 and writes one float2; masked rows are written as 0.  The lane constants (beta, v) sit in LDS.
+template <int ORDER>
+__global__ __launch_bounds__(WLS_THREADS) void wls_bwd_grid_kernel(
+    const float* __restrict__ logits, const float* __restrict__ grid, long grid_bs, int NK, int H, int W, int zero_rows, float y_off,
+    int act_kind, const double* __restrict__ beta, const double* __restrict__ zinv, const double* __restrict__ gbeta,
+    float* __restrict__ ggrid) {
+    constexpr int D = ORDER + 1;
+    extern __shared__ double lane_consts[];              // [NK][2][D]
+    const long P = (long)H * W;
+    const long nk0 = (long)blockIdx.y * NK;              // NK = lanes summed by one thread: K (per-image grid) or N*K (shared)
+    for (int t = threadIdx.x; t < NK; t += WLS_THREADS) {
+        double b[D], v[D];
+        fit_lane_consts<D>(beta, zinv, gbeta, nk0 + t, b, v);
+#pragma unroll
+        for (int i = 0; i < D; ++i) { lane_consts[(t * 2) * D + i] = b[i]; lane_consts[(t * 2 + 1) * D + i] = v[i]; }
+    }
+    __syncthreads();
+    const long p = (long)blockIdx.x * WLS_THREADS + threadIdx.x;
+    if (p >= P) return;
+    float2 out = make_float2(0.f, 0.f);
+    if (p >= (long)zero_rows * W) {
+        const float2 g = *reinterpret_cast<const float2*>(grid + (long)blockIdx.y * grid_bs + 2 * p);
+        double sx = 0.0, sy = 0.0;
+        for (int t = 0; t < NK; ++t) {
+            double b[D], v[D], dgx, dgy;
+#pragma unroll
+            for (int i = 0; i < D; ++i) { b[i] = lane_consts[(t * 2) * D + i]; v[i] = lane_consts[(t * 2 + 1) * D + i]; }
+            fit_pixel_bwd<D>(b, v, logits[(nk0 + t) * P + p], g.x, g.y, y_off, act_kind, dgx, dgy);
+            sx += dgx;
+            sy += dgy;
+        }
+        out = make_float2((float)sx, (float)sy);
+    }
+    *reinterpret_cast<float2*>(ggrid + ((long)blockIdx.y * P + p) * 2) = out;
+}
+
+int theta_bwd_chunks(int H, int W) {
+    const long units = (long)H * W / (W % 4 == 0 ? 4 : 1);
+    const int gx = lf_cdiv(units, WLS_THREADS);
+    return gx > TH_CHUNKS ? TH_CHUNKS : gx;
+}
+
+template <int ORDER>
+int wls_fwd_theta_launch(const float* logits, const float* theta, long tbs, const float* xs, const float* ys, int N, int K, int H,
+                         int W, int zr, double reg, double y_off, int act, int solver, double* beta, double* zinv, float* masked,
+                         double* partials, int32_t* status, hipStream_t st) {
+    dim3 g1(WLS_CHUNKS, N * K);
+    if (W % 4 == 0)
+        hipLaunchKernelGGL((wls_moments_theta_kernel<ORDER, 4>), g1, dim3(WLS_THREADS), 0, st, logits, theta, tbs, xs, ys, K, H, W,
+                           zr, (float)y_off, act, masked, partials);
+    else
+        hipLaunchKernelGGL((wls_moments_theta_kernel<ORDER, 1>), g1, dim3(WLS_THREADS), 0, st, logits, theta, tbs, xs, ys, K, H, W,
+                           zr, (float)y_off, act, masked, partials);
+    LF_CHECK_LAUNCH("wls_moments_theta");
+    hipLaunchKernelGGL((wls_solve_kernel<ORDER>), dim3(lf_cdiv(N * K, 64)), dim3(64), 0, st, partials, N * K, reg, solver, beta,
+                       zinv, status);
+    LF_CHECK_LAUNCH("wls_solve");
+    return 0;
+}
+
+template <int ORDER>
+int wls_bwd_theta_launch(const float* logits, const float* theta, long tbs, const float* xs, const float* ys, int N, int K, int H,
+                         int W, int zr, double y_off, int act, const double* beta, const double* zinv, const double* gbeta,
+                         float* gout, double* gtheta, double* partials, hipStream_t st) {
+    const int chunks = theta_bwd_chunks(H, W);
+    dim3 g1(chunks, N * K);
+    if (W % 4 == 0)
+        hipLaunchKernelGGL((wls_bwd_theta_kernel<ORDER, 4>), g1, dim3(WLS_THREADS), 0, st, logits, theta, tbs, xs, ys, K, H, W, zr,
+                           (float)y_off, act, beta, zinv, gbeta, gout, partials);
+    else
+        hipLaunchKernelGGL((wls_bwd_theta_kernel<ORDER, 1>), g1, dim3(WLS_THREADS), 0, st, logits, theta, tbs, xs, ys, K, H, W, zr,
+                           (float)y_off, act, beta, zinv, gbeta, gout, partials);
+    LF_CHECK_LAUNCH("wls_bwd_theta");
+    // per-image theta: K lanes x chunks rows each; shared theta: all N*K lanes into one matrix
+    const int outs = tbs ? N : 1, rows = (tbs ? K : N * K) * chunks;
+    hipLaunchKernelGGL(theta_finish_kernel, dim3(outs), dim3(LF_WAVE), 0, st, partials, rows, gtheta);
+    LF_CHECK_LAUNCH("theta_finish");
+    return 0;
+}
+
+}  // namespace
+
+#define LF_THETA_REQUIRE(name)                                                                                         \
+    LF_REQUIRE(theta && xs && ys, name ": null pointer");                                                              \
+    LF_REQUIRE(theta_batch_stride == 0 || theta_batch_stride == 9, name ": theta_batch_stride %ld is neither 0 nor 9", \
+               theta_batch_stride);                                                                                    \
+    LF_REQUIRE(N > 0 && H > 0 && W > 0, name ": bad shape %d %d %d", N, H, W);                                         \
+    LF_REQUIRE(((size_t)xs & 15) == 0, name ": the x table is read as vectors: misaligned")
+
+// theta (3,3) fp32 (theta_batch_stride 0) or (N,3,3) (9); xs (W), ys (H) fp32 base coordinates; grid out (N | 1, H*W, 2) fp32.
+extern "C" int lf_theta_grid(const float* theta, long theta_batch_stride, const float* xs, const float* ys, int N, int H, int W,
+                             float* grid_xy, void* stream) {
+    LF_THETA_REQUIRE("lf_theta_grid");
+    LF_REQUIRE(grid_xy && ((size_t)grid_xy & 7) == 0, "lf_theta_grid: grid null or misaligned");
+    hipLaunchKernelGGL(theta_grid_kernel, dim3(lf_cdiv((long)H * W, WLS_THREADS), theta_batch_stride ? N : 1), dim3(WLS_THREADS), 0,
+                       (hipStream_t)stream, theta, theta_batch_stride, xs, ys, H, W, grid_xy);
+    LF_CHECK_LAUNCH("theta_grid");
+    return 0;
+}
+
+extern "C" size_t lf_theta_grid_bwd_workspace_bytes(int N) { return (size_t)N * TH_CHUNKS * 9 * sizeof(double); }
+
+// grad_grid (N | 1, H*W, 2) fp32 (the shape lf_theta_grid wrote) -> grad_theta (N | 1, 3, 3) fp64.
+extern "C" int lf_theta_grid_bwd(const float* theta, long theta_batch_stride, const float* xs, const float* ys,
+                                 const float* grad_grid, int N, int H, int W, double* grad_theta, void* workspace, void* stream) {
+    LF_THETA_REQUIRE("lf_theta_grid_bwd");
+    LF_REQUIRE(grad_grid && grad_theta && workspace && ((size_t)grad_grid & 7) == 0, "lf_theta_grid_bwd: null or misaligned pointer");
+    hipStream_t st = (hipStream_t)stream;
+    int chunks = lf_cdiv((long)H * W, WLS_THREADS);
+    if (chunks > TH_CHUNKS) chunks = TH_CHUNKS;
+    const int outs = theta_batch_stride ? N : 1;
+    hipLaunchKernelGGL(theta_grid_bwd_kernel, dim3(chunks, outs), dim3(WLS_THREADS), 0, st, theta, theta_batch_stride, xs, ys,
+                       grad_grid, H, W, (double*)workspace);
+    LF_CHECK_LAUNCH("theta_grid_bwd");
+    hipLaunchKernelGGL(theta_finish_kernel, dim3(outs), dim3(LF_WAVE), 0, st, (const double*)workspace, chunks, grad_theta);
+    LF_CHECK_LAUNCH("theta_finish");
+    return 0;
+}
+
+// lf_wls_fwd with the grid computed inline from theta: arguments as lf_wls_fwd with (theta, theta_batch_stride, xs, ys) in the
+// place of (grid_xy, grid_batch_stride); partials >= lf_wls_workspace_bytes.
+extern "C" int lf_wls_fwd_theta(const float* logits, const float* theta, long theta_batch_stride, const float* xs, const float* ys,
+                                int N, int K, int H, int W, int zero_rows, int order, double reg, double y_offset, int act_kind,
+                                int solver, double* beta, double* zinv, float* masked, void* partials, int32_t* status,
+                                void* stream) {
+    LF_THETA_REQUIRE("lf_wls_fwd_theta");
+    LF_REQUIRE(logits && beta && zinv && partials && status && K > 0, "lf_wls_fwd_theta: null pointer or K = %d", K);
+    LF_REQUIRE(zero_rows >= 0 && zero_rows < H, "lf_wls_fwd_theta: zero_rows %d out of [0,%d)", zero_rows, H);
+    LF_REQUIRE(order >= 0 && order <= 3, "lf_wls_fwd_theta: order %d not in 0..3", order);
+    LF_REQUIRE(act_kind >= 0 && act_kind <= LF_ACT_NONE, "lf_wls_fwd_theta: bad activation %d", act_kind);
+    hipStream_t st = (hipStream_t)stream;
+    double* p = (double*)partials;
+    switch (order) {
+        case 0: return wls_fwd_theta_launch<0>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
+        case 1: return wls_fwd_theta_launch<1>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
+        case 2: return wls_fwd_theta_launch<2>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
+        default: return wls_fwd_theta_launch<3>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
+    }
+}
+
+extern "C" size_t lf_wls_bwd_theta_workspace_bytes(int N, int K) { return (size_t)N * K * TH_CHUNKS * 9 * sizeof(double); }
+
+// lf_wls_bwd on the inline route: grad_logits as lf_wls_bwd writes it, and grad_theta (N | 1, 3, 3) fp64 in the same pass;
+// workspace >= lf_wls_bwd_theta_workspace_bytes(N, K).
+extern "C" int lf_wls_bwd_theta(const float* logits, const float* theta, long theta_batch_stride, const float* xs, const float* ys,
+                                int N, int K, int H, int W, int zero_rows, int order, double y_offset, int act_kind,
+                                const double* beta, const double* zinv, const double* grad_beta, float* grad_logits,
+                                double* grad_theta, void* workspace, void* stream) {
+    LF_THETA_REQUIRE("lf_wls_bwd_theta");
+    LF_REQUIRE(logits && beta && zinv && grad_beta && grad_logits && grad_theta && workspace && K > 0,
+               "lf_wls_bwd_theta: null pointer or K = %d", K);
+    LF_REQUIRE(zero_rows >= 0 && zero_rows < H, "lf_wls_bwd_theta: zero_rows %d out of [0,%d)", zero_rows, H);
+    LF_REQUIRE(order >= 0 && order <= 3, "lf_wls_bwd_theta: order %d not in 0..3", order);
+    LF_REQUIRE(act_kind >= 0 && act_kind <= LF_ACT_NONE, "lf_wls_bwd_theta: bad activation %d", act_kind);
+    hipStream_t st = (hipStream_t)stream;
+    double* p = (double*)workspace;
+    switch (order) {
+        case 0: return wls_bwd_theta_launch<0>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, y_offset, act_kind, beta, zinv, grad_beta, grad_logits, grad_theta, p, st);
+        case 1: return wls_bwd_theta_launch<1>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, y_offset, act_kind, beta, zinv, grad_beta, grad_logits, grad_theta, p, st);
+        case 2: return wls_bwd_theta_launch<2>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, y_offset, act_kind, beta, zinv, grad_beta, grad_logits, grad_theta, p, st);
+        default: return wls_bwd_theta_launch<3>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, y_offset, act_kind, beta, zinv, grad_beta, grad_logits, grad_theta, p, st);
+    }
+}
+#undef LF_THETA_REQUIRE
+
+// d loss / d grid of lf_wls_fwd's explicit grid (arguments as lf_wls_bwd): grad_grid (N, H*W, 2) fp32, or (H*W, 2) summed over
+// the images when grid_batch_stride = 0.
+extern "C" int lf_wls_bwd_grid(const float* logits, const float* grid_xy, long grid_batch_stride, int N, int K, int H, int W,
+                               int zero_rows, int order, double y_offset, int act_kind, const double* beta, const double* zinv,
+                               const double* grad_beta, float* grad_grid, void* stream) {
+    LF_REQUIRE(logits && grid_xy && beta && zinv && grad_beta && grad_grid, "lf_wls_bwd_grid: null pointer");
+    LF_REQUIRE(N > 0 && K > 0 && H > 0 && W > 0, "lf_wls_bwd_grid: bad shape");
+    LF_REQUIRE(zero_rows >= 0 && zero_rows < H, "lf_wls_bwd_grid: zero_rows %d out of [0,%d)", zero_rows, H);
+    LF_REQUIRE(order >= 0 && order <= 3, "lf_wls_bwd_grid: order %d not in 0..3", order);
+    LF_REQUIRE(act_kind >= 0 && act_kind <= LF_ACT_NONE, "lf_wls_bwd_grid: bad activation %d", act_kind);
+    LF_REQUIRE(grid_batch_stride % 2 == 0 && ((size_t)grid_xy & 7) == 0 && ((size_t)grad_grid & 7) == 0,
+               "lf_wls_bwd_grid: grid / grad_grid are read and written as float2: misaligned");
+    const int NK = grid_batch_stride ? K : N * K;
+    const size_t lds = (size_t)NK * 2 * (order + 1) * sizeof(double);
+    LF_REQUIRE(lds <= 48 * 1024, "lf_wls_bwd_grid: %d lanes on one grid exceed the LDS table (%zu bytes)", NK, lds);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 g1(lf_cdiv((long)H * W, WLS_THREADS), grid_batch_stride ? N : 1);
+#define LF_BWD_GRID(OO)                                                                                                          \
+    hipLaunchKernelGGL(wls_bwd_grid_kernel<OO>, g1, dim3(WLS_THREADS), lds, st, logits, grid_xy, grid_batch_stride, NK, H, W,    \
+                       zero_rows, (float)y_offset, act_kind, beta, zinv, grad_beta, grad_grid)
+    switch (order) {
+        case 0: LF_BWD_GRID(0); break;
+        case 1: LF_BWD_GRID(1); break;
+        case 2: LF_BWD_GRID(2); break;
+        default: LF_BWD_GRID(3); break;
+    }
+#undef LF_BWD_GRID
+    LF_CHECK_LAUNCH("wls_bwd_grid");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // Area loss (single workgroup; N is a batch size)
 // ---------------------------------------------------------------------------------------
 namespace {

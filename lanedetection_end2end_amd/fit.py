@@ -8,15 +8,24 @@ import torch.nn as nn
 from . import ops
 
 
-def fit_lanes(logits, grid, zero_rows=0, order=2, reg_ls=0.0, y_offset=1.0, activation="square",
-              use_cholesky=False, return_masked=True, check_singular=True):
+def fit_lanes(logits, grid=None, zero_rows=0, order=2, reg_ls=0.0, y_offset=1.0, activation="square",
+              use_cholesky=False, return_masked=True, check_singular=True, theta=None, normalised=True):
     """Fused activation -> row mask -> normal equations -> solve.
 
-    logits (N,K,H,W) fp32 on the GPU, grid (H*W,2) or (N,H*W,2) fp32.
+    logits (N,K,H,W) fp32 on the GPU, grid (H*W,2) or (N,H*W,2) fp32; a grid that requires a gradient receives one.
+    ``theta=`` (instead of ``grid``): a (3,3) or per-image (N,3,3) homography; the grid is computed inline from it and the
+    base coordinates (``normalised``: the BEV tree's [0, 1) coordinates, else the BP tree's pixel indices) and never
+    stored, and ``theta`` receives its gradient (in its own dtype) in the same pass as the logits.
     Returns (beta (N,K,order+1) fp64, masked (N,K,H,W) fp32 or None, status (N*K) int32).
     Raises RuntimeError for a singular system when ``check_singular`` (one D2H sync, like the
     reference's torch.inverse); with check_singular=False inspect ``status`` yourself.
     """
+    if (grid is None) == (theta is None):
+        raise ValueError("fit_lanes takes either grid or theta=, not %s" % ("both" if grid is not None else "neither"))
+    if theta is not None:
+        return ops.WLSFitTheta.apply(logits, theta, bool(normalised), int(zero_rows), int(order), float(reg_ls),
+                                     float(y_offset), ops.ACT_KINDS[activation], 1 if use_cholesky else 0,
+                                     bool(return_masked), bool(check_singular))
     return ops.WLSFit.apply(logits, grid, int(zero_rows), int(order), float(reg_ls), float(y_offset),
                             ops.ACT_KINDS[activation], 1 if use_cholesky else 0, bool(return_masked),
                             bool(check_singular))

@@ -67,6 +67,7 @@ class _LaneFitNet(nn.Module):
         # constant (H*W,2) grid, computed once on the host with the reference's fp32 ops
         self._grid_cpu = geometry.projective_grid(resize, 2 * resize, M, self.normalised)
         self._grid = None
+        self._theta = None              # BEVNet.set_homography: fit through this homography instead of the constant grid
 
     def grid_on(self, device):
         if self._grid is None or self._grid.device != device:
@@ -85,19 +86,31 @@ class _LaneFitNet(nn.Module):
         lanes = 2 if self.nclasses < 3 else 4
         return ops.seg_maps(output, gt_line, self.zero_rows, lanes)
 
+    def _homography(self):
+        """What ``BEVNet.set_homography`` was given: the registered Parameter (followed through ``.cuda()`` / ``.to()``), a plain
+        tensor, or None."""
+        return self._parameters.get("homography", self._theta)
+
+    def _geometry(self, device):
+        """The fit's source of coordinates: the constant grid, or the homography of ``set_homography`` for the inline route."""
+        theta = self._homography()
+        if theta is None:
+            return dict(grid=self.grid_on(device))
+        return dict(theta=theta if theta.device == device else theta.to(device), normalised=self.normalised)
+
     def _fit(self, output, end_to_end, gt_line=None):
-        grid = self.grid_on(output.device)
+        geo = self._geometry(output.device)
         reg = 0.0 if (self.use_cholesky and self.cholesky_drops_reg) else self.reg_ls
         if end_to_end:
-            beta, masked, status = fit.fit_lanes(output, grid, self.zero_rows, self.order, reg, self.y_offset,
+            beta, masked, status = fit.fit_lanes(output, geo.pop("grid", None), self.zero_rows, self.order, reg, self.y_offset,
                                                  self.activation_name, self.use_cholesky, self.return_masked,
-                                                 self.check_singular)
+                                                 self.check_singular, **geo)
         else:
             maps = self._seg_maps(output, gt_line)
             # (the masked rows are zeros already; handing zero_rows to the fit keeps its kernels from reading them at all --
             # at 320 x 640 the BP grid has a pole on a masked row, and 0 * inf is NaN)
-            beta, _, status = fit.fit_lanes(maps, grid, self.zero_rows, self.order, reg, self.y_offset, "none",
-                                            self.use_cholesky, False, self.check_singular)
+            beta, _, status = fit.fit_lanes(maps, geo.pop("grid", None), self.zero_rows, self.order, reg, self.y_offset, "none",
+                                            self.use_cholesky, False, self.check_singular, **geo)
             masked = maps
         self.last_status = status
         return fit.split_lanes(beta, self.nclasses, self.beta_dtype), masked
@@ -132,11 +145,15 @@ class _LaneFitNet(nn.Module):
             finally:
                 self.net.inference_engine = was
             maps = self._seg_maps(output, gt_line)
-            beta, _, status = fit.fit_lanes(maps, self.grid_on(output.device), self.zero_rows, self.order, reg, self.y_offset,
-                                            "none", self.use_cholesky, False, self.check_singular)
+            geo = self._geometry(output.device)
+            beta, _, status = fit.fit_lanes(maps, geo.pop("grid", None), self.zero_rows, self.order, reg, self.y_offset,
+                                            "none", self.use_cholesky, False, self.check_singular, **geo)
             self.last_status = status
             return fit.split_lanes(beta, self.nclasses, self.beta_dtype) + (None, None)
-        beta, status, enc = self.net._lane_infer(input, self.grid_on(input.device), self.zero_rows, self.order, reg, self.y_offset,
+        # (with a homography set, the fused head + fit reads the per-image grid lf_theta_grid makes from it)
+        grid = (self.grid_on(input.device) if self._homography() is None else
+                ops.theta_grid(self._geometry(input.device)["theta"], input.shape[2], input.shape[3], self.normalised))
+        beta, status, enc = self.net._lane_infer(input, grid, self.zero_rows, self.order, reg, self.y_offset,
                                                  ops.ACT_KINDS[self.activation_name], self.use_cholesky, self.classification_branch)
         self.last_status = status
         if self.check_singular:
@@ -160,11 +177,30 @@ class BEVNet(_LaneFitNet):
         self._common_init(args, M, erfnet.Net)
         self.M = torch.from_numpy(M).unsqueeze(0).expand(args.batch_size, 3, 3).float().cuda()
 
+    def set_homography(self, theta):
+        """Fit through ``theta`` -- a (3, 3) or per-image (N, 3, 3) tensor or ``nn.Parameter`` -- instead of the constant grid:
+        ``forward`` computes the grid inline from it (``lf_wls_fwd_theta``), returns it in the tuple's ``M`` slot and lets the
+        gradient reach it (the reference's ``ProjectiveGridGenerator.forward(M)`` on every step, LSQ_layer.py:84-87,318); ``detect``
+        uses it too.  A Parameter is registered as ``homography`` (optimisers and ``state_dict`` see it).  ``None`` restores the
+        constant grid."""
+        self._parameters.pop("homography", None)
+        self._theta = None
+        if theta is None:
+            return
+        if not torch.is_tensor(theta) or theta.dim() not in (2, 3) or tuple(theta.shape[-2:]) != (3, 3):
+            raise ValueError("set_homography takes a (3, 3) or (N, 3, 3) tensor, or None")
+        if isinstance(theta, nn.Parameter):
+            self.register_parameter("homography", theta)
+        else:
+            self._theta = theta
+
     def forward(self, input, end_to_end):
         shared_encoder, output = self.net(input, end_to_end * self.pretrained)
         line, horizon = self._heads(shared_encoder, end_to_end)
         (b0, b1, b2, b3), masked = self._fit(output, end_to_end)
-        return b0, b1, b2, b3, masked, self.M, output, line, horizon
+        theta = self._homography()
+        M = self.M if theta is None else theta
+        return b0, b1, b2, b3, masked, M, output, line, horizon
 
 
 class _BPBackbone(erfnet.Net):

@@ -6,7 +6,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, geometry
 
 ACT_KINDS = {"square": 0, "abs": 1, "relu": 2, "sigmoid": 3, "softplus": 4, "none": 5}
 WEIGHT_FUNCTS = {"none": 0, "linear": 1, "quadratic": 2}
@@ -71,14 +71,122 @@ class WLSFit(torch.autograd.Function):
         logits, grid, beta, zinv = ctx.saved_tensors
         gbs, zero_rows, order, y_offset, act_kind = ctx.cfg
         N, K, H, W = logits.shape
+        want_grid = ctx.needs_input_grad[1]
         if gbeta is None:          # the coefficients were not used downstream
-            return torch.zeros_like(logits), None, None, None, None, None, None, None, None, None
+            return (torch.zeros_like(logits), torch.zeros_like(grid) if want_grid else None,
+                    None, None, None, None, None, None, None, None)
         gbeta = gbeta.to(torch.float64).contiguous()
         gl = torch.empty_like(logits)
         _lib.check(lib.lf_wls_bwd(_lib.ptr(logits), _lib.ptr(grid), gbs, N, K, H, W, zero_rows, order, y_offset,
                                   act_kind, _lib.ptr(beta), _lib.ptr(zinv), _lib.ptr(gbeta), _lib.ptr(gl),
                                   _lib.stream()), "lf_wls_bwd")
-        return gl, None, None, None, None, None, None, None, None, None
+        gg = None
+        if want_grid:              # (a shared grid -- (P, 2) or (1, P, 2) -- collects every image and lane)
+            gg = torch.empty_like(grid)
+            if gbs and grid.shape[0] > N:          # (grids of images beyond the batch took no part)
+                gg[N:].zero_()
+            _lib.check(lib.lf_wls_bwd_grid(_lib.ptr(logits), _lib.ptr(grid), gbs, N, K, H, W, zero_rows, order, y_offset,
+                                           act_kind, _lib.ptr(beta), _lib.ptr(zinv), _lib.ptr(gbeta), _lib.ptr(gg),
+                                           _lib.stream()), "lf_wls_bwd_grid")
+        return gl, gg, None, None, None, None, None, None, None, None
+
+
+def _theta32(theta, N=None):
+    """theta (3,3) | (1,3,3) | (N,3,3) of any float dtype -> (contiguous fp32 tensor, batch stride 0 | 9, number of matrices)."""
+    if theta.dim() not in (2, 3) or tuple(theta.shape[-2:]) != (3, 3):
+        raise ValueError("lanefit: a homography is (3, 3) or (N, 3, 3), got %s" % (tuple(theta.shape),))
+    n = theta.shape[0] if theta.dim() == 3 else 1
+    if N is not None and n not in (1, N):
+        raise ValueError("lanefit: %d homographies for a batch of %d" % (n, N))
+    return theta.detach().to(torch.float32).contiguous(), (9 if n > 1 else 0), n
+
+
+class ThetaGrid(torch.autograd.Function):
+    """theta (3,3) | (N,3,3) -> grid (1 | N, H*W, 2) fp32 (``lf_theta_grid``); backward = the theta reduction of
+    ``lf_theta_grid_bwd`` on the incoming grid gradient, cast to theta's dtype."""
+
+    @staticmethod
+    def forward(ctx, theta, H, W, normalised):
+        lib = _lib.load()
+        t32, tbs, n = _theta32(theta)
+        xs, ys = geometry.base_tables_on(t32.device, H, W, normalised)
+        grid = torch.empty(n, H * W, 2, dtype=torch.float32, device=t32.device)
+        _lib.check(lib.lf_theta_grid(_lib.ptr(t32), tbs, _lib.ptr(xs), _lib.ptr(ys), n, H, W, _lib.ptr(grid), _lib.stream()),
+                   "lf_theta_grid")
+        ctx.save_for_backward(t32, xs, ys)
+        ctx.cfg = (tbs, n, H, W, theta.shape, theta.dtype)
+        return grid
+
+    @staticmethod
+    def backward(ctx, ggrid):
+        lib = _lib.load()
+        t32, xs, ys = ctx.saved_tensors
+        tbs, n, H, W, shape, dtype = ctx.cfg
+        ggrid = ggrid.to(torch.float32).contiguous()
+        gt = torch.empty(n, 3, 3, dtype=torch.float64, device=t32.device)
+        ws = torch.empty(lib.lf_theta_grid_bwd_workspace_bytes(n), dtype=torch.uint8, device=t32.device)
+        _lib.check(lib.lf_theta_grid_bwd(_lib.ptr(t32), tbs, _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(ggrid), n, H, W, _lib.ptr(gt),
+                                         _lib.ptr(ws), _lib.stream()), "lf_theta_grid_bwd")
+        return gt.view(shape).to(dtype), None, None, None
+
+
+def theta_grid(theta, H, W, normalised=True):
+    """The projective grid of ``theta`` on the device: (1, H*W, 2) for a (3,3) theta, (N, H*W, 2) for (N,3,3); differentiable."""
+    return ThetaGrid.apply(theta, int(H), int(W), bool(normalised))
+
+
+class WLSFitTheta(torch.autograd.Function):
+    """``WLSFit`` with the grid computed inline from a homography: (logits NCHW fp32, theta (3,3) | (N,3,3)) -> the same outputs.
+    Backward writes the logits gradient and the theta gradient in one pass (``lf_wls_bwd_theta``); no grid tensor exists."""
+
+    @staticmethod
+    def forward(ctx, logits, theta, normalised, zero_rows, order, reg, y_offset, act_kind, solver, want_masked, check):
+        lib = _lib.load()
+        logits = logits.contiguous()
+        assert logits.dtype == torch.float32 and logits.dim() == 4
+        N, K, H, W = logits.shape
+        t32, tbs, n = _theta32(theta, N)
+        xs, ys = geometry.base_tables_on(logits.device, H, W, normalised)
+        D = order + 1
+        dev = logits.device
+        beta = torch.empty(N, K, D, dtype=torch.float64, device=dev)
+        zinv = torch.empty(N, K, D * D, dtype=torch.float64, device=dev)
+        status = torch.empty(N * K, dtype=torch.int32, device=dev)
+        masked = torch.empty_like(logits) if want_masked else None
+        ws = torch.empty(lib.lf_wls_workspace_bytes(N, K, order), dtype=torch.uint8, device=dev)
+        _lib.check(lib.lf_wls_fwd_theta(_lib.ptr(logits), _lib.ptr(t32), tbs, _lib.ptr(xs), _lib.ptr(ys), N, K, H, W, zero_rows,
+                                        order, float(reg), float(y_offset), act_kind, solver, _lib.ptr(beta), _lib.ptr(zinv),
+                                        _lib.ptr(masked), _lib.ptr(ws), _lib.ptr(status), _lib.stream()), "lf_wls_fwd_theta")
+        if check:
+            _raise_if_singular(status, solver)
+        ctx.save_for_backward(logits, t32, xs, ys, beta, zinv)
+        ctx.cfg = (tbs, n, zero_rows, order, float(y_offset), act_kind, theta.shape, theta.dtype)
+        ctx.status = status
+        ctx.set_materialize_grads(False)
+        if want_masked:
+            ctx.mark_non_differentiable(masked)
+            return beta, masked, status
+        return beta, None, status
+
+    @staticmethod
+    def backward(ctx, gbeta, _gm, _gs):
+        lib = _lib.load()
+        logits, t32, xs, ys, beta, zinv = ctx.saved_tensors
+        tbs, n, zero_rows, order, y_offset, act_kind, tshape, tdtype = ctx.cfg
+        N, K, H, W = logits.shape
+        want_theta = ctx.needs_input_grad[1]
+        tail = (None,) * 9
+        if gbeta is None:
+            gt0 = torch.zeros(tshape, dtype=tdtype, device=logits.device) if want_theta else None
+            return (torch.zeros_like(logits), gt0) + tail
+        gbeta = gbeta.to(torch.float64).contiguous()
+        gl = torch.empty_like(logits)
+        gt = torch.empty(n, 3, 3, dtype=torch.float64, device=logits.device)
+        ws = torch.empty(lib.lf_wls_bwd_theta_workspace_bytes(N, K), dtype=torch.uint8, device=logits.device)
+        _lib.check(lib.lf_wls_bwd_theta(_lib.ptr(logits), _lib.ptr(t32), tbs, _lib.ptr(xs), _lib.ptr(ys), N, K, H, W, zero_rows,
+                                        order, y_offset, act_kind, _lib.ptr(beta), _lib.ptr(zinv), _lib.ptr(gbeta), _lib.ptr(gl),
+                                        _lib.ptr(gt), _lib.ptr(ws), _lib.stream()), "lf_wls_bwd_theta")
+        return (gl, gt.view(tshape).to(tdtype) if want_theta else None) + tail
 
 
 class AreaLossFn(torch.autograd.Function):
