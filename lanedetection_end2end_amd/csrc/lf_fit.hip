@@ -17,6 +17,8 @@
 
 #include <stdarg.h>
 
+#include <type_traits>
+
 thread_local char lf_err_buf[512] = "";
 int lf_fail(const char* fmt, ...) {
     va_list ap;
@@ -57,11 +59,7 @@ __device__ __forceinline__ float act_bwd(float o, int kind) {
 template <int ORDER>
 struct Moments {
     static constexpr int NM = 2 * ORDER + 1, NQ = ORDER + 1, N = NM + NQ;
-    double v[N];
-    __device__ __forceinline__ void zero() {
-#pragma unroll
-        for (int i = 0; i < N; ++i) v[i] = 0.0;
-    }
+    double v[N] = {};
     // one pixel: weight w (after activation), grid x', grid y', y = y_offset - y' in fp32 as the reference does
     __device__ __forceinline__ void add(float w, float gx, float gy, float y_off) {
         const double s = (double)w * (double)w;
@@ -77,63 +75,151 @@ struct Moments {
     }
 };
 
-// Pass 1: per (chunk, image*lane) partial moments; optionally writes the masked weight map.
-template <int ORDER, int VEC>
+// Workgroup sum of N per-thread values -> out[0..N): a butterfly per wave, then thread j < N adds the waves in ascending order.
+// The whole workgroup calls it (it holds a barrier); a second call in one kernel needs a __syncthreads() first: same LDS rows.
+template <int N>
+__device__ __forceinline__ void block_store_sums(const double (&v)[N], double* __restrict__ out) {
+    __shared__ double red[WLS_THREADS / LF_WAVE][N];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const double s = lf_wave_sum(v[j]);
+        if (lane == 0) red[wave][j] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < WLS_THREADS / LF_WAVE; ++w) s += red[w][threadIdx.x];
+        out[threadIdx.x] = s;
+    }
+}
+
+// VEC = 4 (W % 4 == 0: one 16-byte access, the four pixels share a row) or 1
+template <int VEC>
+__device__ __forceinline__ void load_px(const float* __restrict__ p, float (&v)[VEC]) {
+    if constexpr (VEC == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+        v[0] = *p;
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void store_px(float* __restrict__ p, const float (&v)[VEC]) {
+    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else *p = v[0];
+}
+
+// ---------------------------------------------------------------------------------------
+// Where the fit's grid comes from: a table in memory, or a homography (BEV/Networks/LSQ_layer.py:84-87
+// ProjectiveGridGenerator.forward): theta (3,3) shared or (N,3,3) per image, the base coordinates from two host-made tables
+// xs (W) / ys (H).
+//   (a, b, c) = theta [px, py, 1],  gx = a / c,  gy = b / c          (fp32, one fixed contraction: every kernel here agrees bit for bit)
+// ---------------------------------------------------------------------------------------
+struct Theta { float t[9]; };
+__device__ __forceinline__ Theta theta_load(const float* __restrict__ theta, long theta_bs, int n) {
+    Theta h;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) h.t[i] = theta[(long)n * theta_bs + i];
+    return h;
+}
+__device__ __forceinline__ void theta_point(const Theta& h, float px, float py, float& gx, float& gy, float& c) {
+    const float a = fmaf(py, h.t[1], fmaf(px, h.t[0], h.t[2]));
+    const float b = fmaf(py, h.t[4], fmaf(px, h.t[3], h.t[5]));
+    c = fmaf(py, h.t[7], fmaf(px, h.t[6], h.t[8]));
+    gx = a / c;
+    gy = b / c;
+}
+
+// One pixel's grid point; (c, px, py) are filled by GridTheta only.
+struct GridPoint { float gx, gy, c, px, py; };
+
+// Both sources: Args is what the host passes, the constructor binds image n, load() reads what the unit of VEC pixels at p needs
+// and point() gives pixel e of that unit.
+struct GridTable {
+    static constexpr bool kTheta = false;
+    struct Args { const float* grid; long bs; };         // (N | 1, H*W, 2) fp32, batch stride 0 when shared
+    template <int VEC> struct Unit { float xy[2 * VEC]; };
+    const float* g;
+    __device__ GridTable(const Args& a, int n) : g(a.grid + (long)n * a.bs) {}
+    template <int VEC>
+    __device__ __forceinline__ void load(long p, int, Unit<VEC>& u) const {
+        if constexpr (VEC == 4) {
+            const float4 g0 = *reinterpret_cast<const float4*>(g + 2 * p);
+            const float4 g1 = *reinterpret_cast<const float4*>(g + 2 * p + 4);
+            u.xy[0] = g0.x; u.xy[1] = g0.y; u.xy[2] = g0.z; u.xy[3] = g0.w;
+            u.xy[4] = g1.x; u.xy[5] = g1.y; u.xy[6] = g1.z; u.xy[7] = g1.w;
+        } else {
+            u.xy[0] = g[2 * p];
+            u.xy[1] = g[2 * p + 1];
+        }
+    }
+    template <int VEC>
+    __device__ __forceinline__ void point(const Unit<VEC>& u, int e, GridPoint& q) const {
+        q.gx = u.xy[2 * e];
+        q.gy = u.xy[2 * e + 1];
+    }
+};
+struct GridTheta {                                       // the 8 B/pixel grid read is gone
+    static constexpr bool kTheta = true;
+    struct Args { const float* theta; long bs; const float* xs; const float* ys; };
+    template <int VEC> struct Unit { float px[VEC], py; };
+    Theta h;
+    const float* xs;
+    const float* ys;
+    __device__ GridTheta(const Args& a, int n) : h(theta_load(a.theta, a.bs, n)), xs(a.xs), ys(a.ys) {}
+    template <int VEC>
+    __device__ __forceinline__ void load(long p, int W, Unit<VEC>& u) const {
+        const int i = (int)(p / W), j = (int)(p - (long)i * W);
+        u.py = ys[i];
+        load_px<VEC>(xs + j, u.px);
+    }
+    template <int VEC>
+    __device__ __forceinline__ void point(const Unit<VEC>& u, int e, GridPoint& q) const {
+        q.px = u.px[e];
+        q.py = u.py;
+        theta_point(h, q.px, q.py, q.gx, q.gy, q.c);
+    }
+};
+
+// Pass 1: per (chunk, image*lane) partial moments; optionally writes the masked weight map.  The first unmasked pixel is
+// zero_rows * W: masked rows are never read (nor their grid points evaluated: a pole of theta there stays harmless).
+template <int ORDER, int VEC, typename Src>
 __global__ __launch_bounds__(WLS_THREADS) void wls_moments_kernel(
-    const float* __restrict__ logits, const float* __restrict__ grid, long grid_bs, int K, int H, int W,
-    int zero_rows, float y_off, int act_kind, float* __restrict__ masked, double* __restrict__ partials) {
+    const float* __restrict__ logits, const typename Src::Args grid, int K, int H, int W, int zero_rows, float y_off, int act_kind,
+    float* __restrict__ masked, double* __restrict__ partials) {
     using M = Moments<ORDER>;
     const int nk = blockIdx.y, chunk = blockIdx.x;
     const long P = (long)H * W;
     const float* o = logits + (long)nk * P;
-    const float* g = grid + (long)(nk / K) * grid_bs;
+    const Src src(grid, nk / K);
     float* mo = masked ? masked + (long)nk * P : nullptr;
     const long first = (long)zero_rows * W;             // first unmasked pixel
     const long units = (P - first) / VEC;
     const long u0 = units * chunk / WLS_CHUNKS, u1 = units * (chunk + 1) / WLS_CHUNKS;
     M acc;
-    acc.zero();
     for (long u = u0 + threadIdx.x; u < u1; u += WLS_THREADS) {
         const long p = first + u * VEC;
-        if constexpr (VEC == 4) {
-            const float4 ov = *reinterpret_cast<const float4*>(o + p);
-            const float4 g0 = *reinterpret_cast<const float4*>(g + 2 * p);
-            const float4 g1 = *reinterpret_cast<const float4*>(g + 2 * p + 4);
-            float4 w;
-            w.x = act_fwd(ov.x, act_kind); w.y = act_fwd(ov.y, act_kind);
-            w.z = act_fwd(ov.z, act_kind); w.w = act_fwd(ov.w, act_kind);
-            acc.add(w.x, g0.x, g0.y, y_off);
-            acc.add(w.y, g0.z, g0.w, y_off);
-            acc.add(w.z, g1.x, g1.y, y_off);
-            acc.add(w.w, g1.z, g1.w, y_off);
-            if (mo) *reinterpret_cast<float4*>(mo + p) = w;
-        } else {
-            const float w = act_fwd(o[p], act_kind);
-            acc.add(w, g[2 * p], g[2 * p + 1], y_off);
-            if (mo) mo[p] = w;
+        float w[VEC];
+        typename Src::template Unit<VEC> unit;
+        load_px<VEC>(o + p, w);
+        src.load(p, W, unit);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            GridPoint q;
+            w[e] = act_fwd(w[e], act_kind);
+            src.point(unit, e, q);
+            acc.add(w[e], q.gx, q.gy, y_off);
         }
+        if (mo) store_px<VEC>(mo + p, w);
     }
     if (mo) {   // masked rows are zeros (index_fill), written without reading the logits
         const long zu = first / VEC, z0 = zu * chunk / WLS_CHUNKS, z1 = zu * (chunk + 1) / WLS_CHUNKS;
-        for (long u = z0 + threadIdx.x; u < z1; u += WLS_THREADS) {
-            if constexpr (VEC == 4) *reinterpret_cast<float4*>(mo + u * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-            else mo[u] = 0.f;
-        }
+        const float zero[VEC] = {};
+        for (long u = z0 + threadIdx.x; u < z1; u += WLS_THREADS) store_px<VEC>(mo + u * VEC, zero);
     }
-    __shared__ double red[WLS_THREADS / LF_WAVE][M::N];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < M::N; ++j) {
-        const double s = lf_wave_sum(acc.v[j]);
-        if (lane == 0) red[wave][j] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < M::N) {
-        double s = 0.0;
-#pragma unroll
-        for (int w = 0; w < WLS_THREADS / LF_WAVE; ++w) s += red[w][threadIdx.x];
-        partials[((long)nk * WLS_CHUNKS + chunk) * M::N + threadIdx.x] = s;
-    }
+    block_store_sums(acc.v, partials + ((long)nk * WLS_CHUNKS + chunk) * M::N);
 }
 
 // In-register inverse of a DxD matrix (Gauss-Jordan, partial pivoting = what LAPACK getrf/getri
@@ -265,90 +351,174 @@ __global__ void wls_solve_kernel(const double* __restrict__ partials, int NK, do
     status[nk] = st;
 }
 
-// Backward: d/d logits of sum_k <grad_beta_k, beta_k>.  Elementwise over the whole map.
-template <int ORDER, int VEC>
+// The backward, with v = Z^-1 gbeta, q = Y.v, r = x - Y.beta, s = w^2, y = y_off - gy, per pixel and lane:
+//   dL/dlogit = 2 w q r act'(o),   dL/dgx = s q,   dL/dgy = -sum_k s (r v_k - q beta_k) (d - k) y^(d-k-1)
+//   dL/dtheta_0 = sum (dgx / c) p,  dL/dtheta_1 = sum (dgy / c) p,  dL/dtheta_2 = sum -((dgx gx + dgy gy) / c) p,   p = [px, py, 1]
+// The nine theta sums run in fp64 as per-workgroup partials in a caller-owned workspace, added in a fixed order by a second small
+// launch: no atomics, two runs are bit-identical.  Masked rows are neither read nor evaluated (a pole there stays harmless).
+
+// The per-pixel terms of one lane: returns grad_logits, and (dL/dgx, dL/dgy) of that lane.
+template <int D>
+__device__ __forceinline__ float fit_pixel_bwd(const double (&b)[D], const double (&v)[D], float ov, float gx, float gy, float y_off,
+                                               int act_kind, double& dgx, double& dgy) {
+    const double y = (double)(y_off - gy);
+    double yv = v[0], yb = b[0];
+#pragma unroll
+    for (int i = 1; i < D; ++i) { yv = fma(yv, y, v[i]); yb = fma(yb, y, b[i]); }   // Horner, highest power first
+    const double w = (double)act_fwd(ov, act_kind);
+    const double r = (double)gx - yb, s = w * w;
+    double dy = 0.0;                                      // sum_k (r v_k - q beta_k) (d - k) y^(d-k-1), Horner
+#pragma unroll
+    for (int k = 0; k < D - 1; ++k) dy = fma(dy, y, (double)(D - 1 - k) * (r * v[k] - yv * b[k]));
+    dgx = s * yv;
+    dgy = -s * dy;
+    return (float)(2.0 * w * yv * r * (double)act_bwd(ov, act_kind));
+}
+
+// beta and v = Z^-1 gbeta of lane nk (Z^-1 is symmetric, so Z^-T g = Z^-1 g)
+template <int D>
+__device__ __forceinline__ void fit_lane_consts(const double* __restrict__ beta, const double* __restrict__ zinv,
+                                                const double* __restrict__ gbeta, long nk, double (&b)[D], double (&v)[D]) {
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        b[i] = beta[nk * D + i];
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) s = fma(zinv[(nk * D + i) * D + j], gbeta[nk * D + j], s);
+        v[i] = s;
+    }
+}
+
+constexpr int TH_CHUNKS = 64;    // workgroups per (image, lane) of the backward launches = partial rows per (image, lane)
+
+// nine fp64 sums of one thread: rows (dgx / c, dgy / c, -(dgx gx + dgy gy) / c) times (px, py, 1)
+struct ThetaAcc {
+    double v[9] = {};
+    __device__ __forceinline__ void add(double dgx, double dgy, float gx, float gy, float c, float px, float py) {
+        const double ic = 1.0 / (double)c;
+        const double t0 = dgx * ic, t1 = dgy * ic, t2 = -(dgx * (double)gx + dgy * (double)gy) * ic;
+        const double x = (double)px, y = (double)py;
+        v[0] = fma(t0, x, v[0]); v[1] = fma(t0, y, v[1]); v[2] += t0;
+        v[3] = fma(t1, x, v[3]); v[4] = fma(t1, y, v[4]); v[5] += t1;
+        v[6] = fma(t2, x, v[6]); v[7] = fma(t2, y, v[7]); v[8] += t2;
+    }
+};
+
+// d/d logits of sum_k <grad_beta_k, beta_k>, elementwise over the whole map (masked rows are written as zeros); with GridTheta
+// also the nine theta sums of this workgroup's pixels -> partials[(nk, blockIdx.x)].
+template <int ORDER, int VEC, typename Src>
 __global__ __launch_bounds__(WLS_THREADS) void wls_bwd_kernel(
-    const float* __restrict__ logits, const float* __restrict__ grid, long grid_bs, int K, int H, int W,
-    int zero_rows, float y_off, int act_kind, const double* __restrict__ beta, const double* __restrict__ zinv,
-    const double* __restrict__ gbeta, float* __restrict__ gout) {
+    const float* __restrict__ logits, const typename Src::Args grid, int K, int H, int W, int zero_rows, float y_off, int act_kind,
+    const double* __restrict__ beta, const double* __restrict__ zinv, const double* __restrict__ gbeta, float* __restrict__ gout,
+    double* __restrict__ partials) {
     constexpr int D = ORDER + 1;
     const int nk = blockIdx.y;
     const long P = (long)H * W;
     const float* o = logits + (long)nk * P;
-    const float* g = grid + (long)(nk / K) * grid_bs;
     float* go = gout + (long)nk * P;
+    const Src src(grid, nk / K);
     double b[D], v[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-        b[i] = beta[(long)nk * D + i];
-        double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < D; ++j) s = fma(zinv[((long)nk * D + i) * D + j], gbeta[(long)nk * D + j], s);
-        v[i] = s;   // Z^-1 is symmetric, so Z^-T g = Z^-1 g
-    }
+    fit_lane_consts<D>(beta, zinv, gbeta, nk, b, v);
     const long first = (long)zero_rows * W;
-    auto one = [&](float ov, float gx, float gy) -> float {
-        const double y = (double)(y_off - gy);
-        double yv = v[0], yb = b[0];
-#pragma unroll
-        for (int i = 1; i < D; ++i) { yv = fma(yv, y, v[i]); yb = fma(yb, y, b[i]); }   // Horner, highest power first
-        const double w = (double)act_fwd(ov, act_kind);
-        return (float)(2.0 * w * yv * ((double)gx - yb) * (double)act_bwd(ov, act_kind));
+    ThetaAcc acc;
+    auto one = [&](float ov, const typename Src::template Unit<VEC>& unit, int e) -> float {
+        GridPoint q;
+        double dgx, dgy;
+        src.point(unit, e, q);
+        const float g = fit_pixel_bwd<D>(b, v, ov, q.gx, q.gy, y_off, act_kind, dgx, dgy);
+        if constexpr (Src::kTheta) acc.add(dgx, dgy, q.gx, q.gy, q.c, q.px, q.py);
+        return g;
     };
     const long units = P / VEC;
     for (long u = (long)blockIdx.x * WLS_THREADS + threadIdx.x; u < units; u += (long)gridDim.x * WLS_THREADS) {
         const long p = u * VEC;
-        if constexpr (VEC == 4) {
-            float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (p >= first) {
-                const float4 ov = *reinterpret_cast<const float4*>(o + p);
-                const float4 g0 = *reinterpret_cast<const float4*>(g + 2 * p);
-                const float4 g1 = *reinterpret_cast<const float4*>(g + 2 * p + 4);
-                r.x = one(ov.x, g0.x, g0.y); r.y = one(ov.y, g0.z, g0.w);
-                r.z = one(ov.z, g1.x, g1.y); r.w = one(ov.w, g1.z, g1.w);
-            }
-            *reinterpret_cast<float4*>(go + p) = r;
-        } else {
-            go[p] = (p >= first) ? one(o[p], g[2 * p], g[2 * p + 1]) : 0.f;
+        float r[VEC] = {};
+        if (p >= first) {
+            float ov[VEC];
+            typename Src::template Unit<VEC> unit;
+            src.load(p, W, unit);
+            load_px<VEC>(o + p, ov);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) r[e] = one(ov[e], unit, e);
         }
+        store_px<VEC>(go + p, r);
     }
+    if constexpr (Src::kTheta) block_store_sums(acc.v, partials + ((long)nk * gridDim.x + blockIdx.x) * 9);
 }
 
-template <int ORDER>
-int wls_fwd_launch(const float* logits, const float* grid, long gbs, int N, int K, int H, int W, int zr,
-                   double reg, double y_off, int act, int solver, double* beta, double* zinv, float* masked,
-                   double* partials, int32_t* status, hipStream_t st) {
-    const bool vec = (W % 4 == 0);
-    dim3 g1(WLS_CHUNKS, N * K);
-    if (vec)
-        hipLaunchKernelGGL((wls_moments_kernel<ORDER, 4>), g1, dim3(WLS_THREADS), 0, st, logits, grid, gbs, K, H, W,
-                           zr, (float)y_off, act, masked, partials);
-    else
-        hipLaunchKernelGGL((wls_moments_kernel<ORDER, 1>), g1, dim3(WLS_THREADS), 0, st, logits, grid, gbs, K, H, W,
-                           zr, (float)y_off, act, masked, partials);
-    LF_CHECK_LAUNCH("wls_moments");
-    hipLaunchKernelGGL((wls_solve_kernel<ORDER>), dim3(lf_cdiv(N * K, 64)), dim3(64), 0, st, partials, N * K, reg,
-                       solver, beta, zinv, status);
-    LF_CHECK_LAUNCH("wls_solve");
+// ---- host side: one dispatcher per compile-time choice, one launcher per pass ---------------------------------------------
+
+// the run-time order (0..3, checked by the caller) as a compile-time constant: f(std::integral_constant<int, ORDER>)
+template <typename F>
+int with_order(int order, F&& f) {
+    switch (order) {
+        case 0: return f(std::integral_constant<int, 0>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        default: return f(std::integral_constant<int, 3>{});
+    }
+}
+inline int fit_vec(int W) { return W % 4 == 0 ? 4 : 1; }
+template <typename F>
+int with_vec(int W, F&& f) {
+    return fit_vec(W) == 4 ? f(std::integral_constant<int, 4>{}) : f(std::integral_constant<int, 1>{});
+}
+// workgroups per (image, lane) of the elementwise backward = partial rows of the theta sums
+inline int fit_bwd_chunks(int H, int W) {
+    const int gx = lf_cdiv((long)H * W / fit_vec(W), WLS_THREADS);
+    return gx > TH_CHUNKS ? TH_CHUNKS : gx;
+}
+
+// What the fit entry points share; `name` (the entry point) leads the message.
+int fit_check(const char* name, int N, int K, int H, int W, int zero_rows, int order, int act_kind) {
+    LF_REQUIRE(N > 0 && K > 0 && H > 0 && W > 0, "%s: bad shape %d %d %d %d", name, N, K, H, W);
+    LF_REQUIRE(zero_rows >= 0 && zero_rows < H, "%s: zero_rows %d out of [0,%d)", name, zero_rows, H);
+    LF_REQUIRE(order >= 0 && order <= 3, "%s: order %d not in 0..3", name, order);
+    LF_REQUIRE(act_kind >= 0 && act_kind <= LF_ACT_NONE, "%s: bad activation %d", name, act_kind);
+    return 0;
+}
+// ... and the entry points that take a homography
+int theta_check(const char* name, const float* theta, long theta_bs, const float* xs, const float* ys, int N, int H, int W) {
+    LF_REQUIRE(theta && xs && ys, "%s: null pointer", name);
+    LF_REQUIRE(theta_bs == 0 || theta_bs == 9, "%s: theta_batch_stride %ld is neither 0 nor 9", name, theta_bs);
+    LF_REQUIRE(N > 0 && H > 0 && W > 0, "%s: bad shape %d %d %d", name, N, H, W);
+    LF_REQUIRE(((size_t)xs & 15) == 0, "%s: the x table is read as vectors: misaligned", name);
     return 0;
 }
 
 template <int ORDER>
-int wls_bwd_launch(const float* logits, const float* grid, long gbs, int N, int K, int H, int W, int zr,
-                   double y_off, int act, const double* beta, const double* zinv, const double* gbeta, float* gout,
+int wls_solve_launch(const double* partials, int NK, double reg, int solver, double* beta, double* zinv, int32_t* status,
+                     hipStream_t st) {
+    hipLaunchKernelGGL((wls_solve_kernel<ORDER>), dim3(lf_cdiv(NK, 64)), dim3(64), 0, st, partials, NK, reg, solver, beta, zinv,
+                       status);
+    LF_CHECK_LAUNCH("wls_solve");
+    return 0;
+}
+
+template <int ORDER, typename Src>
+int wls_fwd_launch(const float* logits, const typename Src::Args grid, int N, int K, int H, int W, int zr, double reg, double y_off,
+                   int act, int solver, double* beta, double* zinv, float* masked, double* partials, int32_t* status,
                    hipStream_t st) {
-    const bool vec = (W % 4 == 0);
-    const long units = (long)H * W / (vec ? 4 : 1);
-    int gx = lf_cdiv(units, WLS_THREADS);
-    if (gx > 64) gx = 64;
-    dim3 g1(gx, N * K);
-    if (vec)
-        hipLaunchKernelGGL((wls_bwd_kernel<ORDER, 4>), g1, dim3(WLS_THREADS), 0, st, logits, grid, gbs, K, H, W, zr,
-                           (float)y_off, act, beta, zinv, gbeta, gout);
-    else
-        hipLaunchKernelGGL((wls_bwd_kernel<ORDER, 1>), g1, dim3(WLS_THREADS), 0, st, logits, grid, gbs, K, H, W, zr,
-                           (float)y_off, act, beta, zinv, gbeta, gout);
-    LF_CHECK_LAUNCH("wls_bwd");
+    with_vec(W, [&](auto V) {
+        hipLaunchKernelGGL((wls_moments_kernel<ORDER, V(), Src>), dim3(WLS_CHUNKS, N * K), dim3(WLS_THREADS), 0, st, logits, grid, K,
+                           H, W, zr, (float)y_off, act, masked, partials);
+        return 0;
+    });
+    LF_CHECK_LAUNCH(Src::kTheta ? "wls_moments_theta" : "wls_moments");
+    return wls_solve_launch<ORDER>(partials, N * K, reg, solver, beta, zinv, status, st);
+}
+
+// theta_partials: GridTheta only, fit_bwd_chunks(H, W) rows of nine per (image, lane)
+template <int ORDER, typename Src>
+int wls_bwd_launch(const float* logits, const typename Src::Args grid, int N, int K, int H, int W, int zr, double y_off, int act,
+                   const double* beta, const double* zinv, const double* gbeta, float* gout, double* theta_partials,
+                   hipStream_t st) {
+    with_vec(W, [&](auto V) {
+        hipLaunchKernelGGL((wls_bwd_kernel<ORDER, V(), Src>), dim3(fit_bwd_chunks(H, W), N * K), dim3(WLS_THREADS), 0, st, logits,
+                           grid, K, H, W, zr, (float)y_off, act, beta, zinv, gbeta, gout, theta_partials);
+        return 0;
+    });
+    LF_CHECK_LAUNCH(Src::kTheta ? "wls_bwd_theta" : "wls_bwd");
     return 0;
 }
 
@@ -382,20 +552,7 @@ __global__ __launch_bounds__(WLS_THREADS) void gels_moments_kernel(const float* 
 #pragma unroll
         for (int i = 0; i < D; ++i) acc[D * (D + 1) / 2 + i] = fma(a[i], bv, acc[D * (D + 1) / 2 + i]);
     }
-    __shared__ double red[WLS_THREADS / LF_WAVE][NS];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-        const double v = lf_wave_sum(acc[j]);
-        if (lane == 0) red[wave][j] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NS) {
-        double v = 0.0;
-#pragma unroll
-        for (int w = 0; w < WLS_THREADS / LF_WAVE; ++w) v += red[w][threadIdx.x];
-        partials[((long)n * WLS_CHUNKS + chunk) * NS + threadIdx.x] = v;
-    }
+    block_store_sums(acc, partials + ((long)n * WLS_CHUNKS + chunk) * NS);
 }
 
 template <int D>
@@ -506,18 +663,22 @@ extern "C" int lf_wls_fwd(const float* logits, const float* grid_xy, long grid_b
                           int W, int zero_rows, int order, double reg, double y_offset, int act_kind, int solver,
                           double* beta, double* zinv, float* masked, void* partials, int32_t* status, void* stream) {
     LF_REQUIRE(logits && grid_xy && beta && zinv && partials && status, "lf_wls_fwd: null pointer");
-    LF_REQUIRE(N > 0 && K > 0 && H > 0 && W > 0, "lf_wls_fwd: bad shape %d %d %d %d", N, K, H, W);
-    LF_REQUIRE(zero_rows >= 0 && zero_rows < H, "lf_wls_fwd: zero_rows %d out of [0,%d)", zero_rows, H);
-    LF_REQUIRE(order >= 0 && order <= 3, "lf_wls_fwd: order %d not in 0..3", order);
-    LF_REQUIRE(act_kind >= 0 && act_kind <= LF_ACT_NONE, "lf_wls_fwd: bad activation %d", act_kind);
-    hipStream_t st = (hipStream_t)stream;
-    double* p = (double*)partials;
-    switch (order) {
-        case 0: return wls_fwd_launch<0>(logits, grid_xy, grid_batch_stride, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
-        case 1: return wls_fwd_launch<1>(logits, grid_xy, grid_batch_stride, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
-        case 2: return wls_fwd_launch<2>(logits, grid_xy, grid_batch_stride, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
-        default: return wls_fwd_launch<3>(logits, grid_xy, grid_batch_stride, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
-    }
+    if (fit_check("lf_wls_fwd", N, K, H, W, zero_rows, order, act_kind)) return -1;
+    return with_order(order, [&](auto O) {
+        return wls_fwd_launch<O(), GridTable>(logits, {grid_xy, grid_batch_stride}, N, K, H, W, zero_rows, reg, y_offset, act_kind,
+                                              solver, beta, zinv, masked, (double*)partials, status, (hipStream_t)stream);
+    });
+}
+
+extern "C" int lf_wls_bwd(const float* logits, const float* grid_xy, long grid_batch_stride, int N, int K, int H,
+                          int W, int zero_rows, int order, double y_offset, int act_kind, const double* beta,
+                          const double* zinv, const double* grad_beta, float* grad_logits, void* stream) {
+    LF_REQUIRE(logits && grid_xy && beta && zinv && grad_beta && grad_logits, "lf_wls_bwd: null pointer");
+    if (fit_check("lf_wls_bwd", N, K, H, W, zero_rows, order, act_kind)) return -1;
+    return with_order(order, [&](auto O) {
+        return wls_bwd_launch<O(), GridTable>(logits, {grid_xy, grid_batch_stride}, N, K, H, W, zero_rows, y_offset, act_kind, beta,
+                                              zinv, grad_beta, grad_logits, nullptr, (hipStream_t)stream);
+    });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -558,8 +719,6 @@ __global__ __launch_bounds__(WLS_THREADS) void head_moments_kernel(
     const long units = (long)h * wd - first;
     const long u0 = units * chunk / WLS_CHUNKS, u1 = units * (chunk + 1) / WLS_CHUNKS;
     M acc[HM_LANES];
-#pragma unroll
-    for (int kk = 0; kk < HM_LANES; ++kk) acc[kk].zero();
     for (long u = u0 + threadIdx.x; u < u1; u += WLS_THREADS) {
         const long p = first + u;
         const int i = (int)(p / wd), j = (int)(p - (long)i * wd);
@@ -614,43 +773,11 @@ __global__ __launch_bounds__(WLS_THREADS) void head_moments_kernel(
             }
         }
     }
-    __shared__ double red[WLS_THREADS / LF_WAVE][HM_LANES][M::N];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int kk = 0; kk < HM_LANES; ++kk)
-#pragma unroll
-        for (int t = 0; t < M::N; ++t) {
-            const double s = lf_wave_sum(acc[kk].v[t]);
-            if (lane == 0) red[wave][kk][t] = s;
-        }
-    __syncthreads();
-    if (threadIdx.x < HM_LANES * M::N) {
-        const int kk = threadIdx.x / M::N, t = threadIdx.x % M::N;
-        if (k0 + kk < K) {
-            double s = 0.0;
-#pragma unroll
-            for (int wv = 0; wv < WLS_THREADS / LF_WAVE; ++wv) s += red[wv][kk][t];
-            partials[(((long)n * K + k0 + kk) * WLS_CHUNKS + chunk) * M::N + t] = s;
-        }
+    for (int kk = 0; kk < HM_LANES; ++kk) {
+        if (kk) __syncthreads();  // (the guard below is uniform over the workgroup -- k0 from blockIdx -- as the barrier inside needs)
+        if (k0 + kk < K) block_store_sums(acc[kk].v, partials + (((long)n * K + k0 + kk) * WLS_CHUNKS + chunk) * M::N);
     }
-}
-
-template <int ORDER>
-int head_fit_launch(const void* x, int s16, const float* w, const float* b, const float* grid, long gbs, int N, int h, int wd, int K,
-                    int zr, double reg, double y_off, int act, int solver, float* logits, double* beta, double* zinv,
-                    double* partials, int32_t* status, hipStream_t st) {
-    const dim3 g1(WLS_CHUNKS, N * ((K + HM_LANES - 1) / HM_LANES));
-    if (s16)
-        hipLaunchKernelGGL((head_moments_kernel<ORDER, lf_bf16>), g1, dim3(WLS_THREADS), 0, st, reinterpret_cast<const lf_bf16*>(x), w, b,
-                           grid, gbs, K, h, wd, zr, (float)y_off, act, logits, partials);
-    else
-        hipLaunchKernelGGL((head_moments_kernel<ORDER, float>), g1, dim3(WLS_THREADS), 0, st, reinterpret_cast<const float*>(x), w, b,
-                           grid, gbs, K, h, wd, zr, (float)y_off, act, logits, partials);
-    LF_CHECK_LAUNCH("head_moments");
-    hipLaunchKernelGGL((wls_solve_kernel<ORDER>), dim3(lf_cdiv(N * K, 64)), dim3(64), 0, st, partials, N * K, reg, solver, beta, zinv,
-                       status);
-    LF_CHECK_LAUNCH("wls_solve");
-    return 0;
 }
 
 }  // namespace
@@ -669,92 +796,26 @@ extern "C" int lf_head_fit(const void* x, int x_bf16, const float* head_w, const
     LF_REQUIRE(grid_batch_stride % 4 == 0 && ((size_t)grid_xy & 15) == 0 && ((size_t)x & 15) == 0 &&
                (!logits_or_null || ((size_t)logits_or_null & 7) == 0), "lf_head_fit: grid / input / logits are read and written as vectors: misaligned");
     hipStream_t st = (hipStream_t)stream;
-    double* p = (double*)partials;
-    switch (order) {
-        case 0: return head_fit_launch<0>(x, x_bf16, head_w, head_b, grid_xy, grid_batch_stride, N, h, w, K, zero_rows, reg, y_offset, act_kind, solver, logits_or_null, beta, zinv, p, status, st);
-        case 1: return head_fit_launch<1>(x, x_bf16, head_w, head_b, grid_xy, grid_batch_stride, N, h, w, K, zero_rows, reg, y_offset, act_kind, solver, logits_or_null, beta, zinv, p, status, st);
-        case 2: return head_fit_launch<2>(x, x_bf16, head_w, head_b, grid_xy, grid_batch_stride, N, h, w, K, zero_rows, reg, y_offset, act_kind, solver, logits_or_null, beta, zinv, p, status, st);
-        default: return head_fit_launch<3>(x, x_bf16, head_w, head_b, grid_xy, grid_batch_stride, N, h, w, K, zero_rows, reg, y_offset, act_kind, solver, logits_or_null, beta, zinv, p, status, st);
-    }
-}
-
-extern "C" int lf_wls_bwd(const float* logits, const float* grid_xy, long grid_batch_stride, int N, int K, int H,
-                          int W, int zero_rows, int order, double y_offset, int act_kind, const double* beta,
-                          const double* zinv, const double* grad_beta, float* grad_logits, void* stream) {
-    LF_REQUIRE(logits && grid_xy && beta && zinv && grad_beta && grad_logits, "lf_wls_bwd: null pointer");
-    LF_REQUIRE(N > 0 && K > 0 && H > 0 && W > 0, "lf_wls_bwd: bad shape");
-    LF_REQUIRE(order >= 0 && order <= 3, "lf_wls_bwd: order %d not in 0..3", order);
-    hipStream_t st = (hipStream_t)stream;
-    switch (order) {
-        case 0: return wls_bwd_launch<0>(logits, grid_xy, grid_batch_stride, N, K, H, W, zero_rows, y_offset, act_kind, beta, zinv, grad_beta, grad_logits, st);
-        case 1: return wls_bwd_launch<1>(logits, grid_xy, grid_batch_stride, N, K, H, W, zero_rows, y_offset, act_kind, beta, zinv, grad_beta, grad_logits, st);
-        case 2: return wls_bwd_launch<2>(logits, grid_xy, grid_batch_stride, N, K, H, W, zero_rows, y_offset, act_kind, beta, zinv, grad_beta, grad_logits, st);
-        default: return wls_bwd_launch<3>(logits, grid_xy, grid_batch_stride, N, K, H, W, zero_rows, y_offset, act_kind, beta, zinv, grad_beta, grad_logits, st);
-    }
+    const dim3 g1(WLS_CHUNKS, N * ((K + HM_LANES - 1) / HM_LANES));
+    return with_order(order, [&](auto O) {
+        if (x_bf16)
+            hipLaunchKernelGGL((head_moments_kernel<O(), lf_bf16>), g1, dim3(WLS_THREADS), 0, st, (const lf_bf16*)x, head_w, head_b,
+                               grid_xy, grid_batch_stride, K, h, w, zero_rows, (float)y_offset, act_kind, logits_or_null,
+                               (double*)partials);
+        else
+            hipLaunchKernelGGL((head_moments_kernel<O(), float>), g1, dim3(WLS_THREADS), 0, st, (const float*)x, head_w, head_b,
+                               grid_xy, grid_batch_stride, K, h, w, zero_rows, (float)y_offset, act_kind, logits_or_null,
+                               (double*)partials);
+        LF_CHECK_LAUNCH("head_moments");
+        return wls_solve_launch<O()>((const double*)partials, N * K, reg, solver, beta, zinv, status, st);
+    });
 }
 
 // ---------------------------------------------------------------------------------------
-// Homography through the fit (BEV/Networks/LSQ_layer.py:84-87 ProjectiveGridGenerator.forward + autograd of the fit w.r.t. its
-// grid): theta (3,3) shared or (N,3,3) per image, the base coordinates from two host-made tables xs (W) / ys (H).
-//   (a, b, c) = theta [px, py, 1],  gx = a / c,  gy = b / c          (fp32, one fixed contraction: every kernel here agrees bit for bit)
-// With v = Z^-1 gbeta, q = Y.v, r = x - Y.beta, s = w^2, y = y_off - gy (wls_bwd_kernel's notation), per pixel and lane
-//   dL/dgx = s q,   dL/dgy = -sum_k s (r v_k - q beta_k) (d - k) y^(d-k-1)
-//   dL/dtheta_0 = sum (dgx / c) p,  dL/dtheta_1 = sum (dgy / c) p,  dL/dtheta_2 = sum -((dgx gx + dgy gy) / c) p,   p = [px, py, 1]
-// The nine sums run in fp64 as per-workgroup partials in a caller-owned workspace, added in a fixed order by a second small
-// launch: no atomics, two runs are bit-identical.  Masked rows are neither read nor evaluated (a pole there stays harmless).
+// Homography through the fit: the grid and its backward as launches of their own, the fit on the inline route (GridTheta), and
+// autograd of the fit w.r.t. an explicit grid.
 // ---------------------------------------------------------------------------------------
 namespace {
-
-constexpr int TH_CHUNKS = 64;    // workgroups per (image, lane) of the backward launches = partial rows per (image, lane)
-
-struct Theta { float t[9]; };
-__device__ __forceinline__ Theta theta_load(const float* __restrict__ theta, long theta_bs, int n) {
-    Theta h;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) h.t[i] = theta[(long)n * theta_bs + i];
-    return h;
-}
-__device__ __forceinline__ void theta_point(const Theta& h, float px, float py, float& gx, float& gy, float& c) {
-    const float a = fmaf(py, h.t[1], fmaf(px, h.t[0], h.t[2]));
-    const float b = fmaf(py, h.t[4], fmaf(px, h.t[3], h.t[5]));
-    c = fmaf(py, h.t[7], fmaf(px, h.t[6], h.t[8]));
-    gx = a / c;
-    gy = b / c;
-}
-
-// nine fp64 sums of one thread: rows (dgx / c, dgy / c, -(dgx gx + dgy gy) / c) times (px, py, 1)
-struct ThetaAcc {
-    double v[9];
-    __device__ __forceinline__ void zero() {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) v[i] = 0.0;
-    }
-    __device__ __forceinline__ void add(double dgx, double dgy, float gx, float gy, float c, float px, float py) {
-        const double ic = 1.0 / (double)c;
-        const double t0 = dgx * ic, t1 = dgy * ic, t2 = -(dgx * (double)gx + dgy * (double)gy) * ic;
-        const double x = (double)px, y = (double)py;
-        v[0] = fma(t0, x, v[0]); v[1] = fma(t0, y, v[1]); v[2] += t0;
-        v[3] = fma(t1, x, v[3]); v[4] = fma(t1, y, v[4]); v[5] += t1;
-        v[6] = fma(t2, x, v[6]); v[7] = fma(t2, y, v[7]); v[8] += t2;
-    }
-    // workgroup sum (wave butterflies, then the waves in order) -> out[0..9)
-    __device__ __forceinline__ void store(double* __restrict__ out) {
-        __shared__ double red[WLS_THREADS / LF_WAVE][9];
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const double s = lf_wave_sum(v[j]);
-            if (lane == 0) red[wave][j] = s;
-        }
-        __syncthreads();
-        if (threadIdx.x < 9) {
-            double s = 0.0;
-#pragma unroll
-            for (int w = 0; w < WLS_THREADS / LF_WAVE; ++w) s += red[w][threadIdx.x];
-            out[threadIdx.x] = s;
-        }
-    }
-};
 
 // Grid from theta: one thread per pixel; grid (N | 1, H*W, 2).
 __global__ __launch_bounds__(WLS_THREADS) void theta_grid_kernel(const float* __restrict__ theta, long theta_bs,
@@ -779,7 +840,6 @@ __global__ __launch_bounds__(WLS_THREADS) void theta_grid_bwd_kernel(const float
     const int n = blockIdx.y;
     const Theta h = theta_load(theta, theta_bs, n);
     ThetaAcc acc;
-    acc.zero();
     for (long p = (long)blockIdx.x * WLS_THREADS + threadIdx.x; p < P; p += (long)gridDim.x * WLS_THREADS) {
         const float2 g = *reinterpret_cast<const float2*>(ggrid + ((long)n * P + p) * 2);
         if (g.x == 0.f && g.y == 0.f) continue;
@@ -789,7 +849,7 @@ __global__ __launch_bounds__(WLS_THREADS) void theta_grid_bwd_kernel(const float
         theta_point(h, px, py, gx, gy, c);
         acc.add((double)g.x, (double)g.y, gx, gy, c, px, py);
     }
-    acc.store(partials + ((long)n * gridDim.x + blockIdx.x) * 9);
+    block_store_sums(acc.v, partials + ((long)n * gridDim.x + blockIdx.x) * 9);
 }
 
 // grad_theta[o] = sum of `rows` consecutive partial rows of nine, one wave per output matrix: each lane adds its rows in
@@ -808,151 +868,6 @@ __global__ __launch_bounds__(LF_WAVE) void theta_finish_kernel(const double* __r
         const double t = lf_wave_sum(s[j]);
         if (threadIdx.x == 0) grad_theta[(long)blockIdx.x * 9 + j] = t;
     }
-}
-
-// wls_moments_kernel with the grid computed inline from theta and the two tables: the 8 B/pixel grid read is gone.
-template <int ORDER, int VEC>
-__global__ __launch_bounds__(WLS_THREADS) void wls_moments_theta_kernel(
-    const float* __restrict__ logits, const float* __restrict__ theta, long theta_bs, const float* __restrict__ xs,
-    const float* __restrict__ ys, int K, int H, int W, int zero_rows, float y_off, int act_kind, float* __restrict__ masked,
-    double* __restrict__ partials) {
-    using M = Moments<ORDER>;
-    const int nk = blockIdx.y, chunk = blockIdx.x;
-    const long P = (long)H * W;
-    const float* o = logits + (long)nk * P;
-    const Theta h = theta_load(theta, theta_bs, nk / K);
-    float* mo = masked ? masked + (long)nk * P : nullptr;
-    const long first = (long)zero_rows * W;
-    const long units = (P - first) / VEC;
-    const long u0 = units * chunk / WLS_CHUNKS, u1 = units * (chunk + 1) / WLS_CHUNKS;
-    M acc;
-    acc.zero();
-    for (long u = u0 + threadIdx.x; u < u1; u += WLS_THREADS) {
-        const long p = first + u * VEC;
-        const int i = (int)(p / W), j = (int)(p - (long)i * W);
-        const float py = ys[i];
-        float gx, gy, c;
-        if constexpr (VEC == 4) {                       // W % 4 == 0: the four pixels share a row
-            const float4 ov = *reinterpret_cast<const float4*>(o + p);
-            const float4 px = *reinterpret_cast<const float4*>(xs + j);
-            float4 w;
-            w.x = act_fwd(ov.x, act_kind); w.y = act_fwd(ov.y, act_kind);
-            w.z = act_fwd(ov.z, act_kind); w.w = act_fwd(ov.w, act_kind);
-            theta_point(h, px.x, py, gx, gy, c); acc.add(w.x, gx, gy, y_off);
-            theta_point(h, px.y, py, gx, gy, c); acc.add(w.y, gx, gy, y_off);
-            theta_point(h, px.z, py, gx, gy, c); acc.add(w.z, gx, gy, y_off);
-            theta_point(h, px.w, py, gx, gy, c); acc.add(w.w, gx, gy, y_off);
-            if (mo) *reinterpret_cast<float4*>(mo + p) = w;
-        } else {
-            const float w = act_fwd(o[p], act_kind);
-            theta_point(h, xs[j], py, gx, gy, c);
-            acc.add(w, gx, gy, y_off);
-            if (mo) mo[p] = w;
-        }
-    }
-    if (mo) {
-        const long zu = first / VEC, z0 = zu * chunk / WLS_CHUNKS, z1 = zu * (chunk + 1) / WLS_CHUNKS;
-        for (long u = z0 + threadIdx.x; u < z1; u += WLS_THREADS) {
-            if constexpr (VEC == 4) *reinterpret_cast<float4*>(mo + u * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-            else mo[u] = 0.f;
-        }
-    }
-    __shared__ double red[WLS_THREADS / LF_WAVE][M::N];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < M::N; ++j) {
-        const double s = lf_wave_sum(acc.v[j]);
-        if (lane == 0) red[wave][j] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < M::N) {
-        double s = 0.0;
-#pragma unroll
-        for (int w = 0; w < WLS_THREADS / LF_WAVE; ++w) s += red[w][threadIdx.x];
-        partials[((long)nk * WLS_CHUNKS + chunk) * M::N + threadIdx.x] = s;
-    }
-}
-
-// The per-pixel terms of one lane: grad_logits as wls_bwd_kernel's `one`, and (dL/dgx, dL/dgy) of that lane.
-template <int D>
-__device__ __forceinline__ float fit_pixel_bwd(const double (&b)[D], const double (&v)[D], float ov, float gx, float gy, float y_off,
-                                               int act_kind, double& dgx, double& dgy) {
-    const double y = (double)(y_off - gy);
-    double yv = v[0], yb = b[0];
-#pragma unroll
-    for (int i = 1; i < D; ++i) { yv = fma(yv, y, v[i]); yb = fma(yb, y, b[i]); }
-    const double w = (double)act_fwd(ov, act_kind);
-    const double r = (double)gx - yb, s = w * w;
-    double dy = 0.0;                                      // sum_k (r v_k - q beta_k) (d - k) y^(d-k-1), Horner
-#pragma unroll
-    for (int k = 0; k < D - 1; ++k) dy = fma(dy, y, (double)(D - 1 - k) * (r * v[k] - yv * b[k]));
-    dgx = s * yv;
-    dgy = -s * dy;
-    return (float)(2.0 * w * yv * r * (double)act_bwd(ov, act_kind));
-}
-
-template <int D>
-__device__ __forceinline__ void fit_lane_consts(const double* __restrict__ beta, const double* __restrict__ zinv,
-                                                const double* __restrict__ gbeta, long nk, double (&b)[D], double (&v)[D]) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-        b[i] = beta[nk * D + i];
-        double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < D; ++j) s = fma(zinv[(nk * D + i) * D + j], gbeta[nk * D + j], s);
-        v[i] = s;
-    }
-}
-
-// wls_bwd_kernel with the grid inline, plus the nine theta sums of this workgroup's pixels -> partials[(nk, blockIdx.x)].
-template <int ORDER, int VEC>
-__global__ __launch_bounds__(WLS_THREADS) void wls_bwd_theta_kernel(
-    const float* __restrict__ logits, const float* __restrict__ theta, long theta_bs, const float* __restrict__ xs,
-    const float* __restrict__ ys, int K, int H, int W, int zero_rows, float y_off, int act_kind, const double* __restrict__ beta,
-    const double* __restrict__ zinv, const double* __restrict__ gbeta, float* __restrict__ gout, double* __restrict__ partials) {
-    constexpr int D = ORDER + 1;
-    const int nk = blockIdx.y;
-    const long P = (long)H * W;
-    const float* o = logits + (long)nk * P;
-    float* go = gout + (long)nk * P;
-    const Theta h = theta_load(theta, theta_bs, nk / K);
-    double b[D], v[D];
-    fit_lane_consts<D>(beta, zinv, gbeta, nk, b, v);
-    const long first = (long)zero_rows * W;
-    ThetaAcc acc;
-    acc.zero();
-    auto one = [&](float ov, float px, float py) -> float {
-        float gx, gy, c;
-        double dgx, dgy;
-        theta_point(h, px, py, gx, gy, c);
-        const float g = fit_pixel_bwd<D>(b, v, ov, gx, gy, y_off, act_kind, dgx, dgy);
-        acc.add(dgx, dgy, gx, gy, c, px, py);
-        return g;
-    };
-    const long units = P / VEC;
-    for (long u = (long)blockIdx.x * WLS_THREADS + threadIdx.x; u < units; u += (long)gridDim.x * WLS_THREADS) {
-        const long p = u * VEC;
-        if constexpr (VEC == 4) {
-            float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (p >= first) {
-                const int i = (int)(p / W), j = (int)(p - (long)i * W);
-                const float py = ys[i];
-                const float4 ov = *reinterpret_cast<const float4*>(o + p);
-                const float4 px = *reinterpret_cast<const float4*>(xs + j);
-                r.x = one(ov.x, px.x, py); r.y = one(ov.y, px.y, py);
-                r.z = one(ov.z, px.z, py); r.w = one(ov.w, px.w, py);
-            }
-            *reinterpret_cast<float4*>(go + p) = r;
-        } else {
-            float r = 0.f;
-            if (p >= first) {
-                const int i = (int)(p / W), j = (int)(p - (long)i * W);
-                r = one(o[p], xs[j], ys[i]);
-            }
-            go[p] = r;
-        }
-    }
-    acc.store(partials + ((long)nk * gridDim.x + blockIdx.x) * 9);
 }
 
 // d loss / d grid of an explicit grid: the thread that owns a pixel adds the lanes (and, for a shared grid, the images) in
@@ -992,63 +907,12 @@ __global__ __launch_bounds__(WLS_THREADS) void wls_bwd_grid_kernel(
     *reinterpret_cast<float2*>(ggrid + ((long)blockIdx.y * P + p) * 2) = out;
 }
 
-int theta_bwd_chunks(int H, int W) {
-    const long units = (long)H * W / (W % 4 == 0 ? 4 : 1);
-    const int gx = lf_cdiv(units, WLS_THREADS);
-    return gx > TH_CHUNKS ? TH_CHUNKS : gx;
-}
-
-template <int ORDER>
-int wls_fwd_theta_launch(const float* logits, const float* theta, long tbs, const float* xs, const float* ys, int N, int K, int H,
-                         int W, int zr, double reg, double y_off, int act, int solver, double* beta, double* zinv, float* masked,
-                         double* partials, int32_t* status, hipStream_t st) {
-    dim3 g1(WLS_CHUNKS, N * K);
-    if (W % 4 == 0)
-        hipLaunchKernelGGL((wls_moments_theta_kernel<ORDER, 4>), g1, dim3(WLS_THREADS), 0, st, logits, theta, tbs, xs, ys, K, H, W,
-                           zr, (float)y_off, act, masked, partials);
-    else
-        hipLaunchKernelGGL((wls_moments_theta_kernel<ORDER, 1>), g1, dim3(WLS_THREADS), 0, st, logits, theta, tbs, xs, ys, K, H, W,
-                           zr, (float)y_off, act, masked, partials);
-    LF_CHECK_LAUNCH("wls_moments_theta");
-    hipLaunchKernelGGL((wls_solve_kernel<ORDER>), dim3(lf_cdiv(N * K, 64)), dim3(64), 0, st, partials, N * K, reg, solver, beta,
-                       zinv, status);
-    LF_CHECK_LAUNCH("wls_solve");
-    return 0;
-}
-
-template <int ORDER>
-int wls_bwd_theta_launch(const float* logits, const float* theta, long tbs, const float* xs, const float* ys, int N, int K, int H,
-                         int W, int zr, double y_off, int act, const double* beta, const double* zinv, const double* gbeta,
-                         float* gout, double* gtheta, double* partials, hipStream_t st) {
-    const int chunks = theta_bwd_chunks(H, W);
-    dim3 g1(chunks, N * K);
-    if (W % 4 == 0)
-        hipLaunchKernelGGL((wls_bwd_theta_kernel<ORDER, 4>), g1, dim3(WLS_THREADS), 0, st, logits, theta, tbs, xs, ys, K, H, W, zr,
-                           (float)y_off, act, beta, zinv, gbeta, gout, partials);
-    else
-        hipLaunchKernelGGL((wls_bwd_theta_kernel<ORDER, 1>), g1, dim3(WLS_THREADS), 0, st, logits, theta, tbs, xs, ys, K, H, W, zr,
-                           (float)y_off, act, beta, zinv, gbeta, gout, partials);
-    LF_CHECK_LAUNCH("wls_bwd_theta");
-    // per-image theta: K lanes x chunks rows each; shared theta: all N*K lanes into one matrix
-    const int outs = tbs ? N : 1, rows = (tbs ? K : N * K) * chunks;
-    hipLaunchKernelGGL(theta_finish_kernel, dim3(outs), dim3(LF_WAVE), 0, st, partials, rows, gtheta);
-    LF_CHECK_LAUNCH("theta_finish");
-    return 0;
-}
-
 }  // namespace
-
-#define LF_THETA_REQUIRE(name)                                                                                         \
-    LF_REQUIRE(theta && xs && ys, name ": null pointer");                                                              \
-    LF_REQUIRE(theta_batch_stride == 0 || theta_batch_stride == 9, name ": theta_batch_stride %ld is neither 0 nor 9", \
-               theta_batch_stride);                                                                                    \
-    LF_REQUIRE(N > 0 && H > 0 && W > 0, name ": bad shape %d %d %d", N, H, W);                                         \
-    LF_REQUIRE(((size_t)xs & 15) == 0, name ": the x table is read as vectors: misaligned")
 
 // theta (3,3) fp32 (theta_batch_stride 0) or (N,3,3) (9); xs (W), ys (H) fp32 base coordinates; grid out (N | 1, H*W, 2) fp32.
 extern "C" int lf_theta_grid(const float* theta, long theta_batch_stride, const float* xs, const float* ys, int N, int H, int W,
                              float* grid_xy, void* stream) {
-    LF_THETA_REQUIRE("lf_theta_grid");
+    if (theta_check("lf_theta_grid", theta, theta_batch_stride, xs, ys, N, H, W)) return -1;
     LF_REQUIRE(grid_xy && ((size_t)grid_xy & 7) == 0, "lf_theta_grid: grid null or misaligned");
     hipLaunchKernelGGL(theta_grid_kernel, dim3(lf_cdiv((long)H * W, WLS_THREADS), theta_batch_stride ? N : 1), dim3(WLS_THREADS), 0,
                        (hipStream_t)stream, theta, theta_batch_stride, xs, ys, H, W, grid_xy);
@@ -1061,7 +925,7 @@ extern "C" size_t lf_theta_grid_bwd_workspace_bytes(int N) { return (size_t)N * 
 // grad_grid (N | 1, H*W, 2) fp32 (the shape lf_theta_grid wrote) -> grad_theta (N | 1, 3, 3) fp64.
 extern "C" int lf_theta_grid_bwd(const float* theta, long theta_batch_stride, const float* xs, const float* ys,
                                  const float* grad_grid, int N, int H, int W, double* grad_theta, void* workspace, void* stream) {
-    LF_THETA_REQUIRE("lf_theta_grid_bwd");
+    if (theta_check("lf_theta_grid_bwd", theta, theta_batch_stride, xs, ys, N, H, W)) return -1;
     LF_REQUIRE(grad_grid && grad_theta && workspace && ((size_t)grad_grid & 7) == 0, "lf_theta_grid_bwd: null or misaligned pointer");
     hipStream_t st = (hipStream_t)stream;
     int chunks = lf_cdiv((long)H * W, WLS_THREADS);
@@ -1081,19 +945,13 @@ extern "C" int lf_wls_fwd_theta(const float* logits, const float* theta, long th
                                 int N, int K, int H, int W, int zero_rows, int order, double reg, double y_offset, int act_kind,
                                 int solver, double* beta, double* zinv, float* masked, void* partials, int32_t* status,
                                 void* stream) {
-    LF_THETA_REQUIRE("lf_wls_fwd_theta");
-    LF_REQUIRE(logits && beta && zinv && partials && status && K > 0, "lf_wls_fwd_theta: null pointer or K = %d", K);
-    LF_REQUIRE(zero_rows >= 0 && zero_rows < H, "lf_wls_fwd_theta: zero_rows %d out of [0,%d)", zero_rows, H);
-    LF_REQUIRE(order >= 0 && order <= 3, "lf_wls_fwd_theta: order %d not in 0..3", order);
-    LF_REQUIRE(act_kind >= 0 && act_kind <= LF_ACT_NONE, "lf_wls_fwd_theta: bad activation %d", act_kind);
-    hipStream_t st = (hipStream_t)stream;
-    double* p = (double*)partials;
-    switch (order) {
-        case 0: return wls_fwd_theta_launch<0>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
-        case 1: return wls_fwd_theta_launch<1>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
-        case 2: return wls_fwd_theta_launch<2>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
-        default: return wls_fwd_theta_launch<3>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, reg, y_offset, act_kind, solver, beta, zinv, masked, p, status, st);
-    }
+    if (theta_check("lf_wls_fwd_theta", theta, theta_batch_stride, xs, ys, N, H, W)) return -1;
+    LF_REQUIRE(logits && beta && zinv && partials && status, "lf_wls_fwd_theta: null pointer");
+    if (fit_check("lf_wls_fwd_theta", N, K, H, W, zero_rows, order, act_kind)) return -1;
+    return with_order(order, [&](auto O) {
+        return wls_fwd_launch<O(), GridTheta>(logits, {theta, theta_batch_stride, xs, ys}, N, K, H, W, zero_rows, reg, y_offset,
+                                              act_kind, solver, beta, zinv, masked, (double*)partials, status, (hipStream_t)stream);
+    });
 }
 
 extern "C" size_t lf_wls_bwd_theta_workspace_bytes(int N, int K) { return (size_t)N * K * TH_CHUNKS * 9 * sizeof(double); }
@@ -1104,22 +962,21 @@ extern "C" int lf_wls_bwd_theta(const float* logits, const float* theta, long th
                                 int N, int K, int H, int W, int zero_rows, int order, double y_offset, int act_kind,
                                 const double* beta, const double* zinv, const double* grad_beta, float* grad_logits,
                                 double* grad_theta, void* workspace, void* stream) {
-    LF_THETA_REQUIRE("lf_wls_bwd_theta");
-    LF_REQUIRE(logits && beta && zinv && grad_beta && grad_logits && grad_theta && workspace && K > 0,
-               "lf_wls_bwd_theta: null pointer or K = %d", K);
-    LF_REQUIRE(zero_rows >= 0 && zero_rows < H, "lf_wls_bwd_theta: zero_rows %d out of [0,%d)", zero_rows, H);
-    LF_REQUIRE(order >= 0 && order <= 3, "lf_wls_bwd_theta: order %d not in 0..3", order);
-    LF_REQUIRE(act_kind >= 0 && act_kind <= LF_ACT_NONE, "lf_wls_bwd_theta: bad activation %d", act_kind);
+    if (theta_check("lf_wls_bwd_theta", theta, theta_batch_stride, xs, ys, N, H, W)) return -1;
+    LF_REQUIRE(logits && beta && zinv && grad_beta && grad_logits && grad_theta && workspace, "lf_wls_bwd_theta: null pointer");
+    if (fit_check("lf_wls_bwd_theta", N, K, H, W, zero_rows, order, act_kind)) return -1;
     hipStream_t st = (hipStream_t)stream;
-    double* p = (double*)workspace;
-    switch (order) {
-        case 0: return wls_bwd_theta_launch<0>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, y_offset, act_kind, beta, zinv, grad_beta, grad_logits, grad_theta, p, st);
-        case 1: return wls_bwd_theta_launch<1>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, y_offset, act_kind, beta, zinv, grad_beta, grad_logits, grad_theta, p, st);
-        case 2: return wls_bwd_theta_launch<2>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, y_offset, act_kind, beta, zinv, grad_beta, grad_logits, grad_theta, p, st);
-        default: return wls_bwd_theta_launch<3>(logits, theta, theta_batch_stride, xs, ys, N, K, H, W, zero_rows, y_offset, act_kind, beta, zinv, grad_beta, grad_logits, grad_theta, p, st);
-    }
+    if (with_order(order, [&](auto O) {
+            return wls_bwd_launch<O(), GridTheta>(logits, {theta, theta_batch_stride, xs, ys}, N, K, H, W, zero_rows, y_offset, act_kind,
+                                                  beta, zinv, grad_beta, grad_logits, (double*)workspace, st);
+        }))
+        return -1;
+    // per-image theta: K lanes x chunks rows each; shared theta: all N*K lanes into one matrix
+    const int outs = theta_batch_stride ? N : 1, rows = (theta_batch_stride ? K : N * K) * fit_bwd_chunks(H, W);
+    hipLaunchKernelGGL(theta_finish_kernel, dim3(outs), dim3(LF_WAVE), 0, st, (const double*)workspace, rows, grad_theta);
+    LF_CHECK_LAUNCH("theta_finish");
+    return 0;
 }
-#undef LF_THETA_REQUIRE
 
 // d loss / d grid of lf_wls_fwd's explicit grid (arguments as lf_wls_bwd): grad_grid (N, H*W, 2) fp32, or (H*W, 2) summed over
 // the images when grid_batch_stride = 0.
@@ -1127,10 +984,7 @@ extern "C" int lf_wls_bwd_grid(const float* logits, const float* grid_xy, long g
                                int zero_rows, int order, double y_offset, int act_kind, const double* beta, const double* zinv,
                                const double* grad_beta, float* grad_grid, void* stream) {
     LF_REQUIRE(logits && grid_xy && beta && zinv && grad_beta && grad_grid, "lf_wls_bwd_grid: null pointer");
-    LF_REQUIRE(N > 0 && K > 0 && H > 0 && W > 0, "lf_wls_bwd_grid: bad shape");
-    LF_REQUIRE(zero_rows >= 0 && zero_rows < H, "lf_wls_bwd_grid: zero_rows %d out of [0,%d)", zero_rows, H);
-    LF_REQUIRE(order >= 0 && order <= 3, "lf_wls_bwd_grid: order %d not in 0..3", order);
-    LF_REQUIRE(act_kind >= 0 && act_kind <= LF_ACT_NONE, "lf_wls_bwd_grid: bad activation %d", act_kind);
+    if (fit_check("lf_wls_bwd_grid", N, K, H, W, zero_rows, order, act_kind)) return -1;
     LF_REQUIRE(grid_batch_stride % 2 == 0 && ((size_t)grid_xy & 7) == 0 && ((size_t)grad_grid & 7) == 0,
                "lf_wls_bwd_grid: grid / grad_grid are read and written as float2: misaligned");
     const int NK = grid_batch_stride ? K : N * K;
@@ -1138,16 +992,11 @@ extern "C" int lf_wls_bwd_grid(const float* logits, const float* grid_xy, long g
     LF_REQUIRE(lds <= 48 * 1024, "lf_wls_bwd_grid: %d lanes on one grid exceed the LDS table (%zu bytes)", NK, lds);
     hipStream_t st = (hipStream_t)stream;
     const dim3 g1(lf_cdiv((long)H * W, WLS_THREADS), grid_batch_stride ? N : 1);
-#define LF_BWD_GRID(OO)                                                                                                          \
-    hipLaunchKernelGGL(wls_bwd_grid_kernel<OO>, g1, dim3(WLS_THREADS), lds, st, logits, grid_xy, grid_batch_stride, NK, H, W,    \
-                       zero_rows, (float)y_offset, act_kind, beta, zinv, grad_beta, grad_grid)
-    switch (order) {
-        case 0: LF_BWD_GRID(0); break;
-        case 1: LF_BWD_GRID(1); break;
-        case 2: LF_BWD_GRID(2); break;
-        default: LF_BWD_GRID(3); break;
-    }
-#undef LF_BWD_GRID
+    with_order(order, [&](auto O) {
+        hipLaunchKernelGGL(wls_bwd_grid_kernel<O()>, g1, dim3(WLS_THREADS), lds, st, logits, grid_xy, grid_batch_stride, NK, H, W,
+                           zero_rows, (float)y_offset, act_kind, beta, zinv, grad_beta, grad_grid);
+        return 0;
+    });
     LF_CHECK_LAUNCH("wls_bwd_grid");
     return 0;
 }

@@ -28,12 +28,32 @@ def _raise_if_singular(status, solver):
                                   "could not be completed" % idx)
 
 
+def _fit_outputs(lib, logits, order, want_masked):
+    """The tensors a fit forward writes: -> (beta, zinv, status, masked | None, workspace)."""
+    (N, K), D, dev = logits.shape[:2], order + 1, logits.device
+    return (torch.empty(N, K, D, dtype=torch.float64, device=dev), torch.empty(N, K, D * D, dtype=torch.float64, device=dev),
+            torch.empty(N * K, dtype=torch.int32, device=dev), torch.empty_like(logits) if want_masked else None,
+            torch.empty(lib.lf_wls_workspace_bytes(N, K, order), dtype=torch.uint8, device=dev))
+
+
+def _fit_finish(ctx, saved, status, masked, solver, check):
+    """After the forward call of either fit Function: raise on a singular system, save, mark what has no gradient."""
+    if check:
+        _raise_if_singular(status, solver)
+    ctx.save_for_backward(*saved)
+    ctx.status = status
+    # (no zero tensors for the outputs nobody differentiates: autograd otherwise fills an (N, K, H, W) fp32 gradient for `masked`
+    # every step -- 205 MB, 27 us at config 3)
+    ctx.set_materialize_grads(False)
+    if masked is not None:
+        ctx.mark_non_differentiable(masked)
+
+
 class WLSFit(torch.autograd.Function):
     """(logits NCHW fp32, grid (P,2)|(N,P,2) fp32) -> beta (N,K,order+1) fp64 [, masked (N,K,H,W) fp32]."""
 
     @staticmethod
     def forward(ctx, logits, grid, zero_rows, order, reg, y_offset, act_kind, solver, want_masked, check):
-        lib = _lib.load()
         logits = logits.contiguous()
         assert logits.dtype == torch.float32 and logits.dim() == 4
         N, K, H, W = logits.shape
@@ -42,28 +62,14 @@ class WLSFit(torch.autograd.Function):
         gbs = H * W * 2 if grid.dim() == 3 and grid.shape[0] > 1 else 0
         if grid.dim() == 3 and grid.shape[0] > 1:
             assert grid.shape[0] >= N
-        D = order + 1
-        dev = logits.device
-        beta = torch.empty(N, K, D, dtype=torch.float64, device=dev)
-        zinv = torch.empty(N, K, D * D, dtype=torch.float64, device=dev)
-        status = torch.empty(N * K, dtype=torch.int32, device=dev)
-        masked = torch.empty_like(logits) if want_masked else None
-        ws = torch.empty(lib.lf_wls_workspace_bytes(N, K, order), dtype=torch.uint8, device=dev)
+        lib = _lib.load()
+        beta, zinv, status, masked, ws = _fit_outputs(lib, logits, order, want_masked)
         _lib.check(lib.lf_wls_fwd(_lib.ptr(logits), _lib.ptr(grid), gbs, N, K, H, W, zero_rows, order, float(reg),
                                   float(y_offset), act_kind, solver, _lib.ptr(beta), _lib.ptr(zinv),
                                   _lib.ptr(masked), _lib.ptr(ws), _lib.ptr(status), _lib.stream()), "lf_wls_fwd")
-        if check:
-            _raise_if_singular(status, solver)
-        ctx.save_for_backward(logits, grid, beta, zinv)
         ctx.cfg = (gbs, zero_rows, order, float(y_offset), act_kind)
-        ctx.status = status
-        # (no zero tensors for the outputs nobody differentiates: autograd otherwise fills an (N, K, H, W) fp32 gradient for `masked`
-        # every step -- 205 MB, 27 us at config 3)
-        ctx.set_materialize_grads(False)
-        if want_masked:
-            ctx.mark_non_differentiable(masked)
-            return beta, masked, status
-        return beta, None, status
+        _fit_finish(ctx, (logits, grid, beta, zinv), status, masked, solver, check)
+        return beta, masked, status
 
     @staticmethod
     def backward(ctx, gbeta, _gm, _gs):
@@ -72,9 +78,8 @@ class WLSFit(torch.autograd.Function):
         gbs, zero_rows, order, y_offset, act_kind = ctx.cfg
         N, K, H, W = logits.shape
         want_grid = ctx.needs_input_grad[1]
-        if gbeta is None:          # the coefficients were not used downstream
-            return (torch.zeros_like(logits), torch.zeros_like(grid) if want_grid else None,
-                    None, None, None, None, None, None, None, None)
+        if gbeta is None:          # (the coefficients were not used downstream)
+            return (torch.zeros_like(logits), torch.zeros_like(grid) if want_grid else None) + (None,) * 8
         gbeta = gbeta.to(torch.float64).contiguous()
         gl = torch.empty_like(logits)
         _lib.check(lib.lf_wls_bwd(_lib.ptr(logits), _lib.ptr(grid), gbs, N, K, H, W, zero_rows, order, y_offset,
@@ -141,32 +146,19 @@ class WLSFitTheta(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, theta, normalised, zero_rows, order, reg, y_offset, act_kind, solver, want_masked, check):
-        lib = _lib.load()
         logits = logits.contiguous()
         assert logits.dtype == torch.float32 and logits.dim() == 4
         N, K, H, W = logits.shape
         t32, tbs, n = _theta32(theta, N)
         xs, ys = geometry.base_tables_on(logits.device, H, W, normalised)
-        D = order + 1
-        dev = logits.device
-        beta = torch.empty(N, K, D, dtype=torch.float64, device=dev)
-        zinv = torch.empty(N, K, D * D, dtype=torch.float64, device=dev)
-        status = torch.empty(N * K, dtype=torch.int32, device=dev)
-        masked = torch.empty_like(logits) if want_masked else None
-        ws = torch.empty(lib.lf_wls_workspace_bytes(N, K, order), dtype=torch.uint8, device=dev)
+        lib = _lib.load()
+        beta, zinv, status, masked, ws = _fit_outputs(lib, logits, order, want_masked)
         _lib.check(lib.lf_wls_fwd_theta(_lib.ptr(logits), _lib.ptr(t32), tbs, _lib.ptr(xs), _lib.ptr(ys), N, K, H, W, zero_rows,
                                         order, float(reg), float(y_offset), act_kind, solver, _lib.ptr(beta), _lib.ptr(zinv),
                                         _lib.ptr(masked), _lib.ptr(ws), _lib.ptr(status), _lib.stream()), "lf_wls_fwd_theta")
-        if check:
-            _raise_if_singular(status, solver)
-        ctx.save_for_backward(logits, t32, xs, ys, beta, zinv)
         ctx.cfg = (tbs, n, zero_rows, order, float(y_offset), act_kind, theta.shape, theta.dtype)
-        ctx.status = status
-        ctx.set_materialize_grads(False)
-        if want_masked:
-            ctx.mark_non_differentiable(masked)
-            return beta, masked, status
-        return beta, None, status
+        _fit_finish(ctx, (logits, t32, xs, ys, beta, zinv), status, masked, solver, check)
+        return beta, masked, status
 
     @staticmethod
     def backward(ctx, gbeta, _gm, _gs):
@@ -175,10 +167,9 @@ class WLSFitTheta(torch.autograd.Function):
         tbs, n, zero_rows, order, y_offset, act_kind, tshape, tdtype = ctx.cfg
         N, K, H, W = logits.shape
         want_theta = ctx.needs_input_grad[1]
-        tail = (None,) * 9
-        if gbeta is None:
-            gt0 = torch.zeros(tshape, dtype=tdtype, device=logits.device) if want_theta else None
-            return (torch.zeros_like(logits), gt0) + tail
+        if gbeta is None:          # (the coefficients were not used downstream)
+            return (torch.zeros_like(logits),
+                    torch.zeros(tshape, dtype=tdtype, device=logits.device) if want_theta else None) + (None,) * 9
         gbeta = gbeta.to(torch.float64).contiguous()
         gl = torch.empty_like(logits)
         gt = torch.empty(n, 3, 3, dtype=torch.float64, device=logits.device)
@@ -186,7 +177,7 @@ class WLSFitTheta(torch.autograd.Function):
         _lib.check(lib.lf_wls_bwd_theta(_lib.ptr(logits), _lib.ptr(t32), tbs, _lib.ptr(xs), _lib.ptr(ys), N, K, H, W, zero_rows,
                                         order, y_offset, act_kind, _lib.ptr(beta), _lib.ptr(zinv), _lib.ptr(gbeta), _lib.ptr(gl),
                                         _lib.ptr(gt), _lib.ptr(ws), _lib.stream()), "lf_wls_bwd_theta")
-        return (gl, gt.view(tshape).to(tdtype) if want_theta else None) + tail
+        return (gl, gt.view(tshape).to(tdtype) if want_theta else None) + (None,) * 9
 
 
 class AreaLossFn(torch.autograd.Function):

@@ -26,8 +26,9 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 NEW_SYMBOLS = ("lf_theta_grid", "lf_theta_grid_bwd_workspace_bytes", "lf_theta_grid_bwd", "lf_wls_fwd_theta",
                "lf_wls_bwd_theta_workspace_bytes", "lf_wls_bwd_theta", "lf_wls_bwd_grid")
-NEW_KERNELS = ("theta_grid_kernel", "theta_grid_bwd_kernel", "theta_finish_kernel", "wls_moments_theta_kernel<",
-               "wls_bwd_theta_kernel<", "wls_bwd_grid_kernel<")
+# name prefix -> instantiations: orders 0..3; the two fit kernels in both vector widths, from both grid sources
+NEW_KERNELS = {"theta_grid_kernel": 1, "theta_grid_bwd_kernel": 1, "theta_finish_kernel": 1, "wls_moments_kernel<": 16,
+               "wls_bwd_kernel<": 16, "wls_bwd_grid_kernel<": 4}
 
 BEV_CASES = [(order, reg) for order in (0, 1, 2) for reg in (0.0, 1e-3)]
 BEV = dict(N=3, K=2, H=64, W=128, logits_seed=11, gbeta_seed=5, y_off=1.0, normalised=True, step=(4, 4))
@@ -158,10 +159,11 @@ def test_new_kernels_do_not_spill(tmp_path):
     asm = glob.glob(str(tmp_path / "*gfx950*.s"))
     assert asm, "no device assembly produced"
     kernels = isa_meta.kernels(asm[0])
-    for prefix in NEW_KERNELS:
+    for prefix, count in NEW_KERNELS.items():
         mine = [k for k in kernels if k["name"].startswith(prefix)]
-        # orders 0..3; the fit kernels in both vector widths
-        assert len(mine) == (8 if "theta_kernel<" in prefix else 4 if prefix.endswith("<") else 1), (prefix, [k["name"] for k in mine])
+        assert len(mine) == count, (prefix, [k["name"] for k in mine])
+        if count == 16:         # eight on the homography, eight on the constant grid
+            assert sum("GridTheta>" in k["name"] for k in mine) == 8 and sum("GridTable>" in k["name"] for k in mine) == 8, mine
         for k in mine:
             assert k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0 and k["scratch"] == 0, k
             assert k["vgpr"] + k["agpr"] <= 128, k          # four waves per SIMD at least
