@@ -121,6 +121,8 @@ def _declare(lib):
     dbg = {
         "lf_debug_set_split_any_size": (None, [I]),
         "lf_debug_set_bf16_lds": (None, [I]),
+        "lf_debug_set_bf16_no_partial_fast": (None, [I]),
+        "lf_debug_stride2_epi": (I, [I, I, P, P, P, P, I, P, P, P, P, I, I, I, I, I, P, P]),
         "lf_debug_set_ops_precision": (None, [I]),
         "lf_debug_conv1d_fwd_phases": (I, [P, P, P, P, I, I, I, I, I, I, P, P, P]),
         "lf_debug_conv1d_wgrad_phases": (I, [P, P, I, I, I, I, I, I, P, P, P]),
@@ -130,6 +132,7 @@ def _declare(lib):
         "lf_debug_conv1d_epi": (I, [P, P, P, P, I, I, P, P, P, P, P, P, I, I, I, I, I, I, P, P]),
         "lf_debug_conv1d_wgrad_pro": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P, P]),
         "lf_debug_bias_residual_launches": (L, []),
+        "lf_debug_partial_fast_launches": (L, []),
     }
     for table in (sig, dbg):
         for name, (res, args) in table.items():

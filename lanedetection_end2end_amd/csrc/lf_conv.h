@@ -11,6 +11,7 @@
 #include "lf_common.h"
 
 #define LF_MAX_TAPS 9
+struct TapIdx { int v[LF_MAX_TAPS]; };     // a kernel argument: packed tap t <- weight element v[t] of the layer's kernel
 
 struct LfTapGeom {
     int N, Hl, Wl;                 // logical pixel grid the kernel iterates over
@@ -62,6 +63,8 @@ struct LfTapArgs {
 
 void lf_tapgemm_set_split_any_size(int v);
 void lf_tapgemm_set_bf16_lds(int v);
+void lf_tapgemm_set_bf16_no_partial_fast(int v);   // 1: launches with Cs % 32 != 0 decline the compiled-in whole-step forms (tests)
+long lf_tapgemm_partial_fast_launches();            // launches with Cs % 32 != 0 that took a compiled-in whole-step form since the process started (tests)
 int lf_tapgemm_stat_rows(const LfTapGeom& g);                          // upper bound over the kernels (buffer sizing)
 int lf_tapgemm_stat_rows_for(const LfTapGeom& g, const LfTapArgs& a);  // rows the launch with these arguments writes
 int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, hipStream_t st);

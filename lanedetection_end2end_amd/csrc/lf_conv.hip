@@ -72,6 +72,16 @@ __device__ __forceinline__ f32x4 max0(f32x4 v) {
     b.x = b.x > 0 ? b.x : 0; b.y = b.y > 0 ? b.y : 0; b.z = b.z > 0 ? b.z : 0; b.w = b.w > 0 ? b.w : 0;
     return __builtin_bit_cast(f32x4, b);
 }
+// ReLU of LF_TAPGEMM_EPILOGUE on bf16 tensors (the streaming, ring and lean bf16 kernels), where a NaN stays a NaN: the matrix
+// cores return NaN with its sign bit set (0 * Inf, Inf - Inf), which max0 stores as 0 -- so a non-finite value in a window showed
+// in the output without ReLU and vanished with it (tests/test_bf16_stride2_kernels_gpu.py plants them).  v <= 0 is false for a
+// NaN (v_cmp + v_cndmask, two VALU instructions per element); on every other input the result has max0's bits (-0 and -Inf
+// included).  NOT changed, and not tested with non-finite values: the whole-line and wave-private bf16 kernels' own epilogues,
+// the fp32 kernels and every BN+ReLU operand prologue keep max0 and store 0 for a sign-set NaN.
+__device__ __forceinline__ f32x4 relu_keep_nan(f32x4 v) {
+    v.x = v.x <= 0.f ? 0.f : v.x; v.y = v.y <= 0.f ? 0.f : v.y; v.z = v.z <= 0.f ? 0.f : v.z; v.w = v.w <= 0.f ? 0.f : v.w;
+    return v;
+}
 __device__ __forceinline__ f32x4 keep_pos(f32x4 v, f32x4 m) {
     v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
     return v;
@@ -196,7 +206,7 @@ _Pragma("unroll") \
             if (epi & LF_EPI_MASK) v = keep_pos(v, lm[j]); \
             const int co = cob + n * 16 + kq * 4;   /* per-channel vectors: L1-resident, re-read instead of held in registers */ \
             if (epi & LF_EPI_MASKBN) v = keep_pos(v, lx[j] * (HOISTM ? hv[HOISTV ? n : 0][0] : ldb4(r_msc, co * 4u, 0u)) + (HOISTM ? hv[HOISTV ? n : 0][1] : ldb4(r_msh, co * 4u, 0u))); \
-            if (epi & LF_EPI_RELU) v = max0(v); \
+            if (epi & LF_EPI_RELU) v = S16 ? relu_keep_nan(v) : max0(v); \
             if (S16) v = round_bf16(v);   /* statistics are taken from the values as stored */ \
             if (pv[m]) epi_st<S16>(r_dst, dbase + n * 16, v); \
             if (!pv[m]) v = zero4(); \
@@ -603,7 +613,16 @@ __global__ __launch_bounds__(256, 2) void tapgemm_bf16_kernel(const LfTapGeom g,
     struct Step { u32x4 w[NT]; f32x4 xl[MT]; f32x4 sc0, sc1, sh0, sh1; unsigned ok; };
     __shared__ uint4 tab_off[WG_WAVES][LF_MAX_TAPS][64];
     __shared__ unsigned tab_ok[WG_WAVES][LF_MAX_TAPS][64];
-    for (int t = 0; t < g.ntaps; ++t) {
+    const int ncb = (g.Cs + 31) >> 5;                       // 32-channel steps per tap
+    const int nsteps = g.ntaps * ncb;
+    // FAST with a partial last step (16 or 48 source channels): the table has one row per (tap, step) instead of one per tap -- the
+    // launcher admits nsteps <= LF_MAX_TAPS -- and a lane whose 8 channels lie at or beyond Cs holds the out-of-range offset: it
+    // reads the buffer bound's zeros, not the memory behind the pixel's channels (the next pixel, another tensor's slice: their
+    // Inf / NaN against the zero-padded weights would be NaN in every output channel).  Whole steps: one row per tap, as before.
+    const bool part = FAST && (g.Cs & 31) != 0;
+    const int nrows = part ? nsteps : g.ntaps;
+    for (int r = 0; r < nrows; ++r) {
+        const int t = part ? r / ncb : r, c0 = (part ? r - t * ncb : 0) * 32 + kq * 8;
         const int dh = g.tdh[t], dw = g.tdw[t];
         unsigned o[MT], okb = 0;
 #pragma unroll
@@ -612,14 +631,12 @@ __global__ __launch_bounds__(256, 2) void tapgemm_bf16_kernel(const LfTapGeom g,
             const bool in = pv[m] && sy >= 0 && sy < g.Hs && sx >= 0 && sx < g.Ws;
             const int syc = min(max(sy, 0), g.Hs - 1), sxc = min(max(sx, 0), g.Ws - 1);
             o[m] = (unsigned)(((pn[m] * g.Hs + syc) * g.Ws + sxc) * g.s_pix + g.s_choff);
-            if constexpr (FAST) o[m] = in ? (o[m] + kq * 8) * 2u : LF_OOB;      // bytes, this lane's 8 channels
+            if constexpr (FAST) o[m] = (in && c0 < g.Cs) ? (o[m] + c0) * 2u : LF_OOB;      // bytes, this lane's 8 channels
             okb |= (in ? 1u : 0u) << m;
         }
-        tab_off[wave][t][lane] = make_uint4(o[0], o[1], o[2], o[3]);
-        tab_ok[wave][t][lane] = okb;
+        tab_off[wave][r][lane] = make_uint4(o[0], o[1], o[2], o[3]);
+        tab_ok[wave][r][lane] = okb;
     }
-    const int ncb = (g.Cs + 31) >> 5;                       // 32-channel steps per tap
-    const int nsteps = g.ntaps * ncb;
     const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.wp16, 0xffffffffu),
                                  rx = make_rsrc(a.src, FAST ? (unsigned)min((long)g.N * g.Hs * g.Ws * g.s_pix * 2, (long)LF_OOB) : 0xffffffffu),
                                  rsc = make_rsrc(a.pro_sc, 0xffffffffu), rsh = make_rsrc(a.pro_sh, 0xffffffffu);
@@ -630,7 +647,7 @@ __global__ __launch_bounds__(256, 2) void tapgemm_bf16_kernel(const LfTapGeom g,
     int t_ld = 0, cb_ld = 0, wofs = 0;
     auto issue = [&](Step& S) {
         const bool live = t_ld < ntaps;
-        const int tc = live ? t_ld : ntaps - 1;
+        const int tc = live ? (part ? t_ld * ncb + cb_ld : t_ld) : nrows - 1;      // (scalar) a table ROW: per (tap, step) if part, else per tap; a dead step takes the last one
         const uint4 o = tab_off[wave][tc][lane];
         const unsigned okb = tab_ok[wave][tc][lane];
 #pragma unroll
@@ -638,7 +655,7 @@ __global__ __launch_bounds__(256, 2) void tapgemm_bf16_kernel(const LfTapGeom g,
         const int c8 = min(cb_ld * 32 + kq * 8, g.Cs - 8);  // a partial last step re-reads valid channels (weights are 0)
         if constexpr (FAST) {
             const unsigned dead = live ? 0u : LF_OOB;        // a dead step (odd step count) reads zeros
-            const unsigned cs = (unsigned)cb_ld * 64u;
+            const unsigned cs = part ? 0u : (unsigned)cb_ld * 64u;      // (a per-step row holds its channel offset)
             S.xl[0] = ldb4(rx, o.x | dead, cs); S.xl[1] = ldb4(rx, o.y | dead, cs);
             S.xl[2] = ldb4(rx, o.z | dead, cs); S.xl[3] = ldb4(rx, o.w | dead, cs);
         } else {                                             // buffer-addressed (see ldb4): bf16 elements, 16 bytes = 8 channels
@@ -2122,6 +2139,8 @@ std::atomic<long> g_bres_launches{0};   // compiled-in bias + residual + ReLU la
 int g_bf16_lds = 4;            // tools / A-B runs only: 4 = wave-private (64 ch) / whole-line (128 ch) + 16-channel kernels where they apply, else the ring (shipped);
                                // 3 = the whole-line kernel at 64 channels too (round 5's routing); 2 = the ring
                                // for every launch it takes; 0 = the streaming bf16 kernel only
+std::atomic<long> g_part_fast_launches{0};   // launches with Cs % 32 != 0 that took a compiled-in whole-step form (lf_tapgemm_partial_fast_launches)
+int g_bf16_no_partial_fast = 0; // kernel-level tests only: launches with Cs % 32 != 0 decline the compiled-in whole-step forms of tapgemm_bf16_kernel
 
 int pick_nt(int Cd) {
     const int tiles = Cd / 16;
@@ -2136,6 +2155,8 @@ int pick_nt(int Cd) {
 void lf_tapgemm_set_split_any_size(int v) { g_split_any_size = v; }
 long lf_tapgemm_bias_residual_launches() { return g_bres_launches.load(); }
 void lf_tapgemm_set_bf16_lds(int v) { g_bf16_lds = v; }
+void lf_tapgemm_set_bf16_no_partial_fast(int v) { g_bf16_no_partial_fast = v; }
+long lf_tapgemm_partial_fast_launches() { return g_part_fast_launches.load(); }
 
 // launches the split kernel takes: whole 32-channel K-steps, 64-channel output slabs (NT = 4), whole 512-pixel
 // workgroups (its two 4-wave groups each own one 256-pixel statistics row), 16-byte aligned pixels
@@ -2404,6 +2425,8 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
                 return 0;
             }
         }
+        // compiled-in whole-step forms at Cs % 32 != 0 (below): their tap table has one row per (tap, step)
+        const bool part_fast = !g_bf16_no_partial_fast && g.ntaps * ((g.Cs + 31) / 32) <= LF_MAX_TAPS;
         const bool ring = fast16 && g_bf16_lds >= 2 && g.Wl % 16 == 0 && g.Cd % 64 == 0;
         const unsigned nitems = (unsigned)(lf_cdiv(npix, PIX_PER_WG) * (g.Cd / 64));
         if (ring && a.dbg) {        // stamps (tools/kbench.py --phases16): the plain convolution only
@@ -2436,32 +2459,36 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
                 case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_TG16F(LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
                 default: LF_TG16F(-1); break;
             }
-        } else if (nt == 4 && a.s16 && pro != LF_PRO_BNRELU && g.Cs == 16 && (epis == (LF_EPI_MASK | LF_EPI_STATS_XHAT) || epis == 0) &&
+        } else if (nt == 4 && a.s16 && pro != LF_PRO_BNRELU && g.Cs == 16 && (epis == (LF_EPI_MASK | LF_EPI_STATS_XHAT) || epis == 0) && part_fast &&
                    (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB) {
             // 16 source channels into a 64-channel slab (the data gradient of UpsamplerBlock(64, 16): 9 taps, stride 2, with the previous
             // layer's mask + BN-backward sums; 204 us per launch at config 3 on the run-time-flag form): ONE 32-channel step per tap on the
-            // compiled-in form.  Lanes kq = 2, 3 read the 16 elements BEHIND the pixel's 16 channels -- the next pixel's (or, past the
-            // tensor's end, the buffer bound's zeros): finite values against the zero-padded half of the packed weights
+            // compiled-in form.  Lanes kq = 2, 3 -- channels 16..31 of the step, which the pixel does not have -- hold the out-of-range
+            // offset and read the buffer bound's zeros against the zero-padded half of the packed weights
             if (epis == 0) LF_TG16F(0); else LF_TG16F(LF_EPI_MASK | LF_EPI_STATS_XHAT);
-        } else if (nt == 3 && a.s16 && pro != LF_PRO_BNRELU && g.Cs == 16 && (epis == LF_EPI_STATS_SQ || epis == LF_EPI_RELU || epis == 0) &&
+            ++g_part_fast_launches;
+        } else if (nt == 3 && a.s16 && pro != LF_PRO_BNRELU && g.Cs == 16 && (epis == LF_EPI_STATS_SQ || epis == LF_EPI_RELU || epis == 0) && part_fast &&
                    (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB) {
             // ... and the 16 -> 48 channel convolution of DownsamplerBlock(16, 64) (9 taps, stride 2, BN forward sums; 112 us on the run-time-flag form)
             // (RELU: the inference engine's folded form of the same convolution)
             if (epis == 0) hipLaunchKernelGGL((tapgemm_bf16_kernel<3, 0, 0, true>), grid, dim3(256), 0, st, g, a, pro, epi);
             else if (epis == LF_EPI_RELU) hipLaunchKernelGGL((tapgemm_bf16_kernel<3, 0, LF_EPI_RELU, true>), grid, dim3(256), 0, st, g, a, pro, epi);
             else hipLaunchKernelGGL((tapgemm_bf16_kernel<3, 0, LF_EPI_STATS_SQ, true>), grid, dim3(256), 0, st, g, a, pro, epi);
+            ++g_part_fast_launches;
         } else if (nt == 4 && a.s16 && pro == LF_PRO_BNRELU && epi == LF_EPI_RELU) {
             hipLaunchKernelGGL((tapgemm_bf16_kernel<4, 1, LF_EPI_RELU, false>), grid, dim3(256), 0, st, g, a, pro, epi);
         } else if (nt == 1 && a.s16 && pro != LF_PRO_BNRELU && ((g.Cs + 31) / 32 * 32 + g.s_choff <= g.s_pix) && (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB &&
+                   (g.Cs % 32 == 0 || part_fast) &&
                    (epis == 0 || epis == LF_EPI_STATS_SQ || epis == LF_EPI_ADD || epis == LF_EPI_RELU)) {
             // 16 output channels from whole 32-channel steps (round 6: the sub-pixel phases of UpsamplerBlock(64, 16) and the data gradient
             // of DownsamplerBlock(16, 64)'s convolution: 8 launches per step on the run-time-flag form before): padding as out-of-range
-            // offsets, compiled-in epilogue.  A partial last step (48 source channels) reads the pixel's next channels -- they exist:
-            // the condition above -- against zero-padded weights
+            // offsets, compiled-in epilogue.  In a partial last step (48 source channels) the lanes of channels 48..63 hold the out-of-range
+            // offset too: zeros against the zero-padded weights, not the pixel's next channels (another tensor's slice)
             if (epis == 0) hipLaunchKernelGGL((tapgemm_bf16_kernel<1, 0, 0, true>), grid, dim3(256), 0, st, g, a, pro, epi);
             else if (epis == LF_EPI_STATS_SQ) hipLaunchKernelGGL((tapgemm_bf16_kernel<1, 0, LF_EPI_STATS_SQ, true>), grid, dim3(256), 0, st, g, a, pro, epi);
             else if (epis == LF_EPI_RELU) hipLaunchKernelGGL((tapgemm_bf16_kernel<1, 0, LF_EPI_RELU, true>), grid, dim3(256), 0, st, g, a, pro, epi);   // (inference: folded phases)
             else hipLaunchKernelGGL((tapgemm_bf16_kernel<1, 0, LF_EPI_ADD, true>), grid, dim3(256), 0, st, g, a, pro, epi);
+            if (g.Cs % 32 != 0) ++g_part_fast_launches;
         } else
         switch (nt) {
             case 4: LF_TG16(4); break;
@@ -3411,8 +3438,6 @@ int lf_tapwgrad_launch(const LfTapGeom& g, const LfWgradArgs& a, int pro, hipStr
 // split-K reduction + scatter into the PyTorch parameter-gradient layout; bias rows; packing
 // ---------------------------------------------------------------------------------------
 namespace {
-
-struct TapIdx { int v[LF_MAX_TAPS]; };
 
 __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const float* __restrict__ partial, int splits, int ntaps,
                                                            int Cs, int Cd, float* __restrict__ grad, long sk, long sn,

@@ -11,6 +11,12 @@ void lf_debug_set_split_any_size(int v);
    where they apply, else the ring; 3 the whole-line kernel at 64 channels too (round 5's routing); 2 the ring for every launch it takes;
    0 the streaming kernel only (A/B timing, bit-identity of the forms: tools/bf16_ab.py, tests/test_bf16_kernels_gpu.py) */
 void lf_debug_set_bf16_lds(int v);
+/* 1: bf16-tensor launches whose source-channel count is no multiple of 32 (16, 48) decline the compiled-in whole-step forms of
+   tapgemm_bf16_kernel and run on its run-time-flag form, which clamps a partial step's channel offsets inside the pixel; 0 (shipped):
+   the compiled-in forms.  The two agree bit for bit (tests/test_bf16_stride2_kernels_gpu.py) */
+void lf_debug_set_bf16_no_partial_fast(int v);
+/* launches with Cs % 32 != 0 that took one of those compiled-in forms since the process started: which form a launch selected */
+long lf_debug_partial_fast_launches(void);
 /* precision mode of the lf_conv1d_* calls: 0 fp32, 2 bf16 matrix cores on bf16 tensors (x, y, gx, gy, mask_src hold bf16; w, bias,
  * gw, gb stay fp32), 9 fp32 from 9-term split operands (modes 1 and 6 were removed in round 6 and select 0) */
 void lf_debug_set_ops_precision(int mode);
@@ -42,6 +48,20 @@ int lf_debug_conv1d_bwd_data_epi3(const float* gy, const float* w, const float* 
 int lf_debug_conv1d_epi(const float* src, const float* w, const float* bias, float* dst, int transposed, int epi, const float* mask_src,
                         const float* add_src, const float* aux, const float* msc, const float* msh, float* stats, int N, int H, int W, int C,
                         int axis, int dilation, float* scratch, void* stream);
+/* one tap-GEMM launch of a stride-2 layer, with the geometry and the weight gather the ERFNet plan builds (lf_plan.h), any epilogue flag
+ * set of csrc/lf_conv.h and the precision of lf_debug_set_ops_precision (0 fp32, 2 bf16 tensors).  (N, H, W): the LARGER tensor, H and W even.
+ *   kind 0  DownsamplerBlock conv forward: Conv2d(Cin, Cout, 3, stride 2, pad 1); src (N,H,W,Cin) -> channels [0, Cout) of dst
+ *           (N,H/2,W/2,Cin+Cout), the block's concat buffer; w (Cout,Cin,3,3)
+ *   kind 1  its data gradient, sub-pixel phase (a, b) = (phase >> 1, phase & 1): src (N,H/2,W/2,Cin+Cout) read at channels [0, Cout)
+ *           -> pixels (2i+a, 2j+b) of dst (N,H,W,Cin)
+ *   kind 2  UpsamplerBlock forward phase: ConvTranspose2d(Cin, Cout, 3, stride 2, pad 1, output_padding 1), w (Cin,Cout,3,3);
+ *           src (N,H/2,W/2,Cin) -> pixels (2i+a, 2j+b) of dst (N,H,W,Cout)
+ *   kind 3  its data gradient: src (N,H,W,Cout) -> dst (N,H/2,W/2,Cin)
+ * mask_src, add_src, aux: tensors of the destination's layout; bias fp32 [produced channels]; scratch: 9 * roundup(Kc, 32) * Nc floats.
+ * stats: [2][produced channels][rows], rows = ceil(logical pixels / 256).  Returns the rows written (0 without a sums flag), -1 on error. */
+int lf_debug_stride2_epi(int kind, int phase, const float* src, const float* w, const float* bias, float* dst, int epi, const float* mask_src,
+                         const float* add_src, const float* aux, float* stats, int N, int H, int W, int Cin, int Cout, float* scratch,
+                         void* stream);
 /* tap-GEMM launches that took a compiled-in bias + residual + ReLU epilogue (the inference engine's block tail) since the process
  * started: which kernel form a launch selected (tests/test_infer_gpu.py) */
 long lf_debug_bias_residual_launches(void);

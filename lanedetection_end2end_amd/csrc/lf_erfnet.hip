@@ -130,60 +130,36 @@ void build_conv1d(lf_erfnet_plan* P, ConvRef& c, int N, int H, int W, int C, int
     c.dg[0].pack = add_pack(P, c.p_w, C, C, /*sk (co)*/ (long)C * 3, /*sn (ci)*/ 3, g, idx_d);
 }
 
-// sub-pixel phase tap sets shared by "3x3 s2 conv data-gradient" and "3x3 s2 transposed conv forward"
-int phase_taps(int a, int* k, int* off) {
-    if (a == 0) { k[0] = 1; off[0] = 0; return 1; }
-    k[0] = 0; off[0] = 1; k[1] = 2; off[1] = 0;
-    return 2;
+int add_pack(lf_erfnet_plan* P, int param, const LfStride2Op& op) {
+    return add_pack(P, param, op.Kc, op.Nc, op.sk, op.sn, op.geom, op.tapidx);
 }
 
-// DownsamplerBlock conv: Conv2d(Cin, Cc, 3, stride 2, pad 1) writing channels [0,Cc) of the concat buffer
+// DownsamplerBlock conv: Conv2d(Cin, Cc, 3, stride 2, pad 1) writing channels [0,Cc) of the concat buffer (geometries: lf_plan.h)
 void build_down_conv(lf_erfnet_plan* P, ConvRef& c, int N, int H, int W, int Cin, int Cc, int Ccat) {
-    const int Ho = H / 2, Wo = W / 2;
-    LfTapGeom g = lf_base_geom(N, Ho, Wo, H, W, Cin, Ho, Wo, Ccat, Cin, Cc);
-    g.ssh = 2; g.ssw = 2; g.ntaps = 9;
-    int idx[9];
-    for (int kh = 0; kh < 3; ++kh)
-        for (int kw = 0; kw < 3; ++kw) { g.tdh[kh * 3 + kw] = kh - 1; g.tdw[kh * 3 + kw] = kw - 1; idx[kh * 3 + kw] = kh * 3 + kw; }
-    c.fwd.geom = g;
-    c.fwd.pack = add_pack(P, c.p_w, Cin, Cc, /*sk (ci)*/ 9, /*sn (co)*/ (long)Cin * 9, g, idx);
+    LfStride2Op fwd, dg[4];
+    lf_down_conv_ops(N, H, W, Cin, Cc, Ccat, fwd, dg);
+    c.fwd.geom = fwd.geom;
+    c.fwd.pack = add_pack(P, c.p_w, fwd);
     c.nfph = 0;
     c.ndg = 4;
-    for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < 2; ++b) {
-            LfTapGeom d = lf_base_geom(N, Ho, Wo, Ho, Wo, Ccat, H, W, Cin, Cc, Cin);
-            d.dsh = 2; d.dsw = 2; d.dah = a; d.daw = b;
-            int kh[2], oh[2], kw[2], ow[2], ti[4];
-            const int na = phase_taps(a, kh, oh), nb = phase_taps(b, kw, ow);
-            for (int i = 0; i < na; ++i)
-                for (int j = 0; j < nb; ++j) { d.tdh[d.ntaps] = oh[i]; d.tdw[d.ntaps] = ow[j]; ti[d.ntaps] = kh[i] * 3 + kw[j]; ++d.ntaps; }
-            c.dg[a * 2 + b].geom = d;
-            c.dg[a * 2 + b].pack = add_pack(P, c.p_w, Cc, Cin, /*sk (co)*/ (long)Cin * 9, /*sn (ci)*/ 9, d, ti);
-        }
+    for (int i = 0; i < 4; ++i) {
+        c.dg[i].geom = dg[i].geom;
+        c.dg[i].pack = add_pack(P, c.p_w, dg[i]);
+    }
 }
 
-// UpsamplerBlock conv: ConvTranspose2d(Cin, Co, 3, stride 2, pad 1, output_padding 1), weight (Cin,Co,3,3)
+// UpsamplerBlock conv: ConvTranspose2d(Cin, Co, 3, stride 2, pad 1, output_padding 1), weight (Cin,Co,3,3) (geometries: lf_plan.h)
 void build_up_conv(lf_erfnet_plan* P, ConvRef& c, int N, int Hi, int Wi, int Cin, int Co) {
+    LfStride2Op fph[4], dg;
+    lf_up_conv_ops(N, Hi, Wi, Cin, Co, fph, dg);
     c.nfph = 4;
-    for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < 2; ++b) {
-            LfTapGeom g = lf_base_geom(N, Hi, Wi, Hi, Wi, Cin, 2 * Hi, 2 * Wi, Co, Cin, Co);
-            g.dsh = 2; g.dsw = 2; g.dah = a; g.daw = b;
-            int kh[2], oh[2], kw[2], ow[2], ti[4];
-            const int na = phase_taps(a, kh, oh), nb = phase_taps(b, kw, ow);
-            for (int i = 0; i < na; ++i)
-                for (int j = 0; j < nb; ++j) { g.tdh[g.ntaps] = oh[i]; g.tdw[g.ntaps] = ow[j]; ti[g.ntaps] = kh[i] * 3 + kw[j]; ++g.ntaps; }
-            c.fph[a * 2 + b].geom = g;
-            c.fph[a * 2 + b].pack = add_pack(P, c.p_w, Cin, Co, /*sk (ci)*/ (long)Co * 9, /*sn (co)*/ 9, g, ti);
-        }
-    LfTapGeom d = lf_base_geom(N, Hi, Wi, 2 * Hi, 2 * Wi, Co, Hi, Wi, Cin, Co, Cin);
-    d.ssh = 2; d.ssw = 2; d.ntaps = 9;
-    int idx[9];
-    for (int kh = 0; kh < 3; ++kh)
-        for (int kw = 0; kw < 3; ++kw) { d.tdh[kh * 3 + kw] = kh - 1; d.tdw[kh * 3 + kw] = kw - 1; idx[kh * 3 + kw] = kh * 3 + kw; }
+    for (int i = 0; i < 4; ++i) {
+        c.fph[i].geom = fph[i].geom;
+        c.fph[i].pack = add_pack(P, c.p_w, fph[i]);
+    }
     c.ndg = 1;
-    c.dg[0].geom = d;
-    c.dg[0].pack = add_pack(P, c.p_w, Co, Cin, /*sk (co)*/ 9, /*sn (ci)*/ (long)Co * 9, d, idx);
+    c.dg[0].geom = dg.geom;
+    c.dg[0].pack = add_pack(P, c.p_w, dg);
     c.fwd = c.fph[0];
 }
 

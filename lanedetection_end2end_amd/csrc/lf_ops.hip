@@ -4,11 +4,19 @@
 // Replaces nn.Conv2d(C, C, (3,1)|(1,3), padding=d, dilation=d) of non_bottleneck_1d (ERFNet.py:29-37).
 #include "lf_conv.h"
 #include "lf_debug.h"
+#include "lf_plan.h"
 
 namespace {
 
+TapIdx conv1d_taps(int flip) {
+    TapIdx ti;
+    memset(&ti, 0, sizeof(ti));
+    for (int t = 0; t < 3; ++t) ti.v[t] = flip ? 2 - t : t;
+    return ti;
+}
+
 __global__ __launch_bounds__(256) void pack_one_kernel(const float* __restrict__ w, float* __restrict__ dst, int Kc, int Nc,
-                                                      int ntaps, long sk, long sn, int flip) {
+                                                      int ntaps, long sk, long sn, const TapIdx ti) {
     const long total = (long)ntaps * Kc * Nc;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int k4 = (int)(i & 3);
@@ -17,13 +25,13 @@ __global__ __launch_bounds__(256) void pack_one_kernel(const float* __restrict__
         r /= Nc;
         const int kb = (int)(r % (Kc >> 2));
         const int t = (int)(r / (Kc >> 2));
-        dst[i] = w[(kb * 4 + k4) * sk + n * sn + (flip ? ntaps - 1 - t : t)];
+        dst[i] = w[(kb * 4 + k4) * sk + n * sn + ti.v[t]];
     }
 }
 
 // bf16 operand order of tapgemm_bf16_kernel: [tap][ceil(Kc/32)*4][Nc][8], zero beyond Kc
 __global__ __launch_bounds__(256) void pack_one_bf16_kernel(const float* __restrict__ w, __bf16* __restrict__ dst, int Kc, int Nc,
-                                                           int ntaps, long sk, long sn, int flip) {
+                                                           int ntaps, long sk, long sn, const TapIdx ti) {
     const int kb_per_tap = ((Kc + 31) >> 5) * 4;
     const long total = (long)ntaps * kb_per_tap * Nc * 8;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -34,13 +42,13 @@ __global__ __launch_bounds__(256) void pack_one_bf16_kernel(const float* __restr
         const int kb = (int)(r % kb_per_tap);
         const int t = (int)(r / kb_per_tap);
         const int k = kb * 8 + k8;
-        dst[i] = (__bf16)(k < Kc ? w[k * sk + n * sn + (flip ? ntaps - 1 - t : t)] : 0.f);
+        dst[i] = (__bf16)(k < Kc ? w[k * sk + n * sn + ti.v[t]] : 0.f);
     }
 }
 
 // split operand order of tapgemm_split_kernel: [tap][Kc/8][Nc][3][8] bf16 (pieces h, m, l; h + m + l == w exactly)
 __global__ __launch_bounds__(256) void pack_one_split_kernel(const float* __restrict__ w, __bf16* __restrict__ dst, int Kc, int Nc,
-                                                            int ntaps, long sk, long sn, int flip) {
+                                                            int ntaps, long sk, long sn, const TapIdx ti) {
     const int kb_per_tap = Kc >> 3;
     const long total = (long)ntaps * kb_per_tap * Nc * 8;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -51,7 +59,7 @@ __global__ __launch_bounds__(256) void pack_one_split_kernel(const float* __rest
         r /= Nc;
         const int kb = (int)(r % kb_per_tap);
         const int t = (int)(r / kb_per_tap);
-        const float v = w[(kb * 8 + k8) * sk + n * sn + (flip ? ntaps - 1 - t : t)];
+        const float v = w[(kb * 8 + k8) * sk + n * sn + ti.v[t]];
         const __bf16 vh = (__bf16)v;
         const float r1 = v - (float)vh;
         const __bf16 vm = (__bf16)r1;
@@ -64,19 +72,19 @@ int g_ops_bf16 = 0;     // 0 fp32 cores, 2 bf16 cores on bf16 tensors, 9 fp32 fr
 // pack into scratch in the order the selected kernel wants; returns the LfTapArgs weight fields
 void pack_conv1d(LfTapArgs& a, const float* w, float* scratch, int C, long sk, long sn, int flip, hipStream_t st) {
     if (g_ops_bf16 == 9) {
-        hipLaunchKernelGGL(pack_one_kernel, dim3(64), dim3(256), 0, st, w, scratch, C, C, 3, sk, sn, flip);
+        hipLaunchKernelGGL(pack_one_kernel, dim3(64), dim3(256), 0, st, w, scratch, C, C, 3, sk, sn, conv1d_taps(flip));
         if (C % 32 == 0) {
             hipLaunchKernelGGL(pack_one_split_kernel, dim3(64), dim3(256), 0, st, w, reinterpret_cast<__bf16*>(scratch + 3L * C * C),
-                               C, C, 3, sk, sn, flip);
+                               C, C, 3, sk, sn, conv1d_taps(flip));
             a.split = g_ops_bf16;
             a.wp48 = scratch + 3L * C * C;
         }
     } else if (g_ops_bf16 == 2) {
-        hipLaunchKernelGGL(pack_one_bf16_kernel, dim3(64), dim3(256), 0, st, w, reinterpret_cast<__bf16*>(scratch), C, C, 3, sk, sn, flip);
+        hipLaunchKernelGGL(pack_one_bf16_kernel, dim3(64), dim3(256), 0, st, w, reinterpret_cast<__bf16*>(scratch), C, C, 3, sk, sn, conv1d_taps(flip));
         a.wp16 = scratch;
         a.s16 = 1;
     } else {
-        hipLaunchKernelGGL(pack_one_kernel, dim3(64), dim3(256), 0, st, w, scratch, C, C, 3, sk, sn, flip);
+        hipLaunchKernelGGL(pack_one_kernel, dim3(64), dim3(256), 0, st, w, scratch, C, C, 3, sk, sn, conv1d_taps(flip));
     }
     a.wp = scratch;
 }
@@ -96,6 +104,7 @@ extern "C" {
 
 void lf_debug_set_split_any_size(int v) { lf_tapgemm_set_split_any_size(v); }
 void lf_debug_set_bf16_lds(int v) { lf_tapgemm_set_bf16_lds(v); }
+void lf_debug_set_bf16_no_partial_fast(int v) { lf_tapgemm_set_bf16_no_partial_fast(v); }
 // precision mode of the kernel-level conv1d calls below (tests, kbench): 0 fp32, 2 bf16 matrix cores on bf16 tensors (x, y, gx, gy,
 // mask_src then hold bf16 elements; w, bias, gw, gb stay fp32), 9 fp32 from 9-term split operands; anything else (the removed
 // modes 1 and 6) selects 0
@@ -103,6 +112,7 @@ void lf_debug_set_ops_precision(int mode) { g_ops_bf16 = (mode == 2 || mode == 9
 
 void lf_debug_set_wgrad_ro(int mode, int cap64, int cap128) { lf_tapwgrad_ro_set(mode, cap64, cap128); }
 long lf_debug_bias_residual_launches(void) { return lf_tapgemm_bias_residual_launches(); }
+long lf_debug_partial_fast_launches(void) { return lf_tapgemm_partial_fast_launches(); }
 
 // same as lf_conv1d_fwd with per-wave phase timestamps: dbg receives 8 uint64 per wave
 // (start, tap table built, main loop done, stores retired); waves = ceil(N*H*W/256)*4*(C/64)
@@ -203,6 +213,41 @@ int lf_debug_conv1d_epi(const float* src, const float* w, const float* bias, flo
     else pack_conv1d(a, w, scratch, C, 3L, 3L * C, 0, st);
     a.src = src; a.dst = dst; a.bias = bias; a.mask_src = mask_src; a.add_src = add_src; a.aux = aux; a.msc = msc; a.msh = msh; a.stats = stats;
     a.stats_ld = lf_tapgemm_stat_rows(g);        // the caller's buffer: [2][C][rows], rows = ceil(N * H * W / 256)
+    if (lf_tapgemm_launch(g, a, LF_PRO_NONE, epi, st)) return -1;
+    return (epi & (LF_EPI_STATS_SQ | LF_EPI_STATS_XHAT)) ? lf_tapgemm_stat_rows_for(g, a) : 0;
+}
+
+// One launch of a stride-2 layer (see lf_debug.h); the geometry and the weight gather are the plan's own (lf_plan.h)
+int lf_debug_stride2_epi(int kind, int phase, const float* src, const float* w, const float* bias, float* dst, int epi, const float* mask_src,
+                         const float* add_src, const float* aux, float* stats, int N, int H, int W, int Cin, int Cout, float* scratch,
+                         void* stream) {
+    if (!(src && w && dst && scratch)) { lf_fail("lf_debug_stride2_epi: null pointer"); return -1; }
+    if (kind < 0 || kind > 3 || phase < 0 || phase > 3 || N < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || Cin < 16 || Cout < 16) {
+        lf_fail("lf_debug_stride2_epi: bad arguments (kind %d phase %d N %d H %d W %d Cin %d Cout %d)", kind, phase, N, H, W, Cin, Cout);
+        return -1;
+    }
+    if (g_ops_bf16 != 0 && g_ops_bf16 != 2) { lf_fail("lf_debug_stride2_epi: precision mode 0 or 2 only"); return -1; }
+    hipStream_t st = (hipStream_t)stream;
+    LfStride2Op one, four[4];
+    if (kind <= 1) lf_down_conv_ops(N, H, W, Cin, Cout, Cin + Cout, one, four);
+    else lf_up_conv_ops(N, H / 2, W / 2, Cin, Cout, four, one);
+    const LfStride2Op& op = (kind == 0 || kind == 3) ? one : four[phase];
+    const LfTapGeom& g = op.geom;
+    TapIdx ti;
+    memset(&ti, 0, sizeof(ti));
+    for (int t = 0; t < g.ntaps; ++t) ti.v[t] = op.tapidx[t];
+    LfTapArgs a;
+    memset(&a, 0, sizeof(a));
+    if (g_ops_bf16 == 2) {
+        hipLaunchKernelGGL(pack_one_bf16_kernel, dim3(64), dim3(256), 0, st, w, reinterpret_cast<__bf16*>(scratch), op.Kc, op.Nc, g.ntaps, op.sk, op.sn, ti);
+        a.wp16 = scratch;
+        a.s16 = 1;
+    } else {
+        hipLaunchKernelGGL(pack_one_kernel, dim3(64), dim3(256), 0, st, w, scratch, op.Kc, op.Nc, g.ntaps, op.sk, op.sn, ti);
+    }
+    a.wp = scratch;
+    a.src = src; a.dst = dst; a.bias = bias; a.mask_src = mask_src; a.add_src = add_src; a.aux = aux; a.stats = stats;
+    a.stats_ld = lf_tapgemm_stat_rows(g);        // the caller's buffer: [2][Cd][rows], rows = ceil(logical pixels / 256)
     if (lf_tapgemm_launch(g, a, LF_PRO_NONE, epi, st)) return -1;
     return (epi & (LF_EPI_STATS_SQ | LF_EPI_STATS_XHAT)) ? lf_tapgemm_stat_rows_for(g, a) : 0;
 }

@@ -1,4 +1,4 @@
-// Small host-side helpers shared by the plan builders (lf_erfnet.hip, lf_convchain.hip).
+// Small host-side helpers shared by the plan builders (lf_erfnet.hip, lf_convchain.hip) and the kernel-level hooks (lf_ops.hip).
 #pragma once
 #include <string.h>
 
@@ -28,4 +28,67 @@ inline LfTapGeom lf_base_geom(int N, int Hl, int Wl, int Hs, int Ws, int Cs_pix,
     g.Hd = Hd; g.Wd = Wd; g.d_pix = Cd_pix; g.d_choff = 0; g.dsh = 1; g.dsw = 1; g.dah = 0; g.daw = 0;
     g.Cs = Cs; g.Cd = Cd; g.ntaps = 0;
     return g;
+}
+
+// One tap-GEMM launch of a stride-2 layer: its geometry and how its packed weights are gathered from the layer's (.., .., 3, 3)
+// weight tensor -- wp[t][k][n] = w[k * sk + n * sn + tapidx[t]].  Built here, once, for the plan (lf_erfnet.hip) and for the
+// kernel-level hook (lf_debug_stride2_epi, lf_ops.hip): the tests of the hook test the plan's geometry.
+struct LfStride2Op {
+    LfTapGeom geom;
+    int Kc, Nc;
+    long sk, sn;
+    int tapidx[LF_MAX_TAPS];
+};
+
+// sub-pixel phase tap sets shared by "3x3 s2 conv data-gradient" and "3x3 s2 transposed conv forward"
+inline int lf_phase_taps(int a, int* k, int* off) {
+    if (a == 0) { k[0] = 1; off[0] = 0; return 1; }
+    k[0] = 0; off[0] = 1; k[1] = 2; off[1] = 0;
+    return 2;
+}
+// the taps of phase (a, b) appended to g; ti: the 3x3 kernel element of each
+inline void lf_phase_geom_taps(LfTapGeom& g, int a, int b, int* ti) {
+    int kh[2], oh[2], kw[2], ow[2];
+    const int na = lf_phase_taps(a, kh, oh), nb = lf_phase_taps(b, kw, ow);
+    for (int i = 0; i < na; ++i)
+        for (int j = 0; j < nb; ++j) { g.tdh[g.ntaps] = oh[i]; g.tdw[g.ntaps] = ow[j]; ti[g.ntaps] = kh[i] * 3 + kw[j]; ++g.ntaps; }
+}
+// the 9 taps of a 3x3 stride-2 window appended to g (source stride 2)
+inline void lf_window9_taps(LfTapGeom& g, int* ti) {
+    g.ssh = 2; g.ssw = 2; g.ntaps = 9;
+    for (int kh = 0; kh < 3; ++kh)
+        for (int kw = 0; kw < 3; ++kw) { g.tdh[kh * 3 + kw] = kh - 1; g.tdw[kh * 3 + kw] = kw - 1; ti[kh * 3 + kw] = kh * 3 + kw; }
+}
+
+// DownsamplerBlock conv: Conv2d(Cin, Cc, 3, stride 2, pad 1), weight (Cc,Cin,3,3), writing channels [0,Cc) of the Ccat-wide concat
+// buffer; dg[a * 2 + b]: the data gradient's sub-pixel phase (a, b), reading the Ccat-wide gradient at Cs = Cc
+inline void lf_down_conv_ops(int N, int H, int W, int Cin, int Cc, int Ccat, LfStride2Op& fwd, LfStride2Op dg[4]) {
+    const int Ho = H / 2, Wo = W / 2;
+    fwd.geom = lf_base_geom(N, Ho, Wo, H, W, Cin, Ho, Wo, Ccat, Cin, Cc);
+    lf_window9_taps(fwd.geom, fwd.tapidx);
+    fwd.Kc = Cin; fwd.Nc = Cc; fwd.sk = 9; fwd.sn = (long)Cin * 9;
+    for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b) {
+            LfStride2Op& d = dg[a * 2 + b];
+            d.geom = lf_base_geom(N, Ho, Wo, Ho, Wo, Ccat, H, W, Cin, Cc, Cin);
+            d.geom.dsh = 2; d.geom.dsw = 2; d.geom.dah = a; d.geom.daw = b;
+            lf_phase_geom_taps(d.geom, a, b, d.tapidx);
+            d.Kc = Cc; d.Nc = Cin; d.sk = (long)Cin * 9; d.sn = 9;
+        }
+}
+
+// UpsamplerBlock conv: ConvTranspose2d(Cin, Co, 3, stride 2, pad 1, output_padding 1), weight (Cin,Co,3,3); fph[a * 2 + b]: the
+// forward's sub-pixel phase (a, b); dg: its data gradient (9 taps, stride 2)
+inline void lf_up_conv_ops(int N, int Hi, int Wi, int Cin, int Co, LfStride2Op fph[4], LfStride2Op& dg) {
+    for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b) {
+            LfStride2Op& f = fph[a * 2 + b];
+            f.geom = lf_base_geom(N, Hi, Wi, Hi, Wi, Cin, 2 * Hi, 2 * Wi, Co, Cin, Co);
+            f.geom.dsh = 2; f.geom.dsw = 2; f.geom.dah = a; f.geom.daw = b;
+            lf_phase_geom_taps(f.geom, a, b, f.tapidx);
+            f.Kc = Cin; f.Nc = Co; f.sk = (long)Co * 9; f.sn = 9;
+        }
+    dg.geom = lf_base_geom(N, Hi, Wi, 2 * Hi, 2 * Wi, Co, Hi, Wi, Cin, Co, Cin);
+    lf_window9_taps(dg.geom, dg.tapidx);
+    dg.Kc = Co; dg.Nc = Cin; dg.sk = 9; dg.sn = (long)Co * 9;
 }
