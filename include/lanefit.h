@@ -39,7 +39,8 @@ extern "C" {
                                  additions since 5 (inference engine): lf_erfnet_infer*, lf_erfnet_infer_range*, lf_convchain_infer*,
                                  lf_head_fit, lf_lane_infer*;
                                  additions since 5 (homography through the fit): lf_theta_grid, lf_theta_grid_bwd*, lf_wls_fwd_theta,
-                                 lf_wls_bwd_theta*, lf_wls_bwd_grid */
+                                 lf_wls_bwd_theta*, lf_wls_bwd_grid;
+                                 additions since 5 (scoring of decoded lanes): lf_lane_eval */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -424,6 +425,25 @@ int lf_poolflat_bf16_bwd(const uint16_t* y, const float* gout, int N, int H, int
 int lf_lane_decode(const double* beta, const double* y_eval, const double* y_prime, const double* minv_host,
                    double scale, const float* line_flag, const int* bound, double lo, double hi, double fill,
                    int N, int L, int S, int order, double* x_out, int* x_int, void* stream);
+
+/* additions since 5 -- scoring of decoded lanes (BP/eval_lane.py:15-57, LaneEval.bench, one wave per image):
+ *   pred (N,P,S) int32 x coordinates, pred_count (N) or NULL (= P lanes each; the first pred_count[n] lanes are scored);
+ *   gt (M,G,S) int32 + gt_count (M): the resident label table; image n is scored against row index[n] (int32), or row n with
+ *   index NULL (N <= M);  y_samples (S) fp64 shared by all rows (y_stride 0) or (M,S) per row (y_stride S);
+ *   run_time (N) fp32 or NULL (= 20, what test_model writes).  P, G <= 8, 1 <= S <= 256.
+ * Per gt lane: k = least-squares slope of x on y over its samples with x >= 0 (0 with fewer than two),
+ * thresh = pixel_thresh * sqrt(1 + k^2); negative coordinates on either side become -100; a sample hits when |pred - gt| < thresh;
+ * max_acc = max over pred lanes of hits / S (lowest index on a tie).  fn = gt lanes with max_acc < pt_thresh, fp = P_n - matched;
+ * with G_n > 4 one fn is forgiven and the smallest max_acc leaves the sum; run_time > 200 or G_n + 2 < P_n scores (0, 0, 1).
+ *   per_image (N,3) fp64 = accuracy, fp, fn -- the sum over gt lanes runs in ascending order in fp64;
+ *   best_acc (N,G) fp64 / best_pred (N,G) int32 or NULL: max_acc per gt lane (0 past G_n) and the pred lane reaching it (-1: none);
+ *   totals (3) fp64 or NULL: sums (not means) of per_image over the N images, by a second single-workgroup launch in a fixed order;
+ *   bad_index: device int32, incremented once per image whose index lies outside [0, M); such an image scores (0, 0, 1) and
+ *   reads nothing out of range (the host raises IndexError from the count, as with lf_pipeline_*_indexed). */
+int lf_lane_eval(const int32_t* pred, const int32_t* pred_count, const int32_t* gt, const int32_t* gt_count,
+                 const int32_t* index, const double* y_samples, long y_stride, const float* run_time,
+                 int N, int M, int P, int G, int S, double pixel_thresh, double pt_thresh,
+                 double* per_image, double* best_acc, int32_t* best_pred, double* totals, int32_t* bad_index, void* stream);
 
 /* "Next" row 8f-2: polynomial.trapezoidal (BEV/Loss_crit.py:26-35): area between two parabolas by the
  * trapezium rule on [a, b] with n intervals; p, q (B,3) rows [a2, a1, a0]; fp32 or fp64; out (B). */

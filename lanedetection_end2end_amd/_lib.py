@@ -116,6 +116,7 @@ def _declare(lib):
         "lf_wls_bwd_theta_workspace_bytes": (c_size_t, [I, I]),
         "lf_wls_bwd_theta": (I, [P, P, L, P, P, I, I, I, I, I, I, D, I, P, P, P, P, P, P, P]),
         "lf_wls_bwd_grid": (I, [P, P, L, I, I, I, I, I, I, D, I, P, P, P, P, P]),
+        "lf_lane_eval": (I, [P, P, P, P, P, P, L, P, I, I, I, I, I, D, D, P, P, P, P, P, P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {

@@ -13,8 +13,12 @@ the head outputs are fp32 in every mode.
 
 ``Projections`` mirrors BP/test.py:128-186 and ``decode_lanes`` fuses ``compute_coordinates`` for all lanes
 with the gating of ``test_model`` (BP/test.py:72-88) into one launch (``lf_lane_decode``).
+
+``LaneLabels`` holds a TuSimple label file as a resident device table and ``lane_eval`` / ``Projections.score_lanes`` score
+decoded lanes against it as ``LaneEval.bench`` does (BP/eval_lane.py:15-57), one wave per image (``lf_lane_eval``).
 """
 import ctypes
+import json
 import os
 
 import numpy as np
@@ -277,7 +281,7 @@ class Projections:
             self._dev = (self.y_eval.to(device).contiguous(), self.y_prime.double().to(device).contiguous())
         return self._dev
 
-    def _decode(self, beta, line_flag, bound, lo, hi, fill, want_int):
+    def _decode(self, beta, line_flag, bound, lo, hi, fill, want_int, out_int=None):
         lib = _lib.load()
         if not beta.is_cuda:
             raise _lib.LaneFitLibraryError("lanefit Projections needs its input on the MI355X; there is no CPU path")
@@ -286,8 +290,11 @@ class Projections:
         beta = beta.double().contiguous()
         y_eval, y_prime = self._device_consts(beta.device)
         S = self.num_heights
-        x = torch.empty(N, L, S, dtype=torch.float64, device=beta.device)
-        xi = torch.empty(N, L, S, dtype=torch.int32, device=beta.device) if want_int else None
+        # (out_int: the caller's (N, L, S) int32 rows, written in place; the fp64 copy is then not made)
+        x = torch.empty(N, L, S, dtype=torch.float64, device=beta.device) if out_int is None else None
+        xi = torch.empty(N, L, S, dtype=torch.int32, device=beta.device) if want_int and out_int is None else out_int
+        if out_int is not None:
+            assert out_int.is_cuda and out_int.dtype == torch.int32 and tuple(out_int.shape) == (N, L, S)
         if line_flag is not None:
             line_flag = line_flag.float().contiguous()
         if bound is not None:
@@ -302,17 +309,125 @@ class Projections:
         x, _ = self._decode(params.reshape(params.size(0), 1, -1), None, None, 1.0, 0.0, -2.0, False)
         return x[:, 0]
 
-    def decode_lanes(self, betas, line_pred=None, horizon_pred=None):
+    def decode_lanes(self, betas, line_pred=None, horizon_pred=None, out_int=None):
         """``betas``: the per-lane (N, order+1, 1) tensors in model order; ``line_pred`` (N, 4) the rounded
         line-type sigmoid in the dataset's order (re-indexed [1,2,0,3] as test_model does);
         ``horizon_pred`` (N,) int horizon row.  Returns (lanes (N,L,56) fp64, rounded int32 copy) with -2
-        wherever test_model writes -2 (BP/test.py:77-88)."""
+        wherever test_model writes -2 (BP/test.py:77-88).  ``out_int``: a contiguous (N, L, 56) int32 device tensor (a slice
+        of a buffer for the whole test set, say) to receive the rounded lanes in place; the return is then (None, out_int)."""
         beta = torch.stack([b.reshape(b.size(0), -1) for b in betas], 1)
         flag = None if line_pred is None else line_pred[:, [1, 2, 0, 3]][:, : beta.size(1)]
         bound = None
         if horizon_pred is not None:
             bound = torch.div(horizon_pred.to(torch.int64) - 160, 10, rounding_mode='trunc')
-        return self._decode(beta, flag, bound, 0.0, 1279.0, -2.0, True)
+        return self._decode(beta, flag, bound, 0.0, 1279.0, -2.0, True, out_int)
+
+    def score_lanes(self, lanes_int, labels, index=None, out=None, bad_index=None):
+        """``decode_lanes``' int32 lanes (N, L, 56), read in place -> per-image (N, 3) fp64 accuracy / fp / fn on the device,
+        image n against label ``index[n]`` (int32 device tensor; default: label n) of ``labels`` (a ``LaneLabels``), with
+        test_model's ``run_time`` of 20.  ``out`` / ``bad_index``: see ``lane_eval``; nothing is read back here."""
+        if lanes_int.size(2) != labels.S:
+            raise ValueError("score_lanes: lanes of %d samples against labels of %d" % (lanes_int.size(2), labels.S))
+        return lane_eval(lanes_int, labels, index=index, out=out, bad_index=bad_index)[0]
+
+
+MAX_LANES, MAX_SAMPLES = 8, 256      # lf_lane_eval's limits
+
+
+class LaneLabels:
+    """A TuSimple label file -- one JSON object per line with ``lanes``, ``h_samples`` and ``raw_file`` -- parsed once:
+    ``lanes`` (M, G, S) int32 padded with -2, ``counts`` (M) int32, ``h_samples`` (S) when every label has the same heights
+    (``shared``) or (M, S) fp64.  S is the first label's, G the file's maximum (at least 1).  ``on(device)`` uploads the table
+    once; ``labels`` keeps the parsed dicts (test_model writes its predictions file from them).  ``source``: a path, or the
+    parsed dicts."""
+
+    def __init__(self, source):
+        if isinstance(source, (str, os.PathLike)):
+            with open(source, 'r') as f:
+                source = [json.loads(line) for line in f if line.strip()]
+        self.labels = list(source)
+        if not self.labels:
+            raise ValueError("LaneLabels: no labels")
+        self.S = S = len(self.labels[0]['h_samples'])
+        if S < 1 or S > MAX_SAMPLES:
+            raise ValueError("LaneLabels: %d sample heights, the scoring kernel takes 1..%d" % (S, MAX_SAMPLES))
+        for i, l in enumerate(self.labels):
+            if len(l['h_samples']) != S:
+                raise ValueError("LaneLabels: label %d has %d sample heights, the first has %d" % (i, len(l['h_samples']), S))
+            if any(len(lane) != S for lane in l['lanes']):
+                raise Exception('Format of lanes error.')
+            if len(l['lanes']) > MAX_LANES:
+                raise ValueError("LaneLabels: label %d has %d lanes, the scoring kernel takes %d" % (i, len(l['lanes']), MAX_LANES))
+        self.M = M = len(self.labels)
+        self.G = G = max(1, max(len(l['lanes']) for l in self.labels))
+        self.lanes = np.full((M, G, S), -2, np.int32)
+        self.counts = np.zeros(M, np.int32)
+        h = np.zeros((M, S), np.float64)
+        for i, l in enumerate(self.labels):
+            self.counts[i] = len(l['lanes'])
+            if l['lanes']:
+                self.lanes[i, :len(l['lanes'])] = _int_coordinates(l['lanes'])
+            h[i] = l['h_samples']
+        self.shared = bool((h == h[0]).all())
+        self.h_samples = h[0].copy() if self.shared else h
+        self._dev = None
+
+    def on(self, device):
+        """-> (lanes, counts, h_samples, y_stride) on ``device``, uploaded on first use."""
+        device = torch.device(device)
+        if self._dev is None or self._dev[0].device != device:
+            self._dev = (torch.from_numpy(self.lanes).to(device), torch.from_numpy(self.counts).to(device),
+                         torch.from_numpy(self.h_samples).to(device), 0 if self.shared else self.S)
+        return self._dev
+
+    def rows_by_raw_file(self):
+        """``raw_file`` -> row, the last label winning a repeated name as in ``bench_one_submit``'s dict."""
+        return {l['raw_file']: i for i, l in enumerate(self.labels)}
+
+
+def _int_coordinates(lanes):
+    """Lane lists -> int32; the scoring kernel is integer-only (TuSimple's coordinates are, and test_model rounds its own)."""
+    a = np.asarray(lanes)
+    if a.dtype.kind not in 'iu':
+        if a.dtype.kind != 'f' or not (a == np.rint(a)).all():
+            raise ValueError("lane coordinates must be integers")
+    return a.astype(np.int32)
+
+
+def lane_eval(pred, labels, index=None, pred_count=None, run_time=None, pixel_thresh=20, pt_thresh=0.85, out=None, bad_index=None,
+              want_best=False, want_totals=False):
+    """``LaneEval.bench`` (BP/eval_lane.py:33-57) for N images in one launch (``lf_lane_eval``): ``pred`` (N, P, S) int32 on the
+    device, image n scored against label ``index[n]`` (int32 device tensor; default n) of ``labels`` (a ``LaneLabels``);
+    ``pred_count`` (N) int32 (default: P lanes each); ``run_time`` (N) fp32 (default 20).
+    -> (per_image (N, 3) fp64 = accuracy, fp, fn; best_acc (N, G) fp64; best_pred (N, G) int32; totals (3) fp64 sums; bad_index),
+    the middle three ``None`` unless asked for.  ``out``: an (N, 3) fp64 device tensor to write.  ``bad_index``: an int32 device word
+    that counts the images whose index lies outside the table -- they score (0, 0, 1); it is the caller's to read (one is made,
+    zeroed, when not given)."""
+    lib = _lib.load()
+    if not pred.is_cuda:
+        raise _lib.LaneFitLibraryError("lanefit lane_eval needs its input on the MI355X; there is no CPU path")
+    assert pred.dtype == torch.int32 and pred.dim() == 3 and pred.is_contiguous()
+    N, P, S = pred.shape
+    dev = pred.device
+    gt, gt_count, ys, y_stride = labels.on(dev)
+    M, G = gt.shape[:2]
+    if S != labels.S:
+        raise ValueError("lane_eval: lanes of %d samples against labels of %d" % (S, labels.S))
+    for name, t, dtype in (("index", index, torch.int32), ("pred_count", pred_count, torch.int32), ("run_time", run_time, torch.float32)):
+        assert t is None or (t.is_cuda and t.dtype == dtype and t.numel() == N and t.is_contiguous()), name
+    per_image = torch.empty(N, 3, dtype=torch.float64, device=dev) if out is None else out
+    assert per_image.dtype == torch.float64 and tuple(per_image.shape) == (N, 3)
+    if bad_index is None:
+        bad_index = torch.zeros(1, dtype=torch.int32, device=dev)
+    assert bad_index.is_cuda and bad_index.dtype == torch.int32
+    best_acc = torch.empty(N, G, dtype=torch.float64, device=dev) if want_best else None
+    best_pred = torch.empty(N, G, dtype=torch.int32, device=dev) if want_best else None
+    totals = torch.empty(3, dtype=torch.float64, device=dev) if want_totals else None
+    _lib.check(lib.lf_lane_eval(_lib.ptr(pred), _lib.ptr(pred_count), _lib.ptr(gt), _lib.ptr(gt_count), _lib.ptr(index), _lib.ptr(ys),
+                                y_stride, _lib.ptr(run_time), N, M, P, G, S, float(pixel_thresh), float(pt_thresh),
+                                _lib.ptr(per_image), _lib.ptr(best_acc), _lib.ptr(best_pred), _lib.ptr(totals), _lib.ptr(bad_index),
+                                _lib.stream()), "lf_lane_eval")
+    return per_image, best_acc, best_pred, totals, bad_index
 
 
 def horizon_row(outputs_horizon):

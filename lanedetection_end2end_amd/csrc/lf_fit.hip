@@ -1343,6 +1343,164 @@ extern "C" int lf_lane_decode(const double* beta, const double* y_eval, const do
     return 0;
 }
 
+// ---- TuSimple scoring of decoded lanes (BP/eval_lane.py:15-57, LaneEval.bench) ------------------------------
+// One wave per image, lane = sample index (S <= 256: up to four samples per lane, kept in registers).  Every count is a
+// ballot / popcount and every fp64 sum a butterfly in a fixed order, so a result does not depend on the launch; past the
+// ballots all values are wave-uniform and the statements below are bench's, in its order:
+//   angle      k = slope of x on y over the gt samples with x >= 0 (centred, two passes); 0 with fewer than two of them
+//   threshold  pixel_thresh * sqrt(1 + k^2)      (= pixel_thresh / cos(arctan k))
+//   hits       negative coordinates become -100 on both sides, then |pred - gt| < threshold
+//   max_acc    max over the pred lanes of hits / S (lowest pred index on a tie); 0 without pred lanes
+//   fn / fp    gt lanes below pt_thresh; pred lanes that matched nothing; with more than four gt lanes one miss is forgiven and the
+//              smallest max_acc leaves the sum.  The sum runs in ascending gt order in fp64, as Python's sum() does.
+constexpr int LE_MAXL = 8;       // pred / gt lanes per image
+constexpr int LE_MAXS = 256;     // samples per lane
+constexpr int LE_WAVES = 4;      // images per workgroup
+constexpr int LE_ITER = LE_MAXS / LF_WAVE;
+
+__device__ __forceinline__ int le_wave_count(bool pred) { return __popcll(__ballot(pred)); }
+
+__global__ __launch_bounds__(LE_WAVES * LF_WAVE) void lane_eval_kernel(
+    const int32_t* __restrict__ pred, const int32_t* __restrict__ pred_count, const int32_t* __restrict__ gt,
+    const int32_t* __restrict__ gt_count, const int32_t* __restrict__ index, const double* __restrict__ y_samples, long y_stride,
+    const float* __restrict__ run_time, int N, int M, int P, int G, int S, double pixel_thresh, double pt_thresh,
+    double* __restrict__ per_image, double* __restrict__ best_acc, int32_t* __restrict__ best_pred, int32_t* __restrict__ bad_index) {
+    const int lane = threadIdx.x & (LF_WAVE - 1);
+    const int n = blockIdx.x * LE_WAVES + (threadIdx.x >> 6);
+    if (n >= N) return;                                        // (whole waves leave: no barrier below)
+    double acc_out = 0., fp_out = 0., fn_out = 1.;             // what a bad index and bench's early exit score
+    double lane_best = 0.;                                     // this lane's entry of the (G) rows: lane g holds gt lane g
+    int lane_arg = -1;
+    long row = index ? (long)index[n] : (long)n;
+    const bool in_range = row >= 0 && row < M;
+    if (!in_range) {                                           // counted for the host (IndexError), never dereferenced
+        if (lane == 0) atomicAdd(bad_index, 1);
+        row = 0;
+    }
+    int Pn = pred_count ? pred_count[n] : P;
+    Pn = Pn < 0 ? 0 : (Pn > P ? P : Pn);
+    int Gn = gt_count[row];
+    Gn = Gn < 0 ? 0 : (Gn > G ? G : Gn);
+    const float rt = run_time ? run_time[n] : 20.f;
+    if (in_range && !(rt > 200.f || Gn + 2 < Pn)) {
+        const double* ys = y_samples + row * y_stride;
+        const int32_t* gt_n = gt + row * (long)G * S;
+        const int32_t* pr_n = pred + (long)n * P * S;
+        double y[LE_ITER];
+#pragma unroll
+        for (int i = 0; i < LE_ITER; ++i) {
+            const int s = i * LF_WAVE + lane;
+            y[i] = s < S ? ys[s] : 0.;
+        }
+        double sum = 0., lowest = 0.;
+        int fn = 0;
+        for (int g = 0; g < Gn; ++g) {
+            int xg[LE_ITER];
+            bool ok[LE_ITER];
+            int cnt = 0;
+            double sx = 0., sy = 0.;
+#pragma unroll
+            for (int i = 0; i < LE_ITER; ++i) {
+                const int s = i * LF_WAVE + lane;
+                xg[i] = s < S ? gt_n[(long)g * S + s] : -1;
+                ok[i] = s < S && xg[i] >= 0;
+                cnt += le_wave_count(ok[i]);
+                sx += ok[i] ? (double)xg[i] : 0.;
+                sy += ok[i] ? y[i] : 0.;
+            }
+            double k = 0.;
+            if (cnt > 1) {
+                const double mx = lf_wave_sum(sx) / cnt, my = lf_wave_sum(sy) / cnt;
+                double sxy = 0., syy = 0.;
+#pragma unroll
+                for (int i = 0; i < LE_ITER; ++i) {
+                    const double dy = ok[i] ? y[i] - my : 0.;
+                    sxy += ok[i] ? dy * ((double)xg[i] - mx) : 0.;
+                    syy += dy * dy;
+                }
+                sxy = lf_wave_sum(sxy);
+                syy = lf_wave_sum(syy);
+                k = syy > 0. ? sxy / syy : 0.;
+            }
+            const double thresh = pixel_thresh * sqrt(1. + k * k);
+            double max_acc = 0.;
+            int arg = -1;
+            for (int p = 0; p < Pn; ++p) {
+                int hits = 0;
+#pragma unroll
+                for (int i = 0; i < LE_ITER; ++i) {
+                    const int s = i * LF_WAVE + lane;
+                    const int xp = s < S ? pr_n[(long)p * S + s] : -1;
+                    const double d = fabs((double)(xp >= 0 ? xp : -100) - (double)(xg[i] >= 0 ? xg[i] : -100));
+                    hits += le_wave_count(s < S && d < thresh);
+                }
+                const double a = (double)hits / (double)S;
+                if (p == 0 || a > max_acc) { max_acc = a; arg = p; }
+            }
+            fn += max_acc < pt_thresh ? 1 : 0;
+            sum += max_acc;
+            lowest = (g == 0 || max_acc < lowest) ? max_acc : lowest;
+            if (lane == g) { lane_best = max_acc; lane_arg = arg; }
+        }
+        const int matched = Gn - fn;
+        const double fp = (double)(Pn - matched);
+        if (Gn > 4 && fn > 0) fn -= 1;
+        if (Gn > 4) sum -= lowest;
+        const double denom = (double)(Gn < 4 ? (Gn > 1 ? Gn : 1) : 4);
+        acc_out = sum / denom;
+        fp_out = Pn > 0 ? fp / (double)Pn : 0.;
+        fn_out = (double)fn / denom;
+    }
+    if (lane == 0) {
+        per_image[3 * (long)n + 0] = acc_out;
+        per_image[3 * (long)n + 1] = fp_out;
+        per_image[3 * (long)n + 2] = fn_out;
+    }
+    if (best_acc && lane < G) best_acc[(long)n * G + lane] = lane_best;
+    if (best_pred && lane < G) best_pred[(long)n * G + lane] = lane_arg;
+}
+
+// Sums of the (N, 3) per-image scores: one workgroup; thread t adds rows t, t + 256, ... in that order, then a fixed tree in LDS.
+__global__ __launch_bounds__(256) void lane_eval_totals_kernel(const double* __restrict__ per_image, int N, double* __restrict__ totals) {
+    __shared__ double part[3][256];
+    double a[3] = {0., 0., 0.};
+    for (int n = threadIdx.x; n < N; n += 256)
+        for (int c = 0; c < 3; ++c) a[c] += per_image[3 * (long)n + c];
+    for (int c = 0; c < 3; ++c) part[c][threadIdx.x] = a[c];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            for (int c = 0; c < 3; ++c) part[c][threadIdx.x] += part[c][threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) totals[threadIdx.x] = part[threadIdx.x][0];
+}
+
+// pred (N, P, S) int32, pred_count (N) or NULL (= P lanes each); gt (M, G, S) + gt_count (M): the resident label table, image n
+// scored against row index[n] (or n with index NULL, which needs N <= M); y_samples (S) with y_stride 0 or (M, S) with
+// y_stride S; run_time (N) fp32 or NULL (= 20).  per_image (N, 3) = accuracy, fp, fn; best_acc / best_pred (N, G) or NULL;
+// totals (3) or NULL: the sums over the N images, from a second launch.  An index outside [0, M) bumps *bad_index, scores
+// (0, 0, 1) and reads nothing out of range; counts outside [0, P] / [0, G] are clamped.
+extern "C" int lf_lane_eval(const int32_t* pred, const int32_t* pred_count, const int32_t* gt, const int32_t* gt_count,
+                            const int32_t* index, const double* y_samples, long y_stride, const float* run_time, int N, int M, int P,
+                            int G, int S, double pixel_thresh, double pt_thresh, double* per_image, double* best_acc,
+                            int32_t* best_pred, double* totals, int32_t* bad_index, void* stream) {
+    LF_REQUIRE(pred && gt && gt_count && y_samples && per_image && bad_index, "lf_lane_eval: null pointer");
+    LF_REQUIRE(N > 0 && M > 0, "lf_lane_eval: bad shape N=%d M=%d", N, M);
+    LF_REQUIRE(P >= 1 && P <= LE_MAXL, "lf_lane_eval: P=%d not in 1..%d", P, LE_MAXL);
+    LF_REQUIRE(G >= 1 && G <= LE_MAXL, "lf_lane_eval: G=%d not in 1..%d", G, LE_MAXL);
+    LF_REQUIRE(S >= 1 && S <= LE_MAXS, "lf_lane_eval: S=%d not in 1..%d", S, LE_MAXS);
+    LF_REQUIRE(y_stride == 0 || y_stride == S, "lf_lane_eval: y_stride %ld is neither 0 nor S=%d", y_stride, S);
+    LF_REQUIRE(index || N <= M, "lf_lane_eval: %d images against %d labels need an index", N, M);
+    hipLaunchKernelGGL(lane_eval_kernel, dim3(lf_cdiv(N, LE_WAVES)), dim3(LE_WAVES * LF_WAVE), 0, (hipStream_t)stream, pred,
+                       pred_count, gt, gt_count, index, y_samples, y_stride, run_time, N, M, P, G, S, pixel_thresh, pt_thresh,
+                       per_image, best_acc, best_pred, bad_index);
+    if (totals)
+        hipLaunchKernelGGL(lane_eval_totals_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)per_image, N, totals);
+    LF_CHECK_LAUNCH("lane_eval");
+    return 0;
+}
+
 // ---- exact-area metric (BEV/Loss_crit.py:12-35 polynomial.trapezoidal) ------------------------------------
 // One thread per curve pair; the sum runs in the reference's order and dtype so fp32 inputs round identically.
 template <typename T>
