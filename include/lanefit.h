@@ -40,7 +40,8 @@ extern "C" {
                                  lf_head_fit, lf_lane_infer*;
                                  additions since 5 (homography through the fit): lf_theta_grid, lf_theta_grid_bwd*, lf_wls_fwd_theta,
                                  lf_wls_bwd_theta*, lf_wls_bwd_grid;
-                                 additions since 5 (scoring of decoded lanes): lf_lane_eval */
+                                 additions since 5 (scoring of decoded lanes): lf_lane_eval;
+                                 additions since 5 (whole-step criterion): lf_step_loss, lf_step_loss_workspace_bytes, lf_step_loss_bwd */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -444,6 +445,43 @@ int lf_lane_eval(const int32_t* pred, const int32_t* pred_count, const int32_t* 
                  const int32_t* index, const double* y_samples, long y_stride, const float* run_time,
                  int N, int M, int P, int G, int S, double pixel_thresh, double pt_thresh,
                  double* per_image, double* best_acc, int32_t* best_pred, double* totals, int32_t* bad_index, void* stream);
+
+/* additions since 5 -- whole-step criterion: every criterion statement of one training / validation step as ONE launch
+ * (BP/main.py:296-326 and :459-501 with BP/Loss_crit.py:202-218; BEV/main.py:223-253 and :395-431 with BEV/Loss_crit.py:98-134;
+ * the two head criteria are BP/main.py:109-110 and BEV/main.py:88-89).  One 256-thread workgroup per task (K lanes, line, horizon);
+ * the last one to arrive (a device-scope ticket in the workspace, left at zero) adds the task values up in the loop's order.
+ * No workgroup waits for another and a result is bit-identical from call to call.
+ *   tree: LF_TREE_BP -- fit = (sum over lanes) / nclasses, line head = BCEWithLogits on (N,4) logits against fp32 {0,1} targets;
+ *         LF_TREE_BEV -- fit = plain sum, lanes 2 and 3 have their coefficients multiplied by the lane-present mask first
+ *         (BEV/main.py:226-234), line head = unweighted mean cross entropy of (N,3,4) logits against (N,4) int64 labels (a label outside
+ *         [0,3) carries weight 0 and is counted in out[6], the lf_ce2d_fwd convention).
+ *   kind: LF_LANE_BACKPROJECT (orders 0-3; target = x_gt, valid: (N,Kt,S) fp64 with target_stride = Kt*S elements per image; Y, y_prime,
+ *         minv_host exactly as for lf_backproj_loss; x_cal_valid (N,K,S) fp64 out), LF_LANE_AREA (orders 1-2, weight_funct; target = gt
+ *         coefficients (N,Kt,D) in beta's type, target_stride = Kt*D; an image whose gt has a zero coefficient is dropped, a lane with
+ *         every image dropped contributes 0), LF_LANE_MSE (orders 0-3; mean over the N*D elements).  valid, Y, y_prime, minv_host and
+ *         x_cal_valid may be NULL for the last two.
+ *   beta_lanes: HOST array of K (1..4) device pointers, lane k's coefficients of image n at beta_lanes[k] + n*beta_stride (the unbind
+ *         views of one (N,K,D) tensor are read in place); beta_dtype LF_F32 | LF_F64.
+ *   heads: line_logits / line_target / horizon_logits (N,R) fp32 / horizon_target (N,R) fp32 {0,1}: all four or all NULL.  Horizon loss =
+ *         mean BCEWithLogits, max(x,0) - x*y + log1p(exp(-|x|)); a prediction is x > 0 (BP line, horizon) or the first arg-max over
+ *         the class axis (BEV line); accuracies = hits / (R*N) and hits / (nclasses*N) (BP/main.py:491-497, BEV/main.py:421-427).
+ *   total = fit*weight_fit + (line + horizon)*weight_class with the heads, fit without.  All arithmetic is fp64.
+ *   out (10 fp64): total, fit, line, horizon, acc_line, acc_horizon, bad line labels, line hits, horizon hits, 0.
+ *   grad: the gradient of total, flat: (N,K,D) in beta's type, then the line logits' and the horizon logits' in fp32 (with the heads).
+ *   meters (8 fp64, may be NULL; never read for the results above): += total*N, N, fit*N, N, acc_line, 1, acc_horizon, 1.
+ *   workspace: lf_step_loss_workspace_bytes() bytes, zeroed ONCE when allocated; calls sharing it must be ordered on one stream.
+ * lf_step_loss_bwd: grad_out = grad * upstream[0] (device fp64 scalar) over the n_beta coefficient and n_head fp32 head elements. */
+enum { LF_TREE_BP = 0, LF_TREE_BEV = 1 };
+enum { LF_LANE_BACKPROJECT = 0, LF_LANE_AREA = 1, LF_LANE_MSE = 2 };
+size_t lf_step_loss_workspace_bytes(void);
+int lf_step_loss(int tree, int kind, int K, int N, int order, int weight_funct, int nclasses,
+                 const void* const* beta_lanes, long beta_stride, int beta_dtype,
+                 const void* target, const double* valid, long target_stride, int S,
+                 const double* Y, const double* y_prime, const double* minv_host,
+                 const float* line_logits, const void* line_target, const float* horizon_logits, const float* horizon_target, int R,
+                 double weight_fit, double weight_class,
+                 double* out, double* x_cal_valid, void* grad, double* meters, void* workspace, void* stream);
+int lf_step_loss_bwd(const void* grad, int beta_dtype, long n_beta, long n_head, const double* upstream, void* grad_out, void* stream);
 
 /* "Next" row 8f-2: polynomial.trapezoidal (BEV/Loss_crit.py:26-35): area between two parabolas by the
  * trapezium rule on [a, b] with n intervals; p, q (B,3) rows [a2, a1, a0]; fp32 or fp64; out (B). */

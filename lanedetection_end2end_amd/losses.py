@@ -1,5 +1,7 @@
 """Loss modules with the reference's names and call signatures (BEV/Loss_crit.py, BP/Loss_crit.py),
 computed by liblanefit_hip.so."""
+import collections
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -137,6 +139,131 @@ class backprojection_loss(nn.Module):
 
     def forward(self, params, x_gt, valid_samples):
         return ops.BackprojLossFn.apply(params, x_gt, valid_samples, self.Y, self.y_prime, self.M_inv)
+
+
+StepLoss = collections.namedtuple("StepLoss", "loss loss_fit loss_line loss_horizon acc_line acc_horizon x_cal")
+
+
+class StepMeters:
+    """Device-side ``AverageMeter`` sums of a ``StepCriterion`` (``crit.meters()``): every following call of the criterion adds
+    ``update(loss, N)``, ``update(loss_fit, N)``, ``update(acc_line)`` and ``update(acc_horizon)`` inside its launch.  ``read()`` is
+    the one host synchronisation: the averages as a dict, and the accumulators start over."""
+    names = ("loss", "loss_fit", "acc_line", "acc_horizon")
+
+    def __init__(self):
+        self.buf = None
+
+    def on(self, device):
+        if self.buf is None or self.buf.device != device:
+            self.buf = torch.zeros(8, dtype=torch.float64, device=device)
+        return self.buf
+
+    def read(self):
+        if self.buf is None:
+            return {n: 0.0 for n in self.names}
+        v = self.buf.tolist()
+        self.buf.zero_()
+        return {n: (v[2 * i] / v[2 * i + 1] if v[2 * i + 1] else 0.0) for i, n in enumerate(self.names)}
+
+
+class StepCriterion(nn.Module):
+    """The whole criterion of one training / validation step as one launch: the K lane losses of ``options.loss_policy``, their
+    combination (BP: sum / nclasses, BP/main.py:296-305; BEV: sum, with the lane-present mask on lanes 2 and 3, BEV/main.py:223-237),
+    the line and horizon head losses, ``loss * weight_fit + (loss_line + loss_horizon) * weight_class`` (BP/main.py:321-326,
+    BEV/main.py:247-253) and the two validation accuracies (BP/main.py:491-497, BEV/main.py:421-427) -- values and gradients from
+    ``lf_step_loss``, nothing read back to the host.
+
+        BP:   crit(betas, lanes, valid_points, outputs_line=None, outputs_horizon=None, gt_line=None, gt_horizon=None)
+        BEV:  crit(betas, params, outputs_line=None, outputs_horizon=None, gt_line=None, gt_horizon=None)
+
+    ``betas`` is the model's 4-tuple (``None`` entries end the lane list); ``lanes`` / ``valid_points`` (N, >=K, 56) with the
+    backprojection policy, coefficient targets (N, >=K, order + 1) otherwise.  Returns a ``StepLoss`` of device tensors (``x_cal``: a
+    tuple of per-lane (N, S) views, BP with the backprojection policy; else None); fp64 in the BP tree, the coefficients' dtype in
+    the BEV tree.  Without the heads the total is the fit loss.  ``meters()`` starts device-side running means.  A line label
+    outside [0, 3) (BEV) carries weight 0 and raises one call late or on ``flush()``, as ``CrossEntropyLoss2d`` does."""
+
+    def __init__(self, options, tree):
+        super().__init__()
+        if tree not in ops.TREES:
+            raise ValueError("tree must be 'bp' or 'bev', not %r" % (tree,))
+        policy = options.loss_policy
+        if policy not in ops.LANE_KINDS or (policy == "backproject" and tree != "bp"):
+            raise NotImplementedError('The requested loss criterion is not implemented')
+        self.tree, self.loss_policy, self.kind_is_backproject = tree, policy, policy == "backproject"
+        self.nclasses = int(options.nclasses)
+        self.weight_fit = float(getattr(options, "weight_fit", 1.0))
+        self.weight_class = float(getattr(options, "weight_class", 1.0))
+        self.weight_funct = getattr(options, "weight_funct", "none")
+        self.order = options.order
+        self.Y = self.y_prime = self.M_inv = None
+        if policy == "backproject":
+            bp = backprojection_loss(options)
+            self.Y, self.y_prime, self.M_inv = bp.Y, bp.y_prime, bp.M_inv
+        elif policy == "area":
+            Area_Loss(options.order, self.weight_funct)          # (its checks of order and weight function)
+        self.check_targets = True
+        self._pending = None
+        self._ws = None
+        self._meters = None
+
+    def workspace(self, device):
+        if self._ws is None or self._ws.device != device:        # zeroed once: every call leaves the ticket at zero
+            self._ws = torch.zeros(_lib.load().lf_step_loss_workspace_bytes(), dtype=torch.uint8, device=device)
+        return self._ws
+
+    def meter_buffer(self, device):
+        return None if self._meters is None else self._meters.on(device)
+
+    def meters(self):
+        self._meters = StepMeters()
+        return self._meters
+
+    def flush(self):
+        """Raise now if the previous call saw a line label outside [0, 3)."""
+        pend, self._pending = self._pending, None
+        if pend is not None:
+            bad = float(pend.get()[6])
+            if bad != 0.0:
+                raise RuntimeError("cross entropy: %d target value(s) outside [0, %d)" % (int(bad), 3))
+
+    def train(self, mode=True):
+        self.flush()
+        return super().train(mode)
+
+    def forward(self, betas, *args, **kw):
+        names = (("lanes", "valid_points") if self.tree == "bp" else ("params",)) + \
+            ("outputs_line", "outputs_horizon", "gt_line", "gt_horizon")
+        if len(args) > len(names):
+            raise TypeError("StepCriterion: too many arguments")
+        a = dict(zip(names, args))
+        for k, v in kw.items():
+            if k not in names or k in a:
+                raise TypeError("StepCriterion: unexpected argument %r" % k)
+            a[k] = v
+        target = a.get("lanes") if self.tree == "bp" else a.get("params")
+        if target is None:
+            raise TypeError("StepCriterion: the lane targets are missing")
+        lanes = []
+        for b in betas:
+            if b is None:
+                break
+            lanes.append(b)
+        heads = [a.get(n) for n in names[-4:]]
+        if any(h is None for h in heads):
+            if any(h is not None for h in heads):
+                raise TypeError("StepCriterion: the heads take outputs_line, outputs_horizon, gt_line and gt_horizon together")
+            heads = [None] * 4
+        line, horizon, gt_line, gt_horizon = heads
+        check = self.check_targets and self.tree == "bev" and line is not None
+        if self.check_targets:
+            self.flush()
+        loss, values, xcal = ops.StepLossFn.apply(self, target, a.get("valid_points"), line, gt_line, horizon, gt_horizon, *lanes)
+        if check:
+            self._pending = _lib.DeferredRead(values)
+        if self.tree == "bev" and lanes[0].dtype != torch.float64:      # the BEV loop's loss has the coefficients' dtype
+            loss, values = loss.to(lanes[0].dtype), values.to(lanes[0].dtype)
+        return StepLoss(loss, values[1], values[2], values[3], values[4], values[5],
+                        None if xcal is None else tuple(xcal.unbind(1)))
 
 
 def define_loss_crit_bev(options):

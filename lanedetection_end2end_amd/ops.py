@@ -297,6 +297,88 @@ class CrossEntropy2dFn(torch.autograd.Function):
         return g, None, None, None
 
 
+TREES = {"bp": 0, "bev": 1}
+LANE_KINDS = {"backproject": 0, "area": 1, "mse": 2}
+
+
+class StepLossFn(torch.autograd.Function):
+    """The whole criterion of one step in one launch (lf_step_loss): ``apply(cfg, target, valid, line, gt_line, horizon, gt_horizon,
+    *betas)`` -> ``(loss, values, x_cal)``.  ``cfg`` is the ``losses.StepCriterion`` (tree, lane kind, constants, weights, workspace,
+    meters); ``betas`` are the K lanes' (N, D, 1) | (N, D) coefficients -- the unbind views of one (N, K, D) tensor are read in place.
+    ``loss`` is the fp64 total; ``values`` the ten fp64 words of ``out`` (total, fit, line, horizon, acc_line, acc_horizon, bad line
+    labels, line hits, horizon hits, 0); ``x_cal`` (N, K, S) fp64 with the backprojection kind, else None.  Only ``loss`` carries a
+    gradient; backward is one launch that multiplies the flat gradient buffer of the forward by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, cfg, target, valid, line, gt_line, horizon, gt_horizon, *betas):
+        lib = _lib.load()
+        ps = [b.squeeze(-1) if b.dim() == 3 else b for b in betas]
+        K, (N, D), dt, dev = len(ps), ps[0].shape, ps[0].dtype, ps[0].device
+        assert 1 <= K <= 4 and dt in (torch.float32, torch.float64)
+        if any(p.shape != (N, D) or p.dtype != dt or p.stride(1) != 1 or p.stride(0) != ps[0].stride(0) for p in ps):
+            ps = list(torch.stack([p.to(dt) for p in ps], 1).unbind(1))
+        kind, bp = LANE_KINDS[cfg.loss_policy], cfg.kind_is_backproject
+        tdt = torch.float64 if bp else dt
+        target = target.to(tdt).contiguous()
+        assert target.dim() == 3 and target.shape[0] == N and target.shape[1] >= K, (target.shape, N, K)
+        S = target.shape[2]
+        if bp:
+            valid = valid.to(torch.float64).contiguous()
+            assert valid.shape == target.shape and cfg.Y.shape == (S, D), (valid.shape, target.shape, cfg.Y.shape)
+        else:
+            assert S == D, "coefficient targets %s for order %d" % (tuple(target.shape), D - 1)
+            valid = None
+        heads = line is not None
+        R = n_line = n_hor = 0
+        if heads:
+            line, horizon = line.contiguous(), horizon.contiguous()
+            gt_horizon = gt_horizon.to(torch.float32).contiguous()
+            gt_line = (gt_line.to(torch.int64) if cfg.tree == "bev" else gt_line.to(torch.float32)).contiguous()
+            R = horizon.shape[1]
+            assert line.dtype == torch.float32 and horizon.dtype == torch.float32
+            assert tuple(line.shape) == ((N, 3, 4) if cfg.tree == "bev" else (N, 4)) and tuple(gt_line.shape) == (N, 4), line.shape
+            assert tuple(horizon.shape) == (N, R) and gt_horizon.shape == horizon.shape
+            n_line, n_hor = line.numel(), horizon.numel()
+        out = torch.empty(10, dtype=torch.float64, device=dev)
+        xcal = torch.empty(N, K, S, dtype=torch.float64, device=dev) if bp else None
+        nb = N * K * D * ps[0].element_size()
+        grad = torch.empty(nb + 4 * (n_line + n_hor), dtype=torch.uint8, device=dev)
+        lanes = (ctypes.c_void_p * K)(*[p.data_ptr() for p in ps])
+        m = None if cfg.M_inv is None else (ctypes.c_double * 9)(*[float(v) for v in cfg.M_inv.reshape(-1)])
+        _lib.check(lib.lf_step_loss(
+            TREES[cfg.tree], kind, K, N, D - 1, WEIGHT_FUNCTS[cfg.weight_funct] if kind == 1 else 0, int(cfg.nclasses),
+            ctypes.cast(lanes, ctypes.c_void_p), ps[0].stride(0), 1 if dt == torch.float64 else 0,
+            _lib.ptr(target), _lib.ptr(valid), target.stride(0), S,
+            _lib.ptr(cfg.Y) if bp else None, _lib.ptr(cfg.y_prime) if bp else None, ctypes.cast(m, ctypes.c_void_p) if bp else None,
+            _lib.ptr(line), _lib.ptr(gt_line), _lib.ptr(horizon), _lib.ptr(gt_horizon), R,
+            float(cfg.weight_fit), float(cfg.weight_class), _lib.ptr(out), _lib.ptr(xcal), _lib.ptr(grad),
+            _lib.ptr(cfg.meter_buffer(dev)), _lib.ptr(cfg.workspace(dev)), _lib.stream()), "lf_step_loss")
+        ctx.save_for_backward(grad)
+        ctx.cfg = (N, K, D, dt, nb, n_line, n_hor, [b.shape for b in betas], None if line is None else line.shape)
+        loss = out[0]
+        ctx.mark_non_differentiable(*([out] if xcal is None else [out, xcal]))
+        ctx.set_materialize_grads(False)       # (no zero-filled gradients for the values nobody differentiates)
+        return loss, out, xcal
+
+    @staticmethod
+    def backward(ctx, gloss, _gv, _gx):
+        N, K, D, dt, nb, n_line, n_hor, bshapes, lshape = ctx.cfg
+        if gloss is None:
+            return (None,) * (7 + K)
+        lib = _lib.load()
+        (grad,) = ctx.saved_tensors
+        up = gloss.to(torch.float64).reshape(1).contiguous()
+        g = torch.empty_like(grad)
+        _lib.check(lib.lf_step_loss_bwd(_lib.ptr(grad), 1 if dt == torch.float64 else 0, N * K * D, n_line + n_hor, _lib.ptr(up),
+                                        _lib.ptr(g), _lib.stream()), "lf_step_loss_bwd")
+        gb = g[:nb].view(dt).view(N, K, D)
+        gl = gh = None
+        if n_line:
+            gl = g[nb:nb + 4 * n_line].view(torch.float32).view(lshape)
+            gh = g[nb + 4 * n_line:].view(torch.float32).view(N, -1)
+        return (None, None, None, gl, None, gh, None) + tuple(gb[:, k].view(bshapes[k]) for k in range(K))
+
+
 class LinearFn(torch.autograd.Function):
     """``act(x @ w.T + b)`` with ``act`` = identity or ReLU: the nn.Linear tails of the --clas heads on lf_linear_fwd / lf_linear_bwd
     (fp32, fixed summation order) instead of F.linear / rocBLAS."""
