@@ -41,7 +41,8 @@ extern "C" {
                                  additions since 5 (homography through the fit): lf_theta_grid, lf_theta_grid_bwd*, lf_wls_fwd_theta,
                                  lf_wls_bwd_theta*, lf_wls_bwd_grid;
                                  additions since 5 (scoring of decoded lanes): lf_lane_eval;
-                                 additions since 5 (whole-step criterion): lf_step_loss, lf_step_loss_workspace_bytes, lf_step_loss_bwd */
+                                 additions since 5 (whole-step criterion): lf_step_loss, lf_step_loss_workspace_bytes, lf_step_loss_bwd;
+                                 additions since 5 (BEV lane decoding): lf_lane_decode_bev */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -445,6 +446,29 @@ int lf_lane_eval(const int32_t* pred, const int32_t* pred_count, const int32_t* 
                  const int32_t* index, const double* y_samples, long y_stride, const float* run_time,
                  int N, int M, int P, int G, int S, double pixel_thresh, double pt_thresh,
                  double* per_image, double* best_acc, int32_t* best_pred, double* totals, int32_t* bad_index, void* stream);
+
+/* additions since 5 -- BEV lane decoding (BEV/Dataloader/Load_Data_new.py:334-420 write_lsq_results, the tail of validate(),
+ * BEV/main.py:445-488): predicted polynomials -> image-space lane points, one wave per image against the resident label table
+ * lf_lane_eval reads (gt, gt_count, index, h_samples + h_stride exactly as there; S <= 256, G <= 8).
+ *   beta (N,L,order+1) contiguous, highest power first, beta_dtype LF_F32 | LF_F64, order 0..2 (missing leading coefficients are 0,
+ *   the reference's [0]*(3-len(p)) + p), L <= 8;  line_id (N,4) int32 or NULL;  horizon (N,R) fp32 holding 0/1 or NULL, factor =
+ *   640/resize;  m_host / minv_host: 9 doubles each (row-major M and M_inv);  nclasses >= L output rows per image.
+ * Per image n (row = index ? index[n] : n), all in fp64:
+ *   extent of lane j < L: count, min h and max h over the samples of gt lane j with x != -2 (ballot + fixed butterflies, any order
+ *     of h; a gt lane j >= gt_count[row] counts as all -2 -- the reference raises IndexError there);
+ *   without all_branches_ready a lane without a valid gt sample is skipped; with it lane 2 is skipped when line_id[n][0] == 0 and
+ *     lane 3 when line_id[n][3] == 0, a lane without a valid gt sample uses (minimum, maximum) = (250, 710), and with horizon_on
+ *     as well minimum = (sum_r horizon[n][r]) * factor + 80;
+ *   y_d = (h - 80)/639, y' = (M11 y_d + M12)/(M21 y_d + M22);  ortho: y = 1 - y', x' = a y^2 + b y + c,
+ *     x = (Minv row 0 . [x', y', 1]) / (Minv row 2 . [x', y', 1]);  no_ortho: y = 1 - y_d, x = a y^2 + b y + c, no homography;
+ *   lanes[n][j][s] = round-half-even(1279 x) where max(210, minimum) <= h <= maximum, else -2; there is no range clamp (negative x
+ *     is written as it is); the int32 store saturates and NaN becomes INT32_MIN.  Skipped lanes and rows L <= j < nclasses are -2.
+ *   bad_index: device int32, incremented once per image whose row lies outside [0, M); its rows are all -2 and nothing out of
+ *     range is read.  No other atomics: two launches give identical bits. */
+int lf_lane_decode_bev(const void* beta, int beta_dtype, const int32_t* gt, const int32_t* gt_count, const int32_t* index,
+                       const double* h_samples, long h_stride, const int32_t* line_id, const float* horizon, int R, double factor,
+                       const double* m_host, const double* minv_host, int N, int M, int L, int G, int S, int order, int nclasses,
+                       int all_branches_ready, int horizon_on, int no_ortho, int32_t* lanes, int32_t* bad_index, void* stream);
 
 /* additions since 5 -- whole-step criterion: every criterion statement of one training / validation step as ONE launch
  * (BP/main.py:296-326 and :459-501 with BP/Loss_crit.py:202-218; BEV/main.py:223-253 and :395-431 with BEV/Loss_crit.py:98-134;

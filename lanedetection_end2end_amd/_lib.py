@@ -117,6 +117,7 @@ def _declare(lib):
         "lf_wls_bwd_theta": (I, [P, P, L, P, P, I, I, I, I, I, I, D, I, P, P, P, P, P, P, P]),
         "lf_wls_bwd_grid": (I, [P, P, L, I, I, I, I, I, I, D, I, P, P, P, P, P]),
         "lf_lane_eval": (I, [P, P, P, P, P, P, L, P, I, I, I, I, I, D, D, P, P, P, P, P, P]),
+        "lf_lane_decode_bev": (I, [P, I, P, P, P, P, L, P, P, I, D, P, P, I, I, I, I, I, I, I, I, I, I, P, P, P]),
         "lf_step_loss_workspace_bytes": (c_size_t, []),
         "lf_step_loss": (I, [I, I, I, I, I, I, I, P, L, I, P, P, L, I, P, P, P, P, P, P, P, I, D, D, P, P, P, P, P, P]),
         "lf_step_loss_bwd": (I, [P, I, L, L, P, P, P]),

@@ -14,6 +14,10 @@ the head outputs are fp32 in every mode.
 ``Projections`` mirrors BP/test.py:128-186 and ``decode_lanes`` fuses ``compute_coordinates`` for all lanes
 with the gating of ``test_model`` (BP/test.py:72-88) into one launch (``lf_lane_decode``).
 
+``ProjectionsBEV`` is the BEV tree's counterpart: ``decode_lanes`` is ``write_lsq_results`` (BEV/Dataloader/Load_Data_new.py:334-420,
+the tail of ``validate()``, BEV/main.py:445-488) for a batch -- normalised coordinates, every lane gated by the extent of its own
+ground-truth lane in the resident label table -- in one launch (``lf_lane_decode_bev``).
+
 ``LaneLabels`` holds a TuSimple label file as a resident device table and ``lane_eval`` / ``Projections.score_lanes`` score
 decoded lanes against it as ``LaneEval.bench`` does (BP/eval_lane.py:15-57), one wave per image (``lf_lane_eval``).
 """
@@ -326,6 +330,81 @@ class Projections:
         """``decode_lanes``' int32 lanes (N, L, 56), read in place -> per-image (N, 3) fp64 accuracy / fp / fn on the device,
         image n against label ``index[n]`` (int32 device tensor; default: label n) of ``labels`` (a ``LaneLabels``), with
         test_model's ``run_time`` of 20.  ``out`` / ``bad_index``: see ``lane_eval``; nothing is read back here."""
+        if lanes_int.size(2) != labels.S:
+            raise ValueError("score_lanes: lanes of %d samples against labels of %d" % (lanes_int.size(2), labels.S))
+        return lane_eval(lanes_int, labels, index=index, out=out, bad_index=bad_index)[0]
+
+
+class ProjectionsBEV:
+    """``ProjectionsBEV(options)``: the lane decoding of the BEV tree's ``write_lsq_results`` (BEV/Dataloader/Load_Data_new.py:334-420)
+    on the device.  M / M_inv are the normalised-coordinate homography of the fitting head (``geometry.bev_homography``: the same
+    four point pairs); ``options.resize`` gives ``factor = 640 / resize`` of the horizon bound, ``options.nclasses`` the number of
+    output rows per image."""
+
+    def __init__(self, options):
+        M, M_inv = geometry.bev_homography()
+        self.M, self.M_inv = torch.from_numpy(M), torch.from_numpy(M_inv)
+        self.resize = options.resize
+        self.factor = 640 / options.resize
+        self.nclasses = getattr(options, "nclasses", 4)
+        self._m = (ctypes.c_double * 9)(*[float(v) for v in M.reshape(-1)])
+        self._minv = (ctypes.c_double * 9)(*[float(v) for v in M_inv.reshape(-1)])
+
+    def decode_lanes(self, betas, labels, index=None, line_pred=None, horizon_pred=None, all_branches_ready=False, horizon_on=False,
+                     no_ortho=False, out_int=None, bad_index=None):
+        """``betas``: the per-lane (N, K, 1) tensors of the model's 9-tuple (K <= 3 coefficients, highest power first; fp32 as the BEV
+        model makes them, or fp64), image n decoded against label ``index[n]`` (int32 device tensor; default n) of ``labels`` (a
+        ``LaneLabels``).  ``line_pred`` (N, 4): the arg-max over the BEV line head (needed with ``all_branches_ready``);
+        ``horizon_pred`` (N, resize): the rounded horizon sigmoid (needed with ``horizon_on`` as well).
+        -> (lanes (N, nclasses, S) int32, bad_index): -2 wherever write_lsq_results writes -2, rows past the lanes given all -2.
+        ``out_int``: a contiguous (N, nclasses, S) int32 device tensor (a slice of a buffer for the whole validation set, say) written in
+        place.  ``bad_index``: as for ``lane_eval`` -- an image whose index lies outside the table gets -2 everywhere and is counted.
+        One launch, nothing read back."""
+        lib = _lib.load()
+        betas = [b for b in betas if b is not None]
+        if any(b.dim() < 2 or b.size(1) > 3 for b in betas):
+            raise ValueError("ProjectionsBEV.decode_lanes: a lane has more than 3 coefficients (a, b, c)")
+        if not betas[0].is_cuda:
+            raise _lib.LaneFitLibraryError("lanefit ProjectionsBEV needs its input on the MI355X; there is no CPU path")
+        beta = torch.stack([b.reshape(b.size(0), -1) for b in betas], 1)
+        if beta.dtype != torch.float32:
+            beta = beta.double()
+        beta = beta.contiguous()
+        N, L, K = beta.shape
+        dev = beta.device
+        gt, gt_count, hs, h_stride = labels.on(dev)
+        M, G = gt.shape[:2]
+        S = labels.S
+        if L > self.nclasses or L > MAX_LANES:
+            raise ValueError("ProjectionsBEV.decode_lanes: %d lanes into %d rows (at most %d lanes)" % (L, self.nclasses, MAX_LANES))
+        if all_branches_ready and line_pred is None:
+            raise ValueError("ProjectionsBEV.decode_lanes: all_branches_ready needs line_pred")
+        if all_branches_ready and horizon_on and horizon_pred is None:
+            raise ValueError("ProjectionsBEV.decode_lanes: horizon_on needs horizon_pred")
+        if line_pred is not None:
+            assert tuple(line_pred.shape) == (N, 4)
+            line_pred = line_pred.to(torch.int32).contiguous()
+        R = 0
+        if horizon_pred is not None:
+            assert horizon_pred.dim() == 2 and horizon_pred.size(0) == N
+            horizon_pred = horizon_pred.float().contiguous()
+            R = horizon_pred.size(1)
+        assert index is None or (index.is_cuda and index.dtype == torch.int32 and index.numel() == N and index.is_contiguous())
+        lanes = torch.empty(N, self.nclasses, S, dtype=torch.int32, device=dev) if out_int is None else out_int
+        assert lanes.is_cuda and lanes.dtype == torch.int32 and tuple(lanes.shape) == (N, self.nclasses, S) and lanes.is_contiguous()
+        if bad_index is None:
+            bad_index = torch.zeros(1, dtype=torch.int32, device=dev)
+        assert bad_index.is_cuda and bad_index.dtype == torch.int32
+        _lib.check(lib.lf_lane_decode_bev(_lib.ptr(beta), 0 if beta.dtype == torch.float32 else 1, _lib.ptr(gt), _lib.ptr(gt_count),
+                                          _lib.ptr(index), _lib.ptr(hs), h_stride, _lib.ptr(line_pred), _lib.ptr(horizon_pred), R,
+                                          self.factor, self._m, self._minv, N, M, L, G, S, K - 1, self.nclasses,
+                                          int(bool(all_branches_ready)), int(bool(horizon_on)), int(bool(no_ortho)), _lib.ptr(lanes),
+                                          _lib.ptr(bad_index), _lib.stream()), "lf_lane_decode_bev")
+        return lanes, bad_index
+
+    def score_lanes(self, lanes_int, labels, index=None, out=None, bad_index=None):
+        """``decode_lanes``' int32 lanes, read in place -> per-image (N, 3) fp64 accuracy / fp / fn on the device (``lane_eval`` with
+        write_lsq_results' ``run_time`` of 20); nothing is read back here."""
         if lanes_int.size(2) != labels.S:
             raise ValueError("score_lanes: lanes of %d samples against labels of %d" % (lanes_int.size(2), labels.S))
         return lane_eval(lanes_int, labels, index=index, out=out, bad_index=bad_index)[0]

@@ -1501,6 +1501,149 @@ extern "C" int lf_lane_eval(const int32_t* pred, const int32_t* pred_count, cons
     return 0;
 }
 
+// ---- BEV lane decoding (BEV/Dataloader/Load_Data_new.py:334-420 write_lsq_results, the tail of BEV/main.py:445-488) ------
+// One wave per image, LE_WAVES images per workgroup, lane = sample index, as lane_eval_kernel: both read the same label table.
+// Per predicted lane j the extent of gt lane j -- count, lowest and highest sample height among its x != -2 -- comes from a ballot
+// and two fixed butterflies (no order of the heights assumed); past them every gate value is wave-uniform.  The statements are
+// the reference's, in fp64:
+//   y_d = (h - 80) / 639,  y' = (M11 y_d + M12) / (M21 y_d + M22)
+//   ortho:     y = 1 - y',  x' = a y^2 + b y + c,  x = (Minv row 0 . [x', y', 1]) / (Minv row 2 . [x', y', 1])
+//   no_ortho:  y = 1 - y_d, x  = a y^2 + b y + c
+//   out = round-half-even(1279 x) where max(210, minimum) <= h <= maximum, -2 elsewhere
+__device__ __forceinline__ double lf_wave_min(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ double lf_wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+enum { LDB_ALL_BRANCHES = 1, LDB_HORIZON = 2, LDB_NO_ORTHO = 4 };
+
+template <typename T>
+__global__ __launch_bounds__(LE_WAVES * LF_WAVE) void lane_decode_bev_kernel(
+    const T* __restrict__ beta, const int32_t* __restrict__ gt, const int32_t* __restrict__ gt_count,
+    const int32_t* __restrict__ index, const double* __restrict__ h_samples, long h_stride, const int32_t* __restrict__ line_id,
+    const float* __restrict__ horizon, int R, double factor, double m11, double m12, double m21, double m22, double i00, double i01,
+    double i02, double i20, double i21, double i22, int N, int M, int L, int G, int S, int order, int nclasses, int flags,
+    int32_t* __restrict__ lanes, int32_t* __restrict__ bad_index) {
+    const int lane = threadIdx.x & (LF_WAVE - 1);
+    const int n = blockIdx.x * LE_WAVES + (threadIdx.x >> 6);
+    if (n >= N) return;                                        // (whole waves leave: no barrier below)
+    int32_t* out = lanes + (long)n * nclasses * S;
+    const long row = index ? (long)index[n] : (long)n;
+    if (row < 0 || row >= M) {                                 // counted for the host (IndexError), never dereferenced
+        if (lane == 0) atomicAdd(bad_index, 1);
+        for (int u = lane; u < nclasses * S; u += LF_WAVE) out[u] = -2;
+        return;
+    }
+    const bool all_branches = flags & LDB_ALL_BRANCHES, horizon_on = flags & LDB_HORIZON, no_ortho = flags & LDB_NO_ORTHO;
+    int Gn = gt_count[row];
+    Gn = Gn < 0 ? 0 : (Gn > G ? G : Gn);
+    const double* hs = h_samples + row * h_stride;
+    const int32_t* gt_n = gt + row * (long)G * S;
+    double h[LE_ITER], y[LE_ITER], yp[LE_ITER];
+#pragma unroll
+    for (int i = 0; i < LE_ITER; ++i) {
+        const int s = i * LF_WAVE + lane;
+        h[i] = s < S ? hs[s] : 0.;
+        const double y_d = (h[i] - 80.) / 639.;
+        yp[i] = (m11 * y_d + m12) / (m21 * y_d + m22);
+        y[i] = no_ortho ? 1. - y_d : 1. - yp[i];
+    }
+    double horizon_min = 0.;
+    if (all_branches && horizon_on) {                          // sum(horizon_est) * factor + 80: 0/1 values, exact in any order
+        double acc = 0.;
+        for (int r = lane; r < R; r += LF_WAVE) acc += (double)horizon[(long)n * R + r];
+        horizon_min = lf_wave_sum(acc) * factor + 80.;
+    }
+    for (int j = 0; j < nclasses; ++j) {
+        bool skip = j >= L;
+        double lo = 250., hi = 710.;                           // the extent of a gt lane without a valid sample
+        double a = 0., b = 0., c = 0.;
+        if (!skip) {
+            int cnt = 0;
+            double mn = INFINITY, mx = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < LE_ITER; ++i) {
+                const int s = i * LF_WAVE + lane;
+                const bool ok = s < S && j < Gn && gt_n[(long)j * S + s] != -2;
+                cnt += le_wave_count(ok);
+                mn = ok ? fmin(mn, h[i]) : mn;
+                mx = ok ? fmax(mx, h[i]) : mx;
+            }
+            if (cnt > 0) {
+                lo = lf_wave_min(mn);
+                hi = lf_wave_max(mx);
+            }
+            if (all_branches) {
+                skip = (j == 2 && line_id[4 * (long)n + 0] == 0) || (j == 3 && line_id[4 * (long)n + 3] == 0);
+                if (horizon_on) lo = horizon_min;
+            } else {
+                skip = cnt == 0;
+            }
+            const T* bj = beta + ((long)n * L + j) * (order + 1);       // highest power first; missing leading coefficients are 0
+            c = (double)bj[order];
+            if (order >= 1) b = (double)bj[order - 1];
+            if (order >= 2) a = (double)bj[0];
+        }
+        lo = lo > 210. ? lo : 210.;
+#pragma unroll
+        for (int i = 0; i < LE_ITER; ++i) {
+            const int s = i * LF_WAVE + lane;
+            if (s >= S) continue;
+            int32_t v = -2;
+            if (!skip && h[i] >= lo && h[i] <= hi) {
+                double x = a * (y[i] * y[i]) + b * y[i] + c;
+                if (!no_ortho) x = (i00 * x + i01 * yp[i] + i02) / (i20 * x + i21 * yp[i] + i22);
+                const double r = rint(x * 1279.);              // np.round: half to even
+                // int32 store: saturated, NaN -> INT32_MIN (the reference's int64 there is negative or huge; LaneEval maps every
+                // negative to -100 and no label lies within a threshold of either bound)
+                v = r != r ? INT32_MIN : (r <= -2147483648. ? INT32_MIN : (r >= 2147483647. ? INT32_MAX : (int32_t)r));
+            }
+            out[(long)j * S + s] = v;
+        }
+    }
+}
+
+// beta (N, L, order+1) contiguous, fp32 or fp64 by beta_dtype (LF_F32 | LF_F64), order 0..2.  gt / gt_count / index / h_samples +
+// h_stride: the label table exactly as lf_lane_eval takes it.  line_id (N, 4) int32 (needed with all_branches_ready), horizon (N, R)
+// fp32 0/1 values with factor = 640 / resize (needed with all_branches_ready and horizon_on).  lanes (N, nclasses, S) int32 out.
+extern "C" int lf_lane_decode_bev(const void* beta, int beta_dtype, const int32_t* gt, const int32_t* gt_count, const int32_t* index,
+                                  const double* h_samples, long h_stride, const int32_t* line_id, const float* horizon, int R,
+                                  double factor, const double* m_host, const double* minv_host, int N, int M, int L, int G, int S,
+                                  int order, int nclasses, int all_branches_ready, int horizon_on, int no_ortho, int32_t* lanes,
+                                  int32_t* bad_index, void* stream) {
+    LF_REQUIRE(beta && gt && gt_count && h_samples && m_host && minv_host && lanes && bad_index, "lf_lane_decode_bev: null pointer");
+    LF_REQUIRE(beta_dtype == LF_F32 || beta_dtype == LF_F64, "lf_lane_decode_bev: beta_dtype %d is neither LF_F32 nor LF_F64", beta_dtype);
+    LF_REQUIRE(N > 0 && M > 0, "lf_lane_decode_bev: bad shape N=%d M=%d", N, M);
+    LF_REQUIRE(order >= 0 && order <= 2, "lf_lane_decode_bev: order=%d not in 0..2", order);
+    LF_REQUIRE(L >= 1 && L <= LE_MAXL, "lf_lane_decode_bev: L=%d not in 1..%d", L, LE_MAXL);
+    LF_REQUIRE(G >= 1 && G <= LE_MAXL, "lf_lane_decode_bev: G=%d not in 1..%d", G, LE_MAXL);
+    LF_REQUIRE(S >= 1 && S <= LE_MAXS, "lf_lane_decode_bev: S=%d not in 1..%d", S, LE_MAXS);
+    LF_REQUIRE(nclasses >= L && nclasses <= 1024, "lf_lane_decode_bev: nclasses=%d not in L=%d..1024", nclasses, L);
+    LF_REQUIRE(h_stride == 0 || h_stride == S, "lf_lane_decode_bev: h_stride %ld is neither 0 nor S=%d", h_stride, S);
+    LF_REQUIRE(index || N <= M, "lf_lane_decode_bev: %d images against %d labels need an index", N, M);
+    LF_REQUIRE(!all_branches_ready || line_id, "lf_lane_decode_bev: all_branches_ready needs line_id");
+    LF_REQUIRE(!(all_branches_ready && horizon_on) || (horizon && R >= 0), "lf_lane_decode_bev: horizon_on needs horizon (N, R)");
+    const double *m = m_host, *w = minv_host;
+    const int flags = (all_branches_ready ? LDB_ALL_BRANCHES : 0) | (horizon_on ? LDB_HORIZON : 0) | (no_ortho ? LDB_NO_ORTHO : 0);
+    const dim3 grid(lf_cdiv(N, LE_WAVES)), block(LE_WAVES * LF_WAVE);
+    if (beta_dtype == LF_F32)
+        hipLaunchKernelGGL(lane_decode_bev_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)beta, gt, gt_count, index,
+                           h_samples, h_stride, line_id, horizon, R, factor, m[4], m[5], m[7], m[8], w[0], w[1], w[2], w[6], w[7], w[8],
+                           N, M, L, G, S, order, nclasses, flags, lanes, bad_index);
+    else
+        hipLaunchKernelGGL(lane_decode_bev_kernel<double>, grid, block, 0, (hipStream_t)stream, (const double*)beta, gt, gt_count, index,
+                           h_samples, h_stride, line_id, horizon, R, factor, m[4], m[5], m[7], m[8], w[0], w[1], w[2], w[6], w[7], w[8],
+                           N, M, L, G, S, order, nclasses, flags, lanes, bad_index);
+    LF_CHECK_LAUNCH("lane_decode_bev");
+    return 0;
+}
+
 // ---- exact-area metric (BEV/Loss_crit.py:12-35 polynomial.trapezoidal) ------------------------------------
 // One thread per curve pair; the sum runs in the reference's order and dtype so fp32 inputs round identically.
 template <typename T>
