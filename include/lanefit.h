@@ -42,7 +42,9 @@ extern "C" {
                                  lf_wls_bwd_theta*, lf_wls_bwd_grid;
                                  additions since 5 (scoring of decoded lanes): lf_lane_eval;
                                  additions since 5 (whole-step criterion): lf_step_loss, lf_step_loss_workspace_bytes, lf_step_loss_bwd;
-                                 additions since 5 (BEV lane decoding): lf_lane_decode_bev */
+                                 additions since 5 (BEV lane decoding): lf_lane_decode_bev;
+                                 additions since 5 (segmentation-mode step criterion): lf_seg_step, lf_seg_step_workspace_bytes,
+                                 lf_seg_step_bwd */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -506,6 +508,38 @@ int lf_step_loss(int tree, int kind, int K, int N, int order, int weight_funct, 
                  double weight_fit, double weight_class,
                  double* out, double* x_cal_valid, void* grad, double* meters, void* workspace, void* stream);
 int lf_step_loss_bwd(const void* grad, int beta_dtype, long n_beta, long n_head, const double* upstream, void* grad_out, void* stream);
+
+/* additions since 5 -- segmentation-mode step criterion: what a step of Net.forward(end_to_end=False) does behind the backbone
+ * (criterion_seg(output_net, gt) and its gradient, BEV/Loss_crit.py:61-75; the arg-max lane maps and their fit,
+ * BP/Networks/LSQ_layer.py:279-314, BEV/Networks/LSQ_layer.py:302-325) in one read of the logits, one read of the target and one
+ * write of the gradient.  Three launches: a label pass (per-class pixel counts of the target as integers: the normaliser sum w[t] is
+ * exact), the streaming pass (per-workgroup loss and moment partials into fixed workspace slots) and a finish (partials added in a
+ * fixed order, the solve).  No floating-point atomics, no workgroup waits for another; two calls on the same inputs give identical
+ * bits in out, grad_logits and beta.
+ *   logits (N,C,H,W) fp32, target (N,H,W) int64, weights (C) fp32: as lf_ce2d_fwd (C <= 8; a label outside [0, C) carries weight 0
+ *     in the loss and the gradient and is counted in out[3]).  The per-pixel arithmetic is lf_ce2d_fwd's / lf_ce2d_bwd's (fp32),
+ *     the sums are fp64.
+ *   grid_xy (H*W,2) fp32 with grid_batch_stride 0, or (N,H*W,2) with 2*H*W, y_offset, reg, solver: as lf_wls_fwd; NULL = no fit
+ *     (beta, status, maps, gt_line unused; L, order, zero_rows ignored).  On rows >= zero_rows a pixel whose first arg-max (NaN
+ *     counts as maximal, as lf_seg_maps) is class l + 1 <= L adds weight (l + 1)^2 to lane l's moments: the sums lf_wls_fwd forms
+ *     for the map lf_seg_maps writes.  Grid points of masked rows and of pixels of no lane are not read.  L <= 4, order 0..3.
+ *   gt_line (N,L) fp32 or NULL: a flagged lane is solved from the moments of lane (0, 0) ("prevent singular matrix").
+ *   grad_logits (N,C,H,W) fp32 or NULL: d loss / d logits for upstream 1.
+ *   maps (N,L,H,W) fp32 or NULL: exactly what lf_seg_maps writes (one more small launch when gt_line is given as well).
+ *   beta (N,L,order+1) fp64, status (N*L) int32: as lf_wls_fwd.
+ *   out (4 fp64): loss = out[1] / out[2], the weighted loss sum, the weight sum, the number of labels outside [0, C).
+ *   meters (2 fp64) or NULL: += loss * N, N.
+ *   workspace: lf_seg_step_workspace_bytes(N, C, L, H, W, order) bytes (L = 0 without the fit), zeroed ONCE when allocated (the
+ *     finish leaves the label counts at zero); calls sharing it must be ordered on one stream.
+ * lf_seg_step_bwd: grad_logits (n elements) *= upstream[0] (device fp32 scalar), in place; every workgroup returns at once when the
+ *   scalar is exactly 1.0, the case of the loops' loss.backward(). */
+size_t lf_seg_step_workspace_bytes(int N, int C, int L, int H, int W, int order);
+int lf_seg_step(const float* logits, const int64_t* target, const float* weights,
+                const float* grid_xy, long grid_batch_stride, const float* gt_line,
+                int N, int C, int L, int H, int W, int zero_rows, int order, double reg, double y_offset, int solver,
+                float* grad_logits, float* maps, double* beta, int32_t* status, double* out, double* meters,
+                void* workspace, void* stream);
+int lf_seg_step_bwd(float* grad_logits, long n, const float* upstream, void* stream);
 
 /* "Next" row 8f-2: polynomial.trapezoidal (BEV/Loss_crit.py:26-35): area between two parabolas by the
  * trapezium rule on [a, b] with n intervals; p, q (B,3) rows [a2, a1, a0]; fp32 or fp64; out (B). */

@@ -121,6 +121,9 @@ def _declare(lib):
         "lf_step_loss_workspace_bytes": (c_size_t, []),
         "lf_step_loss": (I, [I, I, I, I, I, I, I, P, L, I, P, P, L, I, P, P, P, P, P, P, P, I, D, D, P, P, P, P, P, P]),
         "lf_step_loss_bwd": (I, [P, I, L, L, P, P, P]),
+        "lf_seg_step_workspace_bytes": (c_size_t, [I, I, I, I, I, I]),
+        "lf_seg_step": (I, [P, P, P, P, L, P, I, I, I, I, I, I, I, D, D, I, P, P, P, P, P, P, P, P]),
+        "lf_seg_step_bwd": (I, [P, L, P, P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {

@@ -13,6 +13,7 @@
 // masked rows are never read.  Accumulation is fp64 (the reference's fp32 bmm over 131k
 // pixels is the source of its 5e-5..1e-4 noise floor); HBM-bound.
 #include "lf_common.h"
+#include "lf_solve.h"
 #include "lf_types.h"
 
 #include <stdarg.h>
@@ -220,98 +221,6 @@ __global__ __launch_bounds__(WLS_THREADS) void wls_moments_kernel(
         for (long u = z0 + threadIdx.x; u < z1; u += WLS_THREADS) store_px<VEC>(mo + u * VEC, zero);
     }
     block_store_sums(acc.v, partials + ((long)nk * WLS_CHUNKS + chunk) * M::N);
-}
-
-// In-register inverse of a DxD matrix (Gauss-Jordan, partial pivoting = what LAPACK getrf/getri
-// amount to for torch.inverse).  Returns 0 ok, 1 singular (zero / non-finite pivot).
-template <int D>
-__device__ int invert_lu(double (&A)[D][D], double (&Ai)[D][D]) {
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-        for (int j = 0; j < D; ++j) Ai[i][j] = (i == j) ? 1.0 : 0.0;
-    int bad = 0;
-#pragma unroll
-    for (int c = 0; c < D; ++c) {
-        int piv = c;
-        double best = fabs(A[c][c]);
-#pragma unroll
-        for (int r = c + 1; r < D; ++r) {
-            const double a = fabs(A[r][c]);
-            if (a > best) { best = a; piv = r; }
-        }
-#pragma unroll
-        for (int r = c + 1; r < D; ++r) {   // swap rows without dynamic register indexing
-            if (r == piv) {
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    double t = A[c][j]; A[c][j] = A[r][j]; A[r][j] = t;
-                    t = Ai[c][j]; Ai[c][j] = Ai[r][j]; Ai[r][j] = t;
-                }
-            }
-        }
-        const double p = A[c][c];
-        if (!(fabs(p) > 0.0) || !isfinite(p)) bad = 1;
-        const double ip = 1.0 / p;
-#pragma unroll
-        for (int j = 0; j < D; ++j) { A[c][j] *= ip; Ai[c][j] *= ip; }
-#pragma unroll
-        for (int r = 0; r < D; ++r) {
-            if (r == c) continue;
-            const double f = A[r][c];
-#pragma unroll
-            for (int j = 0; j < D; ++j) { A[r][j] = fma(-f, A[c][j], A[r][j]); Ai[r][j] = fma(-f, Ai[c][j], Ai[r][j]); }
-        }
-    }
-    return bad;
-}
-
-// Cholesky-based inverse (the GELS path).  Returns 0 ok, 2 when A is not positive definite.
-template <int D>
-__device__ int invert_chol(double (&A)[D][D], double (&Ai)[D][D]) {
-    double L[D][D];
-    int bad = 0;
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-        for (int j = 0; j < D; ++j) L[i][j] = 0.0;
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        double d = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
-        if (!(d > 0.0) || !isfinite(d)) bad = 2;
-        const double ljj = sqrt(d);
-        L[j][j] = ljj;
-#pragma unroll
-        for (int i = j + 1; i < D; ++i) {
-            double s = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
-            L[i][j] = s / ljj;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < D; ++c) {   // solve L L^T x = e_c
-        double y[D], x[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            double s = (i == c) ? 1.0 : 0.0;
-#pragma unroll
-            for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
-            y[i] = s / L[i][i];
-        }
-#pragma unroll
-        for (int i = D - 1; i >= 0; --i) {
-            double s = y[i];
-#pragma unroll
-            for (int k = i + 1; k < D; ++k) s -= L[k][i] * x[k];
-            x[i] = s / L[i][i];
-        }
-#pragma unroll
-        for (int i = 0; i < D; ++i) Ai[i][c] = x[i];
-    }
-    return bad;
 }
 
 // Pass 2: one thread per (image, lane): deterministic sum of the chunk partials, build the

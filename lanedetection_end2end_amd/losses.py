@@ -266,6 +266,163 @@ class StepCriterion(nn.Module):
                         None if xcal is None else tuple(xcal.unbind(1)))
 
 
+SegStepLoss = collections.namedtuple("SegStepLoss", "loss metric betas status maps")
+
+
+class SegStepMeters:
+    """Device-side running means of a ``SegStepCriterion`` (``crit.meters()``): ``update(loss, N)`` inside every following call's
+    finish launch, ``update(metric, N)`` inside its ``lf_step_loss`` launch.  ``read()`` is the one host synchronisation: the two
+    averages as a dict, and the accumulators start over."""
+    names = ("loss", "metric")
+
+    def __init__(self, step_meters):
+        self.buf = None
+        self.step = step_meters
+
+    def on(self, device):
+        if self.buf is None or self.buf.device != device:
+            self.buf = torch.zeros(2, dtype=torch.float64, device=device)
+        return self.buf
+
+    def read(self):
+        bufs = [b for b in (self.buf, self.step.buf) if b is not None]
+        if not bufs:
+            return {n: 0.0 for n in self.names}
+        v = torch.cat([b[:2] for b in bufs]).tolist()            # one copy, one synchronisation
+        for b in bufs:
+            b.zero_()
+        res, k = {}, 0
+        for n, b in zip(self.names, (self.buf, self.step.buf)):
+            res[n] = 0.0
+            if b is not None:
+                res[n] = v[k] / v[k + 1] if v[k + 1] else 0.0
+                k += 2
+        return res
+
+
+class SegStepCriterion(nn.Module):
+    """The criterion of an ``end_to_end=False`` step -- ``criterion_seg(output_net, gt)`` with its gradient, the arg-max lane maps,
+    their fit and the lane metric the loops compute under ``no_grad`` (BP/main.py:306-318, :470-482; BEV/main.py:241-244, :413-415)
+    -- in one pass over the logits (``lf_seg_step``) and one ``lf_step_loss`` launch, nothing read back to the host.  Use it with
+    ``model.defer_seg_fit = True`` (the forward then leaves the maps and the fit to this call).
+
+        BP :  crit(output_net, gt, lanes, valid_points, gt_line=None, fit=True) -> SegStepLoss
+        BEV:  crit(output_net, gt, params, fit=True)                            -> SegStepLoss
+
+    ``SegStepLoss`` is ``(loss, metric, betas, status, maps)``: ``loss`` the fp64 cross-entropy scalar (class weights
+    ``[1] + [weight_seg] * nclasses``, as ``CrossEntropyLoss2d``) and the only field with a gradient; ``betas`` the reference's
+    4-tuple with the tree's dtypes; ``metric`` the BP tree's ``(sum of lane losses) / nclasses`` or the BEV tree's sum of the two lane
+    losses, from one ``StepCriterion`` call on ``betas``; ``maps`` None unless ``return_maps``.  ``fit=False`` is the ``skip`` /
+    ``early_return=True`` case: cross entropy only, the other fields None.  The fit's geometry (grid or ``set_homography``'s theta
+    through ``ops.theta_grid``, ``zero_rows``, ``order``, ``reg_ls``, ``use_cholesky``, ``y_offset``) is read from ``model`` at call
+    time.  ``meters()`` starts device-side running means.  A label outside [0, C) carries weight 0 and raises one call late or on
+    ``flush()`` (``check_targets`` as on ``CrossEntropyLoss2d``); ``check_singular=True`` reads ``status`` and raises as ``forward``
+    does, ``False`` leaves it in ``last_status`` without a synchronisation."""
+
+    def __init__(self, options, model):
+        super().__init__()
+        from . import lsq
+        self._model = (model,)                     # (in a tuple: the criterion's train() / cuda() must not reach the model)
+        self.tree = "bp" if isinstance(model, lsq.BPNet) else "bev"
+        self.nclasses = int(options.nclasses)
+        nw = self.nclasses if self.tree == "bp" else 2           # define_loss_crit: the BEV tree's criterion_seg has three weights
+        self.register_buffer("weights", torch.tensor([1.0] + [float(options.weight_seg)] * nw, dtype=torch.float32),
+                             persistent=False)
+        self.step = StepCriterion(options, self.tree)
+        self.check_targets = True
+        self.check_singular = True
+        self.return_maps = False
+        self.last_status = None
+        self._pending = None
+        self._ws = None
+        self._meters = None
+        # the fit's constants, refreshed from the model by every call
+        self.lanes, self.order, self.zero_rows, self.reg, self.y_offset, self.solver = 2, options.order, 0, 0.0, 1.0, 0
+
+    def workspace(self, device, nbytes):
+        if self._ws is None or self._ws.device != device or self._ws.numel() != nbytes:      # zeroed once: lf_seg_step leaves the label counts at zero
+            self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        return self._ws
+
+    def meter_buffer(self, device):
+        return None if self._meters is None else self._meters.on(device)
+
+    def meters(self):
+        self._meters = SegStepMeters(self.step.meters())
+        return self._meters
+
+    def flush(self):
+        """Raise now if the previous call saw a label outside [0, C)."""
+        pend, self._pending = self._pending, None
+        if pend is not None:
+            bad = float(pend[0].get()[3])
+            if bad != 0.0:
+                raise RuntimeError("cross entropy: %d target value(s) outside [0, %d)" % (int(bad), pend[1]))
+
+    def train(self, mode=True):
+        self.flush()
+        return super().train(mode)
+
+    def forward(self, output_net, gt, *args, **kw):
+        names = (("lanes", "valid_points", "gt_line") if self.tree == "bp" else ("params",)) + ("fit",)
+        if len(args) > len(names):
+            raise TypeError("SegStepCriterion: too many arguments")
+        a = dict(zip(names, args))
+        for k, v in kw.items():
+            if k not in names or k in a:
+                raise TypeError("SegStepCriterion: unexpected argument %r" % k)
+            a[k] = v
+        fit = bool(a.get("fit", True))
+        model = self._model[0]
+        if gt.dim() == 4:
+            gt = gt[:, 0, :, :]
+        if self.check_targets:
+            self.flush()
+        grid = flags = None
+        if fit:
+            target = a.get("lanes") if self.tree == "bp" else a.get("params")
+            if target is None:
+                raise TypeError("SegStepCriterion: the lane targets are missing (or pass fit=False)")
+            N, _, H, W = output_net.shape
+            self.lanes = 2 if model.nclasses < 3 else 4
+            self.order, self.zero_rows, self.y_offset = model.order, model.zero_rows, model.y_offset
+            self.reg = 0.0 if (model.use_cholesky and model.cholesky_drops_reg) else model.reg_ls
+            self.solver = 1 if model.use_cholesky else 0
+            theta = model._homography()
+            grid = model.grid_on(output_net.device) if theta is None else \
+                ops.theta_grid(theta.detach().to(output_net.device), H, W, model.normalised)
+            gt_line = a.get("gt_line")
+            if gt_line is not None:
+                flags = gt_line.to(device=output_net.device, dtype=torch.float32).contiguous()
+                if tuple(flags.shape) != (N, self.lanes):
+                    # (as ops.seg_maps: the reference's expand_as fails here, but only when gt_line.sum() != 0 lets it get that far)
+                    if float(flags.sum()) != 0:
+                        raise RuntimeError("seg-mode fit: gt_line %s cannot be expanded to the (%d, %d) lane maps"
+                                           % (tuple(flags.shape), N, self.lanes))
+                    flags = None
+        want_grad = torch.is_grad_enabled() and output_net.requires_grad
+        loss, out, beta, status, maps = ops.SegStepFn.apply(self, output_net, gt.long(), grid, flags, want_grad)
+        if self.check_targets == "always":
+            bad = float(out[3])
+            if bad != 0.0:
+                raise RuntimeError("cross entropy: %d target value(s) outside [0, %d)" % (int(bad), output_net.shape[1]))
+        elif self.check_targets:
+            self._pending = (_lib.DeferredRead(out), output_net.shape[1])
+        if not fit:
+            return SegStepLoss(loss, None, None, None, None)
+        self.last_status = status
+        if self.check_singular:
+            ops._raise_if_singular(status, self.solver)
+        from . import fit as fit_mod
+        betas = fit_mod.split_lanes(beta, model.nclasses, model.beta_dtype)
+        with torch.no_grad():
+            if self.tree == "bp":
+                metric = self.step(betas, target, a.get("valid_points")).loss
+            else:
+                metric = self.step(betas[:2] + (None, None), target).loss
+        return SegStepLoss(loss, metric, betas, status, maps)
+
+
 def define_loss_crit_bev(options):
     """BEV/Loss_crit.py:45-58."""
     if options.loss_policy == 'mse':

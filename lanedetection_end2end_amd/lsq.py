@@ -64,6 +64,9 @@ class _LaneFitNet(nn.Module):
         self.check_singular = True      # False: skip the per-step D2H status read; inspect self.last_status
         self.return_masked = True
         self.last_status = None
+        # True: an end_to_end=False forward leaves the lane maps and their fit to losses.SegStepCriterion (coefficients and masked
+        # come back as None)
+        self.defer_seg_fit = False
         # constant (H*W,2) grid, computed once on the host with the reference's fp32 ops
         self._grid_cpu = geometry.projective_grid(resize, 2 * resize, M, self.normalised)
         self._grid = None
@@ -99,6 +102,8 @@ class _LaneFitNet(nn.Module):
         return dict(theta=theta if theta.device == device else theta.to(device), normalised=self.normalised)
 
     def _fit(self, output, end_to_end, gt_line=None):
+        if self.defer_seg_fit and not end_to_end:
+            return (None, None, None, None), None
         geo = self._geometry(output.device)
         reg = 0.0 if (self.use_cholesky and self.cholesky_drops_reg) else self.reg_ls
         if end_to_end:

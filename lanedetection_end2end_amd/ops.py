@@ -379,6 +379,67 @@ class StepLossFn(torch.autograd.Function):
         return (None, None, None, gl, None, gh, None) + tuple(gb[:, k].view(bshapes[k]) for k in range(K))
 
 
+class SegStepFn(torch.autograd.Function):
+    """The segmentation-mode step behind the backbone in three launches (lf_seg_step): ``apply(cfg, logits, target, grid, flags,
+    want_grad)`` -> ``(loss, out, beta, status, maps)``.  ``cfg`` is the ``losses.SegStepCriterion`` (class weights, the fit's
+    constants, workspace, meters); ``grid`` None = cross entropy only (``beta``, ``status``, ``maps`` None).  ``loss`` is the fp64
+    cross-entropy scalar and the only output with a gradient; ``out`` the four fp64 words (loss, weighted sum, weight sum, labels
+    outside [0, C)).  The logits' gradient is written by the forward -- only with ``want_grad`` (the caller's grad mode: inside
+    ``forward`` it is always off) -- and backward multiplies it by the upstream scalar in place (``lf_seg_step_bwd``: nothing is
+    touched when that is 1, the loops' ``loss.backward()``), so one forward serves one backward."""
+
+    @staticmethod
+    def forward(ctx, cfg, logits, target, grid, flags, want_grad):
+        lib = _lib.load()
+        logits = logits.contiguous()
+        target = target.contiguous()
+        assert logits.dtype == torch.float32 and logits.dim() == 4 and target.dtype == torch.int64
+        N, C, H, W = logits.shape
+        assert target.shape == (N, H, W), (target.shape, logits.shape)
+        dev = logits.device
+        weights = cfg.weights.to(device=dev, dtype=torch.float32).contiguous()
+        if weights.numel() != C:
+            raise RuntimeError("seg-mode criterion: %d class weights for %d logit planes" % (weights.numel(), C))
+        fit = grid is not None
+        L, order, gbs = (cfg.lanes, cfg.order, 0) if fit else (0, 0, 0)
+        beta = status = maps = None
+        if fit:
+            grid = grid.detach().contiguous()
+            assert grid.dtype == torch.float32 and grid.shape[-2:] == (H * W, 2), (grid.shape, H, W)
+            if grid.dim() == 3 and grid.shape[0] > 1:
+                assert grid.shape[0] >= N
+                gbs = H * W * 2
+            beta = torch.empty(N, L, order + 1, dtype=torch.float64, device=dev)
+            status = torch.empty(N * L, dtype=torch.int32, device=dev)
+            maps = torch.empty(N, L, H, W, dtype=torch.float32, device=dev) if cfg.return_maps else None
+        out = torch.empty(4, dtype=torch.float64, device=dev)
+        grad = torch.empty_like(logits) if want_grad else None
+        ws = cfg.workspace(dev, lib.lf_seg_step_workspace_bytes(N, C, L, H, W, order))
+        _lib.check(lib.lf_seg_step(_lib.ptr(logits), _lib.ptr(target), _lib.ptr(weights), _lib.ptr(grid), gbs, _lib.ptr(flags),
+                                   N, C, L, H, W, int(cfg.zero_rows), order, float(cfg.reg), float(cfg.y_offset), int(cfg.solver),
+                                   _lib.ptr(grad), _lib.ptr(maps), _lib.ptr(beta), _lib.ptr(status), _lib.ptr(out),
+                                   _lib.ptr(cfg.meter_buffer(dev)), _lib.ptr(ws), _lib.stream()), "lf_seg_step")
+        ctx.grad = grad
+        ctx.scaled = False
+        loss = out[0]
+        ctx.mark_non_differentiable(*[t for t in (out, beta, status, maps) if t is not None])
+        ctx.set_materialize_grads(False)
+        return loss, out, beta, status, maps
+
+    @staticmethod
+    def backward(ctx, gloss, _go, _gb, _gs, _gm):
+        grad = ctx.grad
+        if gloss is None or grad is None:
+            return (None,) * 6
+        if ctx.scaled:
+            raise RuntimeError("seg-mode criterion: its gradient buffer was scaled in place by an earlier backward; call the "
+                               "criterion again")
+        ctx.scaled = True
+        up = gloss.to(torch.float32).reshape(1).contiguous()
+        _lib.check(_lib.load().lf_seg_step_bwd(_lib.ptr(grad), grad.numel(), _lib.ptr(up), _lib.stream()), "lf_seg_step_bwd")
+        return None, grad, None, None, None, None
+
+
 class LinearFn(torch.autograd.Function):
     """``act(x @ w.T + b)`` with ``act`` = identity or ReLU: the nn.Linear tails of the --clas heads on lf_linear_fwd / lf_linear_bwd
     (fp32, fixed summation order) instead of F.linear / rocBLAS."""
