@@ -44,7 +44,8 @@ extern "C" {
                                  additions since 5 (whole-step criterion): lf_step_loss, lf_step_loss_workspace_bytes, lf_step_loss_bwd;
                                  additions since 5 (BEV lane decoding): lf_lane_decode_bev;
                                  additions since 5 (segmentation-mode step criterion): lf_seg_step, lf_seg_step_workspace_bytes,
-                                 lf_seg_step_bwd */
+                                 lf_seg_step_bwd;
+                                 additions since 5 (resident dataset's label batch): lf_label_batch_bp, lf_label_batch_bev */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -582,6 +583,38 @@ int lf_pipeline_image_indexed(const lf_pipeline_plan* plan, const uint8_t* pool,
 int lf_pipeline_label_indexed(const lf_pipeline_plan* plan, const uint8_t* pool, long pool_frames, const int64_t* sel, int N,
                               const void* tables_dev, const uint8_t* flip, int mode, const int64_t* lut, int64_t* out, float* horizon,
                               int* bad_index, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The LABEL half of LaneDataset.__getitem__ for a whole batch in one launch (csrc/lf_labels.hip), next to the pixel half above:
+ * the parsed label tables of a resident dataset of M rows stay on the device, batch element n is table row sel[n].
+ * Shared by both entry points:
+ *   lines     (M,10) int8   the "lines" list of label_new.json;
+ *   file_idx  (M)    int64  the reference's `idx`, file number - 1;
+ *   is_valid  (M)    uint8  1 = the row belongs to the validation split;
+ *   valid_pos (M)    int32  position in the dataset's valid_idx list, -1 for a training row;
+ *   sel       (N)    int64  pool rows of the batch;  flip (N) uint8 the drawn flip flags, or NULL = none;
+ *   idx (N) int64 = file_idx[sel];  index (N) int64 = valid_pos[sel];
+ *   flipped   (N)    uint8  the EFFECTIVE flip, flip[n] && !is_valid[sel[n]] (`if idx not in self.valid_idx and hflip_input`) --
+ *                           hand it to lf_pipeline_*_indexed as their flip so that pixels and labels agree;
+ *   bad (device int32, may be NULL): incremented once per element whose sel[n] lies outside [0, M); row 0 is read in its place.
+ * lf_label_batch_bp (BP/Dataloader/Load_Data_new.py:133-197):
+ *   lanes (M,4,56) int32 raw TuSimple x, left-padded with -2 to 56 columns;  h_samples (M,56) fp64 the label's heights (the first
+ *   h_count[m] entries are read);  h_count (M) int32 <= 56;  resize = R.
+ *   valid_points (N,4,56) fp64 = lanes > 0 with columns 0..7 zero (never flipped);  lanes_out (N,4,56) fp64 = x / 2.5, -2 where that
+ *   is negative, under the flip (2R - 1) - x with rows [1,0,3,2];  horizon (N,R) fp32 = ones on [0 : int(floor(y_val))] in Python's
+ *   slice meaning, y_val the smallest h / 2.5 - 32 of a present point, pairing padded lane column i with height i (R if none);
+ *   gt_line (N,4) fp32 = clamp(mirror?(lines)[3:7] + 1, 0, 1).
+ * lf_label_batch_bev (BEV/Dataloader/Load_Data_new.py:74,86-111):
+ *   params (M,4,3) fp64 -> params_out (N,4,3) fp32; flipped: rows [1,0,3,2], negated, last coefficient 1 + (-c), in fp64, then cast;
+ *   gt_line (N,4) int64 = mirror?(lines)[3:7] + 1.
+ * ---------------------------------------------------------------------------------- */
+int lf_label_batch_bp(const int32_t* lanes, const double* h_samples, const int32_t* h_count, const int8_t* lines,
+                      const int64_t* file_idx, const uint8_t* is_valid, const int32_t* valid_pos, long M, const int64_t* sel,
+                      const uint8_t* flip, int N, int resize, double* valid_points, double* lanes_out, float* horizon,
+                      float* gt_line, int64_t* idx, int64_t* index, uint8_t* flipped, int* bad, void* stream);
+int lf_label_batch_bev(const double* params, const int8_t* lines, const int64_t* file_idx, const uint8_t* is_valid,
+                       const int32_t* valid_pos, long M, const int64_t* sel, const uint8_t* flip, int N, float* params_out,
+                       int64_t* gt_line, int64_t* idx, int64_t* index, uint8_t* flipped, int* bad, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Kernel-level entry points: one factorised convolution of non_bottleneck_1d

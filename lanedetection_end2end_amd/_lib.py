@@ -124,6 +124,8 @@ def _declare(lib):
         "lf_seg_step_workspace_bytes": (c_size_t, [I, I, I, I, I, I]),
         "lf_seg_step": (I, [P, P, P, P, L, P, I, I, I, I, I, I, I, D, D, I, P, P, P, P, P, P, P, P]),
         "lf_seg_step_bwd": (I, [P, L, P, P]),
+        "lf_label_batch_bp": (I, [P, P, P, P, P, P, P, L, P, P, I, I, P, P, P, P, P, P, P, P, P]),
+        "lf_label_batch_bev": (I, [P, P, P, P, P, L, P, P, I, P, P, P, P, P, P, P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {

@@ -2,9 +2,11 @@
 ``(image, gt[, horizon])`` tensors ``LaneDataset.__getitem__`` produces (BEV/Dataloader/Load_Data_new.py:62-117,
 BP/Dataloader/Load_Data_new.py:110-197), batched, bit-identical to the PIL/torchvision result.
 
-Only the pixel work lives here (crop, BILINEAR / NEAREST resize, class remap, flip, ToTensor).  The per-sample
-label metadata (polynomial parameters, lane x-coordinates, line-type lists) stays host-side numpy as in the
-reference; ``flip_params_bev`` / ``flip_lanes_bp`` / ``mirror_list`` below mirror its flip statements.
+Only the pixel work lives here (crop, BILINEAR / NEAREST resize, class remap, flip, ToTensor).  The label half (polynomial
+parameters, lane x-coordinates, valid points, the BP horizon, line-type lists) of a RESIDENT dataset is one launch in
+``loader.ResidentDataset`` (``lf_label_batch_bp`` / ``lf_label_batch_bev``), which hands its effective flips to this pipeline; for a
+loader of one's own that keeps it host-side numpy as the reference does, ``flip_params_bev`` / ``flip_lanes_bp`` / ``mirror_list``
+below mirror the flip statements.
 """
 import ctypes
 
