@@ -36,6 +36,19 @@ def _work_list(numels, chunk, device, cache):
     return hit
 
 
+def _require_aligned(who, rec, plist, group_params):
+    """The kernels take 16-byte vector loads and stores on the parameter and on its state buffers (only the gradient, a view
+    at an arbitrary element offset of the flat buffer, has a scalar form): refuse anything else before it is launched on."""
+    if not ((rec[:, 0] | rec[:, 2] | rec[:, 3]) & 15).any():
+        return
+    for row, p in zip(rec, plist):
+        for name, addr in zip(("parameter", "first state buffer", "second state buffer"), (row[0], row[2], row[3])):
+            if int(addr) % 16:
+                index = next(j for j, q in enumerate(group_params) if q is p)
+                raise _lib.LaneFitLibraryError("%s: the %s of tensor %d (%d elements) is not 16-byte aligned"
+                                               % (who, name, index, p.numel()))
+
+
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -69,6 +82,7 @@ class FusedAdam(torch.optim.Optimizer):
             st = self.state[p]
             n = int(st["step"])
             rec[i] = (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), n, n)
+        _require_aligned("FusedAdam", rec, plist, self.param_groups[gi]["params"])
         dev = plist[0].device
         t_work, _, nwork = _work_list([p.numel() for p in plist], chunk, dev, self._works)
         t_rec, pin = _upload(rec, dev)
@@ -138,6 +152,7 @@ class _FusedMomentum(torch.optim.Optimizer):
             m = st["momentum_buffer"]
             v = st["square_avg"] if "square_avg" in st else m
             rec[i] = (p.data_ptr(), p.grad.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), 0, 0)
+        _require_aligned(type(self).__name__, rec, plist, self.param_groups[gi]["params"])
         dev = plist[0].device
         t_work, _, nwork = _work_list([p.numel() for p in plist], chunk, dev, self._works)
         t_rec, pin = _upload(rec, dev)
@@ -165,9 +180,10 @@ class _FusedMomentum(torch.optim.Optimizer):
                 for name in self._state_names:
                     if st.get(name) is None:
                         st[name] = torch.zeros_like(p)
-                st["step"] = st.get("step", 0) + 1
             _, t_rec, t_work, nblocks = self._table(gi, plist)[:4]
             self._launch(group, t_rec, t_work, nblocks)
+            for p in plist:
+                self.state[p]["step"] = self.state[p].get("step", 0) + 1
         return loss
 
 
