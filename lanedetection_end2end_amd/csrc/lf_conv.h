@@ -65,6 +65,7 @@ void lf_tapgemm_set_split_any_size(int v);
 void lf_tapgemm_set_bf16_lds(int v);
 void lf_tapgemm_set_bf16_no_partial_fast(int v);   // 1: launches with Cs % 32 != 0 decline the compiled-in whole-step forms (tests)
 long lf_tapgemm_partial_fast_launches();            // launches with Cs % 32 != 0 that took a compiled-in whole-step form since the process started (tests)
+void lf_tapgemm_set_fp32_stream(int mode, int max_workgroups);   // tapstream_kernel routing (lf_debug_set_fp32_stream, lf_debug.h)
 int lf_tapgemm_stat_rows(const LfTapGeom& g);                          // upper bound over the kernels (buffer sizing)
 int lf_tapgemm_stat_rows_for(const LfTapGeom& g, const LfTapArgs& a);  // rows the launch with these arguments writes
 int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, hipStream_t st);

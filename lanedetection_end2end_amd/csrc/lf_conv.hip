@@ -148,7 +148,12 @@ __device__ __forceinline__ float sum16(float v) {
 #define LF_EPI_ROW1 false      /* tapgemm_kernel: its ROW1 (a wave's 64 pixels in one image row) */
 #define LF_EPI_PIVOT true      /* BN forward sums about a pivot (below); the run-time-flag forms of the 128-register split kernel and of the LDS-ring \
                                   kernels (cold paths: no network launch) have no registers for it and sum about 0 -- same row format */
-#define LF_TAPGEMM_EPILOGUE \
+#define LF_EPI_ACC(n, m) acc[n][m]   /* the finished sum of channel tile n, pixel tile m (tapstream_kernel: its one live pixel tile) */
+#define LF_EPI_FIRST(m) ((m) == 0)   /* the pixel tile whose first pixel is the pivot of the BN forward sums */
+#define LF_EPI_ROW_OK(tg) true       /* 4-wave group tg owns a tile of the launch (tapstream_kernel: the last pair of tiles may be half empty) */
+/* The epilogue in three parts, so that a kernel can run the per-pixel-tile part one tile at a time (tapstream_kernel); LF_TAPGEMM_EPILOGUE
+ * below is the three in a row, the form every other kernel expands. */
+#define LF_EPI_HEAD \
     /* Pixel-tile outer, channel-tile inner: the loads of one operand tensor issued back to back cover one pixel's     \
      * contiguous channel run, so every cache line is touched once while it is hot (the channel-tile-outer order        \
      * revisited each line NT times with the whole grid's working set in between: 4x the HBM reads with bf16 tensors). \
@@ -161,7 +166,6 @@ __device__ __forceinline__ float sum16(float v) {
     /* MASKBN + STATS_XHAT: the mask's two per-channel vectors are re-read (L1) instead of held -- 32 registers, the difference \
      * between two and three waves per SIMD for that variant */ \
     constexpr bool HOISTM = HOISTV && !(EPIC >= 0 && (EPIC & LF_EPI_MASKBN) && (EPIC & LF_EPI_STATS_XHAT)); \
-    __builtin_amdgcn_s_setprio(3);   /* ahead of the partner wave's MFMA stream: the sooner this wave retires, the sooner its slot refills */ \
     const __amdgpu_buffer_rsrc_t r_dst = make_rsrc(a.dst, 0xffffffffu), r_add = make_rsrc(a.add_src, 0xffffffffu), \
                                  r_msk = make_rsrc(a.mask_src, 0xffffffffu), r_aux = make_rsrc(a.aux, 0xffffffffu), \
                                  r_bias = make_rsrc(a.bias, 0xffffffffu), r_msc = make_rsrc(a.msc, 0xffffffffu), \
@@ -182,9 +186,10 @@ _Pragma("unroll") \
         if (HOISTV) { \
             if (HOISTM && (epi & LF_EPI_MASKBN)) { hv[n][0] = ldb4(r_msc, co * 4u, 0u); hv[n][1] = ldb4(r_msh, co * 4u, 0u); } \
         } \
-    } \
-_Pragma("unroll") \
-    for (int m = 0; m < MT; ++m) { \
+    }
+/* one 16-pixel tile m: operand loads, bias / residual / masks / ReLU, the stores and the per-lane statistics */
+#define LF_EPI_TILE(m) \
+    { \
         const unsigned dbase = (unsigned)(((pn[m] * g.Hd + pi[m] * g.dsh + g.dah) * g.Wd + pj[m] * g.dsw + g.daw) * g.d_pix + g.d_choff + cob + kq * 4); \
 _Pragma("unroll") \
         for (int n0 = 0; n0 < NT; n0 += NC) { \
@@ -200,7 +205,7 @@ _Pragma("unroll") \
 _Pragma("unroll") \
         for (int j = 0; j < NC; ++j) { \
             const int n = n0 + j; \
-            f32x4 v = acc[n][m]; \
+            f32x4 v = LF_EPI_ACC(n, m); \
             if constexpr (!NOBIAS) v += bs[n]; \
             if (epi & LF_EPI_ADD) v += la[j]; \
             if (epi & LF_EPI_MASK) v = keep_pos(v, lm[j]); \
@@ -211,7 +216,7 @@ _Pragma("unroll") \
             if (pv[m]) epi_st<S16>(r_dst, dbase + n * 16, v); \
             if (!pv[m]) v = zero4(); \
             if (epi & LF_EPI_STATS_SQ) { \
-                if (LF_EPI_PIVOT && m == 0) piv[LF_EPI_PIVOT ? n : 0] = bcast16(v); \
+                if (LF_EPI_PIVOT && LF_EPI_FIRST(m)) piv[LF_EPI_PIVOT ? n : 0] = bcast16(v); \
                 f32x4 dv = LF_EPI_PIVOT ? v - piv[LF_EPI_PIVOT ? n : 0] : v; \
                 if (!pv[m]) dv = zero4(); \
                 s1[n] += dv; s2[n] += dv * dv; \
@@ -222,7 +227,9 @@ _Pragma("unroll") \
             } \
         } \
         } \
-    } \
+    }
+/* once per 256-pixel tile: the wave's sums -> one partial row (DPP row sums, LDS staging, Chan merge of the four waves) */
+#define LF_EPI_TAIL \
     if (LF_EPI_ROW1 && (epi & LF_EPI_STATS_XHAT) && a.dm) { \
         /* a wave's pixels lie in ONE image: the Dropout2d factor of (image, channel) scales the wave's sums once */ \
 _Pragma("unroll") \
@@ -254,7 +261,7 @@ _Pragma("unroll") \
             } \
         } \
         __syncthreads(); \
-        if ((LF_EPI_TID & 255) < NT * 4 * 8) { \
+        if ((LF_EPI_TID & 255) < NT * 4 * 8 && LF_EPI_ROW_OK(LF_EPI_TID >> 8)) { \
             const int tg = LF_EPI_TID >> 8, tt = LF_EPI_TID & 255; \
             const int j = tt & 7, q = (tt >> 3) & 3, n = tt >> 5; \
             float v = sred[tg][0][n][q][j] + sred[tg][1][n][q][j] + sred[tg][2][n][q][j] + sred[tg][3][n][q][j]; \
@@ -276,7 +283,13 @@ _Pragma("unroll") \
             const int co = cob + n * 16 + q * 4 + (j & 3); \
             a.stats[((long)(j >> 2) * g.Cd + co) * a.stats_ld + ((long)bx * LF_EPI_GROUPS + tg)] = v;      /* channel-major rows */ \
         } \
-    } \
+    }
+#define LF_TAPGEMM_EPILOGUE \
+    __builtin_amdgcn_s_setprio(3);   /* ahead of the partner wave's MFMA stream: the sooner this wave retires, the sooner its slot refills */ \
+    LF_EPI_HEAD \
+_Pragma("unroll") \
+    for (int m = 0; m < MT; ++m) LF_EPI_TILE(m) \
+    LF_EPI_TAIL
 
 extern __shared__ __attribute__((aligned(16))) unsigned char lf_tap_lds[];      // tap tables of tapgemm_kernel
 constexpr size_t LF_TAP_LDS_PER_TAP = (size_t)WG_WAVES * 64 * (sizeof(uint4) + sizeof(unsigned));
@@ -551,6 +564,170 @@ __global__ __launch_bounds__(256, (EPIC >= 0 || NT < 4) ? 2 : 1) void tapgemm_ke
             d[4] = (unsigned long long)hwid | ((unsigned long long)xcc << 32);
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------
+// tapstream_kernel: the fp32 3-tap C -> C convolutions and data gradients (C = CS = 64 or 128, Wl % 64 == 0) with the weights
+// RESIDENT IN LDS and the pixels streamed past them.  Ownership is tapgemm_kernel's -- a 4-wave group owns a 256-pixel tile, a wave
+// 64 pixels x 64 output channels, tiles walked inside the XCD's contiguous range, one statistics row per tile -- but a wave computes
+// its 64 pixels as FOUR 16-pixel sub-tiles in turn (16 + 16 accumulator registers instead of 64 + 64): per K-step one dwordx4 X
+// load per lane, four lane-contiguous ds_read_b128 of the weights ([K-step][channel tile][lane] float4, copied once per workgroup:
+// 48 KB at 64 channels, 96 KB at 128) and 16 MFMAs.  X runs through a register ring filled R K-steps ahead with buffer loads; the
+// ring wraps across sub-tiles and across the workgroup's tiles, so the operands of the next sub-tile (or tile) are in flight while
+// this one's epilogue runs, and the stores of a tile leave in four pieces spread over its life instead of in one burst at its end.
+// A prefetch past the last tile reads the out-of-range offset (zeros; with the operand prologue: pixel 0 of the tensor, masked).
+// Results are tapgemm_kernel's bit for bit: the same K order, the same 32-product segments flushed into accl, the same epilogue
+// text (LF_EPI_HEAD / LF_EPI_TILE / LF_EPI_TAIL) over the sub-tiles in the order 0, 1, 2, 3.
+// G: 4-wave groups per workgroup (128 channels: one 512-thread workgroup per CU, its two groups own tiles 2u and 2u + 1).
+template <int CS, int PROC, int EPIC, int G>
+__global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void tapstream_kernel(const LfTapGeom g, const LfTapArgs a) {
+    constexpr int NT = 4, NCG = CS / 16, NS = 3 * NCG, R = 8;
+    constexpr int epi = EPIC;
+    constexpr bool S16 = false, HOISTV = true;
+    static_assert((4 * NS) % R == 0 && R <= NS && NS % 2 == 0, "ring positions and K-step pairs must be compile-time");
+    const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl);
+    const int cob = blockIdx.y * 64;
+    const unsigned ntiles = (npix + PIX_PER_WG - 1) / PIX_PER_WG, nunits = (ntiles + G - 1) / G;
+    unsigned u_first = blockIdx.x, u_stride = gridDim.x, u_end = nunits;      // (see tapgemm_kernel: XCD-contiguous ranges)
+    if ((gridDim.x & 7u) == 0 && (nunits & 7u) == 0) {
+        const unsigned per = nunits >> 3;
+        u_first = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); u_stride = gridDim.x >> 3; u_end = (blockIdx.x & 7u) * per + per;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pl = lane & 15, kq = lane >> 4;
+    const unsigned wtile = (unsigned)__builtin_amdgcn_readfirstlane(wave);    // tile (u * G + wave / 4), wave % 4 of it: pixels from (u * 4G + wave) * 64
+
+
+    f32x4* const wl = reinterpret_cast<f32x4*>(lf_tap_lds);
+    float* const pvec = reinterpret_cast<float*>(wl + NS * 256);              // BN+ReLU operand prologue: scale [CS], shift [CS]
+    // a wave's 64 pixels lie in one image row: (image, row, first column) are wave-uniform
+    struct WT { int n0, i0, j0; bool v; };
+    auto coords = [&](unsigned u, bool live) -> WT {
+        const unsigned tile0 = (u * (unsigned)(4 * G) + wtile) * 64u;
+        WT c;
+        c.v = live && tile0 < npix;
+        const unsigned q = c.v ? tile0 : 0u;
+        const unsigned r = q / (unsigned)g.Wl;
+        c.j0 = __builtin_amdgcn_readfirstlane((int)(q - r * (unsigned)g.Wl));
+        c.n0 = __builtin_amdgcn_readfirstlane((int)(r / (unsigned)g.Hl));
+        c.i0 = __builtin_amdgcn_readfirstlane((int)r) - c.n0 * g.Hl;
+        return c;
+    };
+    // byte offset of this lane's four source channels of (sub-tile, tap) -- tapgemm_kernel's tap table, computed where it is used
+    auto xoff = [&](const WT& c, int sub, int t, bool& in) -> unsigned {
+        const int sy = c.i0 * g.ssh + g.tdh[t], sx = (c.j0 + sub * 16 + pl) * g.ssw + g.tdw[t];
+        in = c.v && sy >= 0 && sy < g.Hs && sx >= 0 && sx < g.Ws;
+        const int syc = min(max(sy, 0), g.Hs - 1), sxc = min(max(sx, 0), g.Ws - 1);
+        const unsigned o = (unsigned)(((c.n0 * g.Hs + syc) * g.Ws + sxc) * g.s_pix + g.s_choff + kq * 4) * 4u;
+        return (PROC == 0 && !in) ? LF_OOB : o;
+    };
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.src, (unsigned)min((long)g.N * g.Hs * g.Ws * g.s_pix * 4, (long)LF_OOB));
+    // position p of a tile's K sequence: sub-tile p / NS, then tap-major, then 16-channel groups
+    auto xload = [&](const WT& c, int p) -> f32x4 {
+        const int k = p % NS;
+        bool in;
+        const unsigned o = xoff(c, p / NS, k / NCG, in);
+        return ldb4(rx, o, (unsigned)(k % NCG) * 64u);
+    };
+
+    // the first R K-steps of X are requested BEFORE the weights are copied: their latency runs under the copy
+    f32x4 ring[R], wn[NT];
+    WT cur = coords(u_first, u_first < u_end);
+#pragma unroll
+    for (int p = 0; p < R; ++p) ring[p] = xload(cur, p);
+    // the workgroup's 64-output-channel slice of the packed weights [tap][CS/4][Cd][4] -> LDS [K-step][channel tile n][kq][pl] float4
+    {
+        const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.wp, (unsigned)(3 * CS * CS * 4));
+        for (int idx = threadIdx.x; idx < NS * 256; idx += 256 * G) {
+            const int col = idx & 63, row = idx >> 6;                          // row = tap * (CS / 4) + 4 * channel group + kq
+            wl[((row >> 2) * 4 + (col >> 4)) * 64 + (row & 3) * 16 + (col & 15)] = ldb4(rw, (unsigned)(row * CS + cob + col) * 16u, 0u);
+        }
+        if constexpr (PROC == LF_PRO_BNRELU) {
+            const __amdgpu_buffer_rsrc_t rsc = make_rsrc(a.pro_sc, CS * 4u), rsh = make_rsrc(a.pro_sh, CS * 4u);
+            for (int i = threadIdx.x; i < 2 * CS; i += 256 * G)
+                pvec[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(i < CS ? rsc : rsh, (i < CS ? i : i - CS) * 4, 0, 0));
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < NT; ++n) wn[n] = wl[n * 64 + lane];
+
+#undef LF_EPI_GROUPS
+#define LF_EPI_GROUPS G
+#undef LF_EPI_ROW1
+#define LF_EPI_ROW1 true
+#undef LF_EPI_ACC
+#define LF_EPI_ACC(n, m) acc[n]
+#undef LF_EPI_FIRST
+#define LF_EPI_FIRST(m) (sub == 0)
+#undef LF_EPI_ROW_OK
+#define LF_EPI_ROW_OK(tg) (bx * (unsigned)G + (unsigned)(tg) < ntiles)
+    LF_EPI_HEAD
+    for (unsigned bx = u_first; bx < u_end; bx += u_stride) {
+        const WT nxt = coords(bx + u_stride, bx + u_stride < u_end);
+        const int pn[1] = {cur.n0}, pi[1] = {cur.i0};
+        const bool pv[1] = {cur.v};
+#pragma unroll
+        for (int sub = 0; sub < 4; ++sub) {
+            f32x4 acc[NT], accl[NT];
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                const int p = sub * NS + k, cg = k % NCG;
+                f32x4 w[NT];
+#pragma unroll
+                for (int n = 0; n < NT; ++n) w[n] = wn[n];
+#pragma unroll
+                for (int n = 0; n < NT; ++n) wn[n] = wl[(((k + 1) % NS) * 4 + n) * 64 + lane];    // the next K-step's weights
+                f32x4 x = ring[p % R];
+                if constexpr (PROC == LF_PRO_BNRELU) {
+                    bool in;
+                    (void)xoff(cur, sub, k / NCG, in);
+                    const f32x4 sc = *reinterpret_cast<const f32x4*>(pvec + cg * 16 + kq * 4);
+                    const f32x4 sh = *reinterpret_cast<const f32x4*>(pvec + CS + cg * 16 + kq * 4);
+                    f32x4 v = max0(x * sc + sh);
+                    v.x = in ? v.x : 0.f; v.y = in ? v.y : 0.f; v.z = in ? v.z : 0.f; v.w = in ? v.w : 0.f;
+                    x = v;
+                }
+                if (k % 2 == 0) {       // a pair of K-steps = one 32-product chain: flush the finished one, restart from C = 0
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) {
+                        if (k == 0) accl[n] = zero4();
+                        else { accl[n] += acc[n]; asm volatile("" : "+v"(accl[n])); }
+                        acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[n][0], x[0], zero4(), 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int s = (k % 2 == 0) ? 1 : 0; s < 4; ++s)
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[n][s], x[s], acc[n], 0, 0, 0);
+                // this ring slot's next occupant, R K-steps ahead: this tile's, or the first of the workgroup's next tile
+                if (p + R < 4 * NS) ring[p % R] = xload(cur, p + R);
+                else ring[p % R] = xload(nxt, p + R - 4 * NS);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc[n] += accl[n];
+            const int pj[1] = {cur.j0 + sub * 16 + pl};
+            LF_EPI_TILE(0)
+        }
+        LF_EPI_TAIL
+        if (stats) {
+#pragma unroll
+            for (int n = 0; n < NT; ++n) { s1[n] = zero4(); s2[n] = zero4(); }
+            if (bx + u_stride < u_end) __syncthreads();      // the statistics staging area is reused by the next tile
+        }
+        cur = nxt;
+    }
+#undef LF_EPI_GROUPS
+#define LF_EPI_GROUPS 1
+#undef LF_EPI_ROW1
+#define LF_EPI_ROW1 false
+#undef LF_EPI_ACC
+#define LF_EPI_ACC(n, m) acc[n][m]
+#undef LF_EPI_FIRST
+#define LF_EPI_FIRST(m) ((m) == 0)
+#undef LF_EPI_ROW_OK
+#define LF_EPI_ROW_OK(tg) true
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2188,7 +2365,7 @@ int current_device() {
 }
 // Workgroups of `kernel` the whole chip holds at once (occupancy x CUs), cached per (device, kernel, dynamic LDS bytes).
 template <typename K>
-int resident_workgroups(K kernel, size_t lds) {
+int resident_workgroups(K kernel, size_t lds, int block = 256) {
     static std::map<std::tuple<int, const void*, size_t>, int> cache;
     const int dev = current_device();
     const std::tuple<int, const void*, size_t> key(dev, reinterpret_cast<const void*>(kernel), lds);
@@ -2197,7 +2374,7 @@ int resident_workgroups(K kernel, size_t lds) {
     if (it != cache.end()) return it->second;
     int cus = 0, nb = 0;
     if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, lds) != hipSuccess || nb < 1 || cus < 1)
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, lds) != hipSuccess || nb < 1 || cus < 1)
         return cache[key] = 1 << 30;                 // unknown: one tile per workgroup
     return cache[key] = nb * cus;
 }
@@ -2258,7 +2435,45 @@ bool launch_bf16_wv(unsigned ntiles, hipStream_t st, const LfTapGeom& g, const L
     hipLaunchKernelGGL(kern, dim3(gx), dim3(256), lds, st, g, a, pro, epi);
     return true;
 }
+// tapstream_kernel (see there).  lf_debug_set_fp32_stream: mode 0 = tapgemm_kernel takes every launch, 1 = the shipped routing
+// (g_stream_routed: which (channel count, variant) pairs were faster in the step); max_workgroups > 0 caps the grid, so that a
+// workgroup walks several tiles at small shapes.  Mode 2 routes every variant the kernel is compiled for (A/B runs, tests).
+std::atomic<int> g_stream_mode{1}, g_stream_cap{0};
+enum { LF_STREAM_RELU = 1, LF_STREAM_STATS = 2, LF_STREAM_MASK = 4, LF_STREAM_PRO = 8, LF_STREAM_X48 = 16, LF_STREAM_X38 = 32 };   // X48, X38: 64 channels only
+constexpr int g_stream_routed[2] = {LF_STREAM_RELU | LF_STREAM_STATS | LF_STREAM_MASK | LF_STREAM_PRO | LF_STREAM_X48 | LF_STREAM_X38,      // 64 channels
+                                    0};     // 128 channels: one tile per wave at batch 32 -- the 96 KB copy is never amortised: +2 us alone, +2..5 in the step
+// false: the runtime refused the kernel's LDS budget on this device (nothing launched: the caller takes tapgemm_kernel)
+template <int CS, int PROV, int EPIV>
+bool launch_tapstream(hipStream_t st, const LfTapGeom& g, const LfTapArgs& a) {
+    constexpr int G = CS == 128 ? 2 : 1;
+    auto kern = tapstream_kernel<CS, PROV, EPIV, G>;
+    const size_t lds = (size_t)3 * (CS / 16) * 4096 + (PROV == LF_PRO_BNRELU ? 2 * CS * sizeof(float) : 0);
+    if (!allow_big_lds(reinterpret_cast<const void*>(kern), 160 * 1024 - 4096)) return false;
+    const unsigned ntiles = (unsigned)lf_cdiv((long)g.N * g.Hl * g.Wl, PIX_PER_WG);
+    dim3 grid((ntiles + G - 1) / G, CS / 64);
+    const unsigned res = (unsigned)resident_workgroups(kern, lds, 256 * G) / grid.y;
+    if (grid.x > res && res >= 8) grid.x = res & ~7u;
+    const unsigned cap = (unsigned)g_stream_cap.load();
+    if (cap > 0 && grid.x > cap) grid.x = cap;
+    if (g_launch_flags) hipExtLaunchKernelGGL(kern, grid, dim3(256 * G), (unsigned)lds, st, nullptr, nullptr, g_launch_flags, g, a);
+    else hipLaunchKernelGGL(kern, grid, dim3(256 * G), lds, st, g, a);
+    return true;
+}
+template <int CS>
+bool route_tapstream(int variant, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a) {
+    switch (variant) {
+        case LF_STREAM_RELU: return launch_tapstream<CS, 0, LF_EPI_RELU>(st, g, a);
+        case LF_STREAM_STATS: return launch_tapstream<CS, 0, LF_EPI_STATS_SQ>(st, g, a);
+        case LF_STREAM_MASK: return launch_tapstream<CS, 0, LF_EPI_MASK>(st, g, a);
+        case LF_STREAM_PRO: return launch_tapstream<CS, 1, LF_EPI_RELU>(st, g, a);
+        case LF_STREAM_X48: if constexpr (CS == 64) return launch_tapstream<CS, 0, LF_EPI_MASKBN | LF_EPI_STATS_XHAT>(st, g, a); else return false;
+        case LF_STREAM_X38: if constexpr (CS == 64) return launch_tapstream<CS, 0, LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT>(st, g, a); else return false;
+        default: return false;
+    }
+}
 }  // namespace
+
+void lf_tapgemm_set_fp32_stream(int mode, int max_workgroups) { g_stream_mode = mode; g_stream_cap = max_workgroups > 0 ? max_workgroups : 0; }
 
 int lf_tapgemm_launch_unordered(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, hipStream_t st) {
     g_launch_flags = hipExtAnyOrderLaunch;
@@ -2507,6 +2722,17 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
         else hipLaunchKernelGGL((tapgemm_kernel<4, 0, 0, false, true>), grid, dim3(256), tap_lds, st, g, a, pro, epi);
         LF_CHECK_LAUNCH("tapgemm (stamps)");
         return 0;
+    }
+    if (g_stream_mode.load() != 0 && nt == 4 && g.ntaps == 3 && g.Cs == g.Cd && (g.Cs == 64 || g.Cs == 128) && (g.Wl & 63) == 0) {
+        // the 3-tap C -> C launches of the non_bottleneck_1d blocks: weights resident in LDS, pixels streamed (tapstream_kernel)
+        const int variant = pro == LF_PRO_BNRELU ? (epi == LF_EPI_RELU ? LF_STREAM_PRO : 0)
+                          : epis == LF_EPI_RELU ? LF_STREAM_RELU : epis == LF_EPI_STATS_SQ ? LF_STREAM_STATS : epis == LF_EPI_MASK ? LF_STREAM_MASK
+                          : epis == (LF_EPI_MASKBN | LF_EPI_STATS_XHAT) ? LF_STREAM_X48 : epis == (LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT) ? LF_STREAM_X38 : 0;
+        if (variant && (g_stream_mode.load() == 2 || (g_stream_routed[g.Cs == 128] & variant)) &&
+            (g.Cs == 64 ? route_tapstream<64>(variant, st, g, a) : route_tapstream<128>(variant, st, g, a))) {
+            LF_CHECK_LAUNCH("tapstream");
+            return 0;
+        }
     }
     switch (nt) {
         case 4:

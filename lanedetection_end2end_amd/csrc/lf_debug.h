@@ -33,6 +33,10 @@ int lf_debug_conv1d_fwd_pro(const float* x, const float* w, const float* bias, c
 /* the read-once bf16 weight gradient (lf_wgrad_ro.hip): mode 0 = off (tapwgrad_kernel's job form takes every launch), 1 = shipped;
  * cap64 / cap128 > 0: workgroups per launch at 64 / 128 channels (A/B runs; at most the shipped 512 / 256 the buffers are sized for) */
 void lf_debug_set_wgrad_ro(int mode, int cap64, int cap128);
+/* the fp32 3-tap C -> C tap-GEMM launches at 64 / 128 channels and whole-row waves (tapstream_kernel, lf_conv.hip): mode 0 =
+ * tapgemm_kernel takes every launch, 1 = the shipped routing, 2 = every variant tapstream_kernel is compiled for; max_workgroups > 0
+ * caps the grid, so that one workgroup walks several tiles at small shapes.  The kernels agree bit for bit (tests/test_fp32_stream_gpu.py) */
+void lf_debug_set_fp32_stream(int mode, int max_workgroups);
 /* lf_conv1d_bwd_weight with the BN+ReLU operand prologue on x (the weight gradient of a non_bottleneck_1d block's third convolution):
  * gw = d/dw of conv1d(relu(x * sc + sh)), gb = column sums of gy */
 int lf_debug_conv1d_wgrad_pro(const float* x, const float* gy, const float* sc, const float* sh, float* gw, float* gb, int N, int H, int W,

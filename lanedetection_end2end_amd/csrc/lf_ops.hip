@@ -111,6 +111,7 @@ void lf_debug_set_bf16_no_partial_fast(int v) { lf_tapgemm_set_bf16_no_partial_f
 void lf_debug_set_ops_precision(int mode) { g_ops_bf16 = (mode == 2 || mode == 9) ? mode : 0; }
 
 void lf_debug_set_wgrad_ro(int mode, int cap64, int cap128) { lf_tapwgrad_ro_set(mode, cap64, cap128); }
+void lf_debug_set_fp32_stream(int mode, int max_workgroups) { lf_tapgemm_set_fp32_stream(mode, max_workgroups); }
 long lf_debug_bias_residual_launches(void) { return lf_tapgemm_bias_residual_launches(); }
 long lf_debug_partial_fast_launches(void) { return lf_tapgemm_partial_fast_launches(); }
 
