@@ -133,6 +133,12 @@ def _declare(lib):
         "lf_debug_set_bf16_lds": (None, [I]),
         "lf_debug_set_bf16_no_partial_fast": (None, [I]),
         "lf_debug_stride2_epi": (I, [I, I, P, P, P, P, I, P, P, P, P, I, I, I, I, I, P, P]),
+        "lf_debug_stride2_wgrad_scratch_floats": (L, [I, I, I, I, I, I, I]),
+        "lf_debug_stride2_wgrad": (I, [I, I, P, P, P, P, I, I, I, I, I, P, P]),
+        "lf_debug_stem_wgrad_scratch_floats": (L, [I, I, I, I]),
+        "lf_debug_stem_wgrad": (I, [I, P, P, P, P, I, I, I, I, P, P]),
+        "lf_debug_head_wgrad_scratch_floats": (L, [I, I, I, I]),
+        "lf_debug_head_wgrad": (I, [I, P, P, P, P, I, I, I, I, P, P]),
         "lf_debug_set_ops_precision": (None, [I]),
         "lf_debug_conv1d_fwd_phases": (I, [P, P, P, P, I, I, I, I, I, I, P, P, P]),
         "lf_debug_conv1d_wgrad_phases": (I, [P, P, I, I, I, I, I, I, P, P, P]),

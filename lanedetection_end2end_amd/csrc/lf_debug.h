@@ -66,6 +66,34 @@ int lf_debug_conv1d_epi(const float* src, const float* w, const float* bias, flo
 int lf_debug_stride2_epi(int kind, int phase, const float* src, const float* w, const float* bias, float* dst, int epi, const float* mask_src,
                          const float* add_src, const float* aux, float* stats, int N, int H, int W, int Cin, int Cout, float* scratch,
                          void* stream);
+/* the weight + bias gradient of a stride-2 layer as the ERFNet plan issues it (run_wgrad, lf_erfnet.hip): tapwgrad_kernel over the plan's
+ * forward geometries (lf_plan.h) and one of the two reductions, in the precision of lf_debug_set_ops_precision (0 fp32, 2: x and g hold
+ * bf16; partial rows, gw, gb stay fp32).  (N, H, W): the LARGER tensor, H and W even.  Its own kind numbering (NOT lf_debug_stride2_epi's):
+ *   kind 0  DownsamplerBlock conv: x (N,H,W,Cin), g (N,H/2,W/2,Cin+Cout) read at channels [0, Cout); gw (Cout,Cin,3,3); one launch
+ *   kind 2  UpsamplerBlock transposed conv: x (N,H/2,W/2,Cin), g (N,H,W,Cout); gw (Cin,Cout,3,3); four sub-pixel-phase launches, which
+ *           reduce into disjoint 3x3 elements of gw and into ONE bias gradient
+ *   reduce 0  immediate: lf_wgrad_reduce_launch behind every launch from one shared partial region, the bias accumulating for phases
+ *             1..3 (run_wgrad with batch_off)
+ *   reduce 1  batched: every launch keeps its own partial region, the phases' bias rows are chained end to end (LfBiasChain, lf_plan.h:
+ *             only the last job carries a bias pointer) and one lf_wgrad_reduce_batch_launch follows
+ * gb [Cout] may be null (a bias that does not require grad: no bias rows are written).  scratch: lf_debug_stride2_wgrad_scratch_floats
+ * floats -- exactly what the call may touch: [weight regions][bias regions], each sized from lf_tapwgrad_splits_bound as the plan
+ * sizes its own, without padding.  Returns the partial rows written, summed over the launches; -1 on error. */
+long lf_debug_stride2_wgrad_scratch_floats(int kind, int reduce, int N, int H, int W, int Cin, int Cout);
+int lf_debug_stride2_wgrad(int kind, int reduce, const float* x, const float* g, float* gw, float* gb, int N, int H, int W, int Cin,
+                           int Cout, float* scratch, void* stream);
+/* the stem's weight gradient (stem_wgrad_kernel + its row sums, lf_stem.hip): img (N,Cin,H,W) fp32 NCHW, gcat (N,H/2,W/2,16) -- bf16 in
+ * mode 2 -- read at channels [0, 16 - Cin); gw (16 - Cin,Cin,3,3), gb [16 - Cin] or null.  reduce 0: lf_rows_reduce_launch per tensor;
+ * 1: the row-sum jobs of row_sums_finish (lf_plan.h) in one lf_wgrad_reduce_batch_launch.  scratch: [rows][gw elements] then
+ * [rows][gb elements], rows = the workgroups of the launch (at most 1024).  Returns the rows written, -1 on error. */
+long lf_debug_stem_wgrad_scratch_floats(int N, int Cin, int H, int W);
+int lf_debug_stem_wgrad(int reduce, const float* img, const float* gcat, float* gw, float* gb, int N, int Cin, int H, int W, float* scratch,
+                        void* stream);
+/* the head's weight gradient (head_wgrad_kernel + its row sums): x (N,h,w,16) -- bf16 in mode 2 --, gout (N,K,2h,2w) fp32 NCHW;
+ * gw (16,K,2,2), gb [K] or null; reduce, scratch layout and return value as above */
+long lf_debug_head_wgrad_scratch_floats(int N, int h, int w, int K);
+int lf_debug_head_wgrad(int reduce, const float* x, const float* gout, float* gw, float* gb, int N, int h, int w, int K, float* scratch,
+                        void* stream);
 /* tap-GEMM launches that took a compiled-in bias + residual + ReLU epilogue (the inference engine's block tail) since the process
  * started: which kernel form a launch selected (tests/test_infer_gpu.py) */
 long lf_debug_bias_residual_launches(void);

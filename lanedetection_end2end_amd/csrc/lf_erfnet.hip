@@ -171,8 +171,8 @@ void bn_alloc(LfBump& ws, BNRef& b) {
 void account_fwd_stats(lf_erfnet_plan* P, const LfTapGeom& g) {
     P->stat_floats = lf_maxl(P->stat_floats, (long)lf_tapgemm_stat_rows(g) * 2 * g.Cd);
 }
-long wneed_of(const LfTapGeom& g, int s16) { return (long)lf_tapwgrad_splits_bound(g, s16) * g.ntaps * g.Cs * g.Cd; }
-long bneed_of(const LfTapGeom& g, int s16) { return (long)lf_tapwgrad_splits_bound(g, s16) * g.Cd; }
+long wneed_of(const LfTapGeom& g, int s16) { return lf_wgrad_wneed(g, s16); }
+long bneed_of(const LfTapGeom& g, int s16) { return lf_wgrad_bneed(g, s16); }
 void account_wgrad(lf_erfnet_plan* P, const LfTapGeom& g) {
     for (int s16 = 0; s16 < 2; ++s16) {
         P->wpart_floats = lf_maxl(P->wpart_floats, wneed_of(g, s16));
@@ -589,9 +589,7 @@ int forward_layers(const Ctx& c, const float* img, int nlayers, int first = 0) {
     return 0;
 }
 
-// The four sub-pixel phases of a transposed convolution have ONE bias gradient: in batched mode their bias partial rows are laid
-// end to end (the phases' own bias regions are adjacent) and summed by the last phase's reduction job
-struct BiasChain { float* base = nullptr; int rows = 0; int phase = 0; };
+typedef LfBiasChain BiasChain;   // the four phases of a transposed convolution share one bias gradient (lf_plan.h)
 
 // weight + bias gradient of one forward-geometry GEMM
 int run_wgrad(const Ctx& c, const GemmOp& op, const ConvRef& cv, const float* x, const float* g, const float* pro_sc,
@@ -614,8 +612,8 @@ int run_wgrad(const Ctx& c, const GemmOp& op, const ConvRef& cv, const float* x,
     a.bias_partial = c.grads[cv.p_b] ? (batched ? c.at(off_bpart_all + c.bpart_used) : c.at(P->off_bpart)) : nullptr;
     if (chain) {
         if (!batched) return lf_fail("erfnet backward: a chained weight gradient does not fit its partial-row regions");
-        if (chain->phase == 0) chain->base = c.at(off_bpart_all + c.bpart_used);
-        if (a.bias_partial) a.bias_partial = chain->base + (long)chain->rows * op.geom.Cd;
+        float* rows = lf_bias_chain_rows(*chain, c.at(off_bpart_all + c.bpart_used), op.geom.Cd);
+        if (a.bias_partial) a.bias_partial = rows;
     }
     {
         ProfScope ps(c, 1, op.geom, 0, ws);
@@ -626,19 +624,8 @@ int run_wgrad(const Ctx& c, const GemmOp& op, const ConvRef& cv, const float* x,
     const int nsplit = lf_tapwgrad_splits_for(op.geom, a, pro_sc ? LF_PRO_BNRELU : LF_PRO_NONE);   // rows this launch wrote
     if (batched) {
         c.wpart_used += wneed; c.bpart_used += bneed;
-        LfReduceJob j;
-        memset(&j, 0, sizeof(j));
-        j.partial = a.partial; j.grad = c.grads[cv.p_w]; j.bias_rows = a.bias_partial; j.bias_grad = c.grads[cv.p_b];
-        j.sk = e.sk; j.sn = e.sn; j.splits = nsplit; j.ntaps = op.geom.ntaps; j.Cs = op.geom.Cs; j.Cd = op.geom.Cd;
-        j.n_bias_rows = nsplit;
-        if (chain) {
-            chain->rows += nsplit;
-            const bool last = ++chain->phase == 4;
-            j.bias_rows = (last && a.bias_partial) ? chain->base : nullptr;
-            j.n_bias_rows = chain->rows;
-            if (!last) j.bias_grad = nullptr;
-        }
-        for (int t = 0; t < op.geom.ntaps; ++t) j.tapidx[t] = e.tapidx[t];
+        LfReduceJob j = lf_wgrad_reduce_job(op.geom, a.partial, nsplit, c.grads[cv.p_w], e.sk, e.sn, e.tapidx, a.bias_partial, c.grads[cv.p_b]);
+        if (chain) lf_bias_chain_job(*chain, j, nsplit, a.bias_partial != nullptr);
         c.reduce_jobs.push_back(j);
         // (launching the reductions gathered so far early and WITHOUT a barrier bit, beside a later weight / data gradient, was
         // measured: same bits, no gain -- DESIGN.md section 9)
@@ -671,11 +658,8 @@ int row_sums_finish(const Ctx& c, const RowSums& r, int rows, int nw, float* gw,
         if (gb) LF_TRY(lf_rows_reduce_launch(r.brows, rows, nb, gb, 0, c.st));
         return 0;
     }
-    LfReduceJob j;
-    memset(&j, 0, sizeof(j));
-    j.partial = r.wrows; j.grad = gw; j.sk = 0; j.sn = 1; j.splits = rows; j.ntaps = 1; j.Cs = 1; j.Cd = nw;      // grad[n] = sum_r rows[r][n]
-    c.reduce_jobs.push_back(j);
-    if (gb) { j.partial = r.brows; j.grad = gb; j.Cd = nb; c.reduce_jobs.push_back(j); }
+    c.reduce_jobs.push_back(lf_row_sum_job(r.wrows, rows, nw, gw));      // grad[n] = sum_r rows[r][n]
+    if (gb) c.reduce_jobs.push_back(lf_row_sum_job(r.brows, rows, nb, gb));
     return 0;
 }
 

@@ -4,6 +4,7 @@
 // Replaces nn.Conv2d(C, C, (3,1)|(1,3), padding=d, dilation=d) of non_bottleneck_1d (ERFNet.py:29-37).
 #include "lf_conv.h"
 #include "lf_debug.h"
+#include "lf_eltwise.h"
 #include "lf_plan.h"
 
 namespace {
@@ -251,6 +252,145 @@ int lf_debug_stride2_epi(int kind, int phase, const float* src, const float* w, 
     a.stats_ld = lf_tapgemm_stat_rows(g);        // the caller's buffer: [2][Cd][rows], rows = ceil(logical pixels / 256)
     if (lf_tapgemm_launch(g, a, LF_PRO_NONE, epi, st)) return -1;
     return (epi & (LF_EPI_STATS_SQ | LF_EPI_STATS_XHAT)) ? lf_tapgemm_stat_rows_for(g, a) : 0;
+}
+
+namespace {
+// the weight-gradient launches of a stride-2 layer: the plan's forward geometries (run_wgrad differentiates L.cv[0].fwd / .fph[ph])
+int stride2_wgrad_ops(int kind, int N, int H, int W, int Cin, int Cout, LfStride2Op ops[4]) {
+    LfStride2Op one, four[4];
+    if (kind == 0) { lf_down_conv_ops(N, H, W, Cin, Cout, Cin + Cout, ops[0], four); return 1; }
+    lf_up_conv_ops(N, H / 2, W / 2, Cin, Cout, ops, one);
+    return 4;
+}
+bool stride2_wgrad_ok(const char* who, int kind, int reduce, int N, int H, int W, int Cin, int Cout) {
+    if ((kind != 0 && kind != 2) || (reduce != 0 && reduce != 1) || N < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || Cin < 16 || Cout < 16) {
+        lf_fail("%s: bad arguments (kind %d reduce %d N %d H %d W %d Cin %d Cout %d)", who, kind, reduce, N, H, W, Cin, Cout);
+        return false;
+    }
+    if (g_ops_bf16 != 0 && g_ops_bf16 != 2) { lf_fail("%s: precision mode 0 or 2 only", who); return false; }
+    return true;
+}
+// floats of the weight / bias partial-row regions: one shared region (immediate route) or one per launch, end to end (batched route)
+void stride2_wgrad_regions(const LfStride2Op* ops, int nops, int reduce, long& wtot, long& btot) {
+    const int s16 = g_ops_bf16 == 2;
+    wtot = btot = 0;
+    for (int i = 0; i < nops; ++i) {
+        const long w = lf_wgrad_wneed(ops[i].geom, s16), b = lf_wgrad_bneed(ops[i].geom, s16);
+        wtot = reduce ? wtot + w : lf_maxl(wtot, w);
+        btot = reduce ? btot + b : lf_maxl(btot, b);
+    }
+}
+}  // namespace
+
+long lf_debug_stride2_wgrad_scratch_floats(int kind, int reduce, int N, int H, int W, int Cin, int Cout) {
+    if (!stride2_wgrad_ok("lf_debug_stride2_wgrad_scratch_floats", kind, reduce, N, H, W, Cin, Cout)) return -1;
+    LfStride2Op ops[4];
+    const int nops = stride2_wgrad_ops(kind, N, H, W, Cin, Cout, ops);
+    long wtot, btot;
+    stride2_wgrad_regions(ops, nops, reduce, wtot, btot);
+    return wtot + btot;
+}
+
+// The weight + bias gradient of a stride-2 layer as run_wgrad (lf_erfnet.hip) issues it: one launch per forward geometry of the
+// plan, then the immediate or the batched reduction.  The jobs and the bias chain are lf_plan.h's, shared with run_wgrad; what is
+// this hook's own is where the partial-row regions lie: scratch = [weight regions][bias regions], unpadded, so that a row written
+// past its region lands in the next one or in the caller's guard band.
+int lf_debug_stride2_wgrad(int kind, int reduce, const float* x, const float* g, float* gw, float* gb, int N, int H, int W, int Cin,
+                           int Cout, float* scratch, void* stream) {
+    if (!(x && g && gw && scratch)) { lf_fail("lf_debug_stride2_wgrad: null pointer"); return -1; }
+    if (!stride2_wgrad_ok("lf_debug_stride2_wgrad", kind, reduce, N, H, W, Cin, Cout)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int s16 = g_ops_bf16 == 2;
+    LfStride2Op ops[4];
+    const int nops = stride2_wgrad_ops(kind, N, H, W, Cin, Cout, ops);
+    long wtot, btot;
+    stride2_wgrad_regions(ops, nops, reduce, wtot, btot);
+    LfBiasChain chain;
+    LfReduceJob jobs[4];
+    long woff = 0, boff = 0;
+    int rows = 0;
+    for (int ph = 0; ph < nops; ++ph) {
+        const LfStride2Op& op = ops[ph];
+        float* bregion = scratch + wtot + boff;
+        LfWgradArgs a;
+        a.x = x; a.g = g; a.pro_sc = nullptr; a.pro_sh = nullptr; a.s16 = s16; a.split = 0;
+        a.partial = scratch + woff;
+        a.bias_partial = gb ? bregion : nullptr;
+        if (reduce && nops == 4) {
+            float* chained = lf_bias_chain_rows(chain, bregion, op.geom.Cd);
+            if (a.bias_partial) a.bias_partial = chained;
+        }
+        if (lf_tapwgrad_launch(op.geom, a, LF_PRO_NONE, st)) return -1;
+        const int nsplit = lf_tapwgrad_splits_for(op.geom, a, LF_PRO_NONE);
+        if (nsplit < 1 || nsplit > lf_tapwgrad_splits_bound(op.geom, s16)) {
+            lf_fail("lf_debug_stride2_wgrad: phase %d wrote %d rows, its region holds %d", ph, nsplit, lf_tapwgrad_splits_bound(op.geom, s16));
+            return -1;
+        }
+        rows += nsplit;
+        if (reduce) {
+            jobs[ph] = lf_wgrad_reduce_job(op.geom, a.partial, nsplit, gw, op.sk, op.sn, op.tapidx, a.bias_partial, gb);
+            if (nops == 4) lf_bias_chain_job(chain, jobs[ph], nsplit, a.bias_partial != nullptr);
+            woff += lf_wgrad_wneed(op.geom, s16); boff += lf_wgrad_bneed(op.geom, s16);
+        } else if (lf_wgrad_reduce_launch(a.partial, nsplit, op.geom.ntaps, op.geom.Cs, op.geom.Cd, gw, op.sk, op.sn, op.tapidx,
+                                          a.bias_partial, nsplit, gb, ph > 0, st)) {
+            return -1;
+        }
+    }
+    if (reduce && lf_wgrad_reduce_batch_launch(jobs, nops, st)) return -1;
+    return rows;
+}
+
+namespace {
+// the stem's / head's partial rows summed as row_sums_finish (lf_erfnet.hip) sums them: immediately, or as lf_plan.h's row-sum jobs
+int debug_row_sums(int reduce, const float* wrows, const float* brows, int rows, int nw, float* gw, int nb, float* gb, hipStream_t st) {
+    if (!reduce) {
+        if (lf_rows_reduce_launch(wrows, rows, nw, gw, 0, st)) return -1;
+        if (gb && lf_rows_reduce_launch(brows, rows, nb, gb, 0, st)) return -1;
+        return rows;
+    }
+    LfReduceJob jobs[2];
+    int n = 0;
+    jobs[n++] = lf_row_sum_job(wrows, rows, nw, gw);
+    if (gb) jobs[n++] = lf_row_sum_job(brows, rows, nb, gb);
+    return lf_wgrad_reduce_batch_launch(jobs, n, st) ? -1 : rows;
+}
+bool ends_wgrad_ok(const char* who, int reduce, bool dims_ok) {
+    if ((reduce != 0 && reduce != 1) || !dims_ok) { lf_fail("%s: bad arguments", who); return false; }
+    if (g_ops_bf16 != 0 && g_ops_bf16 != 2) { lf_fail("%s: precision mode 0 or 2 only", who); return false; }
+    return true;
+}
+}  // namespace
+
+long lf_debug_stem_wgrad_scratch_floats(int N, int Cin, int H, int W) {
+    if (N < 1 || Cin < 1 || Cin > 4 || H < 2 || W < 2) return -1;
+    return (long)lf_stem_wgrad_rows(N, H, W) * ((16 - Cin) * Cin * 9 + (16 - Cin));
+}
+
+int lf_debug_stem_wgrad(int reduce, const float* img, const float* gcat, float* gw, float* gb, int N, int Cin, int H, int W, float* scratch,
+                        void* stream) {
+    if (!(img && gcat && gw && scratch)) { lf_fail("lf_debug_stem_wgrad: null pointer"); return -1; }
+    if (!ends_wgrad_ok("lf_debug_stem_wgrad", reduce, N >= 1 && Cin >= 1 && Cin <= 4 && H >= 2 && W >= 2)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int Cc = 16 - Cin, rows = lf_stem_wgrad_rows(N, H, W), nw = Cc * Cin * 9;
+    float *wrows = scratch, *brows = scratch + (long)rows * nw;
+    if (lf_stem_wgrad(img, gcat, N, Cin, H, W, wrows, brows, g_ops_bf16 == 2, st)) return -1;
+    return debug_row_sums(reduce, wrows, brows, rows, nw, gw, Cc, gb, st);
+}
+
+long lf_debug_head_wgrad_scratch_floats(int N, int h, int w, int K) {
+    if (N < 1 || h < 1 || w < 1 || K < 1 || K > 5) return -1;
+    return (long)lf_head_wgrad_rows(N, h, w) * (16 * K * 4 + K);
+}
+
+int lf_debug_head_wgrad(int reduce, const float* x, const float* gout, float* gw, float* gb, int N, int h, int w, int K, float* scratch,
+                        void* stream) {
+    if (!(x && gout && gw && scratch)) { lf_fail("lf_debug_head_wgrad: null pointer"); return -1; }
+    if (!ends_wgrad_ok("lf_debug_head_wgrad", reduce, N >= 1 && h >= 1 && w >= 1 && K >= 1 && K <= 5)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = lf_head_wgrad_rows(N, h, w), nw = 16 * K * 4;
+    float *wrows = scratch, *brows = scratch + (long)rows * nw;
+    if (lf_head_wgrad(x, gout, wrows, brows, N, h, w, K, g_ops_bf16 == 2, st)) return -1;
+    return debug_row_sums(reduce, wrows, brows, rows, nw, gw, K, gb, st);
 }
 
 namespace {

@@ -92,3 +92,51 @@ inline void lf_up_conv_ops(int N, int Hi, int Wi, int Cin, int Co, LfStride2Op f
     lf_window9_taps(dg.geom, dg.tapidx);
     dg.Kc = Co; dg.Nc = Cin; dg.sk = 9; dg.sn = (long)Co * 9;
 }
+
+// ---- Weight-gradient reductions: how a launch's partial rows become a reduction job, and how the four sub-pixel phases of a
+// transposed convolution share one bias gradient.  Built here, once, for the plan (run_wgrad / row_sums_finish, lf_erfnet.hip) and
+// for the kernel-level hooks (lf_debug_stride2_wgrad, lf_debug_stem_wgrad, lf_debug_head_wgrad, lf_ops.hip): the tests of the hooks
+// test the plan's own jobs.
+
+// floats of the partial-row regions of one weight-gradient launch (upper bound over the kernels that may take it)
+inline long lf_wgrad_wneed(const LfTapGeom& g, int s16) { return (long)lf_tapwgrad_splits_bound(g, s16) * g.ntaps * g.Cs * g.Cd; }
+inline long lf_wgrad_bneed(const LfTapGeom& g, int s16) { return (long)lf_tapwgrad_splits_bound(g, s16) * g.Cd; }
+
+// the batched reduction of one weight-gradient launch that wrote nsplit rows: grad[k * sk + n * sn + tapidx[t]] = sum_s partial[s][t][k][n],
+// bias_grad[n] = sum_r bias_rows[r][n] (bias_rows / bias_grad may be null)
+inline LfReduceJob lf_wgrad_reduce_job(const LfTapGeom& g, const float* partial, int nsplit, float* grad, long sk, long sn,
+                                       const int* tapidx, const float* bias_rows, float* bias_grad) {
+    LfReduceJob j;
+    memset(&j, 0, sizeof(j));
+    j.partial = partial; j.grad = grad; j.bias_rows = bias_rows; j.bias_grad = bias_grad;
+    j.sk = sk; j.sn = sn; j.splits = nsplit; j.ntaps = g.ntaps; j.Cs = g.Cs; j.Cd = g.Cd;
+    j.n_bias_rows = nsplit;
+    for (int t = 0; t < g.ntaps; ++t) j.tapidx[t] = tapidx[t];
+    return j;
+}
+
+// The four sub-pixel phases of a transposed convolution have ONE bias gradient: in batched mode their bias partial rows are laid
+// end to end (the phases' own bias regions are adjacent) and summed by the last phase's reduction job
+struct LfBiasChain { float* base = nullptr; int rows = 0; int phase = 0; };
+// where the next phase writes its bias rows; region: that phase's own bias region (the chain starts at phase 0's)
+inline float* lf_bias_chain_rows(LfBiasChain& ch, float* region, int Cd) {
+    if (ch.phase == 0) ch.base = region;
+    return ch.base + (long)ch.rows * Cd;
+}
+// the phase wrote nsplit rows: its job sums no bias rows, except the last phase's, which sums the whole chain (has_bias: the
+// launches wrote bias rows at all)
+inline void lf_bias_chain_job(LfBiasChain& ch, LfReduceJob& j, int nsplit, bool has_bias) {
+    ch.rows += nsplit;
+    const bool last = ++ch.phase == 4;
+    j.bias_rows = (last && has_bias) ? ch.base : nullptr;
+    j.n_bias_rows = ch.rows;
+    if (!last) j.bias_grad = nullptr;
+}
+
+// plain column sums as a batched job: dst[n] = sum_r rows[r][n], n < width (the stem / head weight-gradient rows)
+inline LfReduceJob lf_row_sum_job(const float* rows, int nrows, int width, float* dst) {
+    LfReduceJob j;
+    memset(&j, 0, sizeof(j));
+    j.partial = rows; j.grad = dst; j.sk = 0; j.sn = 1; j.splits = nrows; j.ntaps = 1; j.Cs = 1; j.Cd = width;
+    return j;
+}
