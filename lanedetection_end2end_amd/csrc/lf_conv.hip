@@ -16,14 +16,17 @@
 //
 // Kernels in this file:
 //   tapgemm_kernel            fp32 matrix cores, operands streamed L2 -> VGPR: the 64- / 128-channel launches of the network
+//   tapstream_kernel          fp32, the 3-tap convolutions at 64 / 128 channels: weights resident in LDS, pixels streamed past them
 //   tapgemm_lean_kernel       16-channel layers in fp32 (HBM-bound)
 //   tapgemm_split_kernel      precision mode fp32x9: fp32 results from exact 3-way bf16 splits on the bf16 matrix cores
 //   tapgemm_bf16_kernel       precision mode bf16, operands streamed into registers (operand prologue, ragged widths)
 //   tapgemm_bf16_wl_kernel    bf16 tensors, the 3-tap convolutions at 64 / 128 channels: memory touched in whole 128-byte lines
 //                             (LDS-DMA operand ring, weights in registers, LDS-transposed stores)
+//   tapgemm_bf16_wv_kernel    bf16 tensors, the 3-tap convolutions at 64 channels: a wave owns its pixels and all 64 output channels
 //   tapgemm_bf16_ring_kernel  bf16 tensors, every other tap table: persistent LDS-DMA ring
 //   tapgemm_bf16_lean_kernel  bf16 tensors, 16 -> 16 channels (two taps per K = 32 MFMA)
 //   tapwgrad_kernel / tapwgrad16_kernel / tapwgrad16_tr_kernel   weight gradients, split-K over pixels
+//   tapwgrad16_f32_kernel     the 16 x 16 channel weight gradient on fp32 tensors through a per-wave LDS-DMA ring
 //   the split-K reductions (one per weight gradient, or batched per backward pass) and the weight-packing kernels.
 // The tap-GEMM kernels share one epilogue (LF_TAPGEMM_EPILOGUE: bias, ReLU, masks, residual, BN sums); the whole-line kernel has
 // its own (same arithmetic, output and operand tensors through LDS tiles).
@@ -34,6 +37,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 #include <utility>
 
 #include <hip/hip_ext.h>
@@ -2388,52 +2392,44 @@ bool allow_big_lds(const void* kernel, int bytes) {
     if (it != done.end()) return it->second;
     return done[key] = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
 }
-// tapgemm_kernel walks its pixel tiles with stride gridDim.x: launch no more workgroups than are resident at once (a multiple
-// of 8 per XCD dealing), so that the tiles beyond the first round are spread one per CU by construction
-// hipExtAnyOrderLaunch for the next launch_tapgemm (set by lf_tapgemm_launch_unordered): the dispatch packet carries no barrier
+// hipExtAnyOrderLaunch for the next fp32 launch (set by lf_tapgemm_launch_unordered): the dispatch packet carries no barrier
 // bit, so the kernel may start while the PREVIOUS packet of the stream is still running -- its workgroups fill the slots the
 // previous kernel's last workgroups leave (the caller guarantees the two are independent).
 thread_local unsigned g_launch_flags = 0;
+// The launch of every kernel that walks its tiles / items with stride gridDim.x: no more workgroups than are resident at once (a
+// multiple of 8 per XCD dealing: XCD-contiguous item ranges), so that the work beyond the first round is spread one per CU by
+// construction; then no more than max_wgs, where that is > 0.
+// lds_attr > 0: the kernel needs that hipFuncAttributeMaxDynamicSharedMemorySize -- false when the runtime refuses it on this device
+// (nothing launched: the caller takes a kernel that needs less LDS).  flags: g_launch_flags where the kernel honours it, else 0.
+template <typename K, typename... Args>
+bool launch_resident(K kernel, dim3 grid, unsigned block, size_t lds, int lds_attr, unsigned max_wgs, unsigned flags, hipStream_t st, const Args&... args) {
+    if (lds_attr > 0 && !allow_big_lds(reinterpret_cast<const void*>(kernel), lds_attr)) return false;
+    const unsigned res = (unsigned)resident_workgroups(kernel, lds, (int)block) / grid.y;
+    if (grid.x > res && res >= 8) grid.x = res & ~7u;
+    if (max_wgs > 0 && grid.x > max_wgs) grid.x = max_wgs;
+    if (flags) hipExtLaunchKernelGGL(kernel, grid, dim3(block), (unsigned)lds, st, nullptr, nullptr, flags, args...);
+    else hipLaunchKernelGGL(kernel, grid, dim3(block), lds, st, args...);
+    return true;
+}
+constexpr int BIG_LDS = 160 * 1024 - 4096;      // the LDS attribute of the whole-line, wave-private and weight-resident kernels
 template <typename K>
 void launch_tapgemm(K kernel, dim3 grid, size_t lds, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
-    const unsigned res = (unsigned)resident_workgroups(kernel, lds) / grid.y;
-    if (grid.x > res && res >= 8) grid.x = res & ~7u;
-    if (g_launch_flags) hipExtLaunchKernelGGL(kernel, grid, dim3(256), (unsigned)lds, st, nullptr, nullptr, g_launch_flags, g, a, pro, epi);
-    else hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, g, a, pro, epi);
+    launch_resident(kernel, grid, 256, lds, 0, 0, g_launch_flags, st, g, a, pro, epi);
 }
-// tapgemm_bf16_ring_kernel: persistent, at most the resident workgroups (a multiple of 8: XCD-contiguous item ranges)
+// tapgemm_bf16_ring_kernel: persistent
 template <int EPIV, bool DBGV = false>
 void launch_bf16_ring(unsigned nitems, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
-    auto kern = tapgemm_bf16_ring_kernel<EPIV, DBGV>;
-    const size_t ring_lds = (size_t)LB_STAGES * LB_STAGE_BYTES;
-    unsigned gx = nitems;
-    const unsigned res = (unsigned)resident_workgroups(kern, ring_lds);
-    if (gx > res && res >= 8) gx = res & ~7u;
-    hipLaunchKernelGGL(kern, dim3(gx), dim3(256), ring_lds, st, g, a, pro, epi);
+    launch_resident(tapgemm_bf16_ring_kernel<EPIV, DBGV>, dim3(nitems), 256, (size_t)LB_STAGES * LB_STAGE_BYTES, 0, 0, 0, st, g, a, pro, epi);
 }
 // false: the runtime refused the kernel's LDS budget on this device (nothing launched: the caller takes the ring / streaming kernel)
 template <int CBV, int EPIV, int PROV = 0>
 bool launch_bf16_wl(unsigned nitems, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
-    auto kern = tapgemm_bf16_wl_kernel<CBV, EPIV, PROV>;
-    const size_t lds = WlCfg<CBV, EPIV, PROV>::LDS;
-    if (!allow_big_lds(reinterpret_cast<const void*>(kern), 160 * 1024 - 4096)) return false;
-    unsigned gx = nitems;
-    const unsigned res = (unsigned)resident_workgroups(kern, lds);
-    if (gx > res && res >= 8) gx = res & ~7u;
-    hipLaunchKernelGGL(kern, dim3(gx), dim3(256), lds, st, g, a, pro, epi);
-    return true;
+    return launch_resident(tapgemm_bf16_wl_kernel<CBV, EPIV, PROV>, dim3(nitems), 256, WlCfg<CBV, EPIV, PROV>::LDS, BIG_LDS, 0, 0, st, g, a, pro, epi);
 }
 // tapgemm_bf16_wv_kernel (64 channels): same contract
 template <int EPIV>
 bool launch_bf16_wv(unsigned ntiles, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
-    auto kern = tapgemm_bf16_wv_kernel<EPIV>;
-    const size_t lds = WvCfg<EPIV>::LDS;
-    if (!allow_big_lds(reinterpret_cast<const void*>(kern), 160 * 1024 - 4096)) return false;
-    unsigned gx = ntiles;
-    const unsigned res = (unsigned)resident_workgroups(kern, lds);
-    if (gx > res && res >= 8) gx = res & ~7u;
-    hipLaunchKernelGGL(kern, dim3(gx), dim3(256), lds, st, g, a, pro, epi);
-    return true;
+    return launch_resident(tapgemm_bf16_wv_kernel<EPIV>, dim3(ntiles), 256, WvCfg<EPIV>::LDS, BIG_LDS, 0, 0, st, g, a, pro, epi);
 }
 // tapstream_kernel (see there).  lf_debug_set_fp32_stream: mode 0 = tapgemm_kernel takes every launch, 1 = the shipped routing
 // (g_stream_routed: which (channel count, variant) pairs were faster in the step); max_workgroups > 0 caps the grid, so that a
@@ -2446,18 +2442,10 @@ constexpr int g_stream_routed[2] = {LF_STREAM_RELU | LF_STREAM_STATS | LF_STREAM
 template <int CS, int PROV, int EPIV>
 bool launch_tapstream(hipStream_t st, const LfTapGeom& g, const LfTapArgs& a) {
     constexpr int G = CS == 128 ? 2 : 1;
-    auto kern = tapstream_kernel<CS, PROV, EPIV, G>;
     const size_t lds = (size_t)3 * (CS / 16) * 4096 + (PROV == LF_PRO_BNRELU ? 2 * CS * sizeof(float) : 0);
-    if (!allow_big_lds(reinterpret_cast<const void*>(kern), 160 * 1024 - 4096)) return false;
     const unsigned ntiles = (unsigned)lf_cdiv((long)g.N * g.Hl * g.Wl, PIX_PER_WG);
-    dim3 grid((ntiles + G - 1) / G, CS / 64);
-    const unsigned res = (unsigned)resident_workgroups(kern, lds, 256 * G) / grid.y;
-    if (grid.x > res && res >= 8) grid.x = res & ~7u;
-    const unsigned cap = (unsigned)g_stream_cap.load();
-    if (cap > 0 && grid.x > cap) grid.x = cap;
-    if (g_launch_flags) hipExtLaunchKernelGGL(kern, grid, dim3(256 * G), (unsigned)lds, st, nullptr, nullptr, g_launch_flags, g, a);
-    else hipLaunchKernelGGL(kern, grid, dim3(256 * G), lds, st, g, a);
-    return true;
+    return launch_resident(tapstream_kernel<CS, PROV, EPIV, G>, dim3((ntiles + G - 1) / G, CS / 64), 256 * G, lds, BIG_LDS,
+                           (unsigned)g_stream_cap.load(), g_launch_flags, st, g, a);
 }
 template <int CS>
 bool route_tapstream(int variant, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a) {
@@ -2471,251 +2459,193 @@ bool route_tapstream(int variant, hipStream_t st, const LfTapGeom& g, const LfTa
         default: return false;
     }
 }
-}  // namespace
 
-void lf_tapgemm_set_fp32_stream(int mode, int max_workgroups) { g_stream_mode = mode; g_stream_cap = max_workgroups > 0 ? max_workgroups : 0; }
-
-int lf_tapgemm_launch_unordered(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, hipStream_t st) {
-    g_launch_flags = hipExtAnyOrderLaunch;
-    const int rc = lf_tapgemm_launch(g, a, pro, epi, st);
-    g_launch_flags = 0;
-    return rc;
+// The compiled-in data-gradient epilogues (mask / residual / BN-backward sums) carry no bias vector (NOBIAS): a launch that
+// combines one of them with a bias takes the run-time-flag kernel -- except the inference engine's residual tail (bias + ADD +
+// ReLU: BRES, compiled into the kernels the forward convolutions route to; the split, ring and streaming-fast kernels keep the
+// run-time form)
+constexpr int BRES = LF_EPI_ADD | LF_EPI_RELU | LF_EPI_BIAS;
+template <int V> using IntC = std::integral_constant<int, V>;
+// The one place that turns the run-time epilogue set into a template argument: f(IntC<E>{}) with E the compiled-in set equal to
+// epis, or -1 (the run-time-flag form) for every other.  WITH_BRES = false: the kernel family has no compiled-in BRES form.
+template <bool WITH_BRES, typename F>
+auto with_epi(int epis, F&& f) {
+    switch (epis) {
+        case 0: return f(IntC<0>{});
+        case LF_EPI_RELU: return f(IntC<LF_EPI_RELU>{});
+        case LF_EPI_MASK: return f(IntC<LF_EPI_MASK>{});
+        case LF_EPI_ADD: return f(IntC<LF_EPI_ADD>{});
+        case LF_EPI_STATS_SQ: return f(IntC<LF_EPI_STATS_SQ>{});
+        case LF_EPI_MASK | LF_EPI_STATS_XHAT: return f(IntC<LF_EPI_MASK | LF_EPI_STATS_XHAT>{});
+        case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: return f(IntC<LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT>{});
+        case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: return f(IntC<LF_EPI_MASKBN | LF_EPI_STATS_XHAT>{});
+        case BRES: return f(IntC<WITH_BRES ? BRES : -1>{});
+        default: return f(IntC<-1>{});
+    }
+}
+// ... and for the kernels that compile the BN+ReLU operand prologue beside the epilogue, f(IntC<PRO>{}, IntC<E>{}): a prologue launch
+// has the compiled-in ReLU epilogue or the run-time flags, only prologue-free launches dispatch on epis
+template <bool WITH_BRES, typename F>
+void with_pro_epi(int pro, int epi, int epis, F&& f) {
+    if (pro == LF_PRO_BNRELU && epi == LF_EPI_RELU) f(IntC<1>{}, IntC<LF_EPI_RELU>{});
+    else if (pro == LF_PRO_BNRELU) f(IntC<1>{}, IntC<-1>{});
+    else with_epi<WITH_BRES>(epis, [&](auto e) { f(IntC<0>{}, e); });
 }
 
-int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, hipStream_t st) {
-    LF_REQUIRE(g.Cs % 16 == 0 && g.Cd % 16 == 0, "tapgemm: channels must be multiples of 16 (Cs=%d Cd=%d)", g.Cs, g.Cd);
-    LF_REQUIRE(g.s_pix % 4 == 0 && g.s_choff % 4 == 0 && g.d_pix % 4 == 0 && g.d_choff % 4 == 0, "tapgemm: unaligned channel layout");
-    LF_REQUIRE(g.ntaps >= 1 && g.ntaps <= LF_MAX_TAPS, "tapgemm: bad tap count %d", g.ntaps);
-    const long npix = (long)g.N * g.Hl * g.Wl;
-    LF_REQUIRE(npix < (1L << 30), "tapgemm: too many pixels (%ld)", npix);
-    const int nt = pick_nt(g.Cd);
-    dim3 grid(lf_cdiv(npix, PIX_PER_WG), g.Cd / (16 * nt));
-    LF_REQUIRE((long)g.N * g.Hs * g.Ws * g.s_pix * 4 < (long)LF_OOB, "tapgemm: source tensor too large for 32-bit byte offsets");
-    LF_REQUIRE((long)g.N * g.Hd * g.Wd * g.d_pix * 4 < (long)LF_OOB, "tapgemm: destination tensor too large for 32-bit byte offsets");
-#define LF_TG(NTV)                                                                                                       \
-    do {                                                                                                                 \
-        if (pro == LF_PRO_BNRELU) launch_tapgemm(tapgemm_kernel<NTV, 1>, grid, tap_lds, st, g, a, pro, epi);  \
-        else launch_tapgemm(tapgemm_kernel<NTV, 0>, grid, tap_lds, st, g, a, pro, epi);                       \
-    } while (0)
-#define LF_TG4(PROV, EPIV)                                                                                               \
-    do {                                                                                                                 \
-        if ((g.Wl & 63) == 0) launch_tapgemm(tapgemm_kernel<4, PROV, EPIV, true>, grid, tap_lds, st, g, a, pro, epi);  \
-        else launch_tapgemm(tapgemm_kernel<4, PROV, EPIV, false>, grid, tap_lds, st, g, a, pro, epi);    \
-    } while (0)
-    const size_t tap_lds = LF_TAP_LDS_PER_TAP * g.ntaps;
-    // the compiled-in data-gradient epilogues (mask / residual / BN-backward sums) carry no bias vector (NOBIAS): a launch
-    // that combines one of them with a bias takes the run-time-flag kernel -- except the inference engine's residual tail
-    // (bias + ADD + ReLU: BRES, compiled into the kernels the forward convolutions route to; the split kernel keeps the run-time form)
-    constexpr int BRES = LF_EPI_ADD | LF_EPI_RELU | LF_EPI_BIAS;
-    const int epis = (epi == (LF_EPI_ADD | LF_EPI_RELU) && a.bias) ? BRES
-                   : ((epi & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) && a.bias) ? -2 : epi;
-    LF_REQUIRE(!a.s16 || a.wp16, "tapgemm: bf16 tensors need the bf16 matrix-core kernel (wp16)");
-    if (a.split && a.wp48 && !a.wp16 && lf_tapgemm_split_ok(g)) {
-        LF_REQUIRE(a.split == 9, "tapgemm: split must be 9 (got %d; the 6-term form was removed in round 6)", a.split);
-        LfTapArgs b = a;
-        b.wp16 = a.wp48;
-        const dim3 grid2((unsigned)(npix / (2 * PIX_PER_WG)), g.Cd / 64);     // 512-pixel workgroups (two 4-wave groups)
-        if (a.dbg) {       // phase stamps (tools/kbench.py --phases): the plain conv only
-            LF_REQUIRE(pro == LF_PRO_NONE && epi == 0, "tapgemm: phase stamps are compiled into the plain convolution only");
-            hipLaunchKernelGGL((tapgemm_split_kernel<4, 0, 0, true>), grid2, dim3(512), 0, st, g, b, pro, epi);
-        } else {
-#define LF_TS9(PROV, EPIV) hipLaunchKernelGGL((tapgemm_split_kernel<4, PROV, EPIV>), grid2, dim3(512), 0, st, g, b, pro, epi)
-            if (pro == LF_PRO_BNRELU && epi == LF_EPI_RELU) LF_TS9(1, LF_EPI_RELU);
-            else if (pro == LF_PRO_BNRELU) LF_TS9(1, -1);
-            else switch (epis) {
-                case 0: LF_TS9(0, 0); break;
-                case LF_EPI_RELU: LF_TS9(0, LF_EPI_RELU); break;
-                case LF_EPI_MASK: LF_TS9(0, LF_EPI_MASK); break;
-                case LF_EPI_ADD: LF_TS9(0, LF_EPI_ADD); break;
-                case LF_EPI_STATS_SQ: LF_TS9(0, LF_EPI_STATS_SQ); break;
-                case LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TS9(0, LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TS9(0, LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_TS9(0, LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
-                default: LF_TS9(0, -1); break;
-            }
-#undef LF_TS9
-        }
-        LF_CHECK_LAUNCH("tapgemm_split");
+// precision mode fp32x9: fp32 tensors, the weights packed as three bf16 terms (tapgemm_split_kernel)
+int launch_split_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, int epis, long npix, hipStream_t st) {
+    LF_REQUIRE(a.split == 9, "tapgemm: split must be 9 (got %d; the 6-term form was removed in round 6)", a.split);
+    LfTapArgs b = a;
+    b.wp16 = a.wp48;
+    const dim3 grid2((unsigned)(npix / (2 * PIX_PER_WG)), g.Cd / 64);     // 512-pixel workgroups (two 4-wave groups)
+    if (a.dbg) {       // phase stamps (tools/kbench.py --phases): the plain conv only
+        LF_REQUIRE(pro == LF_PRO_NONE && epi == 0, "tapgemm: phase stamps are compiled into the plain convolution only");
+        hipLaunchKernelGGL((tapgemm_split_kernel<4, 0, 0, true>), grid2, dim3(512), 0, st, g, b, pro, epi);
+    } else {
+        with_pro_epi<false>(pro, epi, epis, [&](auto p, auto e) {
+            hipLaunchKernelGGL((tapgemm_split_kernel<4, decltype(p)::value, decltype(e)::value>), grid2, dim3(512), 0, st, g, b, pro, epi);
+        });
+    }
+    LF_CHECK_LAUNCH("tapgemm_split");
+    return 0;
+}
+
+// the streaming tapgemm_bf16_kernel (FAST: its whole-step forms, see there); _rt: the run-time-flag form of an output slab width
+template <int NTV, int PROV, int EPIV = -1, bool FAST = false>
+void launch_bf16_stream(dim3 grid, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
+    hipLaunchKernelGGL((tapgemm_bf16_kernel<NTV, PROV, EPIV, FAST>), grid, dim3(256), 0, st, g, a, pro, epi);
+}
+template <int NTV>
+void launch_bf16_stream_rt(dim3 grid, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
+    if (pro == LF_PRO_BNRELU) launch_bf16_stream<NTV, 1>(grid, st, g, a, pro, epi);
+    else launch_bf16_stream<NTV, 0>(grid, st, g, a, pro, epi);
+}
+
+// precision mode bf16: bf16 tensors on the bf16 matrix cores
+int launch_bf16_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, int epis, long npix, int nt, dim3 grid, hipStream_t st) {
+    LF_REQUIRE(a.s16, "tapgemm: the bf16 matrix-core kernels take bf16 tensors (s16); bf16 operands on fp32 tensors were removed in round 6");
+    LF_REQUIRE(g.Cs >= 8 && g.s_pix >= g.s_choff + 8, "tapgemm bf16: needs at least 8 source channels");
+    const bool in_offsets = (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB;    // the bf16 source inside 32-bit byte offsets
+    // the 16 -> 16 channel 3-tap convolutions on bf16 tensors: tapgemm_bf16_lean_kernel
+    if (a.s16 && g_bf16_lds >= 3 && !a.dbg && g.Cs == 16 && g.Cd == 16 && g.ntaps == 3 && g.Wl % 16 == 0 && g.s_pix % 8 == 0 && g.s_choff % 8 == 0 && in_offsets) {
+        with_epi<true>(epis, [&](auto e) {
+            constexpr int E = decltype(e)::value;
+            if (pro == LF_PRO_BNRELU) hipLaunchKernelGGL((tapgemm_bf16_lean_kernel<1, E>), grid, dim3(256), 0, st, g, a, pro, epi);
+            else hipLaunchKernelGGL((tapgemm_bf16_lean_kernel<0, E>), grid, dim3(256), 0, st, g, a, pro, epi);
+        });
+        if (epis == BRES) ++g_bres_launches;
+        LF_CHECK_LAUNCH("tapgemm_bf16_lean");
         return 0;
     }
-    LF_REQUIRE(!a.s16 || (g.s_pix % 8 == 0 && g.s_choff % 8 == 0), "tapgemm: bf16 source layout must be 16-byte aligned per pixel");
-    if (a.wp16) {
-#define LF_TG16(NTV)                                                                                                     \
-    do {                                                                                                                 \
-        if (pro == LF_PRO_BNRELU) hipLaunchKernelGGL((tapgemm_bf16_kernel<NTV, 1>), grid, dim3(256), 0, st, g, a, pro, epi); \
-        else hipLaunchKernelGGL((tapgemm_bf16_kernel<NTV, 0>), grid, dim3(256), 0, st, g, a, pro, epi);                  \
-    } while (0)
-        LF_REQUIRE(a.s16, "tapgemm: the bf16 matrix-core kernels take bf16 tensors (s16); bf16 operands on fp32 tensors were removed in round 6");
-        LF_REQUIRE(g.Cs >= 8 && g.s_pix >= g.s_choff + 8, "tapgemm bf16: needs at least 8 source channels");
-#define LF_TG16F(EPIV) hipLaunchKernelGGL((tapgemm_bf16_kernel<4, 0, EPIV, true>), grid, dim3(256), 0, st, g, a, pro, epi)
-        // the 16 -> 16 channel 3-tap convolutions on bf16 tensors: tapgemm_bf16_lean_kernel
-        if (a.s16 && g_bf16_lds >= 3 && !a.dbg && g.Cs == 16 && g.Cd == 16 && g.ntaps == 3 && g.Wl % 16 == 0 && g.s_pix % 8 == 0 && g.s_choff % 8 == 0 &&
-            (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB) {
-#define LF_TGL(EPIV) do { if (pro == LF_PRO_BNRELU) hipLaunchKernelGGL((tapgemm_bf16_lean_kernel<1, EPIV>), grid, dim3(256), 0, st, g, a, pro, epi); \
-                          else hipLaunchKernelGGL((tapgemm_bf16_lean_kernel<0, EPIV>), grid, dim3(256), 0, st, g, a, pro, epi); } while (0)
-            switch (epis) {
-                case 0: LF_TGL(0); break;
-                case LF_EPI_RELU: LF_TGL(LF_EPI_RELU); break;
-                case LF_EPI_MASK: LF_TGL(LF_EPI_MASK); break;
-                case LF_EPI_ADD: LF_TGL(LF_EPI_ADD); break;
-                case LF_EPI_STATS_SQ: LF_TGL(LF_EPI_STATS_SQ); break;
-                case LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TGL(LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TGL(LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_TGL(LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
-                case BRES: LF_TGL(BRES); ++g_bres_launches; break;
-                default: LF_TGL(-1); break;
-            }
-#undef LF_TGL
-            LF_CHECK_LAUNCH("tapgemm_bf16_lean");
+    const bool fast16 = nt == 4 && a.s16 && pro != LF_PRO_BNRELU && g.Cs % 32 == 0 && in_offsets;
+    // Which kernel (g_bf16_lds = 4, the shipped setting): the 3-tap convolutions of non_bottleneck_1d at 64 / 128 channels ->
+    // tapgemm_bf16_wl_kernel (whole lines); every other prologue-free launch at 64-channel output slabs whose 16-pixel groups lie
+    // in one image row (the 9-tap stride-2 convolution, the transposed-convolution phases, their gradients) ->
+    // tapgemm_bf16_ring_kernel; the rest (operand prologue, ragged widths) -> the streaming tapgemm_bf16_kernel
+    // the block's third convolution (BN+ReLU operand prologue), at 128 channels: 83 -> 60 us per launch at config 3's size; at 64
+    // channels the in-LDS transform is as long as the whole step (88 -> 91 us): those stay on the streaming kernel
+    const bool fast16p = nt == 4 && a.s16 && pro == LF_PRO_BNRELU && epi == LF_EPI_RELU && g.Cs == 128 && in_offsets;
+    const bool line3 = g_bf16_lds >= 3 && !a.dbg && g.ntaps == 3 && g.Cs == g.Cd && (g.Cd == 64 || g.Cd == 128) && g.Wl % 16 == 0 &&
+                       g.ssh == 1 && g.ssw == 1 && g.dsh == 1 && g.dsw == 1 && g.dah == 0 && g.daw == 0 && g.Hs == g.Hl && g.Ws == g.Wl &&
+                       g.Hd == g.Hl && g.Wd == g.Wl && g.s_pix % 8 == 0 && g.s_choff % 8 == 0 && g.d_pix % 8 == 0 && g.d_choff % 8 == 0 &&
+                       (long)g.N * g.Hd * g.Wd * g.d_pix * 2 < (long)LF_OOB;
+    // 64 channels (g_bf16_lds = 4, shipped): tapgemm_bf16_wv_kernel -- a wave owns its pixels and all 64 output channels; 3 = the
+    // whole-line kernel for both channel counts (round 5's routing, kept for A/B runs: tools/bf16_ab.py)
+    const bool wv = line3 && g_bf16_lds == 4 && g.Cd == 64 && fast16;
+    const bool wl = line3 && (fast16 || fast16p);      // (also what the wave-private kernel declines)
+    const unsigned ntiles = (unsigned)lf_cdiv(npix, PIX_PER_WG);
+    if (wv) {
+        const bool launched = with_epi<true>(epis, [&](auto e) {
+            constexpr int E = decltype(e)::value;
+            // (ADD + MASK + BN-backward sums: two staged operand tiles leave room for ONE workgroup per CU here -- 123.6 us in config
+            // 3's step against 115.8 us on the whole-line kernel, which takes these launches: not compiled, `launched` stays false)
+            if constexpr (E == (LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT)) return false;
+            else return launch_bf16_wv<E>(ntiles, st, g, a, pro, epi);
+        });
+        if (launched) {
+            if (epis == BRES) ++g_bres_launches;
+            LF_CHECK_LAUNCH("tapgemm_bf16_wv");
             return 0;
         }
-        const bool fast16 = nt == 4 && a.s16 && pro != LF_PRO_BNRELU && g.Cs % 32 == 0 &&
-                            (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB;
-        // Which kernel (g_bf16_lds = 4, the shipped setting): the 3-tap convolutions of non_bottleneck_1d at 64 / 128 channels ->
-        // tapgemm_bf16_wl_kernel (whole lines); every other prologue-free launch at 64-channel output slabs whose 16-pixel groups lie
-        // in one image row (the 9-tap stride-2 convolution, the transposed-convolution phases, their gradients) ->
-        // tapgemm_bf16_ring_kernel; the rest (operand prologue, ragged widths) -> the streaming tapgemm_bf16_kernel
-        // the block's third convolution (BN+ReLU operand prologue), at 128 channels: 83 -> 60 us per launch at config 3's size; at 64
-        // channels the in-LDS transform is as long as the whole step (88 -> 91 us): those stay on the streaming kernel
-        const bool fast16p = nt == 4 && a.s16 && pro == LF_PRO_BNRELU && epi == LF_EPI_RELU && g.Cs == 128 &&
-                             (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB;
-        const bool line3 = g_bf16_lds >= 3 && !a.dbg && g.ntaps == 3 && g.Cs == g.Cd && (g.Cd == 64 || g.Cd == 128) && g.Wl % 16 == 0 &&
-                           g.ssh == 1 && g.ssw == 1 && g.dsh == 1 && g.dsw == 1 && g.dah == 0 && g.daw == 0 && g.Hs == g.Hl && g.Ws == g.Wl &&
-                           g.Hd == g.Hl && g.Wd == g.Wl && g.s_pix % 8 == 0 && g.s_choff % 8 == 0 && g.d_pix % 8 == 0 && g.d_choff % 8 == 0 &&
-                           (long)g.N * g.Hd * g.Wd * g.d_pix * 2 < (long)LF_OOB;
-        // 64 channels (g_bf16_lds = 4, shipped): tapgemm_bf16_wv_kernel -- a wave owns its pixels and all 64 output channels; 3 = the
-        // whole-line kernel for both channel counts (round 5's routing, kept for A/B runs: tools/bf16_ab.py)
-        const bool wv = line3 && g_bf16_lds == 4 && g.Cd == 64 && fast16;
-        const bool wl = line3 && (fast16 || fast16p);      // (also what the wave-private kernel declines)
-        if (wv) {
-            const unsigned ntiles = (unsigned)lf_cdiv(npix, PIX_PER_WG);
-            bool launched = false;
-#define LF_TGV(EPIV) do { launched = launch_bf16_wv<EPIV>(ntiles, st, g, a, pro, epi); } while (0)
-            switch (epis) {
-                case 0: LF_TGV(0); break;
-                case LF_EPI_RELU: LF_TGV(LF_EPI_RELU); break;
-                case LF_EPI_MASK: LF_TGV(LF_EPI_MASK); break;
-                case LF_EPI_ADD: LF_TGV(LF_EPI_ADD); break;
-                case LF_EPI_STATS_SQ: LF_TGV(LF_EPI_STATS_SQ); break;
-                case LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TGV(LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                // (ADD + MASK + BN-backward sums: two staged operand tiles leave room for ONE workgroup per CU here -- 123.6 us in config
-                // 3's step against 115.8 us on the whole-line kernel, which takes these launches: `launched` stays false)
-                case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: break;
-                case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_TGV(LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
-                case BRES: LF_TGV(BRES); break;
-                default: LF_TGV(-1); break;
-            }
-#undef LF_TGV
-            if (launched) {
-                if (epis == BRES) ++g_bres_launches;
-                LF_CHECK_LAUNCH("tapgemm_bf16_wv");
-                return 0;
-            }
-        }
-        if (wl && fast16p) {        // (128 channels only)
-            if (launch_bf16_wl<4, LF_EPI_RELU, 1>((unsigned)lf_cdiv(npix, PIX_PER_WG), st, g, a, pro, epi)) {
-                LF_CHECK_LAUNCH("tapgemm_bf16_wl (prologue)");
-                return 0;
-            }
-        } else if (wl) {
-            const unsigned nitems = (unsigned)lf_cdiv(npix, PIX_PER_WG);
-            bool launched = false;
-#define LF_TGW(EPIV) do { launched = g.Cs == 128 ? launch_bf16_wl<4, EPIV>(nitems, st, g, a, pro, epi) : launch_bf16_wl<2, EPIV>(nitems, st, g, a, pro, epi); } while (0)
-            switch (epis) {
-                case 0: LF_TGW(0); break;
-                case LF_EPI_RELU: LF_TGW(LF_EPI_RELU); break;
-                case LF_EPI_MASK: LF_TGW(LF_EPI_MASK); break;
-                case LF_EPI_ADD: LF_TGW(LF_EPI_ADD); break;
-                case LF_EPI_STATS_SQ: LF_TGW(LF_EPI_STATS_SQ); break;
-                case LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TGW(LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TGW(LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_TGW(LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
-                case BRES: LF_TGW(BRES); break;
-                default: LF_TGW(-1); break;
-            }
-#undef LF_TGW
-            if (launched) {
-                if (epis == BRES) ++g_bres_launches;
-                LF_CHECK_LAUNCH("tapgemm_bf16_wl");
-                return 0;
-            }
-        }
-        // compiled-in whole-step forms at Cs % 32 != 0 (below): their tap table has one row per (tap, step)
-        const bool part_fast = !g_bf16_no_partial_fast && g.ntaps * ((g.Cs + 31) / 32) <= LF_MAX_TAPS;
-        const bool ring = fast16 && g_bf16_lds >= 2 && g.Wl % 16 == 0 && g.Cd % 64 == 0;
-        const unsigned nitems = (unsigned)(lf_cdiv(npix, PIX_PER_WG) * (g.Cd / 64));
-        if (ring && a.dbg) {        // stamps (tools/kbench.py --phases16): the plain convolution only
-            LF_REQUIRE(epis == 0, "tapgemm bf16 ring: stamps are compiled into the plain convolution only");
-            launch_bf16_ring<0, true>(nitems, st, g, a, pro, epi);
-        } else
-        if (ring) {
-#define LF_TGR(EPIV) launch_bf16_ring<EPIV>(nitems, st, g, a, pro, epi)
-            switch (epis) {
-                case 0: LF_TGR(0); break;
-                case LF_EPI_RELU: LF_TGR(LF_EPI_RELU); break;
-                case LF_EPI_MASK: LF_TGR(LF_EPI_MASK); break;
-                case LF_EPI_ADD: LF_TGR(LF_EPI_ADD); break;
-                case LF_EPI_STATS_SQ: LF_TGR(LF_EPI_STATS_SQ); break;
-                case LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TGR(LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TGR(LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_TGR(LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
-                default: LF_TGR(-1); break;
-            }
-#undef LF_TGR
-        } else if (fast16) {       // the bf16-tensor launches of the network at 64 output channels per workgroup
-            switch (epis) {
-                case 0: LF_TG16F(0); break;
-                case LF_EPI_RELU: LF_TG16F(LF_EPI_RELU); break;
-                case LF_EPI_MASK: LF_TG16F(LF_EPI_MASK); break;
-                case LF_EPI_ADD: LF_TG16F(LF_EPI_ADD); break;
-                case LF_EPI_STATS_SQ: LF_TG16F(LF_EPI_STATS_SQ); break;
-                case LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TG16F(LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TG16F(LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_TG16F(LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
-                default: LF_TG16F(-1); break;
-            }
-        } else if (nt == 4 && a.s16 && pro != LF_PRO_BNRELU && g.Cs == 16 && (epis == (LF_EPI_MASK | LF_EPI_STATS_XHAT) || epis == 0) && part_fast &&
-                   (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB) {
-            // 16 source channels into a 64-channel slab (the data gradient of UpsamplerBlock(64, 16): 9 taps, stride 2, with the previous
-            // layer's mask + BN-backward sums; 204 us per launch at config 3 on the run-time-flag form): ONE 32-channel step per tap on the
-            // compiled-in form.  Lanes kq = 2, 3 -- channels 16..31 of the step, which the pixel does not have -- hold the out-of-range
-            // offset and read the buffer bound's zeros against the zero-padded half of the packed weights
-            if (epis == 0) LF_TG16F(0); else LF_TG16F(LF_EPI_MASK | LF_EPI_STATS_XHAT);
-            ++g_part_fast_launches;
-        } else if (nt == 3 && a.s16 && pro != LF_PRO_BNRELU && g.Cs == 16 && (epis == LF_EPI_STATS_SQ || epis == LF_EPI_RELU || epis == 0) && part_fast &&
-                   (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB) {
-            // ... and the 16 -> 48 channel convolution of DownsamplerBlock(16, 64) (9 taps, stride 2, BN forward sums; 112 us on the run-time-flag form)
-            // (RELU: the inference engine's folded form of the same convolution)
-            if (epis == 0) hipLaunchKernelGGL((tapgemm_bf16_kernel<3, 0, 0, true>), grid, dim3(256), 0, st, g, a, pro, epi);
-            else if (epis == LF_EPI_RELU) hipLaunchKernelGGL((tapgemm_bf16_kernel<3, 0, LF_EPI_RELU, true>), grid, dim3(256), 0, st, g, a, pro, epi);
-            else hipLaunchKernelGGL((tapgemm_bf16_kernel<3, 0, LF_EPI_STATS_SQ, true>), grid, dim3(256), 0, st, g, a, pro, epi);
-            ++g_part_fast_launches;
-        } else if (nt == 4 && a.s16 && pro == LF_PRO_BNRELU && epi == LF_EPI_RELU) {
-            hipLaunchKernelGGL((tapgemm_bf16_kernel<4, 1, LF_EPI_RELU, false>), grid, dim3(256), 0, st, g, a, pro, epi);
-        } else if (nt == 1 && a.s16 && pro != LF_PRO_BNRELU && ((g.Cs + 31) / 32 * 32 + g.s_choff <= g.s_pix) && (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB &&
-                   (g.Cs % 32 == 0 || part_fast) &&
-                   (epis == 0 || epis == LF_EPI_STATS_SQ || epis == LF_EPI_ADD || epis == LF_EPI_RELU)) {
-            // 16 output channels from whole 32-channel steps (round 6: the sub-pixel phases of UpsamplerBlock(64, 16) and the data gradient
-            // of DownsamplerBlock(16, 64)'s convolution: 8 launches per step on the run-time-flag form before): padding as out-of-range
-            // offsets, compiled-in epilogue.  In a partial last step (48 source channels) the lanes of channels 48..63 hold the out-of-range
-            // offset too: zeros against the zero-padded weights, not the pixel's next channels (another tensor's slice)
-            if (epis == 0) hipLaunchKernelGGL((tapgemm_bf16_kernel<1, 0, 0, true>), grid, dim3(256), 0, st, g, a, pro, epi);
-            else if (epis == LF_EPI_STATS_SQ) hipLaunchKernelGGL((tapgemm_bf16_kernel<1, 0, LF_EPI_STATS_SQ, true>), grid, dim3(256), 0, st, g, a, pro, epi);
-            else if (epis == LF_EPI_RELU) hipLaunchKernelGGL((tapgemm_bf16_kernel<1, 0, LF_EPI_RELU, true>), grid, dim3(256), 0, st, g, a, pro, epi);   // (inference: folded phases)
-            else hipLaunchKernelGGL((tapgemm_bf16_kernel<1, 0, LF_EPI_ADD, true>), grid, dim3(256), 0, st, g, a, pro, epi);
-            if (g.Cs % 32 != 0) ++g_part_fast_launches;
-        } else
-        switch (nt) {
-            case 4: LF_TG16(4); break;
-            case 3: LF_TG16(3); break;
-            case 2: LF_TG16(2); break;
-            default: LF_TG16(1); break;
-        }
-#undef LF_TG16
-#undef LF_TG16F
-        LF_CHECK_LAUNCH("tapgemm_bf16");
-        return 0;
     }
+    if (wl && fast16p) {        // (128 channels only)
+        if (launch_bf16_wl<4, LF_EPI_RELU, 1>(ntiles, st, g, a, pro, epi)) {
+            LF_CHECK_LAUNCH("tapgemm_bf16_wl (prologue)");
+            return 0;
+        }
+    } else if (wl) {
+        const bool launched = with_epi<true>(epis, [&](auto e) {
+            constexpr int E = decltype(e)::value;
+            return g.Cs == 128 ? launch_bf16_wl<4, E>(ntiles, st, g, a, pro, epi) : launch_bf16_wl<2, E>(ntiles, st, g, a, pro, epi);
+        });
+        if (launched) {
+            if (epis == BRES) ++g_bres_launches;
+            LF_CHECK_LAUNCH("tapgemm_bf16_wl");
+            return 0;
+        }
+    }
+    // compiled-in whole-step forms at Cs % 32 != 0 (below): their tap table has one row per (tap, step)
+    const bool part_fast = !g_bf16_no_partial_fast && g.ntaps * ((g.Cs + 31) / 32) <= LF_MAX_TAPS;
+    const bool ring = fast16 && g_bf16_lds >= 2 && g.Wl % 16 == 0 && g.Cd % 64 == 0;
+    const unsigned nitems = ntiles * (unsigned)(g.Cd / 64);
+    if (ring && a.dbg) {        // stamps (tools/kbench.py --phases16): the plain convolution only
+        LF_REQUIRE(epis == 0, "tapgemm bf16 ring: stamps are compiled into the plain convolution only");
+        launch_bf16_ring<0, true>(nitems, st, g, a, pro, epi);
+    } else if (ring) {
+        with_epi<false>(epis, [&](auto e) { launch_bf16_ring<decltype(e)::value>(nitems, st, g, a, pro, epi); });
+    } else if (fast16) {       // the bf16-tensor launches of the network at 64 output channels per workgroup
+        with_epi<false>(epis, [&](auto e) { launch_bf16_stream<4, 0, decltype(e)::value, true>(grid, st, g, a, pro, epi); });
+    } else if (nt == 4 && a.s16 && pro != LF_PRO_BNRELU && g.Cs == 16 && (epis == (LF_EPI_MASK | LF_EPI_STATS_XHAT) || epis == 0) && part_fast && in_offsets) {
+        // 16 source channels into a 64-channel slab (the data gradient of UpsamplerBlock(64, 16): 9 taps, stride 2, with the previous
+        // layer's mask + BN-backward sums; 204 us per launch at config 3 on the run-time-flag form): ONE 32-channel step per tap on the
+        // compiled-in form.  Lanes kq = 2, 3 -- channels 16..31 of the step, which the pixel does not have -- hold the out-of-range
+        // offset and read the buffer bound's zeros against the zero-padded half of the packed weights
+        if (epis == 0) launch_bf16_stream<4, 0, 0, true>(grid, st, g, a, pro, epi);
+        else launch_bf16_stream<4, 0, LF_EPI_MASK | LF_EPI_STATS_XHAT, true>(grid, st, g, a, pro, epi);
+        ++g_part_fast_launches;
+    } else if (nt == 3 && a.s16 && pro != LF_PRO_BNRELU && g.Cs == 16 && (epis == LF_EPI_STATS_SQ || epis == LF_EPI_RELU || epis == 0) && part_fast && in_offsets) {
+        // ... and the 16 -> 48 channel convolution of DownsamplerBlock(16, 64) (9 taps, stride 2, BN forward sums; 112 us on the run-time-flag form)
+        // (RELU: the inference engine's folded form of the same convolution)
+        if (epis == 0) launch_bf16_stream<3, 0, 0, true>(grid, st, g, a, pro, epi);
+        else if (epis == LF_EPI_RELU) launch_bf16_stream<3, 0, LF_EPI_RELU, true>(grid, st, g, a, pro, epi);
+        else launch_bf16_stream<3, 0, LF_EPI_STATS_SQ, true>(grid, st, g, a, pro, epi);
+        ++g_part_fast_launches;
+    } else if (nt == 4 && a.s16 && pro == LF_PRO_BNRELU && epi == LF_EPI_RELU) {
+        launch_bf16_stream<4, 1, LF_EPI_RELU, false>(grid, st, g, a, pro, epi);
+    } else if (nt == 1 && a.s16 && pro != LF_PRO_BNRELU && ((g.Cs + 31) / 32 * 32 + g.s_choff <= g.s_pix) && in_offsets &&
+               (g.Cs % 32 == 0 || part_fast) &&
+               (epis == 0 || epis == LF_EPI_STATS_SQ || epis == LF_EPI_ADD || epis == LF_EPI_RELU)) {
+        // 16 output channels from whole 32-channel steps (round 6: the sub-pixel phases of UpsamplerBlock(64, 16) and the data gradient
+        // of DownsamplerBlock(16, 64)'s convolution: 8 launches per step on the run-time-flag form before): padding as out-of-range
+        // offsets, compiled-in epilogue.  In a partial last step (48 source channels) the lanes of channels 48..63 hold the out-of-range
+        // offset too: zeros against the zero-padded weights, not the pixel's next channels (another tensor's slice)
+        if (epis == 0) launch_bf16_stream<1, 0, 0, true>(grid, st, g, a, pro, epi);
+        else if (epis == LF_EPI_STATS_SQ) launch_bf16_stream<1, 0, LF_EPI_STATS_SQ, true>(grid, st, g, a, pro, epi);
+        else if (epis == LF_EPI_RELU) launch_bf16_stream<1, 0, LF_EPI_RELU, true>(grid, st, g, a, pro, epi);   // (inference: folded phases)
+        else launch_bf16_stream<1, 0, LF_EPI_ADD, true>(grid, st, g, a, pro, epi);
+        if (g.Cs % 32 != 0) ++g_part_fast_launches;
+    } else {
+        switch (nt) {
+            case 4: launch_bf16_stream_rt<4>(grid, st, g, a, pro, epi); break;
+            case 3: launch_bf16_stream_rt<3>(grid, st, g, a, pro, epi); break;
+            case 2: launch_bf16_stream_rt<2>(grid, st, g, a, pro, epi); break;
+            default: launch_bf16_stream_rt<1>(grid, st, g, a, pro, epi); break;
+        }
+    }
+    LF_CHECK_LAUNCH("tapgemm_bf16");
+    return 0;
+}
+
+// the run-time-flag tapgemm_kernel of the output slab widths below 64 channels
+template <int NTV>
+void launch_tapgemm_rt(dim3 grid, size_t tap_lds, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
+    if (pro == LF_PRO_BNRELU) launch_tapgemm(tapgemm_kernel<NTV, 1>, grid, tap_lds, st, g, a, pro, epi);
+    else launch_tapgemm(tapgemm_kernel<NTV, 0>, grid, tap_lds, st, g, a, pro, epi);
+}
+
+// precision mode fp32 (and the fp32x9 launches the split kernel does not take): fp32 tensors on the fp32 matrix cores
+int launch_fp32_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, int epis, int nt, dim3 grid, hipStream_t st) {
+    const size_t tap_lds = LF_TAP_LDS_PER_TAP * g.ntaps;
     if (a.dbg) {           // phase stamps (tools/kbench.py --phases): the plain 64-channel-slab convolution only
         LF_REQUIRE(nt == 4 && pro == LF_PRO_NONE && epi == 0 && !a.wp16, "tapgemm: phase stamps are compiled into the plain fp32 convolution only");
         if ((g.Wl & 63) == 0) hipLaunchKernelGGL((tapgemm_kernel<4, 0, 0, true, true>), grid, dim3(256), tap_lds, st, g, a, pro, epi);
@@ -2736,48 +2666,54 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
     }
     switch (nt) {
         case 4:
-            if (pro == LF_PRO_BNRELU && epi == LF_EPI_RELU) LF_TG4(1, LF_EPI_RELU);
-            else if (pro == LF_PRO_BNRELU) LF_TG4(1, -1);
-            else switch (epis) {
-                case 0: LF_TG4(0, 0); break;
-                case LF_EPI_RELU: LF_TG4(0, LF_EPI_RELU); break;
-                case LF_EPI_MASK: LF_TG4(0, LF_EPI_MASK); break;
-                case LF_EPI_ADD: LF_TG4(0, LF_EPI_ADD); break;
-                case LF_EPI_STATS_SQ: LF_TG4(0, LF_EPI_STATS_SQ); break;
-                case LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TG4(0, LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_TG4(0, LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_TG4(0, LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
-                case BRES: LF_TG4(0, BRES); ++g_bres_launches; break;
-                default: LF_TG4(0, -1); break;
-            }
+            with_pro_epi<true>(pro, epi, epis, [&](auto p, auto e) {
+                constexpr int P = decltype(p)::value, E = decltype(e)::value;
+                if ((g.Wl & 63) == 0) launch_tapgemm(tapgemm_kernel<4, P, E, true>, grid, tap_lds, st, g, a, pro, epi);
+                else launch_tapgemm(tapgemm_kernel<4, P, E, false>, grid, tap_lds, st, g, a, pro, epi);
+                if constexpr (E == BRES) ++g_bres_launches;
+            });
             break;
-        case 3: LF_TG(3); break;
-        case 2: LF_TG(2); break;
+        case 3: launch_tapgemm_rt<3>(grid, tap_lds, st, g, a, pro, epi); break;
+        case 2: launch_tapgemm_rt<2>(grid, tap_lds, st, g, a, pro, epi); break;
         default:
-            {
-#define LF_LEAN(PROV, EPIV) hipLaunchKernelGGL((tapgemm_lean_kernel<1, PROV, EPIV>), grid, dim3(256), 0, st, g, a, pro, epi)
-                if (pro == LF_PRO_BNRELU && epi == LF_EPI_RELU) LF_LEAN(1, LF_EPI_RELU);
-                else if (pro == LF_PRO_BNRELU) LF_LEAN(1, -1);
-                else switch (epis) {
-                    case 0: LF_LEAN(0, 0); break;
-                    case LF_EPI_RELU: LF_LEAN(0, LF_EPI_RELU); break;
-                    case LF_EPI_MASK: LF_LEAN(0, LF_EPI_MASK); break;
-                    case LF_EPI_ADD: LF_LEAN(0, LF_EPI_ADD); break;
-                    case LF_EPI_STATS_SQ: LF_LEAN(0, LF_EPI_STATS_SQ); break;
-                    case LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_LEAN(0, LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                    case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: LF_LEAN(0, LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT); break;
-                    case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: LF_LEAN(0, LF_EPI_MASKBN | LF_EPI_STATS_XHAT); break;
-                    case BRES: LF_LEAN(0, BRES); ++g_bres_launches; break;
-                    default: LF_LEAN(0, -1); break;
-                }
-#undef LF_LEAN
-            }
+            with_pro_epi<true>(pro, epi, epis, [&](auto p, auto e) {
+                constexpr int P = decltype(p)::value, E = decltype(e)::value;
+                hipLaunchKernelGGL((tapgemm_lean_kernel<1, P, E>), grid, dim3(256), 0, st, g, a, pro, epi);
+                if constexpr (E == BRES) ++g_bres_launches;
+            });
             break;
     }
-#undef LF_TG
-#undef LF_TG4
     LF_CHECK_LAUNCH("tapgemm");
     return 0;
+}
+}  // namespace
+
+void lf_tapgemm_set_fp32_stream(int mode, int max_workgroups) { g_stream_mode = mode; g_stream_cap = max_workgroups > 0 ? max_workgroups : 0; }
+
+int lf_tapgemm_launch_unordered(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, hipStream_t st) {
+    g_launch_flags = hipExtAnyOrderLaunch;
+    const int rc = lf_tapgemm_launch(g, a, pro, epi, st);
+    g_launch_flags = 0;
+    return rc;
+}
+
+int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, hipStream_t st) {
+    LF_REQUIRE(g.Cs % 16 == 0 && g.Cd % 16 == 0, "tapgemm: channels must be multiples of 16 (Cs=%d Cd=%d)", g.Cs, g.Cd);
+    LF_REQUIRE(g.s_pix % 4 == 0 && g.s_choff % 4 == 0 && g.d_pix % 4 == 0 && g.d_choff % 4 == 0, "tapgemm: unaligned channel layout");
+    LF_REQUIRE(g.ntaps >= 1 && g.ntaps <= LF_MAX_TAPS, "tapgemm: bad tap count %d", g.ntaps);
+    const long npix = (long)g.N * g.Hl * g.Wl;
+    LF_REQUIRE(npix < (1L << 30), "tapgemm: too many pixels (%ld)", npix);
+    const int nt = pick_nt(g.Cd);
+    const dim3 grid(lf_cdiv(npix, PIX_PER_WG), g.Cd / (16 * nt));
+    LF_REQUIRE((long)g.N * g.Hs * g.Ws * g.s_pix * 4 < (long)LF_OOB, "tapgemm: source tensor too large for 32-bit byte offsets");
+    LF_REQUIRE((long)g.N * g.Hd * g.Wd * g.d_pix * 4 < (long)LF_OOB, "tapgemm: destination tensor too large for 32-bit byte offsets");
+    const int epis = (epi == (LF_EPI_ADD | LF_EPI_RELU) && a.bias) ? BRES             // (see BRES)
+                   : ((epi & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) && a.bias) ? -2 : epi;
+    LF_REQUIRE(!a.s16 || a.wp16, "tapgemm: bf16 tensors need the bf16 matrix-core kernel (wp16)");
+    if (a.split && a.wp48 && !a.wp16 && lf_tapgemm_split_ok(g)) return launch_split_route(g, a, pro, epi, epis, npix, st);
+    LF_REQUIRE(!a.s16 || (g.s_pix % 8 == 0 && g.s_choff % 8 == 0), "tapgemm: bf16 source layout must be 16-byte aligned per pixel");
+    if (a.wp16) return launch_bf16_route(g, a, pro, epi, epis, npix, nt, grid, st);
+    return launch_fp32_route(g, a, pro, epi, epis, nt, grid, st);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3587,6 +3523,24 @@ WgradCfg wgrad_cfg(const LfTapGeom& g) {
     return c;
 }
 
+// tapwgrad_kernel for one (vector mode, channel tiles) choice of wgrad_cfg: picks the storage type, the pixel unroll and -- where
+// both operands are in vector mode (VV) -- the bf16-MFMA form on bf16 tensors and the compiled-in prologue choice on fp32 ones.
+// (VV also compiles the two forms without either, which no launch takes: dropping them is a change of the device code)
+template <bool XV, bool GV, int XT, int GT>
+void launch_wgrad(const LfTapGeom& g, const LfWgradArgs& a, int pro, const WgradCfg& c, dim3 grid, int wb, hipStream_t st) {
+    constexpr bool VV = XV && GV;
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, g, a, pro, c.pps, wb, c.gx); };
+    if (a.s16 && c.u == 4 && VV) go(tapwgrad_kernel<XV, GV, XT, GT, 4, true, VV>);
+    else if (a.s16 && c.u == 4) go(tapwgrad_kernel<XV, GV, XT, GT, 4, true>);
+    else if (a.s16) go(tapwgrad_kernel<XV, GV, XT, GT, 1, true>);
+    else if (c.u == 4 && VV) {
+        if constexpr (VV) {
+            if (pro == LF_PRO_BNRELU) go(tapwgrad_kernel<XV, GV, XT, GT, 4, false, false, 1>);
+            else go(tapwgrad_kernel<XV, GV, XT, GT, 4, false, false, 0>);
+        }
+    } else if (c.u == 4) go(tapwgrad_kernel<XV, GV, XT, GT, 4, false>);
+    else go(tapwgrad_kernel<XV, GV, XT, GT, 1, false>);
+}
 
 }  // namespace
 
@@ -3617,11 +3571,14 @@ int lf_tapwgrad_launch(const LfTapGeom& g, const LfWgradArgs& a, int pro, hipStr
         const size_t ring_lds = (size_t)WG_WAVES * W16_STAGES * W16_STAGE;
         static_assert(W16F_STAGES * W16F_STAGE == W16_STAGES * W16_STAGE, "the two 16-channel rings share their LDS budget");
         const bool pr = pro == LF_PRO_BNRELU;
-#define LF_W16(KERN) do { if (allow_big_lds(reinterpret_cast<const void*>(KERN), 128 * 1024)) { hipLaunchKernelGGL(KERN, dim3(c.gx), dim3(256), ring_lds, st, g, a, c.pps, wb); launched = true; } } while (0)
+        auto ring = [&](auto kern) {
+            if (!allow_big_lds(reinterpret_cast<const void*>(kern), 128 * 1024)) return false;
+            hipLaunchKernelGGL(kern, dim3(c.gx), dim3(256), ring_lds, st, g, a, c.pps, wb);
+            return true;
+        };
         bool launched = false;
-        if (ring_ok && a.s16) { if (pr) LF_W16(tapwgrad16_tr_kernel<true>); else LF_W16(tapwgrad16_tr_kernel<false>); }
-        else if (ring_ok) { if (pr) LF_W16(tapwgrad16_f32_kernel<true>); else LF_W16(tapwgrad16_f32_kernel<false>); }
-#undef LF_W16
+        if (ring_ok && a.s16) launched = pr ? ring(tapwgrad16_tr_kernel<true>) : ring(tapwgrad16_tr_kernel<false>);
+        else if (ring_ok) launched = pr ? ring(tapwgrad16_f32_kernel<true>) : ring(tapwgrad16_f32_kernel<false>);
         if (!launched) {           // (attribute refused, unaligned channel layout): the one-element-per-lane kernel
             if (a.s16) hipLaunchKernelGGL((tapwgrad16_kernel<3, true>), dim3(c.gx), dim3(256), 0, st, g, a, pro, c.pps, wb);
             else hipLaunchKernelGGL((tapwgrad16_kernel<3, false>), dim3(c.gx), dim3(256), 0, st, g, a, pro, c.pps, wb);
@@ -3636,26 +3593,15 @@ int lf_tapwgrad_launch(const LfTapGeom& g, const LfWgradArgs& a, int pro, hipStr
         LF_CHECK_LAUNCH("tapwgrad (stamps)");
         return 0;
     }
-#define LF_WG(XV, GV, XT, GT)                                                                                     \
-    do {                                                                                                          \
-        if (a.s16 && c.u == 4 && XV && GV) hipLaunchKernelGGL((tapwgrad_kernel<XV, GV, XT, GT, 4, true, (XV && GV)>), grid, dim3(256), 0, st, g, a, pro, c.pps, wb, c.gx); \
-        else if (a.s16 && c.u == 4) hipLaunchKernelGGL((tapwgrad_kernel<XV, GV, XT, GT, 4, true>), grid, dim3(256), 0, st, g, a, pro, c.pps, wb, c.gx); \
-        else if (a.s16) hipLaunchKernelGGL((tapwgrad_kernel<XV, GV, XT, GT, 1, true>), grid, dim3(256), 0, st, g, a, pro, c.pps, wb, c.gx);   \
-        else if (c.u == 4 && XV && GV && pro == LF_PRO_BNRELU) hipLaunchKernelGGL((tapwgrad_kernel<XV, GV, XT, GT, 4, false, false, (XV && GV) ? 1 : -1>), grid, dim3(256), 0, st, g, a, pro, c.pps, wb, c.gx); \
-        else if (c.u == 4 && XV && GV) hipLaunchKernelGGL((tapwgrad_kernel<XV, GV, XT, GT, 4, false, false, (XV && GV) ? 0 : -1>), grid, dim3(256), 0, st, g, a, pro, c.pps, wb, c.gx); \
-        else if (c.u == 4) hipLaunchKernelGGL((tapwgrad_kernel<XV, GV, XT, GT, 4, false>), grid, dim3(256), 0, st, g, a, pro, c.pps, wb, c.gx); \
-        else hipLaunchKernelGGL((tapwgrad_kernel<XV, GV, XT, GT, 1, false>), grid, dim3(256), 0, st, g, a, pro, c.pps, wb, c.gx);  \
-    } while (0)
-    if (c.xv && c.gv) LF_WG(true, true, 4, 4);
-    else if (c.xv && c.gt == 1) LF_WG(true, false, 4, 1);
-    else if (c.xv && c.gt == 3) LF_WG(true, false, 4, 3);
-    else if (!c.xv && c.xt == 1 && c.gv) LF_WG(false, true, 1, 4);
-    else if (!c.xv && c.xt == 1 && c.gt == 1) LF_WG(false, false, 1, 1);
-    else if (!c.xv && c.xt == 1 && c.gt == 3) LF_WG(false, false, 1, 3);
-    else if (!c.xv && c.xt == 3 && c.gt == 1) LF_WG(false, false, 3, 1);
-    else if (!c.xv && c.xt == 3 && c.gv) LF_WG(false, true, 3, 4);
+    if (c.xv && c.gv) launch_wgrad<true, true, 4, 4>(g, a, pro, c, grid, wb, st);
+    else if (c.xv && c.gt == 1) launch_wgrad<true, false, 4, 1>(g, a, pro, c, grid, wb, st);
+    else if (c.xv && c.gt == 3) launch_wgrad<true, false, 4, 3>(g, a, pro, c, grid, wb, st);
+    else if (!c.xv && c.xt == 1 && c.gv) launch_wgrad<false, true, 1, 4>(g, a, pro, c, grid, wb, st);
+    else if (!c.xv && c.xt == 1 && c.gt == 1) launch_wgrad<false, false, 1, 1>(g, a, pro, c, grid, wb, st);
+    else if (!c.xv && c.xt == 1 && c.gt == 3) launch_wgrad<false, false, 1, 3>(g, a, pro, c, grid, wb, st);
+    else if (!c.xv && c.xt == 3 && c.gt == 1) launch_wgrad<false, false, 3, 1>(g, a, pro, c, grid, wb, st);
+    else if (!c.xv && c.xt == 3 && c.gv) launch_wgrad<false, true, 3, 4>(g, a, pro, c, grid, wb, st);
     else return lf_fail("tapwgrad: unsupported channel combination Cs=%d Cd=%d", g.Cs, g.Cd);
-#undef LF_WG
     LF_CHECK_LAUNCH("tapwgrad");
     return 0;
 }
