@@ -45,7 +45,10 @@ extern "C" {
                                  additions since 5 (BEV lane decoding): lf_lane_decode_bev;
                                  additions since 5 (segmentation-mode step criterion): lf_seg_step, lf_seg_step_workspace_bytes,
                                  lf_seg_step_bwd;
-                                 additions since 5 (resident dataset's label batch): lf_label_batch_bp, lf_label_batch_bev */
+                                 additions since 5 (resident dataset's label batch): lf_label_batch_bp, lf_label_batch_bev;
+                                 additions since 5 (gradient-norm clipping): lf_grad_norm_workspace_bytes, lf_grad_sumsq,
+                                 lf_grad_norm_finish, lf_grad_scale_inplace, lf_adam_step_clipped, lf_sgd_step_clipped,
+                                 lf_rmsprop_step_clipped */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -367,6 +370,37 @@ int lf_sgd_step(const void* tensors_dev, const void* work_dev, int nblocks, floa
                 float grad_scale, void* stream);
 int lf_rmsprop_step(const void* tensors_dev, const void* work_dev, int nblocks, float lr, float alpha, float eps,
                     float momentum, float weight_decay, float grad_scale, void* stream);
+
+/* additions since 5 -- gradient-norm clipping: nn.utils.clip_grad_norm(model.parameters(), args.clip_grad_norm) between
+ * loss.backward() and optimizer.step() (BP/main.py:334-335) as ONE read of the gradients plus a scalar in device memory that the
+ * step picks up; the host never waits.  All entry points take the record / work tables of lf_adam_step.
+ *   lf_grad_sumsq: one workgroup per work item adds the squares of its gradient elements -- each widened to fp64 before it is
+ *     squared, so 1e30 does not overflow -- and writes one fp64 partial to workspace slot slot0 + block.  Call it once per param
+ *     group with consecutive slot ranges; workspace holds lf_grad_norm_workspace_bytes(total_blocks) bytes, 8-byte aligned.
+ *   lf_grad_norm_finish: one workgroup adds the total_blocks partials in a fixed order and writes two fp32 values,
+ *     out2[0] = total_norm = fl32(grad_scale * sqrt(sum))   (the norm of the gradients the step will use: under summed
+ *                                                            data-parallel gradients and grad_scale = 1/world, of their average),
+ *     out2[1] = coef = max_norm / (total_norm + 1e-6), replaced by 1 where that exceeds 1   (fp32, torch's clamp(max=1.0)).
+ *     No floating-point atomics anywhere: two runs on the same inputs give the same bits.
+ *   lf_grad_scale_inplace: g = fl32(fl32(g * grad_scale) * coef_dev[0]) on every element inside a tensor's numel and nowhere
+ *     else -- the drop-in form, what torch leaves in p.grad.
+ *   lf_*_step_clipped: the step of lf_*_step on the effective gradient fl32(fl32(g * grad_scale) * coef_dev[0]), two separately
+ *     rounded products; the gradients are not written.  lf_grad_scale_inplace followed by lf_*_step with grad_scale 1 leaves the
+ *     same bits.  Adam's per-tensor step counts and the parity slot work as in lf_adam_step.
+ * Non-finite gradients behave as under torch's clip_grad_norm_(error_if_nonfinite=False); there is no step skip.  An Inf gradient
+ * gives total_norm = Inf and coef = 0: every finite gradient then counts as 0 and the Inf element as NaN.  A NaN gradient gives
+ * total_norm = coef = NaN, hence NaN everywhere.  All-zero gradients give total_norm 0 and coef 1. */
+size_t lf_grad_norm_workspace_bytes(int total_blocks);
+int lf_grad_sumsq(const void* tensors_dev, const void* work_dev, int nblocks, int slot0, void* workspace, void* stream);
+int lf_grad_norm_finish(const void* workspace, int total_blocks, float grad_scale, float max_norm, float* out2, void* stream);
+int lf_grad_scale_inplace(const void* tensors_dev, const void* work_dev, int nblocks, float grad_scale, const float* coef_dev,
+                          void* stream);
+int lf_adam_step_clipped(const void* tensors_dev, const void* work_dev, int nblocks, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, int parity, float grad_scale, const float* coef_dev, void* stream);
+int lf_sgd_step_clipped(const void* tensors_dev, const void* work_dev, int nblocks, float lr, float momentum, float weight_decay,
+                        float grad_scale, const float* coef_dev, void* stream);
+int lf_rmsprop_step_clipped(const void* tensors_dev, const void* work_dev, int nblocks, float lr, float alpha, float eps,
+                            float momentum, float weight_decay, float grad_scale, const float* coef_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * "Next" row 8f-3: the `--clas` heads and the inference-side post-processing of BP/test.py.

@@ -126,6 +126,15 @@ def _declare(lib):
         "lf_seg_step_bwd": (I, [P, L, P, P]),
         "lf_label_batch_bp": (I, [P, P, P, P, P, P, P, L, P, P, I, I, P, P, P, P, P, P, P, P, P]),
         "lf_label_batch_bev": (I, [P, P, P, P, P, L, P, P, I, P, P, P, P, P, P, P]),
+        "lf_grad_norm_workspace_bytes": (c_size_t, [I]),
+        "lf_grad_sumsq": (I, [P, P, I, I, P, P]),
+        "lf_grad_norm_finish": (I, [P, I, ctypes.c_float, ctypes.c_float, P, P]),
+        "lf_grad_scale_inplace": (I, [P, P, I, ctypes.c_float, P, P]),
+        "lf_adam_step_clipped": (I, [P, P, I, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                     I, ctypes.c_float, P, P]),
+        "lf_sgd_step_clipped": (I, [P, P, I, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, P, P]),
+        "lf_rmsprop_step_clipped": (I, [P, P, I, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                        ctypes.c_float, P, P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {
