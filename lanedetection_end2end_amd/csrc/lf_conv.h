@@ -61,8 +61,10 @@ struct LfTapArgs {
     unsigned long long* dbg;  // optional: per-wave phase timestamps (s_memtime), 8 words per wave (tools/kbench.py --phases)
 };
 
+// ---- lf_conv.hip: forward and data-gradient launches, their routing switches and counters ----
 void lf_tapgemm_set_split_any_size(int v);
 void lf_tapgemm_set_bf16_lds(int v);
+int lf_tapgemm_bf16_lds();                          // the value set (the 16-channel weight gradient's LDS rings follow it: lf_wgrad.hip)
 void lf_tapgemm_set_bf16_no_partial_fast(int v);   // 1: launches with Cs % 32 != 0 decline the compiled-in whole-step forms (tests)
 long lf_tapgemm_partial_fast_launches();            // launches with Cs % 32 != 0 that took a compiled-in whole-step form since the process started (tests)
 void lf_tapgemm_set_fp32_stream(int mode, int max_workgroups);   // tapstream_kernel routing (lf_debug_set_fp32_stream, lf_debug.h)
@@ -72,7 +74,11 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
 // the same launch WITHOUT the in-order barrier on its dispatch packet (hipExtAnyOrderLaunch; fp32 tap-GEMM kernels only, the other
 // kernels launch in order): it may overlap the previous launch of the stream, which the caller guarantees to be independent of it
 int lf_tapgemm_launch_unordered(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, hipStream_t st);
+bool lf_tapgemm_split_ok(const LfTapGeom& g);
+// launches that took a compiled-in bias + residual + ReLU epilogue since the process started (kernel-level tests)
+long lf_tapgemm_bias_residual_launches();
 
+// ---- lf_wgrad.hip: weight gradients and their split-K reductions (lf_tapwgrad_ro_*: lf_wgrad_ro.hip) ----
 struct LfWgradArgs {
     const float* x;         // source-side tensor (gathered by taps), geometry = source fields of LfTapGeom
     const float* g;         // dest-side gradient tensor, geometry = dest fields
@@ -118,6 +124,7 @@ int lf_wgrad_reduce_batch_launch(const LfReduceJob* jobs_host, int njobs, hipStr
 // dst[n] (+)= sum_r rows[r][n]
 int lf_rows_reduce_launch(const float* rows, int nrows, int C, float* dst, int accumulate, hipStream_t st);
 
+// ---- lf_pack.hip: weight packing and the inference fold-and-pack ----
 // wp[((t*(Kc/4) + k/4)*Nc + n)*4 + k%4] = w[k*sk + n*sn + tapidx[t]]
 struct LfPackEntry {
     long src_off;   // float offset into the flat parameter arena / or pointer index, see lf_erfnet
@@ -134,9 +141,6 @@ long lf_pack_bf16_elems(int Kc, int Nc, int ntaps);
 // split weights: 3 bf16 pieces per element, entry e at 3 * e.dst16_off of arena48 (entries with Kc % 32 != 0 are skipped)
 int lf_pack_weights_split_launch(const LfPackEntry* entries_dev, int nentries, const float* const* params_dev, void* arena48,
                                  hipStream_t st);
-bool lf_tapgemm_split_ok(const LfTapGeom& g);
-// launches that took a compiled-in bias + residual + ReLU epilogue since the process started (kernel-level tests)
-long lf_tapgemm_bias_residual_launches();
 
 // Inference fold-and-pack (eval-mode BatchNorm folded into the convolution that feeds it), one entry per forward convolution and
 // one per per-channel affine (the max-pool channels of a down-sampler, the stem): with s = gamma / sqrt(var + eps) in fp64,

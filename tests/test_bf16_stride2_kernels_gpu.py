@@ -334,7 +334,7 @@ def test_a_non_finite_value_stays_inside_its_tap_windows(case, epi, shape, value
     48..63 of the window's own pixels did (position d).
 
     The ReLU cases ([A-epi1, B-epi1] x the first two shapes x all three values) failed a second way while the epilogue's ReLU was a
-    signed-integer maximum of the bit patterns (max0, lf_conv.hip): the matrix cores return a NaN with its sign bit set, which that
+    signed-integer maximum of the bit patterns (max0, lf_conv_dev.h): the matrix cores return a NaN with its sign bit set, which that
     maximum stores as 0 where torch.relu keeps the NaN -- 0 non-finite pixels where 1-2 are expected, with a planted NaN at every
     position and with +-Inf at position b (channel 9) on the run-time-flag form, whose clamped lanes re-read channels 8..15 of the
     SAME pixel against zero weights (0 * Inf = NaN in every channel of the window pixels).  The bf16 kernels' epilogues now take

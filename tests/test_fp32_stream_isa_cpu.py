@@ -3,12 +3,14 @@ launcher references runs two waves per SIMD without scratch, and its weights fit
 launched with (64 channels: two 256-thread workgroups; 128 channels: one 512-thread workgroup).
 
 Compiles the TU for gfx950 with -save-temps (hipcc cross-compiles without a GPU), as tests/test_isa_cpu.py does."""
-import glob
 import os
 import re
-import subprocess
+import sys
 
 import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 # the (channels, prologue, epilogue flags, 4-wave groups) the launcher instantiates: route_tapstream<64 / 128> in lf_conv.hip
 VARIANTS = [(c, pro, epi, 1 if c == 64 else 2) for c in (64, 128) for pro, epi in ((0, 1), (0, 8), (0, 2), (1, 1))] + [(64, 0, 48, 1), (64, 0, 38, 1)]
@@ -16,22 +18,12 @@ VARIANTS = [(c, pro, epi, 1 if c == 64 else 2) for c in (64, 128) for pro, epi i
 
 @pytest.fixture(scope="module")
 def stream_kernels(tmp_path_factory):
-    from lanedetection_end2end_amd import build
-    d = tmp_path_factory.mktemp("isa_stream")
-    src = os.path.join(build.CSRC, "lf_conv.hip")
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + build.FLAGS + ["-c", src, "-o", str(d / "lf_conv.o"), "-save-temps=obj"]
-    subprocess.check_call(cmd, cwd=str(d))
-    asm = glob.glob(str(d / "*gfx950*.s"))
-    assert asm, "no device assembly produced"
-    s = open(asm[0]).read()
-    md = s[s.index("amdhsa.kernels:"):]                  # the metadata note: nothing of the instruction stream is read
+    import isa_meta
     out = {}
-    for b in md.split("\n  - .agpr_count:")[1:]:
-        g = lambda k: re.search(r"\." + k + r":\s+(\S+)", b).group(1)
-        m = re.search(r"tapstream_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", g("name"))
+    for k in isa_meta.compile_kernels(["lf_conv.hip"], tmp_path_factory.mktemp("isa_stream")):
+        m = re.search(r"tapstream_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", k["mangled"])
         if m:
-            out[tuple(int(v) for v in m.groups())] = dict(agpr=int(b.split("\n")[0].strip()), vgpr=int(g("vgpr_count")), spill=int(g("vgpr_spill_count")),
-                                                         scratch=int(g("private_segment_fixed_size")), lds=int(g("group_segment_fixed_size")))
+            out[tuple(int(v) for v in m.groups())] = dict(agpr=k["agpr"], vgpr=k["vgpr"], spill=k["vgpr_spill"], scratch=k["scratch"], lds=k["lds"])
     return out
 
 

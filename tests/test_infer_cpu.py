@@ -1,10 +1,8 @@
 """The inference engine's CPU-checkable surface: the C entries (header, library, ctypes table), the size of its workspace against
 the training engine's, the compiled-in bias + residual + ReLU epilogues of the forward convolutions (spills, registers), and the
 ``inference_engine`` switch of the ERFNet module (default, environment variable, ``use_inference_engine``)."""
-import glob
 import os
 import re
-import subprocess
 import sys
 
 import pytest
@@ -46,15 +44,8 @@ def test_workspace_is_a_fraction_of_the_training_one():
 
 @pytest.fixture(scope="module")
 def conv_kernels(tmp_path_factory):
-    from lanedetection_end2end_amd import build
     import isa_meta
-    d = tmp_path_factory.mktemp("isa_infer")
-    src = os.path.join(build.CSRC, "lf_conv.hip")
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + build.FLAGS + ["-c", src, "-o", str(d / "lf_conv.o"), "-save-temps=obj"]
-    subprocess.check_call(cmd, cwd=str(d))
-    asm = glob.glob(str(d / "*gfx950*.s"))
-    assert asm, "no device assembly produced"
-    return isa_meta.kernels(asm[0])
+    return isa_meta.compile_kernels(["lf_conv.hip"], tmp_path_factory.mktemp("isa_infer"))
 
 
 def test_bias_residual_epilogues_are_compiled_in(conv_kernels):

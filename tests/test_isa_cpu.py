@@ -1,12 +1,10 @@
 """No hot kernel may spill vector registers to scratch.
 
-Compiles csrc/lf_conv.hip for gfx950 with -save-temps (hipcc cross-compiles without a GPU) and reads the
+Compiles csrc/lf_conv.hip and csrc/lf_wgrad.hip for gfx950 with -save-temps (hipcc cross-compiles without a GPU) and reads the
 .vgpr_spill_count / .private_segment_fixed_size metadata of every instantiation the backbone launches in the
 fp32 and fp32x9 modes (tap-GEMM with every compiled-in epilogue, the 16-channel kernels, the weight gradients).
 """
-import glob
 import os
-import subprocess
 import sys
 
 import pytest
@@ -17,15 +15,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 @pytest.fixture(scope="module")
 def conv_kernels(tmp_path_factory):
-    from lanedetection_end2end_amd import build
     import isa_meta
-    d = tmp_path_factory.mktemp("isa")
-    src = os.path.join(build.CSRC, "lf_conv.hip")
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + build.FLAGS + ["-c", src, "-o", str(d / "lf_conv.o"), "-save-temps=obj"]
-    subprocess.check_call(cmd, cwd=str(d))
-    asm = glob.glob(str(d / "*gfx950*.s"))
-    assert asm, "no device assembly produced"
-    return isa_meta.kernels(asm[0])
+    return isa_meta.compile_kernels(["lf_conv.hip", "lf_wgrad.hip"], tmp_path_factory.mktemp("isa"))
 
 
 def _select(kernels, prefix):

@@ -17,7 +17,7 @@ Two data sets per case:
              test_fp32_kernel_parity_every_addressing_path holds the 3-tap weight gradient to).  Both measured values are printed.
 
 Stride-2 layers: Down(16 -> 48 of 64), Down(64 -> 64 of 128), Up(128 -> 64), Up(64 -> 16).  Shapes (N, H, W) of the LARGER tensor,
-the smallest that reach each path of wgrad_cfg (csrc/lf_conv.hip) as it stands (logical pixels = N * H/2 * W/2; a wave walks its pixels in
+the smallest that reach each path of wgrad_cfg (csrc/lf_wgrad.hip) as it stands (logical pixels = N * H/2 * W/2; a wave walks its pixels in
 groups of 4 * U; rows = workgroup rows = partial rows per launch):
 
   shape        pixels  U  rows       reaches

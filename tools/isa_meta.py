@@ -6,6 +6,8 @@
 Prints demangled name, VGPRs, AGPRs, spilled VGPRs / SGPRs, scratch bytes, LDS bytes.  Used by
 tests/test_isa_cpu.py (no hot kernel may spill) and when tuning kernels without a GPU.
 """
+import glob
+import os
 import re
 import subprocess
 import sys
@@ -40,6 +42,26 @@ def kernels(asm_path):
     for k, n in zip(out, names):
         n = n.replace('(anonymous namespace)::', '')
         k['name'] = re.sub(r'^void ', '', re.sub(r'\(.*', '', n))
+    return out
+
+
+def compile_kernels(src_names, tmp_dir):
+    """kernels() of the named csrc files together: each is compiled for gfx950 with the library's flags and -save-temps=obj
+    into tmp_dir (all at once; hipcc cross-compiles without a GPU).  The ISA tests' fixtures call this."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    from lanedetection_end2end_amd import build
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    procs = [subprocess.Popen([hipcc] + build.FLAGS + ['-c', os.path.join(build.CSRC, n), '-o', os.path.join(str(tmp_dir), n[:-4] + '.o'),
+                               '-save-temps=obj'], cwd=str(tmp_dir)) for n in src_names]
+    failed = [n for n, p in zip(src_names, procs) if p.wait() != 0]
+    assert not failed, 'hipcc failed on %r' % failed
+    out = []
+    for n in src_names:
+        asm = glob.glob(os.path.join(str(tmp_dir), n[:-4] + '-hip-*gfx950*.s'))
+        assert len(asm) == 1, 'no device assembly produced for ' + n
+        out += kernels(asm[0])
     return out
 
 
