@@ -48,7 +48,9 @@ extern "C" {
                                  additions since 5 (resident dataset's label batch): lf_label_batch_bp, lf_label_batch_bev;
                                  additions since 5 (gradient-norm clipping): lf_grad_norm_workspace_bytes, lf_grad_sumsq,
                                  lf_grad_norm_finish, lf_grad_scale_inplace, lf_adam_step_clipped, lf_sgd_step_clipped,
-                                 lf_rmsprop_step_clipped */
+                                 lf_rmsprop_step_clipped;
+                                 additions since 5 (segmentation-mode detect): lf_head_fit_seg, lf_lane_infer_seg_workspace_bytes,
+                                 lf_lane_infer_seg */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -664,6 +666,36 @@ int lf_conv1d_bwd_data(const float* gy, const float* w, const float* mask_src, f
                        int C, int axis, int dilation, float* scratch, void* stream);
 int lf_conv1d_bwd_weight(const float* x, const float* gy, float* gw, float* gb, int N, int H, int W, int C,
                          int axis, int dilation, float* scratch, void* stream);
+
+/* additions since 5 -- segmentation-mode detect: the test-time path of a model trained with end_to_end = False (the reference's
+ * baseline and its pre-training epochs), Net.forward's arg-max branch (BEV/Networks/LSQ_layer.py:302-308,
+ * BP/Networks/LSQ_layer.py:279-293,308-311) fused with decoder.output_conv and the fit.
+ * lf_head_fit_seg: one pass over the last decoder layer's tensor -> the C class logits of every output pixel (lf_head_fit's head),
+ *   their arg-max (first maximum, NaN maximal), the L lane maps valued l + 1 where class l + 1 wins and the moment pass of their fit
+ *   (activation none); neither the logits nor the maps are written.  beta, zinv and status equal lf_seg_maps + lf_wls_fwd on the
+ *   head's logits BIT FOR BIT (the same partition of the pixels over threads, the same order of every fp64 addition).
+ *     x (N,h,w,16) NHWC fp32 (x_bf16 = 0) or bf16 bit patterns (1); head_w (16,C,2,2), head_b (C) fp32; C <= 5, L <= 4; L >= C is
+ *       allowed (a lane whose class does not exist never wins: singular); w must be even (4 output pixels of a unit share a row);
+ *     grid_xy, grid_batch_stride, zero_rows, order, reg, y_offset, solver, beta (N,L,order+1), zinv, partials
+ *       (>= lf_wls_workspace_bytes(N,L,order)), status (N*L): as lf_wls_fwd on the (N,L,2h,2w) maps.  Input rows that feed only
+ *       output rows < zero_rows are never read, nor is the grid on those rows;
+ *     gt_line_or_null (N,L) fp32 flags as lf_seg_maps (BP's "prevent singular matrix"): a flagged lane (n, l) fits the map of image
+ *       0, lane 0 against image n's grid; lane (0, 0) itself is left as it is;
+ *     classes_or_null (N,2h,2w) uint8: the arg-max class of every pixel; when requested every row is computed for it (the fit
+ *       still skips the masked rows).
+ * lf_lane_infer_seg: image -> lane polynomials in one call = lf_erfnet_infer's schedule up to the last decoder layer, then
+ *   lf_head_fit_seg on head 0 with C = the plan's out_channels; every precision mode.  Arguments as lf_lane_infer.
+ * lf_lane_infer_seg_workspace_bytes: the inference workspace + the chunk partials and saved inverses of N * L lanes; 0 for an
+ *   unknown mode, order outside 0..3 or L outside 1..4. */
+int lf_head_fit_seg(const void* x, int x_bf16, const float* head_w, const float* head_b, const float* grid_xy, long grid_batch_stride,
+                    const float* gt_line_or_null, int N, int h, int w, int C, int L, int zero_rows, int order, double reg,
+                    double y_offset, int solver, uint8_t* classes_or_null, double* beta, double* zinv, void* partials,
+                    int32_t* status, void* stream);
+size_t lf_lane_infer_seg_workspace_bytes(const lf_erfnet_plan* plan, int mode, int L, int order);
+int lf_lane_infer_seg(const lf_erfnet_plan* plan, const float* img, const float* const* params_host, const float* const* params_dev,
+                      float* const* running_host, const float* grid_xy, long grid_batch_stride, const float* gt_line_or_null, int L,
+                      int zero_rows, int order, double reg_ls, double y_offset, int use_cholesky, uint8_t* classes_or_null,
+                      double* beta, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,9 @@ def _declare(lib):
         "lf_sgd_step_clipped": (I, [P, P, I, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, P, P]),
         "lf_rmsprop_step_clipped": (I, [P, P, I, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                         ctypes.c_float, P, P]),
+        "lf_head_fit_seg": (I, [P, I, P, P, P, L, P, I, I, I, I, I, I, I, D, D, I, P, P, P, P, P, P]),
+        "lf_lane_infer_seg_workspace_bytes": (c_size_t, [P, I, I, I]),
+        "lf_lane_infer_seg": (I, [P, P, P, P, P, P, L, P, I, I, I, D, D, I, P, P, P, P, c_size_t, P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {

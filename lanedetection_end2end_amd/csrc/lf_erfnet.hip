@@ -1350,4 +1350,30 @@ int lf_lane_infer(const lf_erfnet_plan* P, const float* img, const float* const*
                        reinterpret_cast<double*>(c.ws + LL.zinv), c.ws + LL.partials, status, stream);
 }
 
+// The same for a segmentation-mode model (out_channels = classes, background first): image -> the L lane polynomials of the arg-max
+// maps in one call, lf_head_fit_seg on head 0 in the place of lf_head_fit.  Neither the logits nor the maps are written.
+size_t lf_lane_infer_seg_workspace_bytes(const lf_erfnet_plan* P, int mode, int L, int order) {
+    if (!P || !(mode == 0 || mode == 2 || mode == 3) || L < 1 || L > 4 || order < 0 || order > 3) return 0;
+    return (size_t)lane_layout(P, mode, L, order).total;
+}
+
+int lf_lane_infer_seg(const lf_erfnet_plan* P, const float* img, const float* const* params_host, const float* const* params_dev,
+                      float* const* running_host, const float* grid_xy, long grid_batch_stride, const float* gt_line_or_null, int L,
+                      int zero_rows, int order, double reg_ls, double y_offset, int use_cholesky, uint8_t* classes_or_null,
+                      double* beta, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    LF_REQUIRE(P && img && params_host && params_dev && running_host && grid_xy && beta && status && workspace,
+               "lf_lane_infer_seg: null pointer");
+    LF_REQUIRE(order >= 0 && order <= 3 && L >= 1 && L <= 4, "lf_lane_infer_seg: order %d not in 0..3 or L = %d not in 1..4", order, L);
+    const LaneLayout LL = lane_layout(P, P->precision, L, order);
+    LF_REQUIRE(workspace_bytes >= (size_t)LL.total, "lf_lane_infer_seg: workspace too small (%zu < %ld)", workspace_bytes, LL.total);
+    InferCtx c;
+    LF_TRY(infer_begin(c, P, workspace, params_host, params_dev, running_host, stream));
+    float* last = nullptr;
+    LF_TRY(forward_infer(c, img, params_host, (int)P->layers.size(), &last));
+    return lf_head_fit_seg(last, c.s16, params_host[P->p_head_w[0]], params_host[P->p_head_b[0]], grid_xy, grid_batch_stride,
+                           gt_line_or_null, P->N, P->H / 2, P->W / 2, P->Cout, L, zero_rows, order, reg_ls, y_offset,
+                           use_cholesky ? LF_SOLVE_CHOLESKY : LF_SOLVE_LU, classes_or_null, beta,
+                           reinterpret_cast<double*>(c.ws + LL.zinv), c.ws + LL.partials, status, stream);
+}
+
 }  // extern "C"

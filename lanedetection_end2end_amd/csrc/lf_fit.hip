@@ -721,6 +721,191 @@ extern "C" int lf_head_fit(const void* x, int x_bf16, const float* head_w, const
 }
 
 // ---------------------------------------------------------------------------------------
+// Fused head + arg-max + fit (inference, segmentation mode): decoder.output_conv with C class channels, the arg-max lane maps of
+// Net.forward(end_to_end=False) (BEV/Networks/LSQ_layer.py:302-308, BP/Networks/LSQ_layer.py:279-293,308-311) and the moment pass
+// of their fit in ONE pass over the last decoder layer's tensor: neither the (N,C,H,W) logits nor the (N,L,H,W) maps are written.
+// The result equals lf_head_fwd + lf_seg_maps + lf_wls_fwd BIT FOR BIT (the arg-max is discontinuous: nothing weaker means
+// anything), so the summation is wls_moments_kernel<ORDER, 4, GridTable>'s, restated: a unit is 4 consecutive output pixels of one
+// row from the first unmasked pixel on, chunk c owns units [units * c / 16, units * (c + 1) / 16), thread t takes every 256th of
+// them, each lane's per-thread sums go through block_store_sums into that lane's chunk slot; every lane adds every pixel of its
+// thread (a zero weight too), so each fp64 addition happens in the same thread in the same order.  The logits are
+// head_fwd_kernel's (bias first, channels ascending, fmaf), the arg-max seg_maps_kernel's (first maximum, NaN maximal).
+// ---------------------------------------------------------------------------------------
+namespace {
+
+constexpr int SF_MAXC = 5;       // classes: background + up to 4 lanes
+constexpr int SF_MAXL = 4;
+typedef float sf_f32x2 __attribute__((ext_vector_type(2)));
+
+// the 32 input values of a unit: two adjacent input pixels of row i, 16 channels each (128 contiguous bytes of fp32, 64 of bf16)
+template <typename T>
+__device__ __forceinline__ void segfit_load(const T* __restrict__ p, float (&xv)[2][16]) {
+    if constexpr (sizeof(T) == 2) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            lf_f32x4 v[2];
+            lf_ldq<T, 2>(p + q * 8, v);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { xv[q >> 1][(q & 1) * 8 + e] = v[0][e]; xv[q >> 1][(q & 1) * 8 + 4 + e] = v[1][e]; }
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const lf_f32x4 v = lf_ldv(p + q * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) xv[q >> 2][(q & 3) * 4 + e] = v[e];
+        }
+    }
+}
+
+// arg-max class of the unit's 4 output pixels (tap row a): sw [a][c][ci][b] and sb [c] in LDS
+__device__ __forceinline__ void segfit_argmax(const float (&xv)[2][16], const float* __restrict__ sw, const float* __restrict__ sb,
+                                              int C, int a, int (&am)[4]) {
+    float best[4];
+    for (int c = 0; c < C; ++c) {
+        // the two outputs of an input pixel (b = 0, 1) as one two-wide fma per channel: the same fmaf per element, half the issues
+        sf_f32x2 o01 = {sb[c], sb[c]}, o23 = o01;
+        const sf_f32x2* wc = reinterpret_cast<const sf_f32x2*>(sw) + (a * SF_MAXC + c) * 16;
+#pragma unroll
+        for (int ci = 0; ci < 16; ++ci) {
+            const sf_f32x2 t = wc[ci];
+            o01 = __builtin_elementwise_fma(sf_f32x2{xv[0][ci], xv[0][ci]}, t, o01);
+            o23 = __builtin_elementwise_fma(sf_f32x2{xv[1][ci], xv[1][ci]}, t, o23);
+        }
+        const float o[4] = {o01.x, o01.y, o23.x, o23.y};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float v = o[e];
+            const bool up = c == 0 || v > best[e] || (v != v && best[e] == best[e]);      // (selects, not branches)
+            best[e] = up ? v : best[e];
+            am[e] = up ? c : am[e];
+        }
+    }
+}
+
+// One workgroup: chunk blockIdx.x of image n, lanes [l0, l0 + NL) (blockIdx.y = n * groups + l0 / NL).  flags: gt_line (N,L) or
+// NULL; a flagged lane takes map [0, 0]'s value -- image 0's arg-max == 1 -- against image n's grid (lane (0, 0) thereby stays as
+// it is).  classes (N,H,W) uint8 or NULL: written by the workgroups of lane group 0, every row.
+template <int ORDER, typename T, int NL>
+__global__ __launch_bounds__(WLS_THREADS) void segfit_kernel(
+    const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ grid, long grid_bs,
+    const float* __restrict__ flags, int C, int L, int h, int wd, int zero_rows, float y_off, uint8_t* __restrict__ classes,
+    double* __restrict__ partials) {
+    using M = Moments<ORDER>;
+    const int groups = (L + NL - 1) / NL;
+    const int n = blockIdx.y / groups, l0 = (blockIdx.y % groups) * NL, chunk = blockIdx.x;
+    __shared__ float sw[2 * SF_MAXC * 16 * 2];
+    __shared__ float sb[SF_MAXC];
+    for (int i = threadIdx.x; i < C * 64; i += WLS_THREADS) {
+        const int c = i >> 6, ci = (i >> 2) & 15, ab = i & 3;
+        sw[(((ab >> 1) * SF_MAXC + c) * 16 + ci) * 2 + (ab & 1)] = w[(ci * C + c) * 4 + ab];
+        if (ci == 0 && ab == 0) sb[c] = b[c];
+    }
+    __syncthreads();
+    unsigned flagged = 0;                                 // bit k: lane l0 + k borrows map [0, 0]
+    if (flags)
+        for (int k = 0; k < NL; ++k)
+            if (l0 + k < L && flags[n * L + l0 + k] != 0.f) flagged |= 1u << k;
+    const bool other = flagged && n != 0;                 // image 0's arg-max is needed next to this image's (uniform)
+    const int W = 2 * wd;
+    const long P = (long)(2 * h) * W;
+    const GridTable src({grid, grid_bs}, n);
+    const T* xn = x + (long)n * h * wd * 16;
+    uint8_t* cls = (classes && l0 == 0) ? classes + (long)n * P : nullptr;
+    const long first = (long)zero_rows * W;               // first unmasked pixel
+    const long units = (P - first) / 4;
+    const long u0 = units * chunk / WLS_CHUNKS, u1 = units * (chunk + 1) / WLS_CHUNKS;
+    M acc[NL];
+    for (long u = u0 + threadIdx.x; u < u1; u += WLS_THREADS) {
+        const long p = first + u * 4;
+        const int r = (int)(p / W), col = (int)(p - (long)r * W);
+        const long xo = ((long)(r >> 1) * wd + (col >> 1)) * 16;
+        float xv[2][16];
+        GridTable::Unit<4> unit;
+        segfit_load<T>(xn + xo, xv);
+        src.load<4>(p, W, unit);
+        int am[4], am0[4];
+        segfit_argmax(xv, sw, sb, C, r & 1, am);
+        if (other) {
+            segfit_load<T>(x + xo, xv);
+            segfit_argmax(xv, sw, sb, C, r & 1, am0);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) am0[e] = am[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            GridPoint q;
+            src.point(unit, e, q);
+#pragma unroll
+            for (int k = 0; k < NL; ++k) {
+                const float own = am[e] == l0 + k + 1 ? (float)(l0 + k + 1) : 0.f;
+                const float lent = am0[e] == 1 ? 1.f : 0.f;
+                acc[k].add((flagged >> k) & 1 ? lent : own, q.gx, q.gy, y_off);
+            }
+        }
+        if (cls) *reinterpret_cast<uchar4*>(cls + p) = make_uchar4(am[0], am[1], am[2], am[3]);
+    }
+    if (cls) {   // the class map covers the masked rows too: their pixels are computed for it and stay out of the fit
+        const long zu = first / 4, z0 = zu * chunk / WLS_CHUNKS, z1 = zu * (chunk + 1) / WLS_CHUNKS;
+        for (long u = z0 + threadIdx.x; u < z1; u += WLS_THREADS) {
+            const long p = u * 4;
+            const int r = (int)(p / W), col = (int)(p - (long)r * W);
+            float xm[2][16];
+            int am[4];
+            segfit_load<T>(xn + ((long)(r >> 1) * wd + (col >> 1)) * 16, xm);
+            segfit_argmax(xm, sw, sb, C, r & 1, am);
+            *reinterpret_cast<uchar4*>(cls + p) = make_uchar4(am[0], am[1], am[2], am[3]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NL; ++k) {
+        if (k) __syncthreads();  // (the guard below is uniform over the workgroup -- l0 from blockIdx -- as the barrier inside needs)
+        if (l0 + k < L) block_store_sums(acc[k].v, partials + (((long)n * L + l0 + k) * WLS_CHUNKS + chunk) * M::N);
+    }
+}
+
+}  // namespace
+
+// x, head_w (16,C,2,2), head_b (C) as lf_head_fit, C <= 5 classes; the fit runs on the L <= 4 arg-max lane maps lf_seg_maps would
+// write from the head's logits (gt_line_or_null (N,L) fp32 as there); classes_or_null (N,2h,2w) uint8.  w even.
+extern "C" int lf_head_fit_seg(const void* x, int x_bf16, const float* head_w, const float* head_b, const float* grid_xy,
+                               long grid_batch_stride, const float* gt_line_or_null, int N, int h, int w, int C, int L, int zero_rows,
+                               int order, double reg, double y_offset, int solver, uint8_t* classes_or_null, double* beta,
+                               double* zinv, void* partials, int32_t* status, void* stream) {
+    LF_REQUIRE(x && head_w && head_b && grid_xy && beta && zinv && partials && status, "lf_head_fit_seg: null pointer");
+    LF_REQUIRE(N > 0 && h > 0 && w > 0 && C >= 1 && C <= SF_MAXC && L >= 1 && L <= SF_MAXL,
+               "lf_head_fit_seg: bad shape N=%d C=%d L=%d h=%d w=%d (C <= %d, L <= %d)", N, C, L, h, w, SF_MAXC, SF_MAXL);
+    LF_REQUIRE(w % 2 == 0, "lf_head_fit_seg: w = %d is odd: a unit of 4 output pixels must lie in one row", w);
+    LF_REQUIRE(zero_rows >= 0 && zero_rows < 2 * h, "lf_head_fit_seg: zero_rows %d out of [0,%d)", zero_rows, 2 * h);
+    LF_REQUIRE(order >= 0 && order <= 3, "lf_head_fit_seg: order %d not in 0..3", order);
+    LF_REQUIRE(grid_batch_stride % 4 == 0 && ((size_t)grid_xy & 15) == 0 && ((size_t)x & 15) == 0 && ((size_t)classes_or_null & 3) == 0,
+               "lf_head_fit_seg: grid / input / classes are read and written as vectors: misaligned");
+    hipStream_t st = (hipStream_t)stream;
+    // all lanes in one workgroup (the head and the arg-max are computed once per pixel) when the images alone fill the device; below
+    // that one lane per workgroup: L times as many workgroups, each repeating the (cheap) head
+    const bool split = (long)N * WLS_CHUNKS < 256 && L > 1;
+    return with_order(order, [&](auto O) {
+        auto launch = [&](auto t, auto NLc) {
+            using T = decltype(t);
+            constexpr int NL = decltype(NLc)::value;
+            hipLaunchKernelGGL((segfit_kernel<O(), T, NL>), dim3(WLS_CHUNKS, N * ((L + NL - 1) / NL)), dim3(WLS_THREADS), 0, st,
+                               (const T*)x, head_w, head_b, grid_xy, grid_batch_stride, gt_line_or_null, C, L, h, w, zero_rows,
+                               (float)y_offset, classes_or_null, (double*)partials);
+        };
+        auto lanes = [&](auto t) {
+            if (split) launch(t, std::integral_constant<int, 1>{});
+            else if (L <= 2) launch(t, std::integral_constant<int, 2>{});
+            else launch(t, std::integral_constant<int, 4>{});
+        };
+        if (x_bf16) lanes(lf_bf16{});
+        else lanes(float{});
+        LF_CHECK_LAUNCH("segfit");
+        return wls_solve_launch<O()>((const double*)partials, N * L, reg, solver, beta, zinv, status, st);
+    });
+}
+
+// ---------------------------------------------------------------------------------------
 // Homography through the fit: the grid and its backward as launches of their own, the fit on the inline route (GridTheta), and
 // autograd of the fit w.r.t. an explicit grid.
 // ---------------------------------------------------------------------------------------

@@ -608,6 +608,41 @@ class Net(nn.Module):
                                      _lib.ptr(beta), _lib.ptr(status), _lib.ptr(ws), nbytes, _lib.stream()), "lf_lane_infer")
         return beta, status, (self._infer_encoder_view(plan, ws, mode) if want_encoder else None)
 
+    def _lane_infer_seg(self, x, grid, gt_line, lanes, zero_rows, order, reg_ls, y_offset, use_cholesky, want_classes=False):
+        """Segmentation-mode twin of ``_lane_infer``: image -> (beta (N,lanes,order+1) fp64, status (N*lanes) int32, (N,H,W) uint8
+        arg-max class map or None) in one C call (lf_lane_infer_seg: the inference engine up to the last decoder layer, the fused
+        head + arg-max + moments kernel, the solve); head 0.  ``gt_line``: (N, lanes) fp32 flags on the device, or None.  Neither
+        the class logits nor the lane maps are written."""
+        lib = _lib.load()
+        x = x.contiguous().float()
+        N, C, H, W = x.shape
+        assert C == self.in_channels, "expected %d input channels, got %d" % (self.in_channels, C)
+        plan = self._plan(N, H, W)
+        mode = _PRECISIONS[self.precision]
+        _lib.check(lib.lf_erfnet_set_precision(plan.handle, mode), "lf_erfnet_set_precision")
+        nbytes = lib.lf_lane_infer_seg_workspace_bytes(plan.handle, mode, lanes, order)
+        if nbytes == 0:
+            raise _lib.LaneFitLibraryError("lf_lane_infer_seg_workspace_bytes: unsupported mode / lanes / order (%s, %d, %d)"
+                                           % (self.precision, lanes, order))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        beta = torch.empty(N, lanes, order + 1, dtype=torch.float64, device=x.device)
+        status = torch.empty(N * lanes, dtype=torch.int32, device=x.device)
+        classes = torch.empty(N, H, W, dtype=torch.uint8, device=x.device) if want_classes else None
+        params = [p.detach() for p in self._ordered_params()]
+        for p in params:
+            assert p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+        running = self._ptrs.get("running", self._running_buffers())
+        grid = grid.contiguous()
+        assert grid.dtype == torch.float32 and grid.shape[-2:] == (H * W, 2), (grid.shape, H, W)
+        gstride = H * W * 2 if grid.dim() == 3 and grid.shape[0] > 1 else 0      # (as ops.WLSFit)
+        assert gt_line is None or (gt_line.is_cuda and gt_line.dtype == torch.float32 and tuple(gt_line.shape) == (N, lanes))
+        _lib.check(lib.lf_lane_infer_seg(plan.handle, _lib.ptr(x), self._ptrs.get("params", params),
+                                         _lib.ptr(self._device_ptr_table(params)), running, _lib.ptr(grid), gstride,
+                                         _lib.ptr(gt_line), int(lanes), int(zero_rows), int(order), float(reg_ls), float(y_offset),
+                                         int(bool(use_cholesky)), _lib.ptr(classes), _lib.ptr(beta), _lib.ptr(status), _lib.ptr(ws),
+                                         nbytes, _lib.stream()), "lf_lane_infer_seg")
+        return beta, status, classes
+
     # ---- forward -----------------------------------------------------------------------
     def forward(self, input, flag, only_encode=False):
         if not input.is_cuda:

@@ -30,6 +30,11 @@ class _LaneFitNet(nn.Module):
     max_order = 2
     cholesky_drops_reg = False       # BP only: its --use_cholesky branch is GELS, which has no regulariser
     classification_cls = Classification      # the tree's own --clas head class (the BEV tree's line head differs)
+    # detect() of an end_to_end=False model: True = one call (lf_lane_infer_seg) wherever it is not the slower way -- a batch of
+    # ONE image keeps the three-step path (engine forward, lf_seg_maps, fit): its fused launch has 16 workgroups per lane, the
+    # whole head on that many CUs, and measures 0.7 % behind (profiles/seg_detect_time.json); "always" = the one call at every
+    # batch; False = the three-step path.  All give the same bits; tests and timing alternate them in one process.
+    fused_seg_detect = True
 
     def _common_init(self, args, M, backbone_cls):
         self.nclasses = args.nclasses
@@ -127,21 +132,24 @@ class _LaneFitNet(nn.Module):
         (``validate()``, BP/test.py:35-88), with ``forward``'s dtypes, shapes and ``None``s, on the inference engine whatever the
         ``inference_engine`` switches say and whatever the caller's grad state.  Eval mode only (the wrapper, its backbone and its heads).
 
-        End-to-end models run ONE C call from the image to the lane coefficients (``lf_lane_infer``: the backbone's inference
-        schedule, then head + activation + row mask + moments fused -- neither the logits nor the weight maps are written) and the
-        ``--clas`` heads with their BatchNorms folded in, on the encoder output inside that call's workspace.  A segmentation-mode
-        model (``end_to_end=False``) runs the inference-engine forward, ``lf_seg_maps`` and the existing fit; ``gt_line`` is what
-        BP's ``forward`` takes for its "prevent singular matrix" borrow (lanes flagged in it fit map [0, 0]): pass the same tensor
-        to get ``forward``'s coefficients for such lanes; the default ``None`` borrows nothing, as test time has no labels.
-        ``last_status`` is set; a singular system raises ``RuntimeError`` under ``check_singular`` as in ``forward``."""
-        # (the wrapper, the backbone and the heads: four flags, not a walk over ~300 modules on every call)
-        parts = (self, self.net) + ((self.line_classification, self.horizon_estimation) if self.classification_branch else ())
-        if any(m.training for m in parts):
-            raise RuntimeError("lanefit detect() needs the model, its backbone and its heads in eval mode (model.eval()): it folds "
-                               "the BatchNorm running statistics into the convolutions")
-        if not input.is_cuda:
-            raise erfnet._lib.LaneFitLibraryError("lanefit detect needs its input on the MI355X; there is no CPU path")
+        Either kind of model runs ONE C call from the image to the lane coefficients.  End-to-end models: ``lf_lane_infer`` (the
+        backbone's inference schedule, then head + activation + row mask + moments fused -- neither the logits nor the weight maps
+        are written) and the ``--clas`` heads with their BatchNorms folded in, on the encoder output inside that call's workspace.
+        Segmentation-mode models (``end_to_end=False``): ``lf_lane_infer_seg`` (the same schedule, then head + arg-max + moments
+        fused -- neither the class logits nor the lane maps are written), bit for bit the coefficients and statuses of the
+        engine-on ``forward``.  ``fused_seg_detect = False`` restores the three-step path (inference-engine forward,
+        ``lf_seg_maps``, the fit); a batch of one image keeps it too unless ``fused_seg_detect = "always"`` (the same bits, and
+        there the three steps measure 0.7 % faster), and so does a ``pretrained`` model, whose segmentation head is the decoder's
+        second one.  ``gt_line`` is what BP's ``forward`` takes for its "prevent singular matrix" borrow (lanes flagged in it fit map
+        [0, 0]): pass the same tensor to get ``forward``'s coefficients for such lanes; the default ``None`` borrows nothing, as
+        test time has no labels.  ``last_status`` is set; a singular system raises ``RuntimeError`` under ``check_singular`` as in
+        ``forward``."""
+        self._require_eval_on_device(input, "detect")
         reg = 0.0 if (self.use_cholesky and self.cholesky_drops_reg) else self.reg_ls
+        if not self.end_to_end and not self.pretrained and (
+                self.fused_seg_detect == "always" or (self.fused_seg_detect and input.shape[0] > 1)):
+            beta, _ = self._seg_infer(input, gt_line, False)
+            return fit.split_lanes(beta, self.nclasses, self.beta_dtype) + (None, None)
         if not self.end_to_end:
             was = self.net.inference_engine
             self.net.inference_engine = True
@@ -155,10 +163,7 @@ class _LaneFitNet(nn.Module):
                                             "none", self.use_cholesky, False, self.check_singular, **geo)
             self.last_status = status
             return fit.split_lanes(beta, self.nclasses, self.beta_dtype) + (None, None)
-        # (with a homography set, the fused head + fit reads the per-image grid lf_theta_grid makes from it)
-        grid = (self.grid_on(input.device) if self._homography() is None else
-                ops.theta_grid(self._geometry(input.device)["theta"], input.shape[2], input.shape[3], self.normalised))
-        beta, status, enc = self.net._lane_infer(input, grid, self.zero_rows, self.order, reg, self.y_offset,
+        beta, status, enc = self.net._lane_infer(input, self._detect_grid(input), self.zero_rows, self.order, reg, self.y_offset,
                                                  ops.ACT_KINDS[self.activation_name], self.use_cholesky, self.classification_branch)
         self.last_status = status
         if self.check_singular:
@@ -168,6 +173,45 @@ class _LaneFitNet(nn.Module):
             enc = enc.permute(0, 3, 1, 2)             # logical NCHW, channels-last memory (as Net.forward hands it out)
             line, horizon = self.line_classification(enc, folded=True), self.horizon_estimation(enc, folded=True)
         return fit.split_lanes(beta, self.nclasses, self.beta_dtype) + (line, horizon)
+
+    @torch.no_grad()
+    def segment(self, input):
+        """Image -> the (N, H, W) uint8 arg-max class map of a segmentation-mode model (``end_to_end=False``; 0 = background, k =
+        lane k), from the same one call as ``detect`` (``lf_lane_infer_seg`` with its class map requested: 1 B/pixel, the logits
+        are not written).  Eval mode only.  ``last_status`` is set; a singular fit does not raise here."""
+        self._require_eval_on_device(input, "segment")
+        if self.end_to_end or self.pretrained:
+            raise RuntimeError("lanefit segment() is for segmentation-mode models (end_to_end=False, not pretrained): this model's "
+                               "head 0 has no class channels")
+        return self._seg_infer(input, None, True, check=False)[1]
+
+    def _require_eval_on_device(self, input, what):
+        # (the wrapper, the backbone and the heads: four flags, not a walk over ~300 modules on every call)
+        parts = (self, self.net) + ((self.line_classification, self.horizon_estimation) if self.classification_branch else ())
+        if any(m.training for m in parts):
+            raise RuntimeError("lanefit %s() needs the model, its backbone and its heads in eval mode (model.eval()): it folds "
+                               "the BatchNorm running statistics into the convolutions" % what)
+        if not input.is_cuda:
+            raise erfnet._lib.LaneFitLibraryError("lanefit %s needs its input on the MI355X; there is no CPU path" % what)
+
+    def _detect_grid(self, input):
+        """The grid table the fused calls read: the constant one, or (with a homography set) the per-image grid lf_theta_grid makes
+        from it -- the bits of the inline route, ``theta_point`` is shared."""
+        if self._homography() is None:
+            return self.grid_on(input.device)
+        return ops.theta_grid(self._geometry(input.device)["theta"], input.shape[2], input.shape[3], self.normalised)
+
+    def _seg_infer(self, input, gt_line, want_classes, check=None):
+        """The one-call segmentation-mode path behind ``detect`` and ``segment``: -> (beta (N,lanes,order+1) fp64, class map)."""
+        lanes = 2 if self.nclasses < 3 else 4
+        reg = 0.0 if (self.use_cholesky and self.cholesky_drops_reg) else self.reg_ls
+        flags = ops.seg_flags(gt_line, input.shape[0], lanes, input.device)
+        beta, status, classes = self.net._lane_infer_seg(input, self._detect_grid(input), flags, lanes, self.zero_rows, self.order,
+                                                         reg, self.y_offset, self.use_cholesky, want_classes)
+        self.last_status = status
+        if self.check_singular if check is None else check:
+            ops._raise_if_singular(status, 1 if self.use_cholesky else 0)
+        return beta, classes
 
 
 class BEVNet(_LaneFitNet):

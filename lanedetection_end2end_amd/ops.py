@@ -480,6 +480,19 @@ def linear(x, w, b=None, relu=False):
     return LinearFn.apply(x, w, b, relu)
 
 
+def seg_flags(gt_line, N, lanes, device):
+    """``gt_line`` as the (N, lanes) fp32 device flags lf_seg_maps / lf_head_fit_seg read, or None when nothing is borrowed."""
+    if gt_line is None:
+        return None
+    flags = gt_line.to(device=device, dtype=torch.float32).contiguous()
+    if tuple(flags.shape) != (N, lanes):
+        # the reference's expand_as(masked) fails here -- but only when gt_line.sum() != 0 lets it get that far
+        if float(flags.sum()) != 0:
+            raise RuntimeError("seg-mode fit: gt_line %s cannot be expanded to the (%d, %d) lane maps" % (tuple(flags.shape), N, lanes))
+        return None
+    return flags
+
+
 def seg_maps(logits, gt_line, zero_rows, lanes):
     """Segmentation-mode fit input (lf_seg_maps): arg-max of the class logits -> per-lane maps valued k at class k, masked rows
     zeroed, lanes flagged in ``gt_line`` (N, lanes; BP only) overwritten with map [0, 0].  No gradient (the reference detaches)."""
@@ -487,15 +500,8 @@ def seg_maps(logits, gt_line, zero_rows, lanes):
     logits = logits.detach().contiguous()
     assert logits.dtype == torch.float32 and logits.dim() == 4
     N, C, H, W = logits.shape
-    flags = None
-    if gt_line is not None:
-        flags = gt_line.to(device=logits.device, dtype=torch.float32).contiguous()
-        if tuple(flags.shape) != (N, lanes):
-            # the reference's expand_as(masked) fails here -- but only when gt_line.sum() != 0 lets it get that far
-            if float(flags.sum()) != 0:
-                raise RuntimeError("seg-mode fit: gt_line %s cannot be expanded to the (%d, %d) lane maps" % (tuple(flags.shape), N, lanes))
-            flags = None
-    maps = torch.empty(N, lanes, H, W, dtype=torch.float32, device=logits.device)
+    flags = seg_flags(gt_line, N, lanes, logits.device)
+    maps =torch.empty(N, lanes, H, W, dtype=torch.float32, device=logits.device)
     _lib.check(lib.lf_seg_maps(_lib.ptr(logits), _lib.ptr(flags), _lib.ptr(maps), N, C, lanes, H, W, int(zero_rows), _lib.stream()),
                "lf_seg_maps")
     return maps

@@ -14,6 +14,14 @@ the same protocol: (A) ``forward`` on the existing engine, (B) ``forward`` with 
 they were (unfolded), (C) ``detect`` (lf_lane_infer + the BatchNorm-folded heads).  ``c_clas`` is config 3's model with
 ``--clas 1`` at 256 x 512: the heads are built for a (32, 64) encoder output, so they do not exist at 320 x 640.  With heads, their
 own time (both heads on the encoder output, unfolded and folded) is reported too.
+
+    python tools/infer_bench.py --detect --configs seg5,seg4,seg1 [--out profiles/seg_detect_time.json]
+
+Segmentation-mode rows (``end_to_end=False``): ``detect`` with ``fused_seg_detect`` off (the three-step path: inference-engine
+forward, lf_seg_maps, the fit -- bit for bit the code ``detect`` ran before the fused call existed, hence the baseline) and
+``"always"`` (lf_lane_infer_seg at every batch size, the single image included), alternated in one process.  ``seg5`` is config 5's shard (16 x 512 x 1024, 2 lanes), ``seg4`` the headline
+geometry with 4 lanes (32 x 256 x 512, BP tree), ``seg1`` one 512 x 1024 image (``seg_n2`` / ``seg_n4`` / ``seg_n8``: 2, 4, 8 of them).  Reported: images/s, the min-max range of the
+repeats, the peak memory of one call.
 """
 import argparse
 import json
@@ -107,12 +115,23 @@ DETECT_CONFIGS = dict(CONFIGS)
 DETECT_CONFIGS["c_clas"] = dict(name="bp_4lanes_256x512_b64_bf16_clas", N=64, H=256, W=512, K=4, precision="bf16", tree="bp", clas=True)
 
 
+SEG_CONFIGS = {
+    "seg5": dict(name="seg_bev_2lanes_512x1024_b16_fp32", N=16, H=512, W=1024, K=2, precision="fp32", tree="bev", seg=True),
+    "seg4": dict(name="seg_bp_4lanes_256x512_b32_fp32", N=32, H=256, W=512, K=4, precision="fp32", tree="bp", seg=True),
+    "seg1": dict(name="seg_bev_2lanes_512x1024_b1_fp32", N=1, H=512, W=1024, K=2, precision="fp32", tree="bev", seg=True),
+}
+for _n in (2, 4, 8):          # the batches between: seg_n2, seg_n4, seg_n8
+    SEG_CONFIGS["seg_n%d" % _n] = dict(SEG_CONFIGS["seg1"], name="seg_bev_2lanes_512x1024_b%d_fp32" % _n, N=_n)
+DETECT_CONFIGS.update(SEG_CONFIGS)
+
+
 def make_model(cfg):
     from argparse import Namespace
     from oracle import clas_oracle, erfnet_oracle
     bp = cfg["tree"] == "bp"
     clas = bool(cfg.get("clas"))
-    args = Namespace(batch_size=cfg["N"], nclasses=cfg["K"], resize=cfg["H"], end_to_end=True, mod="erfnet", layers=18, channels_in=3,
+    seg = bool(cfg.get("seg"))
+    args = Namespace(batch_size=cfg["N"], nclasses=cfg["K"], resize=cfg["H"], end_to_end=not seg, mod="erfnet", layers=18, channels_in=3,
                      pretrained=False, pool=True, activation_layer="square", no_cuda=False, order=3 if bp else 2, reg_ls=0.0,
                      use_cholesky=bp, mask_percentage=0.2 if bp else 0.3, clas=clas, no_mapping=False, precision=cfg["precision"])
     if bp:
@@ -120,7 +139,7 @@ def make_model(cfg):
     else:
         from lanedetection_end2end_amd.bev.Networks.LSQ_layer import Net
     model = Net(args)
-    model.net.load_state_dict(erfnet_oracle.make_params(seed=3, out_channels=cfg["K"]))
+    model.net.load_state_dict(erfnet_oracle.make_params(seed=3, out_channels=cfg["K"] + int(seg)))
     if clas:
         model.line_classification.load_state_dict(clas_oracle.make_clas_params("line", seed=11, tree=cfg["tree"]))
         model.horizon_estimation.load_state_dict(clas_oracle.make_clas_params("horizon", seed=12))
@@ -201,6 +220,51 @@ def run_detect(cfg, warmup, iters, repeats):
     return res
 
 
+def run_detect_seg(cfg, warmup, iters, repeats):
+    """detect of a segmentation-mode model: the three-step path against the fused call, alternated."""
+    from oracle import inputs
+    model = make_model(cfg)
+    model.check_singular = False          # (random weights at a random image: the timing does not depend on the statuses)
+    x = torch.from_numpy(inputs.images(cfg["N"], cfg["H"], cfg["W"], seed=1)).cuda()
+    call = lambda: model.detect(x)
+    tags = (False, "always")
+    ms, mem, status = {t: [] for t in tags}, {}, {}
+    for t in tags:
+        model.fused_seg_detect = t
+        for _ in range(warmup):
+            out = call()
+        status[t] = (model.last_status.clone(), [None if b is None else b.clone() for b in out[:4]])
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        out = call()
+        torch.cuda.synchronize()
+        mem[t] = torch.cuda.max_memory_allocated() - base
+        del out
+    same = torch.equal(status[False][0], status["always"][0]) and all(
+        (u is None and v is None) or torch.equal(u.contiguous().view(torch.uint8), v.contiguous().view(torch.uint8)) for u, v in zip(status[False][1], status["always"][1]))
+    for _ in range(repeats):
+        for t in tags:                        # alternated: both paths see the same clocks and neighbours
+            model.fused_seg_detect = t
+            for _ in range(warmup):
+                call()
+            ms[t].append(timed(call, iters))
+    res = {"config": cfg["name"], "same_bits": bool(same)}
+    for t, tag in ((False, "three_step"), ("always", "fused")):
+        med = statistics.median(ms[t])
+        res[tag] = {"ms_per_call": round(med, 4), "images_per_s": round(cfg["N"] * 1e3 / med, 1),
+                    "ms_min_max": [round(min(ms[t]), 4), round(max(ms[t]), 4)], "ms_all": [round(v, 4) for v in ms[t]],
+                    "peak_rise_mb": round(mem[t] / 1e6, 1)}
+    res["fused_over_three_step"] = round(statistics.median(ms[False]) / statistics.median(ms["always"]), 4)
+    # slower only if the ranges of the repeats do not overlap
+    res["fused_slower_beyond_range"] = bool(min(ms["always"]) > max(ms[False]))
+    model.fused_seg_detect = True
+    res["detect_default_takes"] = "fused" if cfg["N"] > 1 else "three_step"
+    del model, x
+    torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=5)
@@ -208,13 +272,23 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--configs", default="a,b,c")
     ap.add_argument("--detect", action="store_true", help="image -> lane coefficients: existing forward / inference forward / detect")
+    ap.add_argument("--out", default=None, help="also write the JSON result to this file")
     args = ap.parse_args()
     assert args.warmup >= 5 and args.iters >= 20, "at least 5 warm-up and 20 timed calls"
     if args.detect:
         cfgs = "a,b,c,c_clas" if args.configs == "a,b,c" else args.configs
+        runs = [(run_detect_seg if DETECT_CONFIGS[c].get("seg") else run_detect)(DETECT_CONFIGS[c], args.warmup, args.iters, args.repeats)
+                for c in cfgs.split(",")]
         out = {"tool": "infer_bench --detect", "device": torch.cuda.get_device_name(0), "warmup": args.warmup, "iters": args.iters,
-               "repeats": args.repeats, "results": [run_detect(DETECT_CONFIGS[c], args.warmup, args.iters, args.repeats) for c in cfgs.split(",")]}
+               "repeats": args.repeats, "results": runs}
+        if any(DETECT_CONFIGS[c].get("seg") for c in cfgs.split(",")):
+            out["seg_baseline"] = ("three_step = detect with fused_seg_detect off: the inference-engine forward, lf_seg_maps and the "
+                                   "fit of the same build, bit for bit the code detect ran before lf_lane_infer_seg existed")
         print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(out, f, indent=1)
+                f.write("\n")
         return
     out = {"tool": "infer_bench", "device": torch.cuda.get_device_name(0), "warmup": args.warmup, "iters": args.iters,
            "repeats": args.repeats, "results": [run(CONFIGS[c], args.warmup, args.iters, args.repeats) for c in args.configs.split(",")]}
