@@ -8,6 +8,8 @@
 // with NHWC fp32 activations, K = (taps x source channels) contracted on the matrix cores.
 // Weight gradients are the transposed contraction over pixels (lf_tapwgrad).
 #pragma once
+#include <atomic>
+
 #include "lf_common.h"
 
 #define LF_MAX_TAPS 9
@@ -61,12 +63,8 @@ struct LfTapArgs {
     unsigned long long* dbg;  // optional: per-wave phase timestamps (s_memtime), 8 words per wave (tools/kbench.py --phases)
 };
 
-// ---- lf_conv.hip: forward and data-gradient launches, their routing switches and counters ----
+// ---- lf_conv.hip: forward and data-gradient launches, the fp32 kernels' routing switches and the counters of both routes ----
 void lf_tapgemm_set_split_any_size(int v);
-void lf_tapgemm_set_bf16_lds(int v);
-int lf_tapgemm_bf16_lds();                          // the value set (the 16-channel weight gradient's LDS rings follow it: lf_wgrad.hip)
-void lf_tapgemm_set_bf16_no_partial_fast(int v);   // 1: launches with Cs % 32 != 0 decline the compiled-in whole-step forms (tests)
-long lf_tapgemm_partial_fast_launches();            // launches with Cs % 32 != 0 that took a compiled-in whole-step form since the process started (tests)
 void lf_tapgemm_set_fp32_stream(int mode, int max_workgroups);   // tapstream_kernel routing (lf_debug_set_fp32_stream, lf_debug.h)
 int lf_tapgemm_stat_rows(const LfTapGeom& g);                          // upper bound over the kernels (buffer sizing)
 int lf_tapgemm_stat_rows_for(const LfTapGeom& g, const LfTapArgs& a);  // rows the launch with these arguments writes
@@ -77,6 +75,15 @@ int lf_tapgemm_launch_unordered(const LfTapGeom& g, const LfTapArgs& a, int pro,
 bool lf_tapgemm_split_ok(const LfTapGeom& g);
 // launches that took a compiled-in bias + residual + ReLU epilogue since the process started (kernel-level tests)
 long lf_tapgemm_bias_residual_launches();
+extern std::atomic<long> g_bres_launches;           // ... the counter itself: ONE object, which both routes increment
+
+// ---- lf_conv_bf16.hip: the kernels on bf16 tensors, their route, routing switches and counters ----
+// lf_tapgemm_launch's route for a launch with packed bf16 weights (a.wp16), after its checks: epis, npix, nt and grid are its values
+int lf_tapgemm_bf16_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, int epis, long npix, int nt, dim3 grid, hipStream_t st);
+void lf_tapgemm_set_bf16_lds(int v);
+int lf_tapgemm_bf16_lds();                          // the value set (the 16-channel weight gradient's LDS rings follow it: lf_wgrad.hip)
+void lf_tapgemm_set_bf16_no_partial_fast(int v);   // 1: launches with Cs % 32 != 0 decline the compiled-in whole-step forms (tests)
+long lf_tapgemm_partial_fast_launches();            // launches with Cs % 32 != 0 that took a compiled-in whole-step form since the process started (tests)
 
 // ---- lf_wgrad.hip: weight gradients and their split-K reductions (lf_tapwgrad_ro_*: lf_wgrad_ro.hip) ----
 struct LfWgradArgs {

@@ -19,168 +19,15 @@
 //   tapstream_kernel          fp32, the 3-tap convolutions at 64 / 128 channels: weights resident in LDS, pixels streamed past them
 //   tapgemm_lean_kernel       16-channel layers in fp32 (HBM-bound)
 //   tapgemm_split_kernel      precision mode fp32x9: fp32 results from exact 3-way bf16 splits on the bf16 matrix cores
-//   tapgemm_bf16_kernel       precision mode bf16, operands streamed into registers (operand prologue, ragged widths)
-//   tapgemm_bf16_wl_kernel    bf16 tensors, the 3-tap convolutions at 64 / 128 channels: memory touched in whole 128-byte lines
-//                             (LDS-DMA operand ring, weights in registers, LDS-transposed stores)
-//   tapgemm_bf16_wv_kernel    bf16 tensors, the 3-tap convolutions at 64 channels: a wave owns its pixels and all 64 output channels
-//   tapgemm_bf16_ring_kernel  bf16 tensors, every other tap table: persistent LDS-DMA ring
-//   tapgemm_bf16_lean_kernel  bf16 tensors, 16 -> 16 channels (two taps per K = 32 MFMA)
-// The weight gradients with their split-K reductions are in lf_wgrad.hip, the weight-packing and BatchNorm-fold kernels in
-// lf_pack.hip; the device helpers shared with lf_wgrad.hip are in lf_conv_dev.h.
-// The tap-GEMM kernels share one epilogue (LF_TAPGEMM_EPILOGUE: bias, ReLU, masks, residual, BN sums); the whole-line kernel has
-// its own (same arithmetic, output and operand tensors through LDS tiles).
+// All four take fp32 tensors; lf_tapgemm_launch, at the end of the file, routes a launch to one of them or, for bf16 tensors, to
+// lf_tapgemm_bf16_route.  The kernels on bf16 tensors and that route are in lf_conv_bf16.hip, the weight gradients with their
+// split-K reductions in lf_wgrad.hip, the weight-packing and BatchNorm-fold kernels in lf_pack.hip; the device helpers and launch
+// helpers shared with lf_conv_bf16.hip and lf_wgrad.hip are in lf_conv_dev.h.
+// The tap-GEMM kernels of both files share one epilogue (LF_TAPGEMM_EPILOGUE, lf_conv_epi.h: bias, ReLU, masks, residual, BN sums).
 #include "lf_conv_dev.h"
+#include "lf_conv_epi.h"
 
 namespace {
-
-#define LF_EPI_GROUPS 1      /* 4-wave groups per workgroup; the 512-thread split kernel redefines it */
-#define LF_EPI_ONE_TILE false  /* tapgemm_kernel: true for the per-lane-row form of the three-tensor epilogue (one register short) */
-#define LF_EPI_TID threadIdx.x  /* tapgemm_kernel: its per-tile laundered copy */
-#define LF_EPI_ROW1 false      /* tapgemm_kernel: its ROW1 (a wave's 64 pixels in one image row) */
-#define LF_EPI_PIVOT true      /* BN forward sums about a pivot (below); the run-time-flag forms of the 128-register split kernel and of the LDS-ring \
-                                  kernels (cold paths: no network launch) have no registers for it and sum about 0 -- same row format */
-#define LF_EPI_ACC(n, m) acc[n][m]   /* the finished sum of channel tile n, pixel tile m (tapstream_kernel: its one live pixel tile) */
-#define LF_EPI_FIRST(m) ((m) == 0)   /* the pixel tile whose first pixel is the pivot of the BN forward sums */
-#define LF_EPI_ROW_OK(tg) true       /* 4-wave group tg owns a tile of the launch (tapstream_kernel: the last pair of tiles may be half empty) */
-/* The epilogue in three parts, so that a kernel can run the per-pixel-tile part one tile at a time (tapstream_kernel); LF_TAPGEMM_EPILOGUE
- * below is the three in a row, the form every other kernel expands. */
-#define LF_EPI_HEAD \
-    /* Pixel-tile outer, channel-tile inner: the loads of one operand tensor issued back to back cover one pixel's     \
-     * contiguous channel run, so every cache line is touched once while it is hot (the channel-tile-outer order        \
-     * revisited each line NT times with the whole grid's working set in between: 4x the HBM reads with bf16 tensors). \
-     * The channel tiles of a pixel tile go in chunks of NC = 2 (one 128-byte line of fp32): with all NT tiles' operand \
-     * loads in flight at once the three-tensor epilogues (ADD + MASK + BN-backward sums) needed 270+ registers and     \
-     * spilled 13-29 of them to scratch.  NOBIAS: data-gradient epilogues (compiled-in flags) carry no bias vector. */  \
-    const bool stats = (epi & (LF_EPI_STATS_SQ | LF_EPI_STATS_XHAT)) != 0; \
-    constexpr bool NOBIAS = EPIC >= 0 && !(EPIC & LF_EPI_BIAS) && (EPIC & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) != 0; \
-    constexpr int NC = (NT % 2 == 0 && !LF_EPI_ONE_TILE) ? 2 : 1; \
-    /* MASKBN + STATS_XHAT: the mask's two per-channel vectors are re-read (L1) instead of held -- 32 registers, the difference \
-     * between two and three waves per SIMD for that variant */ \
-    constexpr bool HOISTM = HOISTV && !(EPIC >= 0 && (EPIC & LF_EPI_MASKBN) && (EPIC & LF_EPI_STATS_XHAT)); \
-    const __amdgpu_buffer_rsrc_t r_dst = make_rsrc(a.dst, 0xffffffffu), r_add = make_rsrc(a.add_src, 0xffffffffu), \
-                                 r_msk = make_rsrc(a.mask_src, 0xffffffffu), r_aux = make_rsrc(a.aux, 0xffffffffu), \
-                                 r_bias = make_rsrc(a.bias, 0xffffffffu), r_msc = make_rsrc(a.msc, 0xffffffffu), \
-                                 r_msh = make_rsrc(a.msh, 0xffffffffu), r_dm = make_rsrc(a.dm, 0xffffffffu); \
-    /* BatchNorm FORWARD statistics (STATS_SQ) are accumulated about a PIVOT: per channel the value of the wave's first pixel   \
-     * (lane 0 of the 16-lane row, broadcast by DPP): sum (v - piv), sum (v - piv)^2.  With |v - piv| ~ sigma neither sum loses the  \
-     * digits that sum v^2 loses when |mean| >> sigma -- E[v^2] - mean^2 from fp32 partials kept 2^-24 (mean / sigma)^2 of the    \
-     * variance: 2.3e-4 on a parameter gradient at 50 sigma, where nn.BatchNorm2d has no such term (round 6).  A wave turns its   \
-     * sums into (sum v, M2 = sum (v - mean_wave)^2) of its 64 pixels, the workgroup's four waves are merged with Chan's formula    \
-     * (differences of wave means, never squares of sums), and the partial row of a 256-pixel tile is [sum v][M2 about the tile's  \
-     * own mean]; the finalise kernel merges the tiles in fp64 (LfStatPart::tile_pix). */ \
-    f32x4 s1[NT], s2[NT], bs[NOBIAS ? 1 : NT], hv[HOISTV ? NT : 1][2], piv[LF_EPI_PIVOT ? NT : 1]; \
-_Pragma("unroll") \
-    for (int n = 0; n < NT; ++n) { \
-        const int co = cob + n * 16 + kq * 4; \
-        s1[n] = zero4(); s2[n] = zero4(); piv[LF_EPI_PIVOT ? n : 0] = zero4(); \
-        if constexpr (!NOBIAS) bs[n] = a.bias ? ldb4(r_bias, co * 4u, 0u) : zero4(); \
-        if (HOISTV) { \
-            if (HOISTM && (epi & LF_EPI_MASKBN)) { hv[n][0] = ldb4(r_msc, co * 4u, 0u); hv[n][1] = ldb4(r_msh, co * 4u, 0u); } \
-        } \
-    }
-/* one 16-pixel tile m: operand loads, bias / residual / masks / ReLU, the stores and the per-lane statistics */
-#define LF_EPI_TILE(m) \
-    { \
-        const unsigned dbase = (unsigned)(((pn[m] * g.Hd + pi[m] * g.dsh + g.dah) * g.Wd + pj[m] * g.dsw + g.daw) * g.d_pix + g.d_choff + cob + kq * 4); \
-_Pragma("unroll") \
-        for (int n0 = 0; n0 < NT; n0 += NC) { \
-        f32x4 la[NC], lm[NC], lx[NC], ld[NC]; \
-_Pragma("unroll") \
-        for (int j = 0; j < NC; ++j) { \
-            const int n = n0 + j; \
-            if (epi & LF_EPI_ADD) la[j] = epi_ld<S16>(r_add, dbase + n * 16); \
-            if (epi & LF_EPI_MASK) lm[j] = epi_ld<S16>(r_msk, dbase + n * 16); \
-            if (epi & (LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) lx[j] = epi_ld<S16>(r_aux, dbase + n * 16); \
-            if ((epi & LF_EPI_STATS_XHAT) && a.dm && !LF_EPI_ROW1) ld[j] = ldb4(r_dm, (unsigned)(pn[m] * g.Cd + cob + n * 16 + kq * 4) * 4u, 0u); \
-        } \
-_Pragma("unroll") \
-        for (int j = 0; j < NC; ++j) { \
-            const int n = n0 + j; \
-            f32x4 v = LF_EPI_ACC(n, m); \
-            if constexpr (!NOBIAS) v += bs[n]; \
-            if (epi & LF_EPI_ADD) v += la[j]; \
-            if (epi & LF_EPI_MASK) v = keep_pos(v, lm[j]); \
-            const int co = cob + n * 16 + kq * 4;   /* per-channel vectors: L1-resident, re-read instead of held in registers */ \
-            if (epi & LF_EPI_MASKBN) v = keep_pos(v, lx[j] * (HOISTM ? hv[HOISTV ? n : 0][0] : ldb4(r_msc, co * 4u, 0u)) + (HOISTM ? hv[HOISTV ? n : 0][1] : ldb4(r_msh, co * 4u, 0u))); \
-            if (epi & LF_EPI_RELU) v = S16 ? relu_keep_nan(v) : max0(v); \
-            if (S16) v = round_bf16(v);   /* statistics are taken from the values as stored */ \
-            if (pv[m]) epi_st<S16>(r_dst, dbase + n * 16, v); \
-            if (!pv[m]) v = zero4(); \
-            if (epi & LF_EPI_STATS_SQ) { \
-                if (LF_EPI_PIVOT && LF_EPI_FIRST(m)) piv[LF_EPI_PIVOT ? n : 0] = bcast16(v); \
-                f32x4 dv = LF_EPI_PIVOT ? v - piv[LF_EPI_PIVOT ? n : 0] : v; \
-                if (!pv[m]) dv = zero4(); \
-                s1[n] += dv; s2[n] += dv * dv; \
-            } \
-            if (epi & LF_EPI_STATS_XHAT) { \
-                const f32x4 gm = (a.dm && !LF_EPI_ROW1) ? v * ld[j] : v; \
-                s1[n] += gm; s2[n] += gm * lx[j];      /* RAW second sum: the finalise kernel applies x^ = t * rstd - mean * rstd in fp64 */ \
-            } \
-        } \
-        } \
-    }
-/* once per 256-pixel tile: the wave's sums -> one partial row (DPP row sums, LDS staging, Chan merge of the four waves) */
-#define LF_EPI_TAIL \
-    if (LF_EPI_ROW1 && (epi & LF_EPI_STATS_XHAT) && a.dm) { \
-        /* a wave's pixels lie in ONE image: the Dropout2d factor of (image, channel) scales the wave's sums once */ \
-_Pragma("unroll") \
-        for (int n = 0; n < NT; ++n) { \
-            const f32x4 dmv = ldb4(r_dm, (unsigned)(pn[0] * g.Cd + cob + n * 16 + kq * 4) * 4u, 0u); \
-            s1[n] *= dmv; s2[n] *= dmv; \
-        } \
-    } \
-    if (stats) { \
-        /* one partial row per 256-pixel tile: 4-wave group EG of the workgroup (EG = 0 in the 256-thread kernels) */ \
-        const int EW = wave & 3, EG = wave >> 2; \
-        __shared__ float sred[LF_EPI_GROUPS][WG_WAVES][NT][4][8]; \
-_Pragma("unroll") \
-        for (int n = 0; n < NT; ++n) { \
-            f32x4 r1, r2; \
-            r1.x = sum16(s1[n].x); r1.y = sum16(s1[n].y); r1.z = sum16(s1[n].z); r1.w = sum16(s1[n].w); \
-            r2.x = sum16(s2[n].x); r2.y = sum16(s2[n].y); r2.z = sum16(s2[n].z); r2.w = sum16(s2[n].w); \
-            if (epi & LF_EPI_STATS_SQ) {      /* pivot sums -> (sum v, M2 about the wave's own mean) of the wave's nw valid pixels */ \
-                const unsigned lf_t0 = (bx * (unsigned)(WG_WAVES * LF_EPI_GROUPS) + (unsigned)wave) * 64u; \
-                const float nw = lf_t0 < npix ? (float)min(npix - lf_t0, 64u) : 0.f; \
-                const float rn = nw > 0.f ? 1.f / nw : 0.f; \
-                r2 = r2 - r1 * r1 * rn; \
-                r2.x = fmaxf(r2.x, 0.f); r2.y = fmaxf(r2.y, 0.f); r2.z = fmaxf(r2.z, 0.f); r2.w = fmaxf(r2.w, 0.f); \
-                if (LF_EPI_PIVOT) r1 = r1 + piv[LF_EPI_PIVOT ? n : 0] * nw; \
-            } \
-            if (pl == 0) { \
-                float* d = sred[EG][EW][n][kq]; \
-                d[0] = r1.x; d[1] = r1.y; d[2] = r1.z; d[3] = r1.w; d[4] = r2.x; d[5] = r2.y; d[6] = r2.z; d[7] = r2.w; \
-            } \
-        } \
-        __syncthreads(); \
-        if ((LF_EPI_TID & 255) < NT * 4 * 8 && LF_EPI_ROW_OK(LF_EPI_TID >> 8)) { \
-            const int tg = LF_EPI_TID >> 8, tt = LF_EPI_TID & 255; \
-            const int j = tt & 7, q = (tt >> 3) & 3, n = tt >> 5; \
-            float v = sred[tg][0][n][q][j] + sred[tg][1][n][q][j] + sred[tg][2][n][q][j] + sred[tg][3][n][q][j]; \
-            if ((epi & LF_EPI_STATS_SQ) && j >= 4) {      /* Chan: M2 = sum_w M2_w + sum_w n_w (mean_w - mean)^2 */ \
-                const unsigned lf_tb = (bx * (unsigned)LF_EPI_GROUPS + (unsigned)tg) * (unsigned)(WG_WAVES * 64); \
-                float nwv[4], sw[4], nt = 0.f, st = 0.f; \
-_Pragma("unroll") \
-                for (int w = 0; w < 4; ++w) { \
-                    const unsigned t0w = lf_tb + (unsigned)w * 64u; \
-                    nwv[w] = t0w < npix ? (float)min(npix - t0w, 64u) : 0.f; \
-                    sw[w] = sred[tg][w][n][q][j - 4]; \
-                    nt += nwv[w]; st += sw[w]; \
-                } \
-                const float mg = nt > 0.f ? st / nt : 0.f; \
-_Pragma("unroll") \
-                for (int w = 0; w < 4; ++w) \
-                    if (nwv[w] > 0.f) { const float dmw = sw[w] / nwv[w] - mg; v += nwv[w] * dmw * dmw; } \
-            } \
-            const int co = cob + n * 16 + q * 4 + (j & 3); \
-            a.stats[((long)(j >> 2) * g.Cd + co) * a.stats_ld + ((long)bx * LF_EPI_GROUPS + tg)] = v;      /* channel-major rows */ \
-        } \
-    }
-#define LF_TAPGEMM_EPILOGUE \
-    __builtin_amdgcn_s_setprio(3);   /* ahead of the partner wave's MFMA stream: the sooner this wave retires, the sooner its slot refills */ \
-    LF_EPI_HEAD \
-_Pragma("unroll") \
-    for (int m = 0; m < MT; ++m) LF_EPI_TILE(m) \
-    LF_EPI_TAIL
 
 constexpr size_t LF_TAP_LDS_PER_TAP = (size_t)WG_WAVES * 64 * (sizeof(uint4) + sizeof(unsigned));
 
@@ -621,1208 +468,6 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void tapstream_kernel(cons
 }
 
 // ---------------------------------------------------------------------------------------
-// bf16 matrix-core kernel, operands streamed into registers (precision mode "bf16": bf16 tensors in HBM, fp32 accumulate; the
-// launches the LDS kernels below do not take: operand prologue, ragged widths, tap tables with few pixels).
-// v_mfma_f32_16x16x32_bf16: a lane supplies 8 consecutive k of its row / column (k-block kq = l>>4 of the 32-channel step), C/D
-// layout as the fp32 form -- so the tap table, the pixel mapping and the whole epilogue are shared with tapgemm_kernel.  Per
-// 32-channel step a lane loads ONE dwordx4 of its pixel (8 bf16 channels: the operand as it is), or, with the BN+ReLU prologue,
-// widens it, applies the prologue and the validity mask in fp32 and converts back with v_cvt_pk_bf16_f32 (round to nearest even);
-// 16 MFMAs (one per 16x16 tile) per step.  Weights are pre-packed bf16 [tap][ceil(Cs/32)*4][Cd][8], zero-padded to whole
-// 32-channel steps, so the partial last step of a 16- or 48-channel contraction multiplies (valid, clamped) pixel data by zeros.
-// At the bf16 rate (16 cycles per MFMA) the loop is bound by the operand path, not by the matrix cores.
-// (Through round 5 the kernel also took fp32 tensors -- precision mode "bf16_mfma": removed, no BASELINE configuration used it.)
-// ---------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bf16x8 cvt_bf16x8(f32x4 lo, f32x4 hi) {
-    bf16x8 r;
-    r[0] = (__bf16)lo.x; r[1] = (__bf16)lo.y; r[2] = (__bf16)lo.z; r[3] = (__bf16)lo.w;
-    r[4] = (__bf16)hi.x; r[5] = (__bf16)hi.y; r[6] = (__bf16)hi.z; r[7] = (__bf16)hi.w;
-    return r;
-}
-
-// EPIC >= 0: epilogue flags compiled in (as in tapgemm_kernel).  FAST (no prologue, whole 32-channel steps): a padding position
-// holds the out-of-range offset and reads as zero bits, the channel step is a scalar offset -- no per-step VALU work at all on
-// bf16 tensors, where the 16 MFMAs of a step take 256 cycles and every VALU instruction beside them ~13.
-template <int NT, int PROC, int EPIC = -1, bool FAST = false>
-__global__ __launch_bounds__(256, 2) void tapgemm_bf16_kernel(const LfTapGeom g, const LfTapArgs a, const int pro, const int epi_rt) {
-    static_assert(!FAST || PROC == 0, "FAST: the out-of-range zero must be the operand itself");
-    const int epi = EPIC >= 0 ? EPIC : epi_rt;
-    constexpr bool HOISTV = true, S16 = true;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pl = lane & 15, kq = lane >> 4;
-    const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl);
-    const int cob = blockIdx.y * NT * 16;
-    unsigned bx = blockIdx.x;
-    if ((gridDim.x & 7u) == 0) bx = (bx & 7u) * (gridDim.x >> 3) + (bx >> 3);
-    const unsigned tile0 = (bx * WG_WAVES + wave) * (MT * 16);
-
-    int pn[MT], pi[MT], pj[MT];
-    bool pv[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        const unsigned p = tile0 + m * 16 + pl;
-        pv[m] = p < npix;
-        const unsigned q = pv[m] ? p : 0u;
-        const unsigned r = q / (unsigned)g.Wl;
-        pj[m] = (int)(q - r * (unsigned)g.Wl);
-        pn[m] = (int)(r / (unsigned)g.Hl);
-        pi[m] = (int)(r - (unsigned)pn[m] * (unsigned)g.Hl);
-    }
-    f32x4 acc[NT][MT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n)
-#pragma unroll
-        for (int m = 0; m < MT; ++m) acc[n][m] = zero4();
-
-    // one dwordx4 per tile is the whole 8-channel operand (xl holds raw bf16 bits)
-    struct Step { u32x4 w[NT]; f32x4 xl[MT]; f32x4 sc0, sc1, sh0, sh1; unsigned ok; };
-    __shared__ uint4 tab_off[WG_WAVES][LF_MAX_TAPS][64];
-    __shared__ unsigned tab_ok[WG_WAVES][LF_MAX_TAPS][64];
-    const int ncb = (g.Cs + 31) >> 5;                       // 32-channel steps per tap
-    const int nsteps = g.ntaps * ncb;
-    // FAST with a partial last step (16 or 48 source channels): the table has one row per (tap, step) instead of one per tap -- the
-    // launcher admits nsteps <= LF_MAX_TAPS -- and a lane whose 8 channels lie at or beyond Cs holds the out-of-range offset: it
-    // reads the buffer bound's zeros, not the memory behind the pixel's channels (the next pixel, another tensor's slice: their
-    // Inf / NaN against the zero-padded weights would be NaN in every output channel).  Whole steps: one row per tap, as before.
-    const bool part = FAST && (g.Cs & 31) != 0;
-    const int nrows = part ? nsteps : g.ntaps;
-    for (int r = 0; r < nrows; ++r) {
-        const int t = part ? r / ncb : r, c0 = (part ? r - t * ncb : 0) * 32 + kq * 8;
-        const int dh = g.tdh[t], dw = g.tdw[t];
-        unsigned o[MT], okb = 0;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const int sy = pi[m] * g.ssh + dh, sx = pj[m] * g.ssw + dw;
-            const bool in = pv[m] && sy >= 0 && sy < g.Hs && sx >= 0 && sx < g.Ws;
-            const int syc = min(max(sy, 0), g.Hs - 1), sxc = min(max(sx, 0), g.Ws - 1);
-            o[m] = (unsigned)(((pn[m] * g.Hs + syc) * g.Ws + sxc) * g.s_pix + g.s_choff);
-            if constexpr (FAST) o[m] = (in && c0 < g.Cs) ? (o[m] + c0) * 2u : LF_OOB;      // bytes, this lane's 8 channels
-            okb |= (in ? 1u : 0u) << m;
-        }
-        tab_off[wave][r][lane] = make_uint4(o[0], o[1], o[2], o[3]);
-        tab_ok[wave][r][lane] = okb;
-    }
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.wp16, 0xffffffffu),
-                                 rx = make_rsrc(a.src, FAST ? (unsigned)min((long)g.N * g.Hs * g.Ws * g.s_pix * 2, (long)LF_OOB) : 0xffffffffu),
-                                 rsc = make_rsrc(a.pro_sc, 0xffffffffu), rsh = make_rsrc(a.pro_sh, 0xffffffffu);
-    const unsigned wlane = (unsigned)(kq * g.Cd + cob + pl) * 16u;      // bytes (8 bf16 per lane and tile)
-    const int wstep = g.Cd * 32;                            // bf16 elements per 32-channel step
-    const int ntaps = g.ntaps;
-    const int wlast = (nsteps - 1) * wstep;
-    int t_ld = 0, cb_ld = 0, wofs = 0;
-    auto issue = [&](Step& S) {
-        const bool live = t_ld < ntaps;
-        const int tc = live ? (part ? t_ld * ncb + cb_ld : t_ld) : nrows - 1;      // (scalar) a table ROW: per (tap, step) if part, else per tap; a dead step takes the last one
-        const uint4 o = tab_off[wave][tc][lane];
-        const unsigned okb = tab_ok[wave][tc][lane];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) S.w[n] = __builtin_bit_cast(u32x4, ldb4(rw, wlane + n * 256, (unsigned)wofs * 2u));
-        const int c8 = min(cb_ld * 32 + kq * 8, g.Cs - 8);  // a partial last step re-reads valid channels (weights are 0)
-        if constexpr (FAST) {
-            const unsigned dead = live ? 0u : LF_OOB;        // a dead step (odd step count) reads zeros
-            const unsigned cs = part ? 0u : (unsigned)cb_ld * 64u;      // (a per-step row holds its channel offset)
-            S.xl[0] = ldb4(rx, o.x | dead, cs); S.xl[1] = ldb4(rx, o.y | dead, cs);
-            S.xl[2] = ldb4(rx, o.z | dead, cs); S.xl[3] = ldb4(rx, o.w | dead, cs);
-        } else {                                             // buffer-addressed (see ldb4): bf16 elements, 16 bytes = 8 channels
-            S.xl[0] = ldb4(rx, (o.x + c8) * 2u, 0u);
-            S.xl[1] = ldb4(rx, (o.y + c8) * 2u, 0u);
-            S.xl[2] = ldb4(rx, (o.z + c8) * 2u, 0u);
-            S.xl[3] = ldb4(rx, (o.w + c8) * 2u, 0u);
-        }
-        if constexpr (PROC == LF_PRO_BNRELU) {
-            S.sc0 = ldb4(rsc, c8 * 4u, 0u); S.sc1 = ldb4(rsc, c8 * 4u + 16u, 0u);
-            S.sh0 = ldb4(rsh, c8 * 4u, 0u); S.sh1 = ldb4(rsh, c8 * 4u + 16u, 0u);
-        }
-        S.ok = live ? okb : 0u;
-        const int cbn = cb_ld + 1;
-        const bool wrap = cbn == ncb;
-        wofs = min(wofs + wstep, wlast);                    // a dead step re-reads the last live weights
-        cb_ld = live ? (wrap ? 0 : cbn) : cb_ld;
-        t_ld = (live && wrap) ? t_ld + 1 : t_ld;
-    };
-    auto mma = [&](const Step& S) {
-        bf16x8 xb[MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const bool in = FAST || ((S.ok >> m) & 1u);
-            if constexpr (PROC != LF_PRO_BNRELU) {       // raw bf16 bits: mask and use as they are
-                u32x4 r = __builtin_bit_cast(u32x4, S.xl[m]);
-                r.x = in ? r.x : 0u; r.y = in ? r.y : 0u; r.z = in ? r.z : 0u; r.w = in ? r.w : 0u;
-                xb[m] = __builtin_bit_cast(bf16x8, r);
-                continue;
-            }
-            f32x4 lo, hi;
-            {
-                const u32x4 r = __builtin_bit_cast(u32x4, S.xl[m]);
-                lo.x = __uint_as_float(r.x << 16); lo.y = __uint_as_float(r.x & 0xffff0000u);
-                lo.z = __uint_as_float(r.y << 16); lo.w = __uint_as_float(r.y & 0xffff0000u);
-                hi.x = __uint_as_float(r.z << 16); hi.y = __uint_as_float(r.z & 0xffff0000u);
-                hi.z = __uint_as_float(r.w << 16); hi.w = __uint_as_float(r.w & 0xffff0000u);
-            }
-            if constexpr (PROC == LF_PRO_BNRELU) { lo = max0(lo * S.sc0 + S.sh0); hi = max0(hi * S.sc1 + S.sh1); }
-            lo.x = in ? lo.x : 0.f; lo.y = in ? lo.y : 0.f; lo.z = in ? lo.z : 0.f; lo.w = in ? lo.w : 0.f;
-            hi.x = in ? hi.x : 0.f; hi.y = in ? hi.y : 0.f; hi.z = in ? hi.z : 0.f; hi.w = in ? hi.w : 0.f;
-            xb[m] = cvt_bf16x8(lo, hi);
-        }
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            const bf16x8 wb = __builtin_bit_cast(bf16x8, S.w[n]);
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-                acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb, xb[m], acc[n][m], 0, 0, 0);
-        }
-    };
-    static_assert(MT == 4, "tab_off packs 4 pixel tiles");
-    Step A, B;
-    issue(A);
-    const int npairs = (nsteps + 1) >> 1;
-    for (int pr = 0; pr < npairs; ++pr) {
-        issue(B);
-        mma(A);
-        issue(A);
-        mma(B);
-    }
-#undef LF_EPI_PIVOT
-#define LF_EPI_PIVOT (EPIC >= 0 || NT < 4)      /* (the 64-channel-slab run-time-flag forms have no registers for the pivot: 282-810 spilled) */
-    LF_TAPGEMM_EPILOGUE
-#undef LF_EPI_PIVOT
-#define LF_EPI_PIVOT true
-}
-
-// ---------------------------------------------------------------------------------------
-// bf16 tensors through LDS (round 4): the launches of precision mode "bf16" without an operand prologue.  Two kernels,
-// tapgemm_bf16_ring_kernel (any tap table; 32-channel K-steps) and tapgemm_bf16_wl_kernel (the 3-tap convolutions, whole
-// 128-byte lines), share the machinery below: operands travel by `buffer_load_dwordx4 ... lds` (LDS-DMA: no register is held
-// while the load is in flight) into a ring of LDS stages; the ring is ordered by hand --
-//     s_waitcnt vmcnt(N) lgkmcnt(0)   my DMA of this step has landed (N instructions of younger steps may be in flight) and my
-//                                     fragment reads of the step before have retired
-//     s_barrier                       ... everyone's
-//     issue the step that is R - 1 ahead into the stage the previous step occupied; read fragments; MFMAs
-// -- with the bare s_barrier, because __syncthreads() carries a release fence that drains vmcnt to 0, i.e. the whole ring, every
-// step.  The lgkmcnt(0) is not optional: hipcc moves a step's last MFMAs, and the waits for their operands, behind the next
-// barrier, and a DMA instruction whose pixels are all padding returns its zeros without a memory round trip and overtakes those
-// reads (wrong tiles in one launch of three at dilation 8 and row width 80 before the wait was there).
-// ---------------------------------------------------------------------------------------
-constexpr int LB_STAGES = 3;
-constexpr int LB_X_BYTES = WG_WAVES * 64 * 64;          // 16 KB
-constexpr int LB_W_BYTES = 4 * 64 * 16;                 // 4 KB
-constexpr int LB_STAGE_BYTES = LB_X_BYTES + LB_W_BYTES;
-
-// (lds_dma16, make_rsrc_words, wait_vm_lgkm0: lf_ldsdma.h)
-
-// ---------------------------------------------------------------------------------------
-// tapgemm_bf16_ring_kernel: LDS-staged bf16 tap-GEMM for ANY tap table (the 9-tap stride-2 convolution, the transposed-convolution
-// phases, their gradients; the 3-tap convolutions go to tapgemm_bf16_wl_kernel), 64-output-channel slabs, 32-channel K-steps.
-//
-// Stage (20 KB) = X [wave 4][pixel 64][slot 4][16 B] + W [k-block 4][cout 64][16 B], 3 stages: two workgroups per CU.
-//  * X: DMA instruction m of wave w carries pixels w*64 + m*16 + (lane >> 2), 16 bytes (8 channels) per lane, lane-linear in LDS
-//    (that is what LDS-DMA does); a pixel's four 16-byte slots are XOR-swizzled by (pixel >> 2) & 3 -- applied to the SOURCE channel
-//    block of the lane -- so that the fragment read of 8 consecutive lanes touches 8 different bank groups.  A padding tap
-//    position carries the out-of-range offset: the DMA writes zeros.
-//  * W: the packed bf16 weights [tap][k-block][Cd][8] make a (tap, 32-channel) step's 64-channel slab four 1 KB runs: one DMA
-//    instruction per wave, fragment reads contiguous.
-//  * PERSISTENT: a workgroup walks its work items (pixel tile x output-channel slab) and its load cursor runs two K-steps ahead
-//    of the compute cursor ACROSS item boundaries: the first operands of the next item land while this item's epilogue stores
-//    (the one-tile form of this kernel spent 2.7 of its 13 us building a per-lane tap table and 2.8 in the epilogue with the
-//    memory pipe idle: profiles/r4_bf16_phases_one_tile.txt).
-//  * No tap table: the launcher admits geometries whose 16-pixel groups lie in one image row (Wl % 16 == 0), so a DMA
-//    instruction's 16 pixels share (image, row) -- wave-uniform, scalar registers: ONE division pair per wave and item -- and a
-//    lane's byte offset is a scalar base plus a per-lane constant, with the column test (one unsigned compare) selecting the
-//    out-of-range offset for padding.
-// K order = tapgemm_bf16_kernel's: results bit-identical (tools/bf16_ab.py).  (A form owning all 128 output channels per
-// workgroup -- X through the ring once per tap -- and the one-tile form are in DESIGN.md section 9.)
-// ---------------------------------------------------------------------------------------
-struct RingGroups { int n[4], i[4], j[4]; bool ok[4]; };
-// the four consecutive 16-pixel groups from group index G0 on: (image, row, first column), all wave-uniform
-__device__ __forceinline__ void groups_at(unsigned G0, int Hl, unsigned GR, unsigned ngroups, RingGroups& o) {
-    const unsigned Gc = G0 < ngroups ? G0 : 0u;
-    const unsigned R = Gc / GR;
-    int jg = __builtin_amdgcn_readfirstlane((int)(Gc - R * GR));
-    int n = __builtin_amdgcn_readfirstlane((int)(R / (unsigned)Hl));
-    int i = __builtin_amdgcn_readfirstlane((int)R) - n * Hl;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        o.ok[m] = G0 + m < ngroups;
-        o.n[m] = n; o.i[m] = i; o.j[m] = jg * 16;
-        if (++jg == (int)GR) { jg = 0; if (++i == Hl) { i = 0; ++n; } }
-    }
-}
-// ... of wave `wave` of the 256-pixel tile `tile`
-__device__ __forceinline__ void ring_groups(unsigned tile, int wave, int Hl, unsigned GR, unsigned ngroups, RingGroups& o) {
-    groups_at((tile * WG_WAVES + (unsigned)wave) * 4u, Hl, GR, ngroups, o);
-}
-
-// DBG: per-wave stamps, 16 x uint64 per wave: start, hardware id, then (K loop done, epilogue stores retired) per item, 7 items
-template <int EPIC, bool DBG = false>
-__global__ __launch_bounds__(256, 2) void tapgemm_bf16_ring_kernel(const LfTapGeom g, const LfTapArgs a, const int pro, const int epi_rt) {
-    constexpr bool S16 = true, HOISTV = true;
-    unsigned long long* dbgp = nullptr;
-    int dbgk = 0;
-    if constexpr (DBG) {
-        dbgp = a.dbg + ((unsigned long long)blockIdx.x * WG_WAVES + (threadIdx.x >> 6)) * 16;
-        if ((threadIdx.x & 63) == 0) {
-            unsigned hwid, xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            dbgp[0] = __builtin_amdgcn_s_memrealtime();
-            dbgp[1] = (unsigned long long)hwid | ((unsigned long long)xcc << 32);
-        }
-    }
-    constexpr int STAGE = LB_STAGE_BYTES;
-    const int epi = EPIC >= 0 ? EPIC : epi_rt;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int pl = lane & 15, kq = lane >> 4;
-    const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl), ngroups = npix >> 4, GR = (unsigned)g.Wl >> 4;
-    const unsigned ntiles = (npix + PIX_PER_WG - 1) / PIX_PER_WG;
-    const int slsh = g.Cd > 64 ? 1 : 0;                           // output-channel slabs per pixel tile: 1 or 2
-    const unsigned nitems = ntiles << slsh;
-    // work items first, first + stride, ... inside this XCD's contiguous range (see tapgemm_kernel)
-    unsigned it_first = blockIdx.x, it_stride = gridDim.x, it_end = nitems;
-    if ((gridDim.x & 7u) == 0 && (nitems & 7u) == 0) {
-        const unsigned per = nitems >> 3;
-        it_first = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); it_stride = gridDim.x >> 3; it_end = (blockIdx.x & 7u) * per + per;
-    }
-    // tap offsets: tap t in lane t (read back with v_readlane: no dependent scalar loads in the issue path)
-    int tapv = 0;
-#pragma unroll
-    for (int t = 0; t < LF_MAX_TAPS; ++t)
-        if (lane == t) tapv = (g.tdh[t] & 0xffff) | (g.tdw[t] << 16);
-
-    const int ncb = g.Cs >> 5;
-    const int nsteps = g.ntaps * ncb;
-    const i32x4s rx = make_rsrc_words(a.src, (unsigned)min((long)g.N * g.Hs * g.Ws * g.s_pix * 2, (long)LF_OOB)),
-                 rw = make_rsrc_words(a.wp16, 0xffffffffu);
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lf_tap_lds;
-    unsigned char* const stages = lf_tap_lds;
-    const int wstep = g.Cd * 64;                               // bytes per 32-channel step (4 k-blocks x Cd x 16)
-    const int spix2 = g.s_pix * 2;
-    // per-lane constants of the DMA mapping: instruction m, this lane -> pixel (group m) + (lane >> 2), channel block
-    // (lane & 3) ^ ((lane >> 4) & 3) of the 32-channel step
-    const int dq = lane >> 2, dkq = (lane & 3) ^ ((lane >> 4) & 3);
-    const unsigned lane_x = (unsigned)((dq * g.ssw * g.s_pix + g.s_choff + dkq * 8) * 2);
-    const int lane_dx = dq * g.ssw;
-    const unsigned lane_w = (unsigned)((wave * g.Cd + lane) * 16);
-
-    // ---- load cursor (wave-uniform): item, tap, channel block, ring stage; the item's four groups as (pixel index of the
-    // row position without the tap, row, column) and a validity mask
-    unsigned it_ld = it_first;
-    int t_ld = 0, cb_ld = 0, st_ld = 0, wofs = 0, cob_ld = 0;
-    int lrow[4], liy[4], lsx[4];
-    unsigned lok = 0;
-    auto cursor_item = [&]() {
-        lok = 0;
-        if (it_ld < it_end) {
-            RingGroups G;
-            ring_groups(it_ld >> slsh, wave, g.Hl, GR, ngroups, G);
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                liy[m] = G.i[m] * g.ssh; lsx[m] = G.j[m] * g.ssw;
-                lrow[m] = (G.n[m] * g.Hs + liy[m]) * g.Ws + lsx[m];
-                lok |= G.ok[m] ? 1u << m : 0u;
-            }
-            cob_ld = (int)(it_ld & (unsigned)slsh) * 64;
-        } else {
-#pragma unroll
-            for (int m = 0; m < 4; ++m) { liy[m] = 0; lsx[m] = 0; lrow[m] = 0; }
-        }
-    };
-    cursor_item();
-    auto issue = [&]() {                                     // DMA of the cursor's step into stage st_ld
-        const unsigned st = lds0 + (unsigned)(st_ld * STAGE);
-        const int tv = __builtin_amdgcn_readlane(tapv, t_ld);
-        const int dh = (int)(short)(tv & 0xffff), dw = tv >> 16;
-        const int tapoff = dh * g.Ws + dw;
-        const unsigned xs = st + (unsigned)wave * 4096u;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const int sy = liy[m] + dh;
-            const bool yok = ((lok >> m) & 1u) && sy >= 0 && sy < g.Hs;
-            const unsigned base = (unsigned)((lrow[m] + tapoff) * spix2 + cb_ld * 64);
-            const bool in = yok && (unsigned)(lsx[m] + dw + lane_dx) < (unsigned)g.Ws;
-            lds_dma16(rx, xs + (unsigned)m * 1024u, in ? base + lane_x : LF_OOB, 0u);
-        }
-        lds_dma16(rw, st + (unsigned)(LB_X_BYTES + wave * 1024), lane_w + (unsigned)(cob_ld * 16), (unsigned)wofs);
-        // advance; past the last item the X part writes zeros (out-of-range offsets) into a stage nobody reads
-        st_ld = st_ld == LB_STAGES - 1 ? 0 : st_ld + 1;
-        wofs += wstep;
-        if (++cb_ld == ncb) {
-            cb_ld = 0;
-            if (++t_ld == g.ntaps) { t_ld = 0; wofs = 0; it_ld += it_stride; cursor_item(); }
-        }
-    };
-    issue();
-    issue();
-    // fragment addresses (bytes inside a stage)
-    const unsigned xfrag = (unsigned)(wave * 4096 + pl * 64 + ((kq ^ (pl >> 2)) & 3) * 16);       // + m * 1024
-    const unsigned wfrag = (unsigned)(LB_X_BYTES + (kq * 64 + pl) * 16);                           // + n * 256
-    int st_c = 0;
-    for (unsigned it = it_first; it < it_end; it += it_stride) {
-        constexpr int NT = 4;
-        f32x4 acc[NT][MT];
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[n][m] = zero4();
-        for (int s = 0; s < nsteps; ++s) {
-            // my DMA of this step has landed (the instructions of the next step may still be in flight) ...
-            asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();        // ... and everyone's; everyone is past the fragment reads of the step before
-            asm volatile("" ::: "memory");
-            issue();                             // two steps ahead -> the stage the previous step occupied
-            const unsigned char* st = stages + st_c * STAGE;
-            st_c = st_c == LB_STAGES - 1 ? 0 : st_c + 1;
-            bf16x8 xb[MT];
-#pragma unroll
-            for (int m = 0; m < MT; ++m) xb[m] = *reinterpret_cast<const bf16x8*>(st + xfrag + m * 1024);
-            bf16x8 wb[NT];
-#pragma unroll
-            for (int n = 0; n < NT; ++n) wb[n] = *reinterpret_cast<const bf16x8*>(st + wfrag + n * 256);
-#pragma unroll
-            for (int n = 0; n < NT; ++n)
-#pragma unroll
-                for (int m = 0; m < MT; ++m)
-                    acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[n], xb[m], acc[n][m], 0, 0, 0);
-        }
-        if constexpr (DBG) {
-            asm volatile("" ::"v"(acc[0][0][0]));
-            if (lane == 0 && dbgk < 7) dbgp[2 + 2 * dbgk] = __builtin_amdgcn_s_memrealtime();
-        }
-        // ---- epilogue of this item (the accumulator layout of tapgemm_bf16_kernel: tile m = group m, pixel m*16 + pl)
-        const unsigned bx = it >> slsh;
-        int pn[MT], pi[MT], pj[MT];
-        bool pv[MT];
-        {
-            RingGroups G;
-            ring_groups(bx, wave, g.Hl, GR, ngroups, G);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) { pn[m] = G.n[m]; pi[m] = G.i[m]; pj[m] = G.j[m] + pl; pv[m] = G.ok[m]; }
-        }
-        const int cob = (int)(it & (unsigned)slsh) * 64;
-#undef LF_EPI_PIVOT
-#define LF_EPI_PIVOT (EPIC >= 0)
-        LF_TAPGEMM_EPILOGUE
-#undef LF_EPI_PIVOT
-#define LF_EPI_PIVOT true
-        __builtin_amdgcn_s_setprio(0);
-        if constexpr (DBG) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0 && dbgk < 7) dbgp[3 + 2 * dbgk] = __builtin_amdgcn_s_memrealtime();
-            ++dbgk;
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the two trailing (dead) steps: nothing may land in LDS after this
-    __builtin_amdgcn_s_barrier();
-}
-
-// ---------------------------------------------------------------------------------------
-// tapgemm_bf16_wl_kernel ("whole lines"): the 3-tap bf16 convolutions of non_bottleneck_1d (Cs = Cd = 64 or 128, stride 1).
-//
-// tools/l2_stream.hip measures what bounds every bf16 kernel above (profiles/r4_l2_stream.txt): an instruction whose 64 lanes
-// touch 16 cache lines moves 16 lines' worth of L1 time whatever it uses of them.  The MFMA operand layout -- a lane = 16 bytes of
-// pixel l & 15 -- makes a register load take 64 bytes of each of 16 lines (3 taps of a 52 MB tensor: 26.9 us, 5.9 TB/s; the same
-// bytes as whole lines: 12.5 us, 12.5 TB/s), and the accumulator layout makes the epilogue store 8 bytes per lane, 32 of each
-// line (+17 us for 52 MB against +7 us as whole lines).  All of the above kernels sit at that ~44 us; this one touches memory
-// in whole 128-byte lines only:
-//  * X: LDS-DMA instructions of 8 pixels x 128 bytes (lane -> pixel l >> 3, 16-byte chunk l & 7) into a ring of K-steps of
-//    64 pixels x 64 channels (8 KB); the waves read MFMA fragments from it (chunk XOR (pixel >> 1) & 7 on the SOURCE side
-//    makes the ds_read_b128 lane groups conflict-free);
-//  * output: the epilogue writes bf16 quads into an LDS tile (16-byte chunks XOR pixel), barrier, then every wave stores
-//    1 KB instructions of 4 pixels x 256 bytes (8 x 128 at 64 channels);
-//  * W: NOT in LDS and not in the ring -- the workgroup's 64 pixels are shared by its four waves, each owning a quarter of the
-//    output channels (wave tile 64 pixels x Cd/4), so a wave's weights are 3 taps x Cs x Cd/4 = 24 KB at 128 channels: 96
-//    REGISTERS per lane, loaded once per persistent workgroup, statically indexed by the fully unrolled K loop.  The LDS
-//    is ring (4 to 8 stages of 8 KB, by variant) + output tile + the epilogue's operand tiles (WlCfg below) = at most 80 KB: two
-//    workgroups per CU, each with its ring's depth - 1 K-steps in flight.
-// Work item = 256 pixels (the BN-statistics row of the other kernels) as four 64-pixel sub-tiles; the ring runs across
-// sub-tiles and items.  K order = tapgemm_bf16_kernel's (tap, then channel): results bit-identical.
-// ---------------------------------------------------------------------------------------
-constexpr int WL_STAGE = 64 * 128;
-// Epilogue operand tensors (the data gradient's ReLU-mask source, residual gradient, BN-backward operand) come in whole lines too: by
-// LDS-DMA into tiles of the output tile's layout, issued behind the first K-step of the sub-tile they belong to and read by the
-// epilogue in the accumulator layout (8 bytes per lane from LDS instead of 32 of every 128-byte line from L2: +40 us per tensor and
-// launch at 80 x 160 x 64 images before).  The residual lands IN the output tile (each lane overwrites what it read); the other
-// two have their own tiles, which come out of the ring's depth: 2 x 80 KB per CU.
-template <int CB, int EPIC, int PROC = 0> struct WlCfg {
-    static constexpr int NT = CB / 2, KS = CB / 2, NSTEP = 3 * KS, CD = CB * 32, PIXB = CD * 2;
-    static constexpr int OUT_BYTES = 64 * PIXB;
-    static constexpr bool ST_ADD = EPIC >= 0 && (EPIC & LF_EPI_ADD) != 0, ST_MSK = EPIC >= 0 && (EPIC & LF_EPI_MASK) != 0,
-                          ST_AUX = EPIC >= 0 && (EPIC & (LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) != 0 &&
-                                   !(CB == 4 && (EPIC & LF_EPI_MASKBN) != 0);          // (that variant has no registers left for it: 7 spilled)
-    static constexpr int NBUF = (ST_MSK ? 1 : 0) + (ST_AUX ? 1 : 0);                  // tiles beside the output tile
-    static constexpr int NI = OUT_BYTES / 1024 / WG_WAVES;                            // 1 KB instructions per wave and tile
-    static constexpr int NAUXI = ((ST_ADD ? 1 : 0) + NBUF) * NI;                      // staging instructions per wave and sub-tile
-    static constexpr int MAXST = CB == 4 ? 6 : 8;
-    static constexpr int FIT = (80 * 1024 - OUT_BYTES * (1 + NBUF)) / WL_STAGE;
-    static constexpr int STAGES = FIT < MAXST ? FIT : MAXST;
-    static constexpr int TILES_END = STAGES * WL_STAGE + OUT_BYTES * (1 + NBUF);        // the prologue's scale / shift vectors live here
-    static constexpr size_t LDS = (size_t)TILES_END + (PROC ? 2 * CD * 4 : 0);
-    static_assert(STAGES >= 3, "ring too shallow");
-};
-
-// PROC = 1 (the block's third convolution: its operand is relu(bn1(t2)), never stored): behind its own vmcnt wait and in front of
-// the step's barrier every wave transforms the 16 pixels x 64 channels IT brought in, in place in the stage (fp32 math on the
-// widened values, tapgemm_bf16_kernel's expressions: results bit-identical), so the four waves that read the fragments do not
-// each redo it; padding pixels (zeros from the DMA) are kept zero by the same column / row test that issued them.
-template <int CB, int EPIC, int PROC = 0>
-__global__ __launch_bounds__(256, 2) void tapgemm_bf16_wl_kernel(const LfTapGeom g, const LfTapArgs a, const int pro, const int epi_rt) {
-    typedef WlCfg<CB, EPIC, PROC> C;
-    constexpr int NT = C::NT, KS = C::KS, NSTEP = C::NSTEP, S = C::STAGES, CD = C::CD, PIXB = C::PIXB, NCH = PIXB / 16;
-    constexpr bool S16 = true;
-    const int epi = EPIC >= 0 ? EPIC : epi_rt;
-    constexpr bool NOBIAS = EPIC >= 0 && !(EPIC & LF_EPI_BIAS) && (EPIC & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) != 0;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int pl = lane & 15, kq = lane >> 4;
-    const int cobw = wave * 16 * NT;                        // this wave's output channels
-    const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl), ngroups = npix >> 4, GR = (unsigned)g.Wl >> 4;
-    const unsigned nitems = (npix + PIX_PER_WG - 1) / PIX_PER_WG;
-    unsigned it_first = blockIdx.x, it_stride = gridDim.x, it_end = nitems;
-    if ((gridDim.x & 7u) == 0 && (nitems & 7u) == 0) {
-        const unsigned per = nitems >> 3;
-        it_first = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); it_stride = gridDim.x >> 3; it_end = (blockIdx.x & 7u) * per + per;
-    }
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lf_tap_lds;
-    unsigned char* const ring = lf_tap_lds;
-    unsigned char* const otile = lf_tap_lds + S * WL_STAGE;
-    unsigned char* const mtile = otile + C::OUT_BYTES;                                 // mask source (when staged)
-    unsigned char* const xtile = otile + C::OUT_BYTES * (C::ST_MSK ? 2 : 1);          // BN-backward operand (when staged)
-
-    // ---- this wave's weights -> registers: [tap][32-channel k-block][16-channel output tile], the MFMA A operand
-    bf16x8 wr[3][CB][NT];
-    {
-        const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.wp16, 0xffffffffu);
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int kb = 0; kb < CB; ++kb)
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-                    wr[t][kb][n] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
-                        rw, (int)((((t * CB + kb) * 4 + kq) * CD + cobw + n * 16 + pl) * 16), 0, 0));
-    }
-    // tap t's offsets in lane t, read back with v_readlane (a select chain over three values indexed by the run-time tap becomes an
-    // indexed array in scratch memory -- and the kernel-argument struct with it)
-    int tapv = 0;
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-        if (lane == t) tapv = (g.tdh[t] & 0xffff) | (g.tdw[t] << 16);
-    const i32x4s rx = make_rsrc_words(a.src, (unsigned)min((long)g.N * g.Hs * g.Ws * g.s_pix * 2, (long)LF_OOB));
-    const int spix2 = g.s_pix * 2;
-    // DMA mapping: this wave carries group `wave` of the sub-tile (pixels wave*16 ..+15) as two instructions jj of 8 pixels;
-    // lane -> pixel jj*8 + (lane >> 3), LDS slot lane & 7 = chunk XOR ((pixel >> 1) & 7)
-    const int dpx = lane >> 3;
-    unsigned lane_x[2];
-    int lane_dx[2];
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
-        const int chunk = (lane & 7) ^ ((jj * 4 + (lane >> 4)) & 7);
-        lane_x[jj] = (unsigned)(((jj * 8 + dpx) * g.s_pix + g.s_choff) * 2 + chunk * 16);
-        lane_dx[jj] = jj * 8 + dpx;
-    }
-    // ---- load cursor (wave-uniform): item, sub-tile, step; this wave's group of the cursor's sub-tile
-    unsigned it_ld = it_first;
-    int sub_ld = 0, s_ld = 0, st_ld = 0;
-    int lrow = 0, liy = 0, lsx = 0;
-    bool lok = false;
-    auto cursor_sub = [&]() __attribute__((always_inline)) {
-        lok = false;
-        if (it_ld < it_end) {
-            const unsigned G = (it_ld * 4u + (unsigned)sub_ld) * 4u + (unsigned)wave;
-            lok = G < ngroups;
-            const unsigned Gc = lok ? G : 0u;
-            const unsigned R = Gc / GR;
-            const int jg = __builtin_amdgcn_readfirstlane((int)(Gc - R * GR));
-            const int n = __builtin_amdgcn_readfirstlane((int)(R / (unsigned)g.Hl));
-            const int i = __builtin_amdgcn_readfirstlane((int)R) - n * g.Hl;
-            liy = i; lsx = jg * 16;
-            lrow = (n * g.Hs + i) * g.Ws + lsx;
-        }
-    };
-    cursor_sub();
-    auto issue = [&]() __attribute__((always_inline)) {
-        const int t = KS == 1 ? s_ld : s_ld >> 1, ks = KS == 1 ? 0 : s_ld & 1;
-        const int tv = __builtin_amdgcn_readlane(tapv, t);
-        const int dh = (int)(short)(tv & 0xffff), dw = tv >> 16;
-        const int sy = liy + dh;
-        const bool yok = lok && sy >= 0 && sy < g.Hs;
-        const unsigned base = (unsigned)((lrow + dh * g.Ws + dw) * spix2 + ks * 128);
-        const unsigned dst = lds0 + (unsigned)(st_ld * WL_STAGE + wave * 2048);
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const bool in = yok && (unsigned)(lsx + dw + lane_dx[jj]) < (unsigned)g.Ws;
-            lds_dma16(rx, dst + (unsigned)jj * 1024u, in ? base + lane_x[jj] : LF_OOB, 0u);
-        }
-        st_ld = st_ld == S - 1 ? 0 : st_ld + 1;
-        if (++s_ld == NSTEP) {
-            s_ld = 0;
-            if (++sub_ld == 4) { sub_ld = 0; it_ld += it_stride; }
-            cursor_sub();
-        }
-    };
-#pragma unroll
-    for (int i = 0; i < S - 1; ++i) issue();
-
-    float* const ptab = reinterpret_cast<float*>(lf_tap_lds + C::TILES_END);           // [2][CD]: scale, shift
-    if constexpr (PROC == LF_PRO_BNRELU) {
-        for (int c = threadIdx.x; c < CD; c += 256) { ptab[c] = a.pro_sc[c]; ptab[CD + c] = a.pro_sh[c]; }
-        __syncthreads();
-    }
-    // ---- staging of the epilogue's operand tensors: wave w carries group w of the sub-tile (NI instructions of 1 KB per tensor);
-    // instruction ii = w * NI + k is bytes ii*1024 .. +1023 of the pixel-major tile: lane -> pixel p, 16-byte slot = chunk XOR p
-    // (resources bounded by the tensor: the out-of-range offset of a group beyond it reads zeros)
-    const unsigned dbytes = (unsigned)min((long)g.N * g.Hd * g.Wd * g.d_pix * 2, (long)LF_OOB);
-    const i32x4s ra_add = make_rsrc_words(a.add_src, dbytes), ra_msk = make_rsrc_words(a.mask_src, dbytes), ra_aux = make_rsrc_words(a.aux, dbytes);
-    auto stage_tensors = [&](const RingGroups& G) __attribute__((always_inline)) {
-        if constexpr (C::NAUXI > 0) {
-            const int gn = wave == 0 ? G.n[0] : wave == 1 ? G.n[1] : wave == 2 ? G.n[2] : G.n[3];
-            const int gi = wave == 0 ? G.i[0] : wave == 1 ? G.i[1] : wave == 2 ? G.i[2] : G.i[3];
-            const int gj = wave == 0 ? G.j[0] : wave == 1 ? G.j[1] : wave == 2 ? G.j[2] : G.j[3];
-            const bool gok = wave == 0 ? G.ok[0] : wave == 1 ? G.ok[1] : wave == 2 ? G.ok[2] : G.ok[3];
-            const unsigned base = (unsigned)(((gn * g.Hd + gi) * g.Wd + gj) * g.d_pix * 2);
-            const unsigned dst0 = lds0 + (unsigned)(S * WL_STAGE + wave * C::NI * 1024);
-#pragma unroll
-            for (int k = 0; k < C::NI; ++k) {
-                const int ii = wave * C::NI + k;
-                const int p = (ii * 1024) / PIXB + (lane * 16) / PIXB, slot = ((lane * 16) % PIXB) / 16;
-                const unsigned st_lane = (unsigned)((((p & 15) * g.d_pix + g.d_choff) * 2) + ((slot ^ p) & (NCH - 1)) * 16);
-                const unsigned vo = gok ? base + st_lane : LF_OOB;                // (a whole group beyond the tensor: zeros)
-                if constexpr (C::ST_ADD) lds_dma16(ra_add, dst0 + (unsigned)(k * 1024), vo, 0u);
-                if constexpr (C::ST_MSK) lds_dma16(ra_msk, dst0 + (unsigned)(C::OUT_BYTES + k * 1024), vo, 0u);
-                if constexpr (C::ST_AUX) lds_dma16(ra_aux, dst0 + (unsigned)(C::OUT_BYTES * (C::ST_MSK ? 2 : 1) + k * 1024), vo, 0u);
-            }
-        }
-    };
-
-    // epilogue constants
-    const __amdgpu_buffer_rsrc_t r_dst = make_rsrc(a.dst, 0xffffffffu), r_add = make_rsrc(a.add_src, 0xffffffffu),
-                                 r_msk = make_rsrc(a.mask_src, 0xffffffffu), r_aux = make_rsrc(a.aux, 0xffffffffu),
-                                 r_bias = make_rsrc(a.bias, 0xffffffffu), r_msc = make_rsrc(a.msc, 0xffffffffu),
-                                 r_msh = make_rsrc(a.msh, 0xffffffffu), r_dm = make_rsrc(a.dm, 0xffffffffu);
-    // fragment read addresses inside a stage: pixel m*16 + pl (128 B rows), chunk kb*4 + kq XOR (pl >> 1) & 7
-    const unsigned xf0 = (unsigned)(pl * 128 + (((0 + kq) ^ (pl >> 1)) & 7) * 16), xf1 = (unsigned)(pl * 128 + (((4 + kq) ^ (pl >> 1)) & 7) * 16);
-    const bool stats = (epi & (LF_EPI_STATS_SQ | LF_EPI_STATS_XHAT)) != 0;
-    int st_c = 0;
-    for (unsigned bx = it_first; bx < it_end; bx += it_stride) {
-        constexpr bool PIVOT = EPIC >= 0;    // the pivot of the BN forward sums (see LF_TAPGEMM_EPILOGUE); the run-time-flag form sums about 0
-        f32x4 s1[NT], s2[NT], piv[PIVOT ? NT : 1];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) { s1[n] = zero4(); s2[n] = zero4(); piv[PIVOT ? n : 0] = zero4(); }
-        for (int sub = 0; sub < 4; ++sub) {
-            f32x4 acc[NT][MT];
-#pragma unroll
-            for (int n = 0; n < NT; ++n)
-#pragma unroll
-                for (int m = 0; m < MT; ++m) acc[n][m] = zero4();
-            RingGroups G;
-            groups_at((bx * 4u + (unsigned)sub) * 4u, g.Hl, GR, ngroups, G);
-#pragma unroll
-            for (int s = 0; s < NSTEP; ++s) {
-                // my DMA of this step has landed: exactly S - 2 younger ring steps of 2 instructions may be in flight -- plus, behind
-                // step 0, this sub-tile's staging instructions while the step's own DMA is older than they are (steps 1 .. S-1; the
-                // count must not EXCEED the younger instructions, or the wait passes early) ...
-                // ... and MY fragment reads of the step before have retired (lgkmcnt): hipcc moves that step's last MFMAs -- and the
-                // waits for their operands -- behind the barrier, and the stage is restaged right behind it: a DMA instruction whose 8
-                // pixels are all padding returns its zeros without a memory round trip and overtook those reads (wrong tiles in 1 of
-                // 3 launches at dilation 8, row width 80)
-                if (s >= 1 && s <= S - 1) wait_vm_lgkm0<2 * (S - 2) + C::NAUXI>();
-                else wait_vm_lgkm0<2 * (S - 2)>();
-                const int t = KS == 1 ? s : s >> 1, ks = KS == 1 ? 0 : s & 1;          // (compile-time after unrolling: wr is indexed statically)
-                if constexpr (PROC == LF_PRO_BNRELU) {
-                    // my part of this step's stage has landed: relu(bn(x)) on it, in place (the other waves read it behind the barrier)
-                    unsigned char* mine = ring + st_c * WL_STAGE + wave * 2048;
-                    const int tv = __builtin_amdgcn_readlane(tapv, t);
-                    const int dh = (int)(short)(tv & 0xffff), dw = tv >> 16;
-                    const int gi = wave == 0 ? G.i[0] : wave == 1 ? G.i[1] : wave == 2 ? G.i[2] : G.i[3];
-                    const int gj = wave == 0 ? G.j[0] : wave == 1 ? G.j[1] : wave == 2 ? G.j[2] : G.j[3];
-                    const bool gok = wave == 0 ? G.ok[0] : wave == 1 ? G.ok[1] : wave == 2 ? G.ok[2] : G.ok[3];
-                    const int sy = gi + dh;
-                    const bool yok = gok && sy >= 0 && sy < g.Hs;
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) {
-                        const bool in = yok && (unsigned)(gj + dw + lane_dx[jj]) < (unsigned)g.Ws;
-                        const int c0 = ks * 64 + (((lane & 7) ^ ((jj * 4 + (lane >> 4)) & 7)) * 8);      // this lane's 8 channels
-                        u32x4v r = *reinterpret_cast<const u32x4v*>(mine + jj * 1024 + lane * 16);
-                        const f32x4 sc0 = *reinterpret_cast<const f32x4*>(ptab + c0), sc1 = *reinterpret_cast<const f32x4*>(ptab + c0 + 4),
-                                    sh0 = *reinterpret_cast<const f32x4*>(ptab + CD + c0), sh1 = *reinterpret_cast<const f32x4*>(ptab + CD + c0 + 4);
-                        f32x4 lo, hv;
-                        lo.x = __uint_as_float(r[0] << 16); lo.y = __uint_as_float(r[0] & 0xffff0000u);
-                        lo.z = __uint_as_float(r[1] << 16); lo.w = __uint_as_float(r[1] & 0xffff0000u);
-                        hv.x = __uint_as_float(r[2] << 16); hv.y = __uint_as_float(r[2] & 0xffff0000u);
-                        hv.z = __uint_as_float(r[3] << 16); hv.w = __uint_as_float(r[3] & 0xffff0000u);
-                        lo = max0(lo * sc0 + sh0); hv = max0(hv * sc1 + sh1);
-                        lo.x = in ? lo.x : 0.f; lo.y = in ? lo.y : 0.f; lo.z = in ? lo.z : 0.f; lo.w = in ? lo.w : 0.f;
-                        hv.x = in ? hv.x : 0.f; hv.y = in ? hv.y : 0.f; hv.z = in ? hv.z : 0.f; hv.w = in ? hv.w : 0.f;
-                        *reinterpret_cast<bf16x8*>(mine + jj * 1024 + lane * 16) = cvt_bf16x8(lo, hv);
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // my writes are in the stage
-                }
-                __builtin_amdgcn_s_barrier();        // ... and everyone's; everyone is past the fragment reads of the step before
-                asm volatile("" ::: "memory");
-                issue();                             // S - 1 steps ahead -> the stage the previous step occupied
-                if (s == 0) stage_tensors(G);        // (everyone is past the previous sub-tile's reads of the tiles: the barrier above)
-                const unsigned char* st = ring + st_c * WL_STAGE;
-                st_c = st_c == S - 1 ? 0 : st_c + 1;
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb) {
-                    bf16x8 xb[MT];
-#pragma unroll
-                    for (int m = 0; m < MT; ++m) xb[m] = *reinterpret_cast<const bf16x8*>(st + (kb ? xf1 : xf0) + m * 2048);
-#pragma unroll
-                    for (int n = 0; n < NT; ++n)
-#pragma unroll
-                        for (int m = 0; m < MT; ++m)
-                            acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[t][ks * 2 + kb][n], xb[m], acc[n][m], 0, 0, 0);
-                }
-            }
-            // ---- epilogue of the sub-tile: accumulator tile (n, m) = channels cobw + n*16 + kq*4 .. +3 of pixel m*16 + pl
-            if constexpr (C::NAUXI > 0) {            // the staged tensors have landed: mine (the ring steps issued since are younger) ...
-                wait_vm_lgkm0<2 * (NSTEP - 1)>();
-                __builtin_amdgcn_s_barrier();        // ... and everyone's
-                asm volatile("" ::: "memory");
-            }
-            // (128 channels, MASKBN + BN-backward sums: the mask's per-channel vectors are re-read from L1 per use -- held, they are the
-            // 9 registers that variant would spill beside its 96 weight registers)
-            constexpr bool HOISTM = !(CB == 4 && EPIC >= 0 && (EPIC & LF_EPI_MASKBN) != 0 && (EPIC & LF_EPI_STATS_XHAT) != 0);
-            f32x4 bs[NOBIAS ? 1 : NT], hsc[HOISTM ? NT : 1], hsh[HOISTM ? NT : 1];
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-                const unsigned co = (unsigned)(cobw + n * 16 + kq * 4);
-                if constexpr (!NOBIAS) bs[n] = a.bias ? ldb4(r_bias, co * 4u, 0u) : zero4();
-                if constexpr (HOISTM) { if (epi & LF_EPI_MASKBN) { hsc[n] = ldb4(r_msc, co * 4u, 0u); hsh[n] = ldb4(r_msh, co * 4u, 0u); } }
-            }
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                const unsigned dbase = (unsigned)(((G.n[m] * g.Hd + G.i[m]) * g.Wd + G.j[m] + pl) * g.d_pix + g.d_choff + cobw + kq * 4);
-                f32x4 la[NT], lm[NT], lx[NT], ld[NT];
-                auto tile_ld = [&](const unsigned char* tile, int n) __attribute__((always_inline)) {      // this lane's 4 channels of (m, n)
-                    const int p = m * 16 + pl, chunk = (cobw + n * 16 + kq * 4) >> 3;
-                    const uint2 q = *reinterpret_cast<const uint2*>(tile + p * PIXB + ((chunk ^ p) & (NCH - 1)) * 16 + (kq & 1) * 8);
-                    f32x4 v;
-                    v.x = __uint_as_float(q.x << 16); v.y = __uint_as_float(q.x & 0xffff0000u);
-                    v.z = __uint_as_float(q.y << 16); v.w = __uint_as_float(q.y & 0xffff0000u);
-                    return v;
-                };
-#pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    if (epi & LF_EPI_ADD) la[n] = C::ST_ADD ? tile_ld(otile, n) : epi_ld<S16>(r_add, dbase + n * 16);
-                    if (epi & LF_EPI_MASK) lm[n] = C::ST_MSK ? tile_ld(mtile, n) : epi_ld<S16>(r_msk, dbase + n * 16);
-                    if (epi & (LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) lx[n] = C::ST_AUX ? tile_ld(xtile, n) : epi_ld<S16>(r_aux, dbase + n * 16);
-                    if ((epi & LF_EPI_STATS_XHAT) && a.dm) ld[n] = ldb4(r_dm, (unsigned)(G.n[m] * g.Cd + cobw + n * 16 + kq * 4) * 4u, 0u);
-                }
-#pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    f32x4 v = acc[n][m];
-                    if constexpr (!NOBIAS) v += bs[n];
-                    if (epi & LF_EPI_ADD) v += la[n];
-                    if (epi & LF_EPI_MASK) v = keep_pos(v, lm[n]);
-                    if (epi & LF_EPI_MASKBN) {
-                        const unsigned co = (unsigned)(cobw + n * 16 + kq * 4);
-                        v = keep_pos(v, lx[n] * (HOISTM ? hsc[HOISTM ? n : 0] : ldb4(r_msc, co * 4u, 0u)) + (HOISTM ? hsh[HOISTM ? n : 0] : ldb4(r_msh, co * 4u, 0u)));
-                    }
-                    if (epi & LF_EPI_RELU) v = max0(v);
-                    lf_bf16x4 b;
-                    b[0] = (lf_bf16)v.x; b[1] = (lf_bf16)v.y; b[2] = (lf_bf16)v.z; b[3] = (lf_bf16)v.w;
-                    // output tile: pixel p = m*16 + pl, 16-byte chunk (channel / 8) XOR p, half kq & 1
-                    const int p = m * 16 + pl, chunk = (cobw + n * 16 + kq * 4) >> 3;
-                    *reinterpret_cast<lf_bf16x4*>(otile + p * PIXB + ((chunk ^ p) & (NCH - 1)) * 16 + (kq & 1) * 8) = b;
-                    if (stats) {
-                        v.x = (float)b[0]; v.y = (float)b[1]; v.z = (float)b[2]; v.w = (float)b[3];     // statistics of the values as stored
-                        if (!G.ok[m]) v = zero4();
-                        if (epi & LF_EPI_STATS_SQ) {
-                            if (PIVOT && sub == 0 && m == 0) piv[PIVOT ? n : 0] = bcast16(v);      // the item's first pixel (this wave owns all 256 of its channels)
-                            f32x4 dv = PIVOT ? v - piv[PIVOT ? n : 0] : v;
-                            if (!G.ok[m]) dv = zero4();
-                            s1[n] += dv; s2[n] += dv * dv;
-                        }
-                        if (epi & LF_EPI_STATS_XHAT) {
-                            const f32x4 gm = a.dm ? v * ld[n] : v;
-                            s1[n] += gm; s2[n] += gm * lx[n];
-                        }
-                    }
-                }
-                if constexpr (!HOISTM) __builtin_amdgcn_sched_barrier(0);      // one pixel tile's operands at a time
-            }
-            __syncthreads();                          // the output tile is complete
-            // whole-line stores: instruction ii of the tile = bytes ii*1024 .. +1023 of the (pixel-major) tile
-            constexpr int NI = C::OUT_BYTES / 1024 / WG_WAVES;
-#pragma unroll
-            for (int k = 0; k < NI; ++k) {
-                const int ii = wave * NI + k;
-                const int p = (ii * 1024) / PIXB + (lane * 16) / PIXB;            // pixel of the sub-tile
-                const int slot = ((lane * 16) % PIXB) / 16;
-                const int grp = (ii * 1024 / PIXB) >> 4;                          // uniform: an instruction's pixels lie in one group
-                const int gn = grp == 0 ? G.n[0] : grp == 1 ? G.n[1] : grp == 2 ? G.n[2] : G.n[3];
-                const int gi = grp == 0 ? G.i[0] : grp == 1 ? G.i[1] : grp == 2 ? G.i[2] : G.i[3];
-                const int gj = grp == 0 ? G.j[0] : grp == 1 ? G.j[1] : grp == 2 ? G.j[2] : G.j[3];
-                const bool gok = grp == 0 ? G.ok[0] : grp == 1 ? G.ok[1] : grp == 2 ? G.ok[2] : G.ok[3];
-                if (gok) {
-                    const u32x4v v = *reinterpret_cast<const u32x4v*>(otile + ii * 1024 + lane * 16);
-                    const unsigned off = (unsigned)((((gn * g.Hd + gi) * g.Wd + gj + (p & 15)) * g.d_pix + g.d_choff) * 2 + ((slot ^ p) & (NCH - 1)) * 16);
-                    __builtin_amdgcn_raw_buffer_store_b128(v, r_dst, (int)off, 0, 0);
-                }
-            }
-            // (the next sub-tile's first barrier orders these reads of the output tile before its next writes)
-        }
-        if (stats) {
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-                f32x4 r1, r2;
-                r1.x = sum16(s1[n].x); r1.y = sum16(s1[n].y); r1.z = sum16(s1[n].z); r1.w = sum16(s1[n].w);
-                r2.x = sum16(s2[n].x); r2.y = sum16(s2[n].y); r2.z = sum16(s2[n].z); r2.w = sum16(s2[n].w);
-                if (epi & LF_EPI_STATS_SQ) {      // pivot sums -> (sum v, M2 about the item's own mean) of the item's valid pixels
-                    const unsigned t0 = bx * (unsigned)PIX_PER_WG;
-                    const float ni = t0 < npix ? (float)min(npix - t0, (unsigned)PIX_PER_WG) : 0.f;
-                    const float rn = ni > 0.f ? 1.f / ni : 0.f;
-                    r2 = r2 - r1 * r1 * rn;
-                    r2.x = fmaxf(r2.x, 0.f); r2.y = fmaxf(r2.y, 0.f); r2.z = fmaxf(r2.z, 0.f); r2.w = fmaxf(r2.w, 0.f);
-                    if (PIVOT) r1 = r1 + piv[PIVOT ? n : 0] * ni;
-                }
-                if (pl == 0) {            // channel-major rows: [2][Cd][stats_ld] (32-bit indices: 2 * Cd * stats_ld floats is far below 2^31)
-                    float* d = a.stats + (unsigned)((cobw + n * 16 + kq * 4) * a.stats_ld) + bx;
-                    const unsigned half = (unsigned)(g.Cd * a.stats_ld);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        d[(unsigned)(e * a.stats_ld)] = r1[e];
-                        d[half + (unsigned)(e * a.stats_ld)] = r2[e];
-                    }
-                }
-            }
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the trailing (dead) steps: nothing may land in LDS after this
-    __builtin_amdgcn_s_barrier();
-}
-
-// ---------------------------------------------------------------------------------------
-// tapgemm_bf16_wv_kernel ("wave-private", round 6): the 3-tap bf16 convolutions of non_bottleneck_1d at 64 channels.
-//
-// At 64 channels the whole-line kernel above shares a 64-pixel sub-tile between its four waves (each owns 16 output channels):
-// 24 MFMAs per wave between five workgroup barriers, and the launch sits at 4.0 TB/s of tensor bytes where the same kernel at 128
-// channels has twice the work per barrier.  But at 64 channels ALL the weights of the convolution are 3 taps x 64 x 64 x 2 B =
-// 24 KB = 96 registers per lane -- what a wave of the 128-channel form holds for its quarter of the output channels.  So here a
-// wave owns its pixels AND every output channel: wave tile = 32 pixels x 64 channels (8 accumulator tiles), the weights live in
-// its registers for the workgroup's life, its operands arrive by LDS-DMA in a PRIVATE ring (stage = one tap of its 32 pixels = 4 KB,
-// 4 instructions of 8 pixels x 128 B: whole lines), its output leaves through a private 4 KB tile as whole-line stores -- and no
-// instruction of the K loop or the epilogue waits for another wave: the only barriers are the two that merge the four waves'
-// BatchNorm partial sums into the 256-pixel statistics row, in the launches that take statistics.
-//   ring order (per wave):   s_waitcnt vmcnt(N) lgkmcnt(0)      my DMA of this step has landed; my fragment reads of the step before
-//                                                               have retired (their stage is restaged next)
-//                            issue the step R - 1 ahead; read fragments; 16 MFMAs
-// N counts the vector-memory instructions YOUNGER than the awaited DMA: 4 (R - 2) ring instructions, the item's staging
-// instructions behind its first step, and -- vmcnt retires loads AND stores in issue order on gfx9-family hardware -- the four
-// whole-line stores of the previous item's epilogue in front of an item's first step (all four are always issued: a group beyond
-// the tensor stores to the out-of-range offset, which the buffer unit drops).
-// Work: a workgroup walks 256-pixel tiles (the statistics rows of the other kernels) inside its XCD's range; wave w takes pixels
-// w*64 .. w*64+63 of the tile as two items of 32.  K order = tapgemm_bf16_kernel's (tap, then channel): results bit-identical.
-// Measured on one box (tools/bf16_ab.py, config 3's 64 x 80 x 160 x 64 launches, whole-line kernel -> this one): forward 52.1 -> 41.6 us,
-// data gradient + mask 65.0 -> 60.3 / 66.7 -> 58.1.  The BN+ReLU operand prologue (the block's third convolution) was built here
-// too -- the wave transforming the stage it brought in, in place, behind its own vmcnt wait -- and is SLOWER than the streaming
-// kernel's register form (102.9 vs 88.3 us: the transform sits between the wave's DMA wait and its fragment reads, three times per
-// pixel, with one partner wave to hide it): removed, those launches stay on tapgemm_bf16_kernel.
-// ---------------------------------------------------------------------------------------
-constexpr int WV_PX = 32, WV_STAGE = WV_PX * 128;
-template <int EPIC> struct WvCfg {
-    static constexpr bool ST_ADD = EPIC >= 0 && (EPIC & LF_EPI_ADD) != 0, ST_MSK = EPIC >= 0 && (EPIC & LF_EPI_MASK) != 0,
-                          ST_AUX = EPIC >= 0 && (EPIC & (LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) != 0;
-    static constexpr int NBUF = (ST_MSK ? 1 : 0) + (ST_AUX ? 1 : 0);                  // tiles beside the output tile
-    static constexpr int R = NBUF == 1 ? 3 : 4;                                       // ring stages (one extra tile: 3 keeps two workgroups per CU)
-    static constexpr int NAUXI = ((ST_ADD ? 1 : 0) + NBUF) * 4;                       // staging instructions per item
-    static constexpr int WAVE_LDS = (R + 1 + NBUF) * WV_STAGE;
-    static constexpr size_t LDS = (size_t)WG_WAVES * WAVE_LDS;
-};
-
-// (two workgroups per CU by LDS except with two staged operand tiles or run-time flags: those get the whole register file)
-template <int EPIC>
-__global__ __launch_bounds__(256, (EPIC >= 0 && WvCfg<EPIC>::NBUF < 2) ? 2 : 1) void tapgemm_bf16_wv_kernel(const LfTapGeom g, const LfTapArgs a, const int pro, const int epi_rt) {
-    typedef WvCfg<EPIC> C;
-    constexpr int NT = 4, MW = 2, R = C::R, CD = 64;
-    constexpr bool S16 = true;
-    const int epi = EPIC >= 0 ? EPIC : epi_rt;
-    constexpr bool NOBIAS = EPIC >= 0 && !(EPIC & LF_EPI_BIAS) && (EPIC & (LF_EPI_MASK | LF_EPI_ADD | LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) != 0;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int pl = lane & 15, kq = lane >> 4;
-    const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl), ngroups = npix >> 4, GR = (unsigned)g.Wl >> 4;
-    const unsigned ntiles = (npix + PIX_PER_WG - 1) / PIX_PER_WG;
-    unsigned it_first = blockIdx.x, it_stride = gridDim.x, it_end = ntiles;
-    if ((gridDim.x & 7u) == 0 && (ntiles & 7u) == 0) {
-        const unsigned per = ntiles >> 3;
-        it_first = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); it_stride = gridDim.x >> 3; it_end = (blockIdx.x & 7u) * per + per;
-    }
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lf_tap_lds + (unsigned)(wave * C::WAVE_LDS);
-    unsigned char* const ring = lf_tap_lds + wave * C::WAVE_LDS;
-    unsigned char* const otile = ring + R * WV_STAGE;
-    unsigned char* const mtile = otile + WV_STAGE;                                     // mask source (when staged)
-    unsigned char* const xtile = otile + WV_STAGE * (C::ST_MSK ? 2 : 1);              // BN-backward operand (when staged)
-
-    // ---- all the weights -> registers: [tap][32-channel k-block][16-channel output tile], the MFMA A operand
-    bf16x8 wr[3][2][NT];
-    {
-        const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.wp16, 0xffffffffu);
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-                    wr[t][kb][n] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
-                        rw, (int)((((t * 2 + kb) * 4 + kq) * CD + n * 16 + pl) * 16), 0, 0));
-    }
-    int tapv = 0;            // tap t's offsets in lane t (v_readlane: see tapgemm_bf16_wl_kernel)
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-        if (lane == t) tapv = (g.tdh[t] & 0xffff) | (g.tdw[t] << 16);
-    const i32x4s rx = make_rsrc_words(a.src, (unsigned)min((long)g.N * g.Hs * g.Ws * g.s_pix * 2, (long)LF_OOB));
-    const int spix2 = g.s_pix * 2;
-    // DMA mapping: instruction q of a step carries pixels q*8 .. q*8+7 of the item (group q >> 1): lane -> pixel q*8 + (lane >> 3),
-    // LDS slot lane & 7 = chunk XOR ((pixel >> 1) & 7) -- which depends on q & 1 only
-    const int dpx = lane >> 3;
-    unsigned lane_x[2];
-    int lane_dx[2];
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
-        const int chunk = (lane & 7) ^ ((jj * 4 + (lane >> 4)) & 7);
-        lane_x[jj] = (unsigned)(((jj * 8 + dpx) * g.s_pix + g.s_choff) * 2 + chunk * 16);
-        lane_dx[jj] = jj * 8 + dpx;
-    }
-    // the two 16-pixel groups of item (tile, h) of this wave: (image, row, first column), wave-uniform
-    struct Item { int n[2], i[2], j[2]; bool ok[2]; };
-    auto item_at = [&](unsigned tile, int h, Item& o) __attribute__((always_inline)) {
-        const unsigned G0 = tile * 16u + (unsigned)(wave * 4 + h * 2);
-        const unsigned Gc = G0 < ngroups ? G0 : 0u;
-        const unsigned Rw = Gc / GR;
-        int jg = __builtin_amdgcn_readfirstlane((int)(Gc - Rw * GR));
-        int n = __builtin_amdgcn_readfirstlane((int)(Rw / (unsigned)g.Hl));
-        int i = __builtin_amdgcn_readfirstlane((int)Rw) - n * g.Hl;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            o.ok[q] = G0 + q < ngroups;
-            o.n[q] = n; o.i[q] = i; o.j[q] = jg * 16;
-            if (++jg == (int)GR) { jg = 0; if (++i == g.Hl) { i = 0; ++n; } }
-        }
-    };
-    // ---- load cursor (wave-uniform): tile, half, tap, ring stage; its item's groups as (pixel index without the tap, row, column)
-    unsigned tile_ld = it_first;
-    int h_ld = 0, t_ld = 0, st_ld = 0;
-    int lrow[2] = {0, 0}, liy[2] = {0, 0}, lsx[2] = {0, 0};
-    bool lok[2] = {false, false};
-    auto cursor_item = [&]() __attribute__((always_inline)) {
-        lok[0] = false; lok[1] = false;
-        if (tile_ld < it_end) {
-            Item I;
-            item_at(tile_ld, h_ld, I);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) { lok[q] = I.ok[q]; liy[q] = I.i[q]; lsx[q] = I.j[q]; lrow[q] = (I.n[q] * g.Hs + I.i[q]) * g.Ws + I.j[q]; }
-        }
-    };
-    cursor_item();
-    auto issue = [&]() __attribute__((always_inline)) {
-        const int tv = __builtin_amdgcn_readlane(tapv, t_ld);
-        const int dh = (int)(short)(tv & 0xffff), dw = tv >> 16;
-        const unsigned dst = lds0 + (unsigned)(st_ld * WV_STAGE);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int gq = q >> 1, jj = q & 1;
-            const int sy = liy[gq] + dh;
-            const bool yok = lok[gq] && sy >= 0 && sy < g.Hs;
-            const unsigned base = (unsigned)((lrow[gq] + dh * g.Ws + dw) * spix2);
-            const bool in = yok && (unsigned)(lsx[gq] + dw + lane_dx[jj]) < (unsigned)g.Ws;
-            lds_dma16(rx, dst + (unsigned)q * 1024u, in ? base + lane_x[jj] : LF_OOB, 0u);
-        }
-        st_ld = st_ld == R - 1 ? 0 : st_ld + 1;
-        if (++t_ld == 3) {
-            t_ld = 0;
-            if (++h_ld == 2) { h_ld = 0; tile_ld += it_stride; }
-            cursor_item();
-        }
-    };
-#pragma unroll
-    for (int i = 0; i < R - 1; ++i) issue();
-
-    // ---- staging of the epilogue's operand tensors (whole lines, the output tile's layout): instruction ii = pixels ii*8 .. +7 of
-    // the item: lane -> pixel p = ii*8 + (lane >> 3), 16-byte slot lane & 7 = chunk XOR (p & 7)
-    const unsigned dbytes = (unsigned)min((long)g.N * g.Hd * g.Wd * g.d_pix * 2, (long)LF_OOB);
-    const i32x4s ra_add = make_rsrc_words(a.add_src, dbytes), ra_msk = make_rsrc_words(a.mask_src, dbytes), ra_aux = make_rsrc_words(a.aux, dbytes);
-    auto tile_lane_off = [&](int ii) __attribute__((always_inline)) {          // byte offset of this lane's chunk inside its group's 16 pixels
-        const int p = ii * 8 + (lane >> 3);
-        return (unsigned)((((p & 15) * g.d_pix + g.d_choff) * 2) + (((lane & 7) ^ p) & 7) * 16);
-    };
-    auto stage_tensors = [&](const Item& I) __attribute__((always_inline)) {
-        if constexpr (C::NAUXI > 0) {
-            const unsigned dst0 = lds0 + (unsigned)(R * WV_STAGE);
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii) {
-                const int gq = ii >> 1;
-                const unsigned base = (unsigned)(((I.n[gq] * g.Hd + I.i[gq]) * g.Wd + I.j[gq]) * g.d_pix * 2);
-                const unsigned vo = I.ok[gq] ? base + tile_lane_off(ii) : LF_OOB;      // (a group beyond the tensor: zeros)
-                if constexpr (C::ST_ADD) lds_dma16(ra_add, dst0 + (unsigned)(ii * 1024), vo, 0u);
-                if constexpr (C::ST_MSK) lds_dma16(ra_msk, dst0 + (unsigned)(WV_STAGE + ii * 1024), vo, 0u);
-                if constexpr (C::ST_AUX) lds_dma16(ra_aux, dst0 + (unsigned)(WV_STAGE * (C::ST_MSK ? 2 : 1) + ii * 1024), vo, 0u);
-            }
-        }
-    };
-
-    // epilogue constants (destination bounded by the tensor: the store of a group beyond it goes to the out-of-range offset and is dropped)
-    const __amdgpu_buffer_rsrc_t r_dst = make_rsrc(a.dst, dbytes), r_add = make_rsrc(a.add_src, 0xffffffffu),
-                                 r_msk = make_rsrc(a.mask_src, 0xffffffffu), r_aux = make_rsrc(a.aux, 0xffffffffu),
-                                 r_bias = make_rsrc(a.bias, 0xffffffffu), r_msc = make_rsrc(a.msc, 0xffffffffu),
-                                 r_msh = make_rsrc(a.msh, 0xffffffffu), r_dm = make_rsrc(a.dm, 0xffffffffu);
-    // fragment read addresses inside a stage: pixel m*16 + pl (128 B rows), chunk kb*4 + kq XOR (pl >> 1) & 7
-    const unsigned xf0 = (unsigned)(pl * 128 + (((0 + kq) ^ (pl >> 1)) & 7) * 16), xf1 = (unsigned)(pl * 128 + (((4 + kq) ^ (pl >> 1)) & 7) * 16);
-    const bool stats = (epi & (LF_EPI_STATS_SQ | LF_EPI_STATS_XHAT)) != 0;
-    int st_c = 0;
-    bool first_item = true;          // no stores in flight in front of the very first step
-    for (unsigned bx = it_first; bx < it_end; bx += it_stride) {
-        constexpr bool PIVOT = EPIC >= 0;    // the pivot of the BN forward sums (see LF_TAPGEMM_EPILOGUE); the run-time-flag form sums about 0
-        f32x4 s1[NT], s2[NT], piv[PIVOT ? NT : 1];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) { s1[n] = zero4(); s2[n] = zero4(); piv[PIVOT ? n : 0] = zero4(); }
-        for (int h = 0; h < 2; ++h) {
-            f32x4 acc[NT][MW];
-#pragma unroll
-            for (int n = 0; n < NT; ++n)
-#pragma unroll
-                for (int m = 0; m < MW; ++m) acc[n][m] = zero4();
-            Item I;
-            item_at(bx, h, I);
-#pragma unroll
-            for (int t = 0; t < 3; ++t) {
-                // my DMA of this step has landed; my fragment reads of the step before have retired (header: what N counts)
-                if (t == 0) {
-                    if (first_item) wait_vm_lgkm0<4 * (R - 2)>();
-                    else wait_vm_lgkm0<4 * (R - 2) + 4>();
-                } else wait_vm_lgkm0<4 * (R - 2) + C::NAUXI>();
-                issue();                             // R - 1 steps ahead -> the stage the previous step occupied
-                if (t == 0) stage_tensors(I);
-                const unsigned char* st = ring + st_c * WV_STAGE;
-                st_c = st_c == R - 1 ? 0 : st_c + 1;
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb) {
-                    bf16x8 xb[MW];
-#pragma unroll
-                    for (int m = 0; m < MW; ++m) xb[m] = *reinterpret_cast<const bf16x8*>(st + (kb ? xf1 : xf0) + m * 2048);
-#pragma unroll
-                    for (int n = 0; n < NT; ++n)
-#pragma unroll
-                        for (int m = 0; m < MW; ++m)
-                            acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[t][kb][n], xb[m], acc[n][m], 0, 0, 0);
-                }
-            }
-            first_item = false;
-            // ---- epilogue of the item: accumulator tile (n, m) = channels n*16 + kq*4 .. +3 of pixel m*16 + pl
-            if constexpr (C::NAUXI > 0) wait_vm_lgkm0<8>();      // the staged tensors have landed (the two ring steps issued since are younger)
-            constexpr bool HOISTM = !(EPIC >= 0 && (EPIC & LF_EPI_MASKBN) != 0 && (EPIC & LF_EPI_STATS_XHAT) != 0);
-            f32x4 bs[NOBIAS ? 1 : NT], hsc[HOISTM ? NT : 1], hsh[HOISTM ? NT : 1];
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-                const unsigned co = (unsigned)(n * 16 + kq * 4);
-                if constexpr (!NOBIAS) bs[n] = a.bias ? ldb4(r_bias, co * 4u, 0u) : zero4();
-                if constexpr (HOISTM) { if (epi & LF_EPI_MASKBN) { hsc[n] = ldb4(r_msc, co * 4u, 0u); hsh[n] = ldb4(r_msh, co * 4u, 0u); } }
-            }
-#pragma unroll
-            for (int m = 0; m < MW; ++m) {
-                const unsigned dbase = (unsigned)(((I.n[m] * g.Hd + I.i[m]) * g.Wd + I.j[m] + pl) * g.d_pix + g.d_choff + kq * 4);
-                auto tile_ld = [&](const unsigned char* tile, int n) __attribute__((always_inline)) {      // this lane's 4 channels of (m, n)
-                    const int p = m * 16 + pl, chunk = (n * 16 + kq * 4) >> 3;
-                    const uint2 q = *reinterpret_cast<const uint2*>(tile + p * 128 + ((chunk ^ p) & 7) * 16 + (kq & 1) * 8);
-                    f32x4 v;
-                    v.x = __uint_as_float(q.x << 16); v.y = __uint_as_float(q.x & 0xffff0000u);
-                    v.z = __uint_as_float(q.y << 16); v.w = __uint_as_float(q.y & 0xffff0000u);
-                    return v;
-                };
-                // (two channel tiles at a time: with all four tiles' operands live beside the 96 weight registers the three-operand
-                // epilogues spilled 10-31 registers)
-#pragma unroll
-                for (int n0 = 0; n0 < NT; n0 += 2) {
-                f32x4 la[NT], lm[NT], lx[NT];
-#pragma unroll
-                for (int n = n0; n < n0 + 2; ++n) {
-                    if (epi & LF_EPI_ADD) la[n] = C::ST_ADD ? tile_ld(otile, n) : epi_ld<S16>(r_add, dbase + n * 16);
-                    if (epi & LF_EPI_MASK) lm[n] = C::ST_MSK ? tile_ld(mtile, n) : epi_ld<S16>(r_msk, dbase + n * 16);
-                    if (epi & (LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) lx[n] = C::ST_AUX ? tile_ld(xtile, n) : epi_ld<S16>(r_aux, dbase + n * 16);
-                }
-#pragma unroll
-                for (int n = n0; n < n0 + 2; ++n) {
-                    f32x4 v = acc[n][m];
-                    if constexpr (!NOBIAS) v += bs[n];
-                    if (epi & LF_EPI_ADD) v += la[n];
-                    if (epi & LF_EPI_MASK) v = keep_pos(v, lm[n]);
-                    if (epi & LF_EPI_MASKBN) {
-                        const unsigned co = (unsigned)(n * 16 + kq * 4);
-                        v = keep_pos(v, lx[n] * (HOISTM ? hsc[HOISTM ? n : 0] : ldb4(r_msc, co * 4u, 0u)) + (HOISTM ? hsh[HOISTM ? n : 0] : ldb4(r_msh, co * 4u, 0u)));
-                    }
-                    if (epi & LF_EPI_RELU) v = max0(v);
-                    lf_bf16x4 b;
-                    b[0] = (lf_bf16)v.x; b[1] = (lf_bf16)v.y; b[2] = (lf_bf16)v.z; b[3] = (lf_bf16)v.w;
-                    // output tile: pixel p = m*16 + pl, 16-byte chunk (channel / 8) XOR p, half kq & 1
-                    const int p = m * 16 + pl, chunk = (n * 16 + kq * 4) >> 3;
-                    *reinterpret_cast<lf_bf16x4*>(otile + p * 128 + ((chunk ^ p) & 7) * 16 + (kq & 1) * 8) = b;
-                    if (stats) {
-                        v.x = (float)b[0]; v.y = (float)b[1]; v.z = (float)b[2]; v.w = (float)b[3];     // statistics of the values as stored
-                        if (!I.ok[m]) v = zero4();
-                        if (epi & LF_EPI_STATS_SQ) {
-                            if (PIVOT && h == 0 && m == 0) piv[PIVOT ? n : 0] = bcast16(v);      // this wave's first pixel of the tile
-                            f32x4 dv = PIVOT ? v - piv[PIVOT ? n : 0] : v;
-                            if (!I.ok[m]) dv = zero4();
-                            s1[n] += dv; s2[n] += dv * dv;
-                        }
-                        if (epi & LF_EPI_STATS_XHAT) {
-                            // (the Dropout2d factor of (image, channel): an L1-resident vector, read where it is used instead of held)
-                            const f32x4 gm = a.dm ? v * ldb4(r_dm, (unsigned)(I.n[m] * g.Cd + n * 16 + kq * 4) * 4u, 0u) : v;
-                            s1[n] += gm; s2[n] += gm * lx[n];
-                        }
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);      // one chunk's operands at a time
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // my quads are in the output tile
-            // whole-line stores: instruction ii = pixels ii*8 .. +7 of the item (all four always issued: header)
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii) {
-                const int gq = ii >> 1;
-                const u32x4v v = *reinterpret_cast<const u32x4v*>(otile + ii * 1024 + lane * 16);
-                const unsigned base = (unsigned)(((I.n[gq] * g.Hd + I.i[gq]) * g.Wd + I.j[gq]) * g.d_pix * 2);
-                __builtin_amdgcn_raw_buffer_store_b128(v, r_dst, (int)(I.ok[gq] ? base + tile_lane_off(ii) : LF_OOB), 0, 0);
-            }
-            // (the next item's first wait carries lgkmcnt(0): these reads of the output tile retire before its next writes)
-        }
-        if (stats) {
-            // the four waves' sums of this 256-pixel tile -> one partial row (the merge of LF_TAPGEMM_EPILOGUE); staging area = the
-            // first 512 bytes of every wave's output tile (free: its stores read it above, the next item writes it 3 steps from now)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            float (*sred)[4][8] = reinterpret_cast<float (*)[4][8]>(otile);           // [n][kq][8]
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-                f32x4 r1, r2;
-                r1.x = sum16(s1[n].x); r1.y = sum16(s1[n].y); r1.z = sum16(s1[n].z); r1.w = sum16(s1[n].w);
-                r2.x = sum16(s2[n].x); r2.y = sum16(s2[n].y); r2.z = sum16(s2[n].z); r2.w = sum16(s2[n].w);
-                if (epi & LF_EPI_STATS_SQ) {      // pivot sums -> (sum v, M2 about the wave's own mean) of the wave's nw valid pixels
-                    const unsigned t0 = (bx * (unsigned)WG_WAVES + (unsigned)wave) * 64u;
-                    const float nw = t0 < npix ? (float)min(npix - t0, 64u) : 0.f;
-                    const float rn = nw > 0.f ? 1.f / nw : 0.f;
-                    r2 = r2 - r1 * r1 * rn;
-                    r2.x = fmaxf(r2.x, 0.f); r2.y = fmaxf(r2.y, 0.f); r2.z = fmaxf(r2.z, 0.f); r2.w = fmaxf(r2.w, 0.f);
-                    if (PIVOT) r1 = r1 + piv[PIVOT ? n : 0] * nw;
-                }
-                if (pl == 0) {
-                    float* d = sred[n][kq];
-                    d[0] = r1.x; d[1] = r1.y; d[2] = r1.z; d[3] = r1.w; d[4] = r2.x; d[5] = r2.y; d[6] = r2.z; d[7] = r2.w;
-                }
-            }
-            __syncthreads();
-            if (threadIdx.x < NT * 4 * 8) {
-                const int tt = threadIdx.x;
-                const int j = tt & 7, q = (tt >> 3) & 3, n = tt >> 5;
-                auto at = [&](int w, int jj) { return reinterpret_cast<const float (*)[4][8]>(lf_tap_lds + w * C::WAVE_LDS + R * WV_STAGE)[n][q][jj]; };
-                float v = at(0, j) + at(1, j) + at(2, j) + at(3, j);
-                if ((epi & LF_EPI_STATS_SQ) && j >= 4) {      // Chan: M2 = sum_w M2_w + sum_w n_w (mean_w - mean)^2
-                    float nwv[4], sw[4], nt = 0.f, stt = 0.f;
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        const unsigned t0w = (bx * (unsigned)WG_WAVES + (unsigned)w) * 64u;
-                        nwv[w] = t0w < npix ? (float)min(npix - t0w, 64u) : 0.f;
-                        sw[w] = at(w, j - 4);
-                        nt += nwv[w]; stt += sw[w];
-                    }
-                    const float mg = nt > 0.f ? stt / nt : 0.f;
-#pragma unroll
-                    for (int w = 0; w < 4; ++w)
-                        if (nwv[w] > 0.f) { const float dmw = sw[w] / nwv[w] - mg; v += nwv[w] * dmw * dmw; }
-                }
-                a.stats[((long)(j >> 2) * g.Cd + n * 16 + q * 4 + (j & 3)) * a.stats_ld + bx] = v;      // channel-major rows
-            }
-            __syncthreads();      // the staging areas are output tiles again
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the trailing (dead) steps: nothing may land in LDS after this
-    __builtin_amdgcn_s_barrier();
-}
-
-// ---------------------------------------------------------------------------------------
-// tapgemm_bf16_lean_kernel: the 16 -> 16 channel 3-tap convolutions on bf16 tensors (decoder, full-resolution stage: HBM-bound,
-// a pixel is 32 bytes).  The general bf16 kernel ran them in its run-time-flag form, one 32-channel K-step per tap with half
-// of every operand register zero padding and one step in flight (101 us per launch at 160 x 320 x 64 images, 2.1 TB/s).  Here
-//  * one MFMA contracts TWO taps: k-blocks 0-1 of the K = 32 step are tap 2i's 16 channels, k-blocks 2-3 tap 2i+1's -- a lane's
-//    16-byte load is half a pixel at the tap its k-block belongs to, an instruction covers 2 x 16 consecutive pixels x 32 B
-//    (whole lines); the three taps are 2 MFMAs per 16 x 16 tile, all 8 loads of a wave requested up front;
-//  * prologue and epilogue flags compiled in, (image, row) of the 16-pixel groups in scalar registers (Wl % 16 == 0).
-// The chain order (tap 0 + tap 1 in one K = 32 dot product, then tap 2) differs from tapgemm_bf16_kernel's three K-steps:
-// results agree to fp32 rounding, not bit for bit.
-// ---------------------------------------------------------------------------------------
-template <int PROC, int EPIC>
-__global__ __launch_bounds__(256, 4) void tapgemm_bf16_lean_kernel(const LfTapGeom g, const LfTapArgs a, const int pro_rt, const int epi_rt) {
-    constexpr int NT = 1;
-    constexpr bool S16 = true, HOISTV = EPIC >= 0;
-    const int epi = EPIC >= 0 ? EPIC : epi_rt;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int pl = lane & 15, kq = lane >> 4;
-    const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl), ngroups = npix >> 4, GR = (unsigned)g.Wl >> 4;
-    const int cob = 0;
-    unsigned bx = blockIdx.x;
-    if ((gridDim.x & 7u) == 0) bx = (bx & 7u) * (gridDim.x >> 3) + (bx >> 3);
-    RingGroups G;
-    ring_groups(bx, wave, g.Hl, GR, ngroups, G);
-    const int hi = kq >> 1, c8 = (kq & 1) * 8;              // which tap of the pair, which half of the pixel
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.wp16, 0xffffffffu),
-                                 rx = make_rsrc(a.src, (unsigned)min((long)g.N * g.Hs * g.Ws * g.s_pix * 2, (long)LF_OOB));
-    // weights: packed [tap][4 k-blocks of 8 channels (2 real, 2 zero)][Cd][8]; MFMA i, lane (pl, kq): tap 2i + hi, k-block kq & 1
-    bf16x8 wb[2];
-    wb[0] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, (int)((((hi ? 1 : 0) * 4 + (kq & 1)) * g.Cd + pl) * 16), 0, 0));
-    {
-        u32x4v w2 = __builtin_amdgcn_raw_buffer_load_b128(rw, (int)(((2 * 4 + (kq & 1)) * g.Cd + pl) * 16), 0, 0);
-        if (hi) { w2[0] = 0u; w2[1] = 0u; w2[2] = 0u; w2[3] = 0u; }       // there is no fourth tap
-        wb[1] = __builtin_bit_cast(bf16x8, w2);
-    }
-    (void)pro_rt;
-    u32x4v xr[2][MT];
-    bool in[2][MT];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int dh = i == 0 ? (hi ? g.tdh[1] : g.tdh[0]) : g.tdh[2], dw = i == 0 ? (hi ? g.tdw[1] : g.tdw[0]) : g.tdw[2];
-        const bool tapok = i == 0 || !hi;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const int sy = G.i[m] * g.ssh + dh, sx = (G.j[m] + pl) * g.ssw + dw;
-            in[i][m] = tapok && G.ok[m] && sy >= 0 && sy < g.Hs && sx >= 0 && sx < g.Ws;
-            const unsigned off = (unsigned)((((G.n[m] * g.Hs + sy) * g.Ws + sx) * g.s_pix + g.s_choff + c8) * 2);
-            xr[i][m] = __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(in[i][m] ? off : LF_OOB), 0, 0);
-        }
-    }
-    f32x4 sc0, sc1, sh0, sh1;
-    if constexpr (PROC == LF_PRO_BNRELU) {
-        sc0 = ldg4(a.pro_sc + c8); sc1 = ldg4(a.pro_sc + c8 + 4);
-        sh0 = ldg4(a.pro_sh + c8); sh1 = ldg4(a.pro_sh + c8 + 4);
-    }
-    f32x4 acc[NT][MT];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            bf16x8 xb;
-            if constexpr (PROC == LF_PRO_BNRELU) {          // relu(bn(x)) in fp32 on the widened values; padding is zero AFTER the transform
-                const u32x4v r = xr[i][m];
-                f32x4 lo, hv;
-                lo.x = __uint_as_float(r[0] << 16); lo.y = __uint_as_float(r[0] & 0xffff0000u);
-                lo.z = __uint_as_float(r[1] << 16); lo.w = __uint_as_float(r[1] & 0xffff0000u);
-                hv.x = __uint_as_float(r[2] << 16); hv.y = __uint_as_float(r[2] & 0xffff0000u);
-                hv.z = __uint_as_float(r[3] << 16); hv.w = __uint_as_float(r[3] & 0xffff0000u);
-                lo = max0(lo * sc0 + sh0); hv = max0(hv * sc1 + sh1);
-                const bool ok = in[i][m];
-                lo.x = ok ? lo.x : 0.f; lo.y = ok ? lo.y : 0.f; lo.z = ok ? lo.z : 0.f; lo.w = ok ? lo.w : 0.f;
-                hv.x = ok ? hv.x : 0.f; hv.y = ok ? hv.y : 0.f; hv.z = ok ? hv.z : 0.f; hv.w = ok ? hv.w : 0.f;
-                xb = cvt_bf16x8(lo, hv);
-            } else xb = __builtin_bit_cast(bf16x8, xr[i][m]);
-            acc[0][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[i], xb, i ? acc[0][m] : zero4(), 0, 0, 0);
-        }
-    int pn[MT], pi[MT], pj[MT];
-    bool pv[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) { pn[m] = G.n[m]; pi[m] = G.i[m]; pj[m] = G.j[m] + pl; pv[m] = G.ok[m]; }
-    LF_TAPGEMM_EPILOGUE
-}
-
-// ---------------------------------------------------------------------------------------
 // fp32 ON THE bf16 MATRIX CORES ("split" mode, LfTapArgs::split = 9).  gfx950 multiplies bf16 16x faster
 // than fp32 (v_mfma_f32_16x16x32_bf16: 16 cycles for K = 32; v_mfma_f32_16x16x4_f32: 8 x 32 cycles for the same K),
 // so an fp32 product is formed from bf16 pieces instead: every fp32 operand is split EXACTLY into three bf16 values
@@ -2202,12 +847,6 @@ __global__ __launch_bounds__(256, 4) void tapgemm_lean_kernel(const LfTapGeom g,
 }
 
 int g_split_any_size = 0;      // kernel-level tests only: let the split kernel take launches below its shipped size rule
-std::atomic<long> g_bres_launches{0};   // compiled-in bias + residual + ReLU launches (lf_tapgemm_bias_residual_launches)
-int g_bf16_lds = 4;            // tools / A-B runs only: 4 = wave-private (64 ch) / whole-line (128 ch) + 16-channel kernels where they apply, else the ring (shipped);
-                               // 3 = the whole-line kernel at 64 channels too (round 5's routing); 2 = the ring
-                               // for every launch it takes; 0 = the streaming bf16 kernel only
-std::atomic<long> g_part_fast_launches{0};   // launches with Cs % 32 != 0 that took a compiled-in whole-step form (lf_tapgemm_partial_fast_launches)
-int g_bf16_no_partial_fast = 0; // kernel-level tests only: launches with Cs % 32 != 0 decline the compiled-in whole-step forms of tapgemm_bf16_kernel
 
 int pick_nt(int Cd) {
     const int tiles = Cd / 16;
@@ -2219,12 +858,11 @@ int pick_nt(int Cd) {
 
 }  // namespace
 
+// (not in the anonymous namespace: lf_tapgemm_bf16_route counts its launches in the same object, declared in lf_conv.h)
+std::atomic<long> g_bres_launches{0};   // compiled-in bias + residual + ReLU launches (lf_tapgemm_bias_residual_launches)
+
 void lf_tapgemm_set_split_any_size(int v) { g_split_any_size = v; }
 long lf_tapgemm_bias_residual_launches() { return g_bres_launches.load(); }
-void lf_tapgemm_set_bf16_lds(int v) { g_bf16_lds = v; }
-int lf_tapgemm_bf16_lds() { return g_bf16_lds; }
-void lf_tapgemm_set_bf16_no_partial_fast(int v) { g_bf16_no_partial_fast = v; }
-long lf_tapgemm_partial_fast_launches() { return g_part_fast_launches.load(); }
 
 // launches the split kernel takes: whole 32-channel K-steps, 64-channel output slabs (NT = 4), whole 512-pixel
 // workgroups (its two 4-wave groups each own one 256-pixel statistics row), 16-byte aligned pixels
@@ -2247,59 +885,13 @@ int lf_tapgemm_stat_rows_for(const LfTapGeom& g, const LfTapArgs& a) {
 }
 
 namespace {
-// Workgroups of `kernel` the whole chip holds at once (occupancy x CUs), cached per (device, kernel, dynamic LDS bytes).
-template <typename K>
-int resident_workgroups(K kernel, size_t lds, int block = 256) {
-    static std::map<std::tuple<int, const void*, size_t>, int> cache;
-    const int dev = current_device();
-    const std::tuple<int, const void*, size_t> key(dev, reinterpret_cast<const void*>(kernel), lds);
-    std::lock_guard<std::mutex> lock(g_launch_state_mutex);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    int cus = 0, nb = 0;
-    if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, lds) != hipSuccess || nb < 1 || cus < 1)
-        return cache[key] = 1 << 30;                 // unknown: one tile per workgroup
-    return cache[key] = nb * cus;
-}
 // hipExtAnyOrderLaunch for the next fp32 launch (set by lf_tapgemm_launch_unordered): the dispatch packet carries no barrier
 // bit, so the kernel may start while the PREVIOUS packet of the stream is still running -- its workgroups fill the slots the
 // previous kernel's last workgroups leave (the caller guarantees the two are independent).
 thread_local unsigned g_launch_flags = 0;
-// The launch of every kernel that walks its tiles / items with stride gridDim.x: no more workgroups than are resident at once (a
-// multiple of 8 per XCD dealing: XCD-contiguous item ranges), so that the work beyond the first round is spread one per CU by
-// construction; then no more than max_wgs, where that is > 0.
-// lds_attr > 0: the kernel needs that hipFuncAttributeMaxDynamicSharedMemorySize -- false when the runtime refuses it on this device
-// (nothing launched: the caller takes a kernel that needs less LDS).  flags: g_launch_flags where the kernel honours it, else 0.
-template <typename K, typename... Args>
-bool launch_resident(K kernel, dim3 grid, unsigned block, size_t lds, int lds_attr, unsigned max_wgs, unsigned flags, hipStream_t st, const Args&... args) {
-    if (lds_attr > 0 && !allow_big_lds(reinterpret_cast<const void*>(kernel), lds_attr)) return false;
-    const unsigned res = (unsigned)resident_workgroups(kernel, lds, (int)block) / grid.y;
-    if (grid.x > res && res >= 8) grid.x = res & ~7u;
-    if (max_wgs > 0 && grid.x > max_wgs) grid.x = max_wgs;
-    if (flags) hipExtLaunchKernelGGL(kernel, grid, dim3(block), (unsigned)lds, st, nullptr, nullptr, flags, args...);
-    else hipLaunchKernelGGL(kernel, grid, dim3(block), lds, st, args...);
-    return true;
-}
-constexpr int BIG_LDS = 160 * 1024 - 4096;      // the LDS attribute of the whole-line, wave-private and weight-resident kernels
 template <typename K>
 void launch_tapgemm(K kernel, dim3 grid, size_t lds, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
     launch_resident(kernel, grid, 256, lds, 0, 0, g_launch_flags, st, g, a, pro, epi);
-}
-// tapgemm_bf16_ring_kernel: persistent
-template <int EPIV, bool DBGV = false>
-void launch_bf16_ring(unsigned nitems, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
-    launch_resident(tapgemm_bf16_ring_kernel<EPIV, DBGV>, dim3(nitems), 256, (size_t)LB_STAGES * LB_STAGE_BYTES, 0, 0, 0, st, g, a, pro, epi);
-}
-// false: the runtime refused the kernel's LDS budget on this device (nothing launched: the caller takes the ring / streaming kernel)
-template <int CBV, int EPIV, int PROV = 0>
-bool launch_bf16_wl(unsigned nitems, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
-    return launch_resident(tapgemm_bf16_wl_kernel<CBV, EPIV, PROV>, dim3(nitems), 256, WlCfg<CBV, EPIV, PROV>::LDS, BIG_LDS, 0, 0, st, g, a, pro, epi);
-}
-// tapgemm_bf16_wv_kernel (64 channels): same contract
-template <int EPIV>
-bool launch_bf16_wv(unsigned ntiles, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
-    return launch_resident(tapgemm_bf16_wv_kernel<EPIV>, dim3(ntiles), 256, WvCfg<EPIV>::LDS, BIG_LDS, 0, 0, st, g, a, pro, epi);
 }
 // tapstream_kernel (see there).  lf_debug_set_fp32_stream: mode 0 = tapgemm_kernel takes every launch, 1 = the shipped routing
 // (g_stream_routed: which (channel count, variant) pairs were faster in the step); max_workgroups > 0 caps the grid, so that a
@@ -2330,38 +922,6 @@ bool route_tapstream(int variant, hipStream_t st, const LfTapGeom& g, const LfTa
     }
 }
 
-// The compiled-in data-gradient epilogues (mask / residual / BN-backward sums) carry no bias vector (NOBIAS): a launch that
-// combines one of them with a bias takes the run-time-flag kernel -- except the inference engine's residual tail (bias + ADD +
-// ReLU: BRES, compiled into the kernels the forward convolutions route to; the split, ring and streaming-fast kernels keep the
-// run-time form)
-constexpr int BRES = LF_EPI_ADD | LF_EPI_RELU | LF_EPI_BIAS;
-template <int V> using IntC = std::integral_constant<int, V>;
-// The one place that turns the run-time epilogue set into a template argument: f(IntC<E>{}) with E the compiled-in set equal to
-// epis, or -1 (the run-time-flag form) for every other.  WITH_BRES = false: the kernel family has no compiled-in BRES form.
-template <bool WITH_BRES, typename F>
-auto with_epi(int epis, F&& f) {
-    switch (epis) {
-        case 0: return f(IntC<0>{});
-        case LF_EPI_RELU: return f(IntC<LF_EPI_RELU>{});
-        case LF_EPI_MASK: return f(IntC<LF_EPI_MASK>{});
-        case LF_EPI_ADD: return f(IntC<LF_EPI_ADD>{});
-        case LF_EPI_STATS_SQ: return f(IntC<LF_EPI_STATS_SQ>{});
-        case LF_EPI_MASK | LF_EPI_STATS_XHAT: return f(IntC<LF_EPI_MASK | LF_EPI_STATS_XHAT>{});
-        case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: return f(IntC<LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT>{});
-        case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: return f(IntC<LF_EPI_MASKBN | LF_EPI_STATS_XHAT>{});
-        case BRES: return f(IntC<WITH_BRES ? BRES : -1>{});
-        default: return f(IntC<-1>{});
-    }
-}
-// ... and for the kernels that compile the BN+ReLU operand prologue beside the epilogue, f(IntC<PRO>{}, IntC<E>{}): a prologue launch
-// has the compiled-in ReLU epilogue or the run-time flags, only prologue-free launches dispatch on epis
-template <bool WITH_BRES, typename F>
-void with_pro_epi(int pro, int epi, int epis, F&& f) {
-    if (pro == LF_PRO_BNRELU && epi == LF_EPI_RELU) f(IntC<1>{}, IntC<LF_EPI_RELU>{});
-    else if (pro == LF_PRO_BNRELU) f(IntC<1>{}, IntC<-1>{});
-    else with_epi<WITH_BRES>(epis, [&](auto e) { f(IntC<0>{}, e); });
-}
-
 // precision mode fp32x9: fp32 tensors, the weights packed as three bf16 terms (tapgemm_split_kernel)
 int launch_split_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, int epis, long npix, hipStream_t st) {
     LF_REQUIRE(a.split == 9, "tapgemm: split must be 9 (got %d; the 6-term form was removed in round 6)", a.split);
@@ -2377,132 +937,6 @@ int launch_split_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi,
         });
     }
     LF_CHECK_LAUNCH("tapgemm_split");
-    return 0;
-}
-
-// the streaming tapgemm_bf16_kernel (FAST: its whole-step forms, see there); _rt: the run-time-flag form of an output slab width
-template <int NTV, int PROV, int EPIV = -1, bool FAST = false>
-void launch_bf16_stream(dim3 grid, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
-    hipLaunchKernelGGL((tapgemm_bf16_kernel<NTV, PROV, EPIV, FAST>), grid, dim3(256), 0, st, g, a, pro, epi);
-}
-template <int NTV>
-void launch_bf16_stream_rt(dim3 grid, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
-    if (pro == LF_PRO_BNRELU) launch_bf16_stream<NTV, 1>(grid, st, g, a, pro, epi);
-    else launch_bf16_stream<NTV, 0>(grid, st, g, a, pro, epi);
-}
-
-// precision mode bf16: bf16 tensors on the bf16 matrix cores
-int launch_bf16_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, int epis, long npix, int nt, dim3 grid, hipStream_t st) {
-    LF_REQUIRE(a.s16, "tapgemm: the bf16 matrix-core kernels take bf16 tensors (s16); bf16 operands on fp32 tensors were removed in round 6");
-    LF_REQUIRE(g.Cs >= 8 && g.s_pix >= g.s_choff + 8, "tapgemm bf16: needs at least 8 source channels");
-    const bool in_offsets = (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB;    // the bf16 source inside 32-bit byte offsets
-    // the 16 -> 16 channel 3-tap convolutions on bf16 tensors: tapgemm_bf16_lean_kernel
-    if (a.s16 && g_bf16_lds >= 3 && !a.dbg && g.Cs == 16 && g.Cd == 16 && g.ntaps == 3 && g.Wl % 16 == 0 && g.s_pix % 8 == 0 && g.s_choff % 8 == 0 && in_offsets) {
-        with_epi<true>(epis, [&](auto e) {
-            constexpr int E = decltype(e)::value;
-            if (pro == LF_PRO_BNRELU) hipLaunchKernelGGL((tapgemm_bf16_lean_kernel<1, E>), grid, dim3(256), 0, st, g, a, pro, epi);
-            else hipLaunchKernelGGL((tapgemm_bf16_lean_kernel<0, E>), grid, dim3(256), 0, st, g, a, pro, epi);
-        });
-        if (epis == BRES) ++g_bres_launches;
-        LF_CHECK_LAUNCH("tapgemm_bf16_lean");
-        return 0;
-    }
-    const bool fast16 = nt == 4 && a.s16 && pro != LF_PRO_BNRELU && g.Cs % 32 == 0 && in_offsets;
-    // Which kernel (g_bf16_lds = 4, the shipped setting): the 3-tap convolutions of non_bottleneck_1d at 64 / 128 channels ->
-    // tapgemm_bf16_wl_kernel (whole lines); every other prologue-free launch at 64-channel output slabs whose 16-pixel groups lie
-    // in one image row (the 9-tap stride-2 convolution, the transposed-convolution phases, their gradients) ->
-    // tapgemm_bf16_ring_kernel; the rest (operand prologue, ragged widths) -> the streaming tapgemm_bf16_kernel
-    // the block's third convolution (BN+ReLU operand prologue), at 128 channels: 83 -> 60 us per launch at config 3's size; at 64
-    // channels the in-LDS transform is as long as the whole step (88 -> 91 us): those stay on the streaming kernel
-    const bool fast16p = nt == 4 && a.s16 && pro == LF_PRO_BNRELU && epi == LF_EPI_RELU && g.Cs == 128 && in_offsets;
-    const bool line3 = g_bf16_lds >= 3 && !a.dbg && g.ntaps == 3 && g.Cs == g.Cd && (g.Cd == 64 || g.Cd == 128) && g.Wl % 16 == 0 &&
-                       g.ssh == 1 && g.ssw == 1 && g.dsh == 1 && g.dsw == 1 && g.dah == 0 && g.daw == 0 && g.Hs == g.Hl && g.Ws == g.Wl &&
-                       g.Hd == g.Hl && g.Wd == g.Wl && g.s_pix % 8 == 0 && g.s_choff % 8 == 0 && g.d_pix % 8 == 0 && g.d_choff % 8 == 0 &&
-                       (long)g.N * g.Hd * g.Wd * g.d_pix * 2 < (long)LF_OOB;
-    // 64 channels (g_bf16_lds = 4, shipped): tapgemm_bf16_wv_kernel -- a wave owns its pixels and all 64 output channels; 3 = the
-    // whole-line kernel for both channel counts (round 5's routing, kept for A/B runs: tools/bf16_ab.py)
-    const bool wv = line3 && g_bf16_lds == 4 && g.Cd == 64 && fast16;
-    const bool wl = line3 && (fast16 || fast16p);      // (also what the wave-private kernel declines)
-    const unsigned ntiles = (unsigned)lf_cdiv(npix, PIX_PER_WG);
-    if (wv) {
-        const bool launched = with_epi<true>(epis, [&](auto e) {
-            constexpr int E = decltype(e)::value;
-            // (ADD + MASK + BN-backward sums: two staged operand tiles leave room for ONE workgroup per CU here -- 123.6 us in config
-            // 3's step against 115.8 us on the whole-line kernel, which takes these launches: not compiled, `launched` stays false)
-            if constexpr (E == (LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT)) return false;
-            else return launch_bf16_wv<E>(ntiles, st, g, a, pro, epi);
-        });
-        if (launched) {
-            if (epis == BRES) ++g_bres_launches;
-            LF_CHECK_LAUNCH("tapgemm_bf16_wv");
-            return 0;
-        }
-    }
-    if (wl && fast16p) {        // (128 channels only)
-        if (launch_bf16_wl<4, LF_EPI_RELU, 1>(ntiles, st, g, a, pro, epi)) {
-            LF_CHECK_LAUNCH("tapgemm_bf16_wl (prologue)");
-            return 0;
-        }
-    } else if (wl) {
-        const bool launched = with_epi<true>(epis, [&](auto e) {
-            constexpr int E = decltype(e)::value;
-            return g.Cs == 128 ? launch_bf16_wl<4, E>(ntiles, st, g, a, pro, epi) : launch_bf16_wl<2, E>(ntiles, st, g, a, pro, epi);
-        });
-        if (launched) {
-            if (epis == BRES) ++g_bres_launches;
-            LF_CHECK_LAUNCH("tapgemm_bf16_wl");
-            return 0;
-        }
-    }
-    // compiled-in whole-step forms at Cs % 32 != 0 (below): their tap table has one row per (tap, step)
-    const bool part_fast = !g_bf16_no_partial_fast && g.ntaps * ((g.Cs + 31) / 32) <= LF_MAX_TAPS;
-    const bool ring = fast16 && g_bf16_lds >= 2 && g.Wl % 16 == 0 && g.Cd % 64 == 0;
-    const unsigned nitems = ntiles * (unsigned)(g.Cd / 64);
-    if (ring && a.dbg) {        // stamps (tools/kbench.py --phases16): the plain convolution only
-        LF_REQUIRE(epis == 0, "tapgemm bf16 ring: stamps are compiled into the plain convolution only");
-        launch_bf16_ring<0, true>(nitems, st, g, a, pro, epi);
-    } else if (ring) {
-        with_epi<false>(epis, [&](auto e) { launch_bf16_ring<decltype(e)::value>(nitems, st, g, a, pro, epi); });
-    } else if (fast16) {       // the bf16-tensor launches of the network at 64 output channels per workgroup
-        with_epi<false>(epis, [&](auto e) { launch_bf16_stream<4, 0, decltype(e)::value, true>(grid, st, g, a, pro, epi); });
-    } else if (nt == 4 && a.s16 && pro != LF_PRO_BNRELU && g.Cs == 16 && (epis == (LF_EPI_MASK | LF_EPI_STATS_XHAT) || epis == 0) && part_fast && in_offsets) {
-        // 16 source channels into a 64-channel slab (the data gradient of UpsamplerBlock(64, 16): 9 taps, stride 2, with the previous
-        // layer's mask + BN-backward sums; 204 us per launch at config 3 on the run-time-flag form): ONE 32-channel step per tap on the
-        // compiled-in form.  Lanes kq = 2, 3 -- channels 16..31 of the step, which the pixel does not have -- hold the out-of-range
-        // offset and read the buffer bound's zeros against the zero-padded half of the packed weights
-        if (epis == 0) launch_bf16_stream<4, 0, 0, true>(grid, st, g, a, pro, epi);
-        else launch_bf16_stream<4, 0, LF_EPI_MASK | LF_EPI_STATS_XHAT, true>(grid, st, g, a, pro, epi);
-        ++g_part_fast_launches;
-    } else if (nt == 3 && a.s16 && pro != LF_PRO_BNRELU && g.Cs == 16 && (epis == LF_EPI_STATS_SQ || epis == LF_EPI_RELU || epis == 0) && part_fast && in_offsets) {
-        // ... and the 16 -> 48 channel convolution of DownsamplerBlock(16, 64) (9 taps, stride 2, BN forward sums; 112 us on the run-time-flag form)
-        // (RELU: the inference engine's folded form of the same convolution)
-        if (epis == 0) launch_bf16_stream<3, 0, 0, true>(grid, st, g, a, pro, epi);
-        else if (epis == LF_EPI_RELU) launch_bf16_stream<3, 0, LF_EPI_RELU, true>(grid, st, g, a, pro, epi);
-        else launch_bf16_stream<3, 0, LF_EPI_STATS_SQ, true>(grid, st, g, a, pro, epi);
-        ++g_part_fast_launches;
-    } else if (nt == 4 && a.s16 && pro == LF_PRO_BNRELU && epi == LF_EPI_RELU) {
-        launch_bf16_stream<4, 1, LF_EPI_RELU, false>(grid, st, g, a, pro, epi);
-    } else if (nt == 1 && a.s16 && pro != LF_PRO_BNRELU && ((g.Cs + 31) / 32 * 32 + g.s_choff <= g.s_pix) && in_offsets &&
-               (g.Cs % 32 == 0 || part_fast) &&
-               (epis == 0 || epis == LF_EPI_STATS_SQ || epis == LF_EPI_ADD || epis == LF_EPI_RELU)) {
-        // 16 output channels from whole 32-channel steps (round 6: the sub-pixel phases of UpsamplerBlock(64, 16) and the data gradient
-        // of DownsamplerBlock(16, 64)'s convolution: 8 launches per step on the run-time-flag form before): padding as out-of-range
-        // offsets, compiled-in epilogue.  In a partial last step (48 source channels) the lanes of channels 48..63 hold the out-of-range
-        // offset too: zeros against the zero-padded weights, not the pixel's next channels (another tensor's slice)
-        if (epis == 0) launch_bf16_stream<1, 0, 0, true>(grid, st, g, a, pro, epi);
-        else if (epis == LF_EPI_STATS_SQ) launch_bf16_stream<1, 0, LF_EPI_STATS_SQ, true>(grid, st, g, a, pro, epi);
-        else if (epis == LF_EPI_RELU) launch_bf16_stream<1, 0, LF_EPI_RELU, true>(grid, st, g, a, pro, epi);   // (inference: folded phases)
-        else launch_bf16_stream<1, 0, LF_EPI_ADD, true>(grid, st, g, a, pro, epi);
-        if (g.Cs % 32 != 0) ++g_part_fast_launches;
-    } else {
-        switch (nt) {
-            case 4: launch_bf16_stream_rt<4>(grid, st, g, a, pro, epi); break;
-            case 3: launch_bf16_stream_rt<3>(grid, st, g, a, pro, epi); break;
-            case 2: launch_bf16_stream_rt<2>(grid, st, g, a, pro, epi); break;
-            default: launch_bf16_stream_rt<1>(grid, st, g, a, pro, epi); break;
-        }
-    }
-    LF_CHECK_LAUNCH("tapgemm_bf16");
     return 0;
 }
 
@@ -2582,6 +1016,6 @@ int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
     LF_REQUIRE(!a.s16 || a.wp16, "tapgemm: bf16 tensors need the bf16 matrix-core kernel (wp16)");
     if (a.split && a.wp48 && !a.wp16 && lf_tapgemm_split_ok(g)) return launch_split_route(g, a, pro, epi, epis, npix, st);
     LF_REQUIRE(!a.s16 || (g.s_pix % 8 == 0 && g.s_choff % 8 == 0), "tapgemm: bf16 source layout must be 16-byte aligned per pixel");
-    if (a.wp16) return launch_bf16_route(g, a, pro, epi, epis, npix, nt, grid, st);
+    if (a.wp16) return lf_tapgemm_bf16_route(g, a, pro, epi, epis, npix, nt, grid, st);
     return launch_fp32_route(g, a, pro, epi, epis, nt, grid, st);
 }

@@ -1,6 +1,7 @@
-// Device helpers and launch state shared by the convolution kernel files lf_conv.hip (tap-GEMM forward / data gradient) and
-// lf_wgrad.hip (weight gradients): the vector types, buffer-addressed loads and stores, the DPP row sums, the tile constants, the
-// per-(device, kernel) LDS attribute and the dynamic-LDS symbol.  Internal: included by those two files only, everything in an
+// Device helpers and launch state shared by the convolution kernel files lf_conv.hip and lf_conv_bf16.hip (tap-GEMM forward / data
+// gradient on fp32 and on bf16 tensors) and lf_wgrad.hip (weight gradients): the vector types, buffer-addressed loads and stores,
+// the DPP row sums, the tile constants, the per-(device, kernel) LDS attribute and occupancy cache with the launch that uses them,
+// the epilogue-set dispatchers and the dynamic-LDS symbol.  Internal: included by those three files only, everything in an
 // anonymous namespace.  (lf_wgrad_ro.hip and lf_stem.hip keep private copies of zero4 and the typedefs.)
 #pragma once
 #include <stdlib.h>
@@ -91,6 +92,8 @@ __device__ __forceinline__ f32x4 round_bf16(f32x4 v) {
 }
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // one pair of fp32 values -> their packed bf16 roundings (v_cvt_pk_bf16_f32); v becomes the exact residuals
 __device__ __forceinline__ unsigned split_pair(f32x2& v) {
     const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
@@ -119,11 +122,11 @@ __device__ __forceinline__ float sum16(float v) {
     return v;
 }
 
-// (This header's anonymous namespace gives each including file ONE COPY OF ITS OWN of the mutex and of allow_big_lds' map.  That is
-// correct because the map is keyed by kernel address and no kernel belongs to two files; the occupancy cache meant by "below" is
-// resident_workgroups in lf_conv.hip, which locks that file's copy.)
-// Per-(device, kernel) launch state shared by the host threads of a process (one process may drive several GPUs): the occupancy
-// cache below and the "dynamic LDS beyond 64 KB allowed" attribute of the LDS-ring kernels.
+// Per-(device, kernel) launch state shared by the host threads of a process (one process may drive several GPUs): the "dynamic
+// LDS beyond 64 KB allowed" attribute of the LDS-ring kernels (allow_big_lds) and the occupancy cache (resident_workgroups), both
+// below.  This header's anonymous namespace gives each including file ONE COPY OF ITS OWN of the mutex and of both maps.  That is
+// correct because every map is keyed by kernel address and no kernel belongs to two files: a file's copies hold exactly the
+// entries of that file's kernels, and each is only ever locked with that file's mutex.
 std::mutex g_launch_state_mutex;
 int current_device() {
     int dev = 0;
@@ -138,6 +141,68 @@ bool allow_big_lds(const void* kernel, int bytes) {
     auto it = done.find(key);
     if (it != done.end()) return it->second;
     return done[key] = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+}
+// Workgroups of `kernel` the whole chip holds at once (occupancy x CUs), cached per (device, kernel, dynamic LDS bytes).
+template <typename K>
+int resident_workgroups(K kernel, size_t lds, int block = 256) {
+    static std::map<std::tuple<int, const void*, size_t>, int> cache;
+    const int dev = current_device();
+    const std::tuple<int, const void*, size_t> key(dev, reinterpret_cast<const void*>(kernel), lds);
+    std::lock_guard<std::mutex> lock(g_launch_state_mutex);
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    int cus = 0, nb = 0;
+    if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, lds) != hipSuccess || nb < 1 || cus < 1)
+        return cache[key] = 1 << 30;                 // unknown: one tile per workgroup
+    return cache[key] = nb * cus;
+}
+// The launch of every kernel that walks its tiles / items with stride gridDim.x: no more workgroups than are resident at once (a
+// multiple of 8 per XCD dealing: XCD-contiguous item ranges), so that the work beyond the first round is spread one per CU by
+// construction; then no more than max_wgs, where that is > 0.
+// lds_attr > 0: the kernel needs that hipFuncAttributeMaxDynamicSharedMemorySize -- false when the runtime refuses it on this device
+// (nothing launched: the caller takes a kernel that needs less LDS).  flags: g_launch_flags (lf_conv.hip) where the kernel honours it, else 0.
+template <typename K, typename... Args>
+bool launch_resident(K kernel, dim3 grid, unsigned block, size_t lds, int lds_attr, unsigned max_wgs, unsigned flags, hipStream_t st, const Args&... args) {
+    if (lds_attr > 0 && !allow_big_lds(reinterpret_cast<const void*>(kernel), lds_attr)) return false;
+    const unsigned res = (unsigned)resident_workgroups(kernel, lds, (int)block) / grid.y;
+    if (grid.x > res && res >= 8) grid.x = res & ~7u;
+    if (max_wgs > 0 && grid.x > max_wgs) grid.x = max_wgs;
+    if (flags) hipExtLaunchKernelGGL(kernel, grid, dim3(block), (unsigned)lds, st, nullptr, nullptr, flags, args...);
+    else hipLaunchKernelGGL(kernel, grid, dim3(block), lds, st, args...);
+    return true;
+}
+constexpr int BIG_LDS = 160 * 1024 - 4096;      // the LDS attribute of the whole-line, wave-private and weight-resident kernels
+// The compiled-in data-gradient epilogues (mask / residual / BN-backward sums) carry no bias vector (NOBIAS): a launch that
+// combines one of them with a bias takes the run-time-flag kernel -- except the inference engine's residual tail (bias + ADD +
+// ReLU: BRES, compiled into the kernels the forward convolutions route to; the split, ring and streaming-fast kernels keep the
+// run-time form)
+constexpr int BRES = LF_EPI_ADD | LF_EPI_RELU | LF_EPI_BIAS;
+template <int V> using IntC = std::integral_constant<int, V>;
+// The one place that turns the run-time epilogue set into a template argument: f(IntC<E>{}) with E the compiled-in set equal to
+// epis, or -1 (the run-time-flag form) for every other.  WITH_BRES = false: the kernel family has no compiled-in BRES form.
+template <bool WITH_BRES, typename F>
+auto with_epi(int epis, F&& f) {
+    switch (epis) {
+        case 0: return f(IntC<0>{});
+        case LF_EPI_RELU: return f(IntC<LF_EPI_RELU>{});
+        case LF_EPI_MASK: return f(IntC<LF_EPI_MASK>{});
+        case LF_EPI_ADD: return f(IntC<LF_EPI_ADD>{});
+        case LF_EPI_STATS_SQ: return f(IntC<LF_EPI_STATS_SQ>{});
+        case LF_EPI_MASK | LF_EPI_STATS_XHAT: return f(IntC<LF_EPI_MASK | LF_EPI_STATS_XHAT>{});
+        case LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT: return f(IntC<LF_EPI_ADD | LF_EPI_MASK | LF_EPI_STATS_XHAT>{});
+        case LF_EPI_MASKBN | LF_EPI_STATS_XHAT: return f(IntC<LF_EPI_MASKBN | LF_EPI_STATS_XHAT>{});
+        case BRES: return f(IntC<WITH_BRES ? BRES : -1>{});
+        default: return f(IntC<-1>{});
+    }
+}
+// ... and for the kernels that compile the BN+ReLU operand prologue beside the epilogue, f(IntC<PRO>{}, IntC<E>{}): a prologue launch
+// has the compiled-in ReLU epilogue or the run-time flags, only prologue-free launches dispatch on epis
+template <bool WITH_BRES, typename F>
+void with_pro_epi(int pro, int epi, int epis, F&& f) {
+    if (pro == LF_PRO_BNRELU && epi == LF_EPI_RELU) f(IntC<1>{}, IntC<LF_EPI_RELU>{});
+    else if (pro == LF_PRO_BNRELU) f(IntC<1>{}, IntC<-1>{});
+    else with_epi<WITH_BRES>(epis, [&](auto e) { f(IntC<0>{}, e); });
 }
 
 extern __shared__ __attribute__((aligned(16))) unsigned char lf_tap_lds[];      // tap tables of tapgemm_kernel

@@ -1,5 +1,5 @@
 // Chain of [Conv2d(k x k, stride 1, pad k/2, bias) -> BatchNorm2d -> ReLU] blocks on an NHWC tensor, forward and
-// backward, on the tap-GEMM kernels of lf_conv.hip.  Precision mode 0 (the default): fp32 tensors on the fp32 matrix cores;
+// backward, on the tap-GEMM kernels of lf_conv.hip and lf_conv_bf16.hip.  Precision mode 0 (the default): fp32 tensors on the fp32 matrix cores;
 // mode 2 (lf_convchain_set_precision, the backbone's "bf16"): x, the pre-BN tensors, y, gy and gx hold bf16 elements and the
 // convolutions and their weight gradients run on the bf16 matrix cores, as the backbone's mode 2 does -- parameters,
 // BatchNorm vectors and statistics, and all gradients of parameters stay fp32.

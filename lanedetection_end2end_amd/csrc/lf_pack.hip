@@ -1,5 +1,5 @@
 // Weight-packing kernels of the tap-GEMM convolutions for gfx950 (see lf_conv.h for the contract): the parameter tensors in the
-// operand orders the kernels of lf_conv.hip read (fp32, bf16, 3-way bf16 split), and the inference engine's fold-and-pack, which
+// operand orders the kernels of lf_conv.hip (fp32, 3-way bf16 split) and lf_conv_bf16.hip (bf16) read, and the inference engine's fold-and-pack, which
 // scales every weight by the BatchNorm factor of its output channel on the way.
 #include "lf_conv.h"
 

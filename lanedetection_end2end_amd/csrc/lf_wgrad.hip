@@ -1,5 +1,5 @@
 // Weight-gradient kernels of the tap-GEMM convolutions for gfx950 (see lf_conv.h for the contract; the forward and data-gradient
-// kernels are in lf_conv.hip, the device helpers shared with them in lf_conv_dev.h, the read-once kernel in lf_wgrad_ro.hip).
+// kernels are in lf_conv.hip and lf_conv_bf16.hip, the device helpers shared with them in lf_conv_dev.h, the read-once kernel in lf_wgrad_ro.hip).
 //
 // Matrix-core mapping (v_mfma_f32_16x16x4_f32, exact fp32, D = A*B + C, wave64):
 //   A[i][k]: lane l supplies row i = l&15, k-slot kq = l>>4      -> weights / x-channels

@@ -45,7 +45,7 @@ def test_workspace_is_a_fraction_of_the_training_one():
 @pytest.fixture(scope="module")
 def conv_kernels(tmp_path_factory):
     import isa_meta
-    return isa_meta.compile_kernels(["lf_conv.hip"], tmp_path_factory.mktemp("isa_infer"))
+    return isa_meta.compile_kernels(["lf_conv.hip", "lf_conv_bf16.hip"], tmp_path_factory.mktemp("isa_infer"))
 
 
 def test_bias_residual_epilogues_are_compiled_in(conv_kernels):

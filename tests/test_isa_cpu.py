@@ -1,6 +1,6 @@
 """No hot kernel may spill vector registers to scratch.
 
-Compiles csrc/lf_conv.hip and csrc/lf_wgrad.hip for gfx950 with -save-temps (hipcc cross-compiles without a GPU) and reads the
+Compiles csrc/lf_conv.hip, csrc/lf_conv_bf16.hip and csrc/lf_wgrad.hip for gfx950 with -save-temps (hipcc cross-compiles without a GPU) and reads the
 .vgpr_spill_count / .private_segment_fixed_size metadata of every instantiation the backbone launches in the
 fp32 and fp32x9 modes (tap-GEMM with every compiled-in epilogue, the 16-channel kernels, the weight gradients).
 """
@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 @pytest.fixture(scope="module")
 def conv_kernels(tmp_path_factory):
     import isa_meta
-    return isa_meta.compile_kernels(["lf_conv.hip", "lf_wgrad.hip"], tmp_path_factory.mktemp("isa"))
+    return isa_meta.compile_kernels(["lf_conv.hip", "lf_conv_bf16.hip", "lf_wgrad.hip"], tmp_path_factory.mktemp("isa"))
 
 
 def _select(kernels, prefix):
