@@ -100,9 +100,19 @@ struct LfWgradArgs {
 // number of k-split rows the kernel will write for this geometry
 int lf_tapwgrad_splits(const LfTapGeom& g);          // upper bound over the kernels that take fp32 tensors
 int lf_tapwgrad_splits_bound(const LfTapGeom& g, int s16);   // ... by storage type: bf16 tensors add the read-once kernel's rows
+long lf_tapwgrad_wave_pixels(const LfTapGeom& g);    // pixels per wave of those kernels (rows = ceil(pixels / (4 * this)))
 // rows the launch with these arguments writes (bf16 tensors: the read-once kernel's row count)
 int lf_tapwgrad_splits_for(const LfTapGeom& g, const LfWgradArgs& a, int pro);
 int lf_tapwgrad_launch(const LfTapGeom& g, const LfWgradArgs& a, int pro, hipStream_t st);
+
+// Weight gradient AND data gradient of a 16 -> 16 channel 3-tap stride-1 convolution on fp32 tensors in one pass (lf_bwd16.hip).
+// gf: the forward (weight-gradient) geometry, gd: the data gradient's -- the plan builds them equal, the data gradient's weights
+// are packed flipped.  w.x is the convolution's input, w.g == a.src the gradient; a.mask_src (MASK) / a.aux (MASKBN) must be w.x.
+// The partial rows are lf_tapwgrad_launch's (lf_tapwgrad_splits_for rows), the statistics rows lf_tapgemm_launch's.
+bool lf_tapbwd16_ok(const LfTapGeom& gf, const LfTapGeom& gd, const LfWgradArgs& w, const LfTapArgs& a, int pro, int epi);
+int lf_tapbwd16_launch(const LfTapGeom& gf, const LfTapGeom& gd, const LfWgradArgs& w, const LfTapArgs& a, int pro, int epi, hipStream_t st);
+void lf_tapbwd16_set(int mode);          // 0: lf_tapbwd16_routed() declines every form; 1: the shipped routing; 2 * m: the forms of bit mask m
+bool lf_tapbwd16_routed(int pro, int epi);   // the network takes the fused launch for this form (the forms that were faster in the step)
 
 // Read-once weight gradient of the 3-tap C -> C convolutions on bf16 tensors (lf_wgrad_ro.hip; C = 64, 128, stride 1, Wl % 16 == 0):
 // one workgroup owns all taps of a 64-channel x-block against every g-channel for its pixel range.  lf_tapwgrad_launch routes to it.

@@ -1,6 +1,6 @@
-// The epilogue the tap-GEMM kernels of lf_conv.hip and lf_conv_bf16.hip share (bias, ReLU, masks, residual, BatchNorm sums), as
+// The epilogue the tap-GEMM kernels of lf_conv.hip, lf_conv_bf16.hip and lf_bwd16.hip share (bias, ReLU, masks, residual, BatchNorm sums), as
 // macros expanded inside the kernel body: they use the kernel's own names (g, a, epi, npix, bx, cob, wave, pl, kq, pn / pi / pj /
-// pv, acc, and the constants NT, EPIC, S16, HOISTV).  Internal: included after lf_conv_dev.h by those two files only.
+// pv, acc, and the constants NT, EPIC, S16, HOISTV).  Internal: included after lf_conv_dev.h by those three files only.
 //
 // Protocol of the LF_EPI_* parameters.  The values defined in this header are the DEFAULTS, and they hold at every point of a file
 // outside a kernel that differs: such a kernel #undef's and redefines a parameter directly before the lines that expand the
@@ -11,6 +11,7 @@
 //                     tapstream_kernel       LF_EPI_GROUPS, LF_EPI_ROW1, LF_EPI_ACC, LF_EPI_FIRST, LF_EPI_ROW_OK
 //                     tapgemm_split_kernel   LF_EPI_GROUPS (around the whole kernel), LF_EPI_PIVOT
 //   lf_conv_bf16.hip  tapgemm_bf16_kernel, tapgemm_bf16_ring_kernel   LF_EPI_PIVOT
+//   lf_bwd16.hip      tapbwd16_kernel        LF_EPI_ACC, LF_EPI_ROW1, LF_EPI_LDADD, LF_EPI_LDMSK, LF_EPI_LDAUX, LF_EPI_HOIST_ALL
 // tapgemm_lean_kernel and tapgemm_bf16_lean_kernel expand the defaults; the whole-line and wave-private bf16 kernels have epilogues
 // of their own and expand nothing from here.
 #pragma once
@@ -24,6 +25,11 @@
 #define LF_EPI_ACC(n, m) acc[n][m]   /* the finished sum of channel tile n, pixel tile m (tapstream_kernel: its one live pixel tile) */
 #define LF_EPI_FIRST(m) ((m) == 0)   /* the pixel tile whose first pixel is the pivot of the BN forward sums */
 #define LF_EPI_ROW_OK(tg) true       /* 4-wave group tg owns a tile of the launch (tapstream_kernel: the last pair of tiles may be half empty) */
+/* the lane's four elements of the residual / mask / BN operand at element offset o (tapbwd16_kernel: its LDS-staged tiles) */
+#define LF_EPI_LDADD(o) epi_ld<S16>(r_add, o)
+#define LF_EPI_LDMSK(o) epi_ld<S16>(r_msk, o)
+#define LF_EPI_LDAUX(o) epi_ld<S16>(r_aux, o)
+#define LF_EPI_HOIST_ALL false       /* tapbwd16_kernel: the MASKBN vectors held in registers beside the BN-backward sums too */
 /* The epilogue in three parts, so that a kernel can run the per-pixel-tile part one tile at a time (tapstream_kernel); LF_TAPGEMM_EPILOGUE
  * below is the three in a row, the form every other kernel expands. */
 #define LF_EPI_HEAD \
@@ -38,7 +44,7 @@
     constexpr int NC = (NT % 2 == 0 && !LF_EPI_ONE_TILE) ? 2 : 1; \
     /* MASKBN + STATS_XHAT: the mask's two per-channel vectors are re-read (L1) instead of held -- 32 registers, the difference \
      * between two and three waves per SIMD for that variant */ \
-    constexpr bool HOISTM = HOISTV && !(EPIC >= 0 && (EPIC & LF_EPI_MASKBN) && (EPIC & LF_EPI_STATS_XHAT)); \
+    constexpr bool HOISTM = HOISTV && (LF_EPI_HOIST_ALL || !(EPIC >= 0 && (EPIC & LF_EPI_MASKBN) && (EPIC & LF_EPI_STATS_XHAT))); \
     const __amdgpu_buffer_rsrc_t r_dst = make_rsrc(a.dst, 0xffffffffu), r_add = make_rsrc(a.add_src, 0xffffffffu), \
                                  r_msk = make_rsrc(a.mask_src, 0xffffffffu), r_aux = make_rsrc(a.aux, 0xffffffffu), \
                                  r_bias = make_rsrc(a.bias, 0xffffffffu), r_msc = make_rsrc(a.msc, 0xffffffffu), \
@@ -70,9 +76,9 @@ _Pragma("unroll") \
 _Pragma("unroll") \
         for (int j = 0; j < NC; ++j) { \
             const int n = n0 + j; \
-            if (epi & LF_EPI_ADD) la[j] = epi_ld<S16>(r_add, dbase + n * 16); \
-            if (epi & LF_EPI_MASK) lm[j] = epi_ld<S16>(r_msk, dbase + n * 16); \
-            if (epi & (LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) lx[j] = epi_ld<S16>(r_aux, dbase + n * 16); \
+            if (epi & LF_EPI_ADD) la[j] = LF_EPI_LDADD(dbase + n * 16); \
+            if (epi & LF_EPI_MASK) lm[j] = LF_EPI_LDMSK(dbase + n * 16); \
+            if (epi & (LF_EPI_MASKBN | LF_EPI_STATS_XHAT)) lx[j] = LF_EPI_LDAUX(dbase + n * 16); \
             if ((epi & LF_EPI_STATS_XHAT) && a.dm && !LF_EPI_ROW1) ld[j] = ldb4(r_dm, (unsigned)(pn[m] * g.Cd + cob + n * 16 + kq * 4) * 4u, 0u); \
         } \
 _Pragma("unroll") \

@@ -37,6 +37,21 @@ void lf_debug_set_wgrad_ro(int mode, int cap64, int cap128);
  * tapgemm_kernel takes every launch, 1 = the shipped routing, 2 = every variant tapstream_kernel is compiled for; max_workgroups > 0
  * caps the grid, so that one workgroup walks several tiles at small shapes.  The kernels agree bit for bit (tests/test_fp32_stream_gpu.py) */
 void lf_debug_set_fp32_stream(int mode, int max_workgroups);
+/* fp32 16-channel 3-tap convolutions in backward: 0 = weight gradient and data gradient as two launches, 1 = the shipped routing
+ * (tapbwd16_kernel, csrc/lf_bwd16.hip, takes the pairs it is routed for in one launch), 2 * m = exactly the forms of bit mask m
+ * (1 mask, 2 recomputed-BN mask + sums with the prologue, 4 residual + mask + sums, 8 residual: A/B runs in the step) */
+void lf_debug_set_bwd16_fused(int mode);
+/* One fused backward launch of a 16 -> 16 channel 3-tap convolution (fp32 tensors) followed by the immediate reduction of its
+ * weight-gradient rows, as lf_conv1d_bwd_weight runs it:
+ *   gx = epilogue(conv1d^T(gy))   with the flag set epi of csrc/lf_conv.h -- one of the four sets the kernel is compiled for;
+ *   gw, gb = the weight and bias gradient against pro(x), pro = relu(x * pro_sc + pro_sh) when pro_sc is given.
+ * The mask (LF_EPI_MASK) and the MASKBN / BN-sums operand of the MASKBN form are x itself; add_src and, beside LF_EPI_MASK, aux are
+ * tensors of their own.  stats: [2][C][rows], rows = ceil(N * H * W / 256).  scratch: lf_debug_conv1d_bwd_pair_scratch_floats floats.
+ * Returns the statistics rows written (0 without a sums flag), -1 on error -- also where the fused kernel does not take the launch. */
+long lf_debug_conv1d_bwd_pair_scratch_floats(int N, int H, int W, int C);
+int lf_debug_conv1d_bwd_pair(const float* x, const float* gy, const float* w, int epi, const float* add_src, const float* aux,
+                             const float* msc, const float* msh, const float* pro_sc, const float* pro_sh, float* gx, float* gw, float* gb,
+                             float* stats, int N, int H, int W, int C, int axis, int dilation, float* scratch, void* stream);
 /* lf_conv1d_bwd_weight with the BN+ReLU operand prologue on x (the weight gradient of a non_bottleneck_1d block's third convolution):
  * gw = d/dw of conv1d(relu(x * sc + sh)), gb = column sums of gy */
 int lf_debug_conv1d_wgrad_pro(const float* x, const float* gy, const float* sc, const float* sh, float* gw, float* gb, int N, int H, int W,

@@ -457,6 +457,7 @@ struct Ctx {
     mutable long wpart_used = 0, bpart_used = 0;
     mutable int last_rows = 0;           // BatchNorm partial rows the last run_gemm wrote (depends on the kernel it selected)
     mutable bool wgrad_launched = false; // the last run_wgrad put a weight-gradient kernel on the stream (not skipped: frozen weight)
+    mutable bool pair_fused = false;     // ... and that kernel computed the convolution's data gradient too (run_bwd_pair)
     // A RANGE of layers may run on a compact workspace (lf_erfnet_range_workspace_bytes): its layers' regions [lo, hi) followed by
     // the globals [cut, ...) -- the full workspace is the case lo = 0, hi = cut.
     long lo = 0, hi = 0, cut = 0;
@@ -470,10 +471,10 @@ double gemm_flops(const LfTapGeom& g) { return 2.0 * (double)g.N * g.Hl * g.Wl *
 struct ProfScope {   // records a HIP event pair on the launch stream around one kernel when profiling is on
     const Ctx& c; int idx = -1;
     hipStream_t pst;
-    ProfScope(const Ctx& ctx, int family, const LfTapGeom& g, int epi, hipStream_t stream) : c(ctx), pst(stream) {
+    ProfScope(const Ctx& ctx, int family, const LfTapGeom& g, int epi, hipStream_t stream, int gemms = 1) : c(ctx), pst(stream) {
         if (!c.P->prof_on) return;
         lf_erfnet_plan::ProfRec r;
-        r.family = family; r.flops = gemm_flops(g);
+        r.family = family; r.flops = gemm_flops(g) * gemms;
         r.layer = c.P->prof_layer; r.Cs = g.Cs; r.Cd = g.Cd; r.ntaps = g.ntaps; r.npix = (long)g.N * g.Hl * g.Wl; r.epi = epi;
         if (hipEventCreate(&r.a) != hipSuccess || hipEventCreate(&r.b) != hipSuccess) return;
         (void)hipEventRecord(r.a, pst);
@@ -591,11 +592,15 @@ int forward_layers(const Ctx& c, const float* img, int nlayers, int first = 0) {
 
 typedef LfBiasChain BiasChain;   // the four phases of a transposed convolution share one bias gradient (lf_plan.h)
 
+// the data gradient that run_bwd_pair offers a weight gradient to compute in the same launch (tapbwd16_kernel, lf_bwd16.hip)
+struct PairDg { const GemmOp* op; float* dst; int epi; LfTapArgs extra; };
+
 // weight + bias gradient of one forward-geometry GEMM
 int run_wgrad(const Ctx& c, const GemmOp& op, const ConvRef& cv, const float* x, const float* g, const float* pro_sc,
-              const float* pro_sh, int bias_accumulate, bool batch_off = false, BiasChain* chain = nullptr) {
+              const float* pro_sh, int bias_accumulate, bool batch_off = false, BiasChain* chain = nullptr, const PairDg* pair = nullptr) {
     const lf_erfnet_plan* P = c.P;
     c.wgrad_launched = false;
+    c.pair_fused = false;
     if (!c.grads[cv.p_w]) return 0;
     hipStream_t ws = c.st;
     LfWgradArgs a;
@@ -615,9 +620,22 @@ int run_wgrad(const Ctx& c, const GemmOp& op, const ConvRef& cv, const float* x,
         float* rows = lf_bias_chain_rows(*chain, c.at(off_bpart_all + c.bpart_used), op.geom.Cd);
         if (a.bias_partial) a.bias_partial = rows;
     }
-    {
+    const int wpro = pro_sc ? LF_PRO_BNRELU : LF_PRO_NONE;
+    if (pair && !chain && !c.s16 && (P->precision == 0 || P->precision == 3) && lf_tapbwd16_routed(wpro, pair->epi)) {
+        // fp32 16-channel pair: one pass over g and x instead of two.  The partial rows, their regions and the reduce job below are
+        // the weight gradient's own; the profiling record is the data gradient's (family 0, both GEMMs' flops).
+        LfTapArgs d = pair->extra;
+        d.src = g; d.dst = pair->dst; d.bias = nullptr; d.wp = c.packed(pair->op->pack); d.s16 = 0;
+        if (lf_tapbwd16_ok(op.geom, pair->op->geom, a, d, wpro, pair->epi)) {
+            c.last_rows = lf_tapgemm_stat_rows_for(pair->op->geom, d);
+            ProfScope ps(c, 0, pair->op->geom, pair->epi, ws, 2);
+            LF_TRY(lf_tapbwd16_launch(op.geom, pair->op->geom, a, d, wpro, pair->epi, ws));
+            c.pair_fused = true;
+        }
+    }
+    if (!c.pair_fused) {
         ProfScope ps(c, 1, op.geom, 0, ws);
-        LF_TRY(lf_tapwgrad_launch(op.geom, a, pro_sc ? LF_PRO_BNRELU : LF_PRO_NONE, ws));
+        LF_TRY(lf_tapwgrad_launch(op.geom, a, wpro, ws));
     }
     c.wgrad_launched = true;
     const LfPackEntry& e = P->packs[op.pack];
@@ -635,6 +653,17 @@ int run_wgrad(const Ctx& c, const GemmOp& op, const ConvRef& cv, const float* x,
                                   c.grads[cv.p_w], e.sk, e.sn, e.tapidx, a.bias_partial, nsplit,
                                   c.grads[cv.p_b], bias_accumulate, ws));
     return 0;
+}
+
+// Weight gradient and data gradient of one 3-tap convolution of a non_bottleneck_1d block: x the convolution's input (with the
+// BN + ReLU recompute pro_sc / pro_sh on it), g the gradient of its output, dst = epilogue(conv^T(g)).  One fused launch where
+// tapbwd16_kernel takes the pair, else the weight gradient and -- beside it -- the data gradient.
+int run_bwd_pair(const Ctx& c, const ConvRef& cv, const float* x, const float* g, const float* pro_sc, const float* pro_sh, float* dst,
+                 int epi, const LfTapArgs& extra) {
+    const PairDg pair = {&cv.dg[0], dst, epi, extra};
+    LF_TRY(run_wgrad(c, cv.fwd, cv, x, g, pro_sc, pro_sh, 0, false, nullptr, &pair));
+    if (c.pair_fused) return 0;
+    return run_gemm(c, cv.dg[0], g, dst, nullptr, LF_PRO_NONE, epi, extra, true);
 }
 
 // Partial rows of the stem / head weight gradients: rows_w [rows][nw] -> gw, rows_b [rows][nb] -> gb (plain column sums).  Batched
@@ -752,32 +781,28 @@ int backward_layers(const Ctx& c, const float* img, float* g0, float* g1, float*
             const float *t1 = c.at(L.b[0]), *t2 = c.at(L.b[1]), *t3 = c.at(L.b[2]);
             const BNRef& b1 = L.bn[0];
             // conv1x3_2: wgrad(t3, g_t4 = X); dgrad -> g_t3 = (.) * [t3 > 0] -> F
-            LF_TRY(run_wgrad(c, L.cv[3].fwd, L.cv[3], t3, X, nullptr, nullptr, 0));
             LfTapArgs a = lf_no_args();
             a.mask_src = t3;
-            LF_TRY(run_gemm(c, L.cv[3].dg[0], X, F, nullptr, LF_PRO_NONE, LF_EPI_MASK, a, true));
+            LF_TRY(run_bwd_pair(c, L.cv[3], t3, X, nullptr, nullptr, F, LF_EPI_MASK, a));
             // conv3x1_2: input relu(bn1(t2)) recomputed on the fly; g_y1 -> X with the bn1-backward sums
-            LF_TRY(run_wgrad(c, L.cv[2].fwd, L.cv[2], t2, F, c.at(b1.sc), c.at(b1.sh), 0));
             a = lf_no_args();
             a.aux = t2; a.msc = c.at(b1.sc); a.msh = c.at(b1.sh); a.asc = c.at(b1.asc); a.ash = c.at(b1.ash);
             a.stats = stat0; a.stats_ld = lf_stat_ld(lf_tapgemm_stat_rows(L.cv[2].dg[0].geom));
-            LF_TRY(run_gemm(c, L.cv[2].dg[0], F, X, nullptr, LF_PRO_NONE, LF_EPI_MASKBN | LF_EPI_STATS_XHAT, a, true));
+            LF_TRY(run_bwd_pair(c, L.cv[2], t2, F, c.at(b1.sc), c.at(b1.sh), X, LF_EPI_MASKBN | LF_EPI_STATS_XHAT, a));
             LfStatPart sp = {stat0, c.last_rows, L.Cout, 0, a.stats_ld};
             LF_TRY(bn_bwd_finalize(c, b1, &sp, 1, (double)npo));
             LF_TRY(lf_bn_bwd_apply(X, nullptr, t2, c.at(b1.asc), c.at(b1.ash), c.params[b1.p_g], c.at(b1.c1), c.at(b1.c2),
                                    nullptr, F /*g_t2*/, nullptr, npo, L.Cout, ppi, c.s16, c.st));
             // conv1x3_1: g_t1 -> X
-            LF_TRY(run_wgrad(c, L.cv[1].fwd, L.cv[1], t1, F, nullptr, nullptr, 0));
             a = lf_no_args();
             a.mask_src = t1;
-            LF_TRY(run_gemm(c, L.cv[1].dg[0], F, X, nullptr, LF_PRO_NONE, LF_EPI_MASK, a, true));
+            LF_TRY(run_bwd_pair(c, L.cv[1], t1, F, nullptr, nullptr, X, LF_EPI_MASK, a));
             // conv3x1_1 (+ residual branch gradient g_z) -> F, optionally prepared for the previous layer
-            LF_TRY(run_wgrad(c, L.cv[0].fwd, L.cv[0], x, X, nullptr, nullptr, 0));
             a = lf_no_args();
             a.add_src = gz;
             int epi = LF_EPI_ADD;
             add_prep(a, epi, L.cv[0].dg[0].geom);
-            LF_TRY(run_gemm(c, L.cv[0].dg[0], X, F, nullptr, LF_PRO_NONE, epi, a, true));
+            LF_TRY(run_bwd_pair(c, L.cv[0], x, X, nullptr, nullptr, F, epi, a));
             out = F;
             if (can_prep) { prepped = true; prep_rows = c.last_rows; prep_ld = a.stats_ld; }
         } else if (L.kind == K_UP) {

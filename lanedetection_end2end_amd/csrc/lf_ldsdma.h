@@ -1,5 +1,6 @@
 // LDS-DMA helpers shared by the bf16 kernels that stage operands through hand-ordered LDS rings (lf_conv_bf16.hip: the ring /
-// whole-line / wave-private tap-GEMMs; lf_wgrad.hip: the 16-channel weight gradient; lf_wgrad_ro.hip: the read-once weight gradient).  gfx950 only.
+// whole-line / wave-private tap-GEMMs; lf_wgrad.hip: the 16-channel weight gradient; lf_wgrad_ro.hip: the read-once weight gradient;
+// lf_bwd16.hip: the fused 16-channel backward).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 

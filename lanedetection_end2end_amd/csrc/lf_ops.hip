@@ -113,6 +113,7 @@ void lf_debug_set_ops_precision(int mode) { g_ops_bf16 = (mode == 2 || mode == 9
 
 void lf_debug_set_wgrad_ro(int mode, int cap64, int cap128) { lf_tapwgrad_ro_set(mode, cap64, cap128); }
 void lf_debug_set_fp32_stream(int mode, int max_workgroups) { lf_tapgemm_set_fp32_stream(mode, max_workgroups); }
+void lf_debug_set_bwd16_fused(int mode) { lf_tapbwd16_set(mode); }
 long lf_debug_bias_residual_launches(void) { return lf_tapgemm_bias_residual_launches(); }
 long lf_debug_partial_fast_launches(void) { return lf_tapgemm_partial_fast_launches(); }
 
@@ -416,6 +417,46 @@ int lf_conv1d_bwd_weight(const float* x, const float* gy, float* gw, float* gb, 
                          int dilation, float* scratch, void* stream) {
     LF_REQUIRE(x && gy && gw && scratch, "lf_conv1d_bwd_weight: null pointer");
     return conv1d_bwd_weight(x, gy, nullptr, nullptr, gw, gb, N, H, W, C, axis, dilation, scratch, (hipStream_t)stream);
+}
+
+// scratch of lf_debug_conv1d_bwd_pair: [packed data-gradient weights 3 C C][partial rows: rows x 3 C C][bias rows: rows x C]
+long lf_debug_conv1d_bwd_pair_scratch_floats(int N, int H, int W, int C) {
+    if (N < 1 || H < 1 || W < 1 || C < 1) return -1;
+    const long rows = lf_tapwgrad_splits(conv1d_geom(N, H, W, C, 0, 1));
+    return 3L * C * C + rows * (3L * C * C + C);
+}
+
+int lf_debug_conv1d_bwd_pair(const float* x, const float* gy, const float* w, int epi, const float* add_src, const float* aux,
+                             const float* msc, const float* msh, const float* pro_sc, const float* pro_sh, float* gx, float* gw, float* gb,
+                             float* stats, int N, int H, int W, int C, int axis, int dilation, float* scratch, void* stream) {
+    if (!(x && gy && w && gx && gw && gb && scratch)) { lf_fail("lf_debug_conv1d_bwd_pair: null pointer"); return -1; }
+    if (N < 1 || H < 1 || W < 1 || C < 1 || dilation < 1 || (axis != 0 && axis != 1)) { lf_fail("lf_debug_conv1d_bwd_pair: bad arguments"); return -1; }
+    if (g_ops_bf16 == 2) { lf_fail("lf_debug_conv1d_bwd_pair: fp32 tensors only"); return -1; }
+    hipStream_t st = (hipStream_t)stream;
+    const LfTapGeom g = conv1d_geom(N, H, W, C, axis, dilation);
+    const long rows = lf_tapwgrad_splits(g);
+    LfTapArgs a;
+    memset(&a, 0, sizeof(a));
+    LfWgradArgs wa;
+    wa.x = x; wa.g = gy; wa.pro_sc = pro_sc; wa.pro_sh = pro_sh; wa.s16 = 0; wa.split = 0;
+    wa.partial = scratch + 3L * C * C;
+    wa.bias_partial = wa.partial + rows * 3L * C * C;
+    a.wp = scratch;
+    a.src = gy; a.dst = gx; a.add_src = add_src; a.msc = msc; a.msh = msh; a.stats = stats;
+    a.mask_src = (epi & LF_EPI_MASK) ? x : nullptr;
+    a.aux = (epi & LF_EPI_MASKBN) ? x : aux;
+    a.stats_ld = lf_tapgemm_stat_rows(g);        // the caller's buffer: [2][C][rows], rows = ceil(N * H * W / 256)
+    const int pro = pro_sc ? LF_PRO_BNRELU : LF_PRO_NONE;
+    if (!lf_tapbwd16_ok(g, g, wa, a, pro, epi)) {
+        lf_fail("lf_debug_conv1d_bwd_pair: the fused kernel does not take this launch (epi %d, prologue %d, %d x %d x %d x %d)", epi, pro, N, H, W, C);
+        return -1;
+    }
+    hipLaunchKernelGGL(pack_one_kernel, dim3(64), dim3(256), 0, st, w, scratch, C, C, 3, 3L * C, 3L, conv1d_taps(1));
+    if (lf_tapbwd16_launch(g, g, wa, a, pro, epi, st)) return -1;
+    const int idx[3] = {0, 1, 2};
+    const int nsplit = lf_tapwgrad_splits_for(g, wa, pro);
+    if (lf_wgrad_reduce_launch(wa.partial, nsplit, 3, C, C, gw, 3L, 3L * C, idx, wa.bias_partial, nsplit, gb, 0, st)) return -1;
+    return (epi & LF_EPI_STATS_XHAT) ? lf_tapgemm_stat_rows_for(g, a) : 0;
 }
 
 int lf_debug_conv1d_wgrad_pro(const float* x, const float* gy, const float* sc, const float* sh, float* gw, float* gb, int N, int H, int W,

@@ -841,6 +841,7 @@ void launch_wgrad(const LfTapGeom& g, const LfWgradArgs& a, int pro, const Wgrad
 }  // namespace
 
 int lf_tapwgrad_splits(const LfTapGeom& g) { return wgrad_cfg(g).gx; }
+long lf_tapwgrad_wave_pixels(const LfTapGeom& g) { return wgrad_cfg(g).pps; }
 int lf_tapwgrad_splits_bound(const LfTapGeom& g, int s16) {
     const int a = lf_tapwgrad_splits(g), c = s16 ? lf_tapwgrad_ro_rows_bound(g) : 0;
     return a > c ? a : c;
