@@ -50,7 +50,9 @@ extern "C" {
                                  lf_grad_norm_finish, lf_grad_scale_inplace, lf_adam_step_clipped, lf_sgd_step_clipped,
                                  lf_rmsprop_step_clipped;
                                  additions since 5 (segmentation-mode detect): lf_head_fit_seg, lf_lane_infer_seg_workspace_bytes,
-                                 lf_lane_infer_seg */
+                                 lf_lane_infer_seg;
+                                 additions since 5 (input-image gradient): lf_stem_bwd_data, lf_erfnet_backward_input (and
+                                 lf_erfnet_backward_range writes a non-NULL gx for first = 0) */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -304,7 +306,8 @@ int lf_wls_bwd_grid(const float* logits, const float* grid_xy, long grid_batch_s
  * The workspace of a range is COMPACT (ABI 4): lf_erfnet_range_workspace_bytes(plan, first, last) = the range's own activations
  * + the plan's globals (packed weights, statistics rows, one partial-row region, three gradient buffers), so that a loop over
  * the blocks of a network keeps the activations of ONE network alive until backward, not one whole-network workspace per block.
- * gx is not produced for first = 0: the image takes no gradient (as in lf_erfnet_backward). */
+ * gx may be NULL for any range.  For first = 0 a non-NULL gx receives the image's gradient (N,Cin,H,W) from one extra launch,
+ * lf_stem_bwd_data, as lf_erfnet_backward_input's grad_img does; with NULL the stem runs its weight gradient only. */
 int lf_erfnet_num_layers(const lf_erfnet_plan* plan);
 size_t lf_erfnet_range_workspace_bytes(const lf_erfnet_plan* plan, int first, int last);
 int lf_erfnet_layer_io(const lf_erfnet_plan* plan, int layer, int* out6_host);   /* Cin, Hin, Win, Cout, Hout, Wout */
@@ -666,6 +669,26 @@ int lf_conv1d_bwd_data(const float* gy, const float* w, const float* mask_src, f
                        int C, int axis, int dilation, float* scratch, void* stream);
 int lf_conv1d_bwd_weight(const float* x, const float* gy, float* gw, float* gb, int N, int H, int W, int C,
                          int axis, int dilation, float* scratch, void* stream);
+
+/* additions since 5 -- input-image gradient: d loss / d input of Net.forward, what `input.requires_grad_()` before the forward and
+ * `loss.backward()` (BEV/main.py:264-266) give in the reference -- the data gradient of the stem DownsamplerBlock's
+ * cat[conv3x3 s2 p1 (input), max_pool2d(input, 2)] (BEV/Networks/ERFNet.py:11-22,66), the one layer that had none.
+ * lf_stem_bwd_data: gcat (N,H/2,W/2,16) NHWC = the gradient of the block's pre-BatchNorm concat buffer (fp32, or bf16 bit patterns
+ *   with s16 = 1, widened exactly), img (N,Cin,H,W) NCHW fp32, w (16-Cin,Cin,3,3) the raw convolution weight -> gimg (N,Cin,H,W)
+ *   NCHW fp32: every element WRITTEN (not accumulated), by a gather without atomics (the same bits on every launch); fp32
+ *   products and sums.  The pooled channels' gradient goes to the first maximum of each 2x2 window in scan order (ATen's
+ *   max_pool2d rule); every other pixel of the window takes exactly nothing from it.  Cin 1..4, any even H and W, both tensors
+ *   within 32-bit byte offsets.
+ * lf_erfnet_backward_input: lf_erfnet_backward with grad_img (N,Cin,H,W) in front of the workspace.  NULL: lf_erfnet_backward
+ *   itself, launch for launch.  Otherwise ONE launch more, lf_stem_bwd_data behind the stem's weight gradient (also when the stem's
+ *   weight is frozen and takes none); every precision mode, training 0 / 1, head -1 / 0 / 1, with and without grad_encoder; no
+ *   workspace beyond lf_erfnet_workspace_bytes_for. */
+int lf_stem_bwd_data(const float* gcat, const float* img, const float* w, int N, int Cin, int H, int W, int s16, float* gimg,
+                     void* stream);
+int lf_erfnet_backward_input(const lf_erfnet_plan* plan, const float* img, const float* grad_logits,
+                             const float* grad_encoder, const float* const* params_host, float* const* grads_host,
+                             const float* dropmask, int training, int head, float* grad_img, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* additions since 5 -- segmentation-mode detect: the test-time path of a model trained with end_to_end = False (the reference's
  * baseline and its pre-training epochs), Net.forward's arg-max branch (BEV/Networks/LSQ_layer.py:302-308,

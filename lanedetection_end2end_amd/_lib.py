@@ -138,6 +138,8 @@ def _declare(lib):
         "lf_head_fit_seg": (I, [P, I, P, P, P, L, P, I, I, I, I, I, I, I, D, D, I, P, P, P, P, P, P]),
         "lf_lane_infer_seg_workspace_bytes": (c_size_t, [P, I, I, I]),
         "lf_lane_infer_seg": (I, [P, P, P, P, P, P, L, P, I, I, I, D, D, I, P, P, P, P, c_size_t, P]),
+        "lf_stem_bwd_data": (I, [P, P, P, I, I, I, I, I, P, P]),
+        "lf_erfnet_backward_input": (I, [P, P, P, P, P, P, P, I, I, P, P, c_size_t, P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {

@@ -451,6 +451,7 @@ struct Ctx {
     int training;
     hipStream_t st;
     const float* g_enc = nullptr;    // backward: extra gradient w.r.t. the encoder output (NHWC) or null
+    float* g_img = nullptr;          // backward: receives d loss / d image (NCHW fp32), or null: the stem runs its weight gradient only
     int s16 = 0;                     // precision mode 2: activation / gradient tensors hold bf16 elements
     // weight-gradient reductions deferred to the end of the backward pass (one batched launch per LF_REDUCE_BATCH jobs)
     mutable std::vector<LfReduceJob> reduce_jobs;
@@ -830,13 +831,14 @@ int backward_layers(const Ctx& c, const float* img, float* g0, float* g1, float*
             out = F;
             if (can_prep) { prepped = true; prep_rows = c.last_rows; prep_ld = a.stats_ld; }
         } else if (L.x < 0) {
-            // stem: weight gradient only (the image needs no gradient)
+            // stem: the weight gradient, and the image's gradient where it was asked for (one more launch on the same X and img)
             const int Cc = 16 - L.Cin, rows = lf_stem_wgrad_rows(N, L.Hin, L.Win);
             if (c.grads[L.cv[0].p_w]) {
                 const RowSums rs = row_sum_regions(c, (long)rows * Cc * L.Cin * 9, (long)rows * Cc);
                 LF_TRY(lf_stem_wgrad(img, X, N, L.Cin, L.Hin, L.Win, rs.wrows, rs.brows, c.s16, c.st));
                 LF_TRY(row_sums_finish(c, rs, rows, Cc * L.Cin * 9, c.grads[L.cv[0].p_w], Cc, c.grads[L.cv[0].p_b]));
             }
+            if (c.g_img) LF_TRY(lf_stem_bwd_data(X, img, c.params[L.cv[0].p_w], N, L.Cin, L.Hin, L.Win, c.s16, c.g_img, c.st));
             out = F;
         } else {
             LF_TRY(run_wgrad(c, L.cv[0].fwd, L.cv[0], c.at(L.x), X, nullptr, nullptr, 0));
@@ -905,14 +907,18 @@ int lf_erfnet_forward(const lf_erfnet_plan* P, const float* img, const float* co
 // encoder.output_conv, the unused head).  Gradients are WRITTEN, not accumulated.
 // head = -1: backward of the encoder-only forward: grad_encoder is the incoming gradient (required), grad_logits is ignored,
 // decoder parameters receive no gradient (their grads_host entries must be NULL).
-int lf_erfnet_backward(const lf_erfnet_plan* P, const float* img, const float* grad_logits,
-                       const float* grad_encoder, const float* const* params_host, float* const* grads_host,
-                       const float* dropmask, int training, int head, void* workspace, size_t workspace_bytes, void* stream) {
+// grad_img (lf_erfnet_backward_input): (N,Cin,H,W) NCHW fp32 receiving d loss / d img from one more launch in the stem's branch
+// (lf_stem_bwd_data), or NULL: the launches of lf_erfnet_backward, which is this call with NULL.
+int lf_erfnet_backward_input(const lf_erfnet_plan* P, const float* img, const float* grad_logits,
+                             const float* grad_encoder, const float* const* params_host, float* const* grads_host,
+                             const float* dropmask, int training, int head, float* grad_img, void* workspace,
+                             size_t workspace_bytes, void* stream) {
     LF_REQUIRE(P && img && (grad_logits || head < 0) && params_host && grads_host && workspace, "lf_erfnet_backward: null pointer");
     LF_REQUIRE(workspace_bytes >= lf_erfnet_workspace_bytes(P), "lf_erfnet_backward: workspace too small");
     LF_REQUIRE(head >= -1 && head < P->n_heads, "lf_erfnet_backward: head %d out of range", head);
     Ctx c{P, (float*)workspace, params_host, grads_host, nullptr, dropmask, training, (hipStream_t)stream};
     c.g_enc = grad_encoder;
+    c.g_img = grad_img;
     c.s16 = P->precision == 2;       // (mode 2: grad_encoder holds bf16 elements, as the encoder output it differentiates)
     float *gA = c.at(P->off_gA), *gB = c.at(P->off_gB), *gC = c.at(P->off_gC);
     if (head < 0) {       // encoder only: the incoming gradient IS d loss / d (encoder output); the pass overwrites its buffers
@@ -939,6 +945,13 @@ int lf_erfnet_backward(const lf_erfnet_plan* P, const float* img, const float* g
     LF_TRY(backward_layers(c, img, gA, gB, gC, (int)P->layers.size()));
     if (!c.reduce_jobs.empty()) LF_TRY(lf_wgrad_reduce_batch_launch(c.reduce_jobs.data(), (int)c.reduce_jobs.size(), c.st));
     return 0;
+}
+
+int lf_erfnet_backward(const lf_erfnet_plan* P, const float* img, const float* grad_logits,
+                       const float* grad_encoder, const float* const* params_host, float* const* grads_host,
+                       const float* dropmask, int training, int head, void* workspace, size_t workspace_bytes, void* stream) {
+    return lf_erfnet_backward_input(P, img, grad_logits, grad_encoder, params_host, grads_host, dropmask, training, head, nullptr,
+                                    workspace, workspace_bytes, stream);
 }
 
 // Per-kernel-family timing for the roofline report.  enable=1 starts recording a HIP event pair around
@@ -1100,7 +1113,7 @@ int lf_erfnet_forward_range(const lf_erfnet_plan* P, int first, int last, int he
 }
 
 // Backward of lf_erfnet_forward_range on the same workspace: gy = d loss / d y (NCHW, the forward's output shape); gx (NCHW,
-// the forward's input shape) or NULL (always NULL-able; ignored when first = 0: the image takes no gradient).
+// the forward's input shape) or NULL (always NULL-able; with first = 0 it is the image's gradient, written by the stem's branch).
 // grads_host: n_params device pointers; only the range's (and the head's) entries are written, NULL entries skipped.
 int lf_erfnet_backward_range(const lf_erfnet_plan* P, int first, int last, int head, const float* x, const float* gy,
                              const float* const* params_host, float* const* grads_host, const float* dropmask, int training,
@@ -1111,6 +1124,7 @@ int lf_erfnet_backward_range(const lf_erfnet_plan* P, int first, int last, int h
     Ctx c{P, (float*)workspace, params_host, grads_host, nullptr, dropmask, training, (hipStream_t)stream};
     compact(c, first, last);
     c.s16 = P->precision == 2;
+    if (first == 0) c.g_img = gx;
     float *gA = c.at(P->off_gA), *gB = c.at(P->off_gB), *gC = c.at(P->off_gC);
     const Layer& Ll = P->layers[last - 1];
     if (head >= 0) {

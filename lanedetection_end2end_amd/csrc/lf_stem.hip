@@ -8,6 +8,8 @@
 // GEMMs with K = 27 (stem) or K = pixels (weight gradients): v_mfma_f32_16x16x4_f32 (exact fp32), operands by 4-byte buffer loads --
 // the NHWC side contiguous 256 bytes per instruction, the NCHW image / logit-gradient side gathers that stay inside a few cache
 // lines per instruction -- with the padding as out-of-range offsets (the load returns 0.0f).
+// The stem's DATA gradient (the input image's gradient, lf_stem_bwd_data) is not a GEMM worth the matrix cores: 9 (16 - Cin) FMAs per
+// image pixel and channel against 40 bytes per pixel -- a gather on the vector ALU, bound by its bytes.
 #include "lf_eltwise.h"
 #include "lf_types.h"
 
@@ -189,6 +191,95 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
     }
 }
 
+// ---- stem data gradient (the input image's gradient).  A gather: one thread owns the 2x2 window (oy, ox) of image pixels
+// (2 oy + a, 2 ox + b) in all CIN channels.  With stride 2 and padding 1 the output pixels whose 3x3 patch holds an image pixel are
+//   (a, b) = (0, 0): (oy, ox) by tap (1, 1);   (0, 1): (oy, ox + 1) by (1, 0) and (oy, ox) by (1, 2);   (1, 0): (oy + 1, ox) by (0, 1)
+//   and (oy, ox) by (2, 1);   (1, 1): (oy + 1, ox + 1), (oy + 1, ox), (oy, ox + 1), (oy, ox) by (0, 0), (0, 2), (2, 0), (2, 2)
+// so the window reads the four gradient pixels (oy .. oy + 1, ox .. ox + 1) -- 16 channels each, four channels per load, the ones
+// past the right / bottom edge as out-of-range offsets (never the next row's first pixel) -- and spends 9 Cc FMAs per channel on
+// them; the weights are LDS broadcasts.  The pooled channel Cc + ci goes to the window's arg-max pixel of image
+// channel ci (pool_bwd_kernel's rule: the first maximum in scan order, strict >) by a select.  Every element of gimg is
+// written once, by plain stores: no atomics, the same bits on every launch.  160 bytes and 9 Cc CIN FMAs per window: bound by bytes.
+template <typename T>
+__device__ __forceinline__ f32x4 ldq4(__amdgpu_buffer_rsrc_t r, unsigned elem, bool in) {
+    if constexpr (sizeof(T) == 2) {
+        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)(in ? elem * 2u : OOB), 0, 0);
+        f32x4 o = {__uint_as_float(v[0] << 16), __uint_as_float(v[0] & 0xffff0000u), __uint_as_float(v[1] << 16),
+                   __uint_as_float(v[1] & 0xffff0000u)};
+        return o;
+    } else {
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        return __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(r, (int)(in ? elem * 4u : OOB), 0, 0));
+    }
+}
+
+template <int CIN, typename T>
+__global__ __launch_bounds__(256) void stem_bwd_data_kernel(const T* __restrict__ gcat, const float* __restrict__ img,
+                                                           const float* __restrict__ w, int N, int H, int W, float* __restrict__ gimg) {
+    constexpr int Cc = 16 - CIN;
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const int Ho = H / 2, Wo = W / 2;
+    const unsigned nwin = (unsigned)(N * Ho * Wo), p = (unsigned)blockIdx.x * 256u + threadIdx.x;
+    const bool valid = p < nwin;
+    // the weights through LDS (as scalar operands the 9 Cc CIN of them are fetched up front and spill SGPRs)
+    __shared__ __attribute__((aligned(16))) float ws[(Cc * CIN * 9 + 3) / 4 * 4];
+    for (int i = threadIdx.x; i < Cc * CIN * 9; i += 256) ws[i] = w[i];
+    __syncthreads();
+    const unsigned q = valid ? p : 0u, rr = q / (unsigned)Wo;
+    const int ox = (int)(q - rr * (unsigned)Wo), n = (int)(rr / (unsigned)Ho), oy = (int)(rr - (unsigned)n * (unsigned)Ho);
+    const __amdgpu_buffer_rsrc_t ri = rsrc_of(img, (long)N * CIN * H * W * 4), rg = rsrc_of(gcat, (long)N * Ho * Wo * 16 * (long)sizeof(T));
+    const bool right = valid && ox + 1 < Wo, down = valid && oy + 1 < Ho;
+    const unsigned ibase = (unsigned)((n * CIN * H + 2 * oy) * W + 2 * ox);      // image element (n, 0, 2 oy, 2 ox)
+    float v[CIN][4];                                                              // the window of every image channel, scan order
+#pragma unroll
+    for (int ci = 0; ci < CIN; ++ci) {
+        const unsigned o = (ibase + (unsigned)(ci * H * W)) * 4u;
+        const u32x2 r0 = __builtin_amdgcn_raw_buffer_load_b64(ri, (int)(valid ? o : OOB), 0, 0);
+        const u32x2 r1 = __builtin_amdgcn_raw_buffer_load_b64(ri, (int)(valid ? o + (unsigned)W * 4u : OOB), 0, 0);
+        v[ci][0] = __uint_as_float(r0[0]); v[ci][1] = __uint_as_float(r0[1]);
+        v[ci][2] = __uint_as_float(r1[0]); v[ci][3] = __uint_as_float(r1[1]);
+    }
+    float acc[CIN][4], gp[CIN];
+#pragma unroll
+    for (int ci = 0; ci < CIN; ++ci) acc[ci][0] = acc[ci][1] = acc[ci][2] = acc[ci][3] = 0.f;
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+        const unsigned e = q * 16u + (unsigned)(4 * c4);
+        const f32x4 g00 = ldq4<T>(rg, e, valid), g01 = ldq4<T>(rg, e + 16u, right), g10 = ldq4<T>(rg, e + (unsigned)Wo * 16u, down),
+                    g11 = ldq4<T>(rg, e + (unsigned)Wo * 16u + 16u, right && down);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int co = 4 * c4 + k;
+            if (co >= Cc) { gp[co - Cc] = g00[k]; continue; }
+#pragma unroll
+            for (int ci = 0; ci < CIN; ++ci) {
+                const float* wk = ws + (co * CIN + ci) * 9;                        // (the same address in every lane: a broadcast)
+                acc[ci][0] += wk[4] * g00[k];
+                acc[ci][1] += wk[3] * g01[k]; acc[ci][1] += wk[5] * g00[k];
+                acc[ci][2] += wk[1] * g10[k]; acc[ci][2] += wk[7] * g00[k];
+                acc[ci][3] += wk[0] * g11[k]; acc[ci][3] += wk[2] * g10[k]; acc[ci][3] += wk[6] * g01[k]; acc[ci][3] += wk[8] * g00[k];
+            }
+        }
+    }
+    if (!valid) return;
+#pragma unroll
+    for (int ci = 0; ci < CIN; ++ci) {
+        int arg = 0;
+        float m = v[ci][0];
+        if (v[ci][1] > m) { m = v[ci][1]; arg = 1; }
+        if (v[ci][2] > m) { m = v[ci][2]; arg = 2; }
+        if (v[ci][3] > m) { m = v[ci][3]; arg = 3; }
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = arg == j ? acc[ci][j] + gp[ci] : acc[ci][j];
+        float* d = gimg + ((size_t)(n * CIN + ci) * H + 2 * oy) * W + 2 * ox;
+        const f32x2 d0 = {o[0], o[1]}, d1 = {o[2], o[3]};
+        __builtin_memcpy(d, &d0, 8); __builtin_memcpy(d + W, &d1, 8);            // (8 contiguous bytes, 4-byte aligned)
+    }
+}
+
 // ---- head weight gradient.  ConvTranspose2d(16, K, 2, stride 2), weight (16, K, 2, 2): dW[ci][k][a][b] = sum_p x[p][ci] *
 // gout[n][k][2 i + a][2 j + b], db[k] = sum gout.  D[ci][col] with col = k * 4 + a * 2 + b: A = x (lane: channel l & 15, pixel slot
 // l >> 4: 256 contiguous bytes per instruction), B = the logit gradients of the pixel's 2x2 output window (gathers from the NCHW
@@ -325,6 +416,26 @@ int lf_stem_wgrad(const float* img, const float* gcat, int N, int Cin, int H, in
     switch (Cin) { case 1: LF_STEMW(1); break; case 2: LF_STEMW(2); break; case 3: LF_STEMW(3); break; default: LF_STEMW(4); break; }
 #undef LF_STEMW
     LF_CHECK_LAUNCH("stem_wgrad");
+    return 0;
+}
+
+// include/lanefit.h, "additions since 5 -- input-image gradient"
+extern "C" int lf_stem_bwd_data(const float* gcat, const float* img, const float* w, int N, int Cin, int H, int W, int s16,
+                                float* gimg, void* stream) {
+    LF_REQUIRE(gcat && img && w && gimg, "stem_bwd_data: null pointer");
+    LF_REQUIRE(N >= 1 && Cin >= 1 && Cin <= 4, "stem_bwd_data: in_channels %d not in 1..4", Cin);
+    LF_REQUIRE(H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "stem_bwd_data: odd image size");
+    LF_REQUIRE((long)N * Cin * H * W * 4 < (long)OOB && (long)N * (H / 2) * (W / 2) * 64 < (long)OOB, "stem_bwd_data: tensor too large for 32-bit byte offsets");
+    const dim3 grid(lf_cdiv((long)N * (H / 2) * (W / 2), 256));
+    hipStream_t st = (hipStream_t)stream;
+#define LF_STEMD(CI)                                                                                                                 \
+    do {                                                                                                                             \
+        if (s16) hipLaunchKernelGGL((stem_bwd_data_kernel<CI, lf_bf16>), grid, dim3(256), 0, st, as<lf_bf16>(gcat), img, w, N, H, W, gimg); \
+        else hipLaunchKernelGGL((stem_bwd_data_kernel<CI, float>), grid, dim3(256), 0, st, gcat, img, w, N, H, W, gimg);             \
+    } while (0)
+    switch (Cin) { case 1: LF_STEMD(1); break; case 2: LF_STEMD(2); break; case 3: LF_STEMD(3); break; default: LF_STEMD(4); break; }
+#undef LF_STEMD
+    LF_CHECK_LAUNCH("stem_bwd_data");
     return 0;
 }
 

@@ -269,11 +269,19 @@ class _BackboneFn(torch.autograd.Function):
         if glogits is not None:
             glogits = glogits.contiguous()
         _lib.check(lib.lf_erfnet_set_precision(plan.handle, ctx.precision), "lf_erfnet_set_precision")
-        _lib.check(lib.lf_erfnet_backward(plan.handle, _lib.ptr(ctx.x), _lib.ptr(glogits), _lib.ptr(genc),
-                                          ctx.net._ptrs.get("params", params), ctx.net._ptrs.get("grads", grads), _lib.ptr(ctx.dropmask), ctx.training,
-                                          ctx.head, _lib.ptr(ctx.ws), ctx.ws_bytes, _lib.stream()), "lf_erfnet_backward")
+        gx = None
+        if ctx.needs_input_grad[2]:      # the image's gradient: one more launch in the stem's branch (lf_stem_bwd_data)
+            gx = torch.empty_like(ctx.x)
+            _lib.check(lib.lf_erfnet_backward_input(plan.handle, _lib.ptr(ctx.x), _lib.ptr(glogits), _lib.ptr(genc),
+                                                    ctx.net._ptrs.get("params", params), ctx.net._ptrs.get("grads", grads),
+                                                    _lib.ptr(ctx.dropmask), ctx.training, ctx.head, _lib.ptr(gx), _lib.ptr(ctx.ws),
+                                                    ctx.ws_bytes, _lib.stream()), "lf_erfnet_backward_input")
+        else:
+            _lib.check(lib.lf_erfnet_backward(plan.handle, _lib.ptr(ctx.x), _lib.ptr(glogits), _lib.ptr(genc),
+                                              ctx.net._ptrs.get("params", params), ctx.net._ptrs.get("grads", grads), _lib.ptr(ctx.dropmask), ctx.training,
+                                              ctx.head, _lib.ptr(ctx.ws), ctx.ws_bytes, _lib.stream()), "lf_erfnet_backward")
         ctx.ws = None
-        return (None, None, None, None, None, None) + tuple(grads)
+        return (None, None, gx, None, None, None) + tuple(grads)
 
 
 class _PointwiseFn(torch.autograd.Function):
@@ -317,7 +325,8 @@ class _RangeFn(torch.autograd.Function):
 
     The call owns a COMPACT workspace (the range's activations + the plan's globals, ``lf_erfnet_range_workspace_bytes``) until its
     backward: ``for l in net.encoder.layers: x = l(x)`` keeps the activations of one network, not a whole-network workspace per
-    block.  With ``first == 0`` the input is the image and receives no gradient (``gx`` is None), as in the full pass."""
+    block.  With ``first == 0`` the input is the image; its gradient comes from the stem's data-gradient launch, as in the full
+    pass."""
 
     @staticmethod
     def forward(ctx, net, plan, x, first, last, head, training, dropmask, *params):
@@ -353,7 +362,7 @@ class _RangeFn(torch.autograd.Function):
         used = ctx.net._range_param_mask(first, last, head)
         needs = ctx.needs_input_grad[8:]
         grads = [torch.empty_like(p) if (n and u) else None for p, n, u in zip(ctx.params, needs, used)]
-        gx = torch.empty_like(ctx.x) if (ctx.needs_input_grad[2] and first > 0) else None
+        gx = torch.empty_like(ctx.x) if ctx.needs_input_grad[2] else None
         _lib.check(lib.lf_erfnet_set_precision(ctx.plan.handle, ctx.precision), "lf_erfnet_set_precision")
         _lib.check(lib.lf_erfnet_backward_range(ctx.plan.handle, first, last, head, _lib.ptr(ctx.x), _lib.ptr(gy),
                                                 _ptr_array(ctx.params), _ptr_array(grads), _lib.ptr(ctx.dropmask), ctx.training,
@@ -376,7 +385,9 @@ class Net(nn.Module):
     result is differentiable through the encoder like the ``--clas`` heads' input.
 
     Deviations: ``encoder_output`` is a channels-last view of the engine's workspace (logical shape (N,128,H/8,W/8) as in
-    the reference, differentiable: the ``--clas`` heads train through it); no gradient is produced for the input image.
+    the reference, differentiable: the ``--clas`` heads train through it).  The input image is differentiable as in the
+    reference (``input.requires_grad_()``: one more launch in the backward, ``lf_stem_bwd_data``; nothing changes when it does
+    not require a gradient); double backward is not supported, as for every Function here.
     """
     three_outputs = False
 
