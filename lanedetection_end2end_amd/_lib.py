@@ -167,6 +167,18 @@ def _declare(lib):
         "lf_debug_conv1d_wgrad_pro": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P, P]),
         "lf_debug_bias_residual_launches": (L, []),
         "lf_debug_partial_fast_launches": (L, []),
+        # one launch of a bandwidth-bound backbone kernel; a source of partial rows = (rows, nrows, ld, C, ch_off, tile_pix, seg_rows, seg_pix)
+        "lf_debug_bn_finalize_fwd": (I, [P, I, I, I, I, I, I, L] * 2 + [I, D, P, P, P, P, ctypes.c_float, ctypes.c_float, I, P, P, P, P, P]),
+        "lf_debug_bn_bwd_finalize": (I, [P, I, I, I, I, I, I, L] * 2 + [I, D, P, P, P, P, P, P, I, P]),
+        "lf_debug_bn_act": (I, [P, P, P, P, P, P, L, I, L, I, P]),
+        "lf_debug_bn_bwd_reduce": (I, [P, P, P, P, P, P, P, I, L, I, L, I, P]),
+        "lf_debug_bn_bwd_apply": (I, [P, P, P, P, P, P, P, P, P, P, P, L, I, L, I, P]),
+        "lf_debug_pool_concat_fwd": (I, [P, I, I, I, I, P, I, I, P, I, I, P]),
+        "lf_debug_pool_affine_fwd": (I, [P, I, I, I, I, P, I, I, P, P, I, P]),
+        "lf_debug_pool_bwd": (I, [P, P, I, I, I, I, I, I, P, I, P]),
+        "lf_debug_stem_fwd": (I, [P, I, I, I, I, P, P, P, P, P, P, I, I, P]),
+        "lf_debug_head_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
+        "lf_debug_head_bwd_data": (I, [P, P, P, I, I, I, I, I, P]),
     }
     for table in (sig, dbg):
         for name, (res, args) in table.items():

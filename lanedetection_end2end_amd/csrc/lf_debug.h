@@ -109,6 +109,77 @@ int lf_debug_stem_wgrad(int reduce, const float* img, const float* gcat, float* 
 long lf_debug_head_wgrad_scratch_floats(int N, int h, int w, int K);
 int lf_debug_head_wgrad(int reduce, const float* x, const float* gout, float* gw, float* gb, int N, int h, int w, int K, float* scratch,
                         void* stream);
+/* ---- ONE launch of a bandwidth-bound backbone kernel (csrc/lf_eltwise.h: BatchNorm finalise / apply / backward, max-pool branch, stem
+ * forward, head forward / data gradient), as the ERFNet plan issues it.  (tests/test_eltwise_gpu.py)
+ * Common to all of them: activation and gradient tensors are NHWC fp32 (s16 = 0) or NHWC bf16 (s16 = 1; the pointers still travel as
+ * float*) -- s16 is an argument, lf_debug_set_ops_precision is NOT read; per-channel vectors, statistics rows, the image, the logits and
+ * every parameter are fp32 either way.  Tensor and vector pointers are 16-byte aligned.  Every hook checks its pointers and sizes on the
+ * host and returns -1 (lf_last_error) WITHOUT launching where the launcher's own geometry would not hold.
+ *
+ * A source of partial rows is eight flat arguments (rows, nrows, ld, C, ch_off, tile_pix, seg_rows, seg_pix) = LfStatPart:
+ *   rows      [2][C][ld] fp32, CHANNEL-MAJOR: element (kind, c, row) = rows[(kind * C + c) * ld + row]; only row < nrows is read -- the
+ *             floats in [nrows, ld) may hold anything.  ld >= nrows, ld % 4 == 0, rows 16-byte aligned.  rows = NULL: no such source.
+ *   C, ch_off the source covers channels [ch_off, ch_off + C) of the layer (multiples of 4); a channel no source covers sums to zero.
+ *   tile_pix  0: RAW rows, kind 0 = sum v, kind 1 = sum v^2 (backward: sum g, sum g * t).
+ *             > 0: CENTRED rows, kind 0 = sum v, kind 1 = M2 = sum (v - row mean)^2; row r covers pixels (r % seg_rows) * tile_pix .. of a
+ *             launch of seg_pix pixels -- n_r = min(tile_pix, seg_pix - (r % seg_rows) * tile_pix) --, nrows % seg_rows == 0 (the four
+ *             sub-pixel phases of a transposed convolution: nrows = 4 * seg_rows), (seg_rows - 1) * tile_pix < seg_pix <= seg_rows * tile_pix.
+ *
+ * lf_debug_bn_finalize_fwd: up to two sources, then the arguments of lf_bn_finalize_fwd.  training = 1: mean / biased variance (clamped
+ * at 0) of `count` values per channel from the rows' fp64 column sums, running_mean / running_var updated in place (momentum; unbiased
+ * variance, count / (count - 1), unless count == 1); training = 0: the running statistics are used and left alone, and zero sources are
+ * allowed.  Writes, [C] each: scale = gamma * rstd, shift = beta - mean * scale, asc = rstd = 1 / sqrt(var + eps), ash = -mean * rstd.
+ * Returns 0. */
+int lf_debug_bn_finalize_fwd(const float* rows0, int nrows0, int ld0, int C0, int ch_off0, int tile_pix0, int seg_rows0, long seg_pix0,
+                             const float* rows1, int nrows1, int ld1, int C1, int ch_off1, int tile_pix1, int seg_rows1, long seg_pix1,
+                             int C, double count, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                             float momentum, float eps, int training, float* scale, float* shift, float* asc, float* ash, void* stream);
+/* one or two sources of RAW backward rows (sum gm, sum gm * t; t = the pre-BatchNorm tensor), then the arguments of lf_bn_bwd_finalize:
+ * with S1, S2 the column sums, gbeta = S1, ggamma = asc * S2 + ash * S1 (= sum gm * xhat), c1 = gbeta / count, c2 = ggamma / count --
+ * c1 = c2 = 0 with training = 0 (the forward normalised with the running statistics).  [C] each.  Returns 0. */
+int lf_debug_bn_bwd_finalize(const float* rows0, int nrows0, int ld0, int C0, int ch_off0, int tile_pix0, int seg_rows0, long seg_pix0,
+                             const float* rows1, int nrows1, int ld1, int C1, int ch_off1, int tile_pix1, int seg_rows1, long seg_pix1,
+                             int C, double count, const float* asc, const float* ash, float* c1, float* c2, float* ggamma, float* gbeta,
+                             int training, void* stream);
+/* y = relu((x * sc + sh) [* dm[n][c]] [+ res]); x, res, y (npix, C), pixel p belongs to image n = p / pix_per_image; dm [npix /
+ * pix_per_image][C] fp32 (Dropout2d's per-image channel mask, already scaled) or NULL; res NULL: no residual.  C % 4 == 0.  Returns 0. */
+int lf_debug_bn_act(const float* x, const float* sc, const float* sh, const float* dm, const float* res, float* y, long npix, int C,
+                    long pix_per_image, int s16, void* stream);
+/* gm = g * [y > 0] (y NULL: no mask) * dm (NULL: none); rows [2][C][ld] receives RAW partial rows (sum gm, sum gm * t), each over one
+ * contiguous run of at most roundup(ceil(npix / rows), 256) pixels: row count = min(ceil(npix / 64), 1024) <= ld, which is also the
+ * return value (lf_bn_bwd_reduce_rows); the floats of [rows, ld) are not written.  C / 4 a power of two <= 64.  asc / ash are not read. */
+int lf_debug_bn_bwd_reduce(const float* g, const float* y, const float* t, const float* asc, const float* ash, const float* dm, float* rows,
+                           int ld, long npix, int C, long pix_per_image, int s16, void* stream);
+/* g_t = gamma * asc * (gm - c1 - (t * asc + ash) * c2), gm as above; g_z (optional) = g * [y > 0], BEFORE the dropout mask: the
+ * gradient of the residual branch.  Returns 0. */
+int lf_debug_bn_bwd_apply(const float* g, const float* y, const float* t, const float* asc, const float* ash, const float* gamma,
+                          const float* c1, const float* c2, const float* dm, float* g_t, float* g_z, long npix, int C, long pix_per_image,
+                          int s16, void* stream);
+/* DownsamplerBlock pool branch: channels [choff, choff + Cin) of cat (N,H/2,W/2,cat_pix) = maxpool2x2(x), x (N,H,W,Cin); the other
+ * channels of cat are not touched.  rows [2][Cin][ld] (or NULL) receives RAW partial rows (sum v, sum v^2) of the STORED values, row count
+ * = min(ceil(N * H/2 * W/2 / 64), 1024) <= ld = the return value (lf_pool_rows), with or without rows; a row covers one contiguous
+ * run of at most roundup(ceil(pixels / rows), 256) output pixels.  H, W even; Cin / 4 a power of two;
+ * choff, cat_pix multiples of 4 (bf16: the 8-channel kernels need Cin, choff, cat_pix multiples of 8, else one quad per thread). */
+int lf_debug_pool_concat_fwd(const float* x, int N, int H, int W, int Cin, float* cat, int cat_pix, int choff, float* rows, int ld, int s16,
+                             void* stream);
+/* inference form: cat[..., choff + c] = relu(maxpool2x2(x)[c] * sc[c] + sh[c]), sc / sh [Cin]; the affine map AFTER the max.  Returns 0. */
+int lf_debug_pool_affine_fwd(const float* x, int N, int H, int W, int Cin, float* cat, int cat_pix, int choff, const float* sc, const float* sh,
+                             int s16, void* stream);
+/* gx (N,H,W,Cin): every element written -- gcat[..., choff + c] at the window's FIRST maximum in the scan order (0,0), (0,1), (1,0),
+ * (1,1) (strict >, ATen's rule), zero at the other three.  Returns 0. */
+int lf_debug_pool_bwd(const float* x, const float* gcat, int N, int H, int W, int Cin, int cat_pix, int choff, float* gx, int s16, void* stream);
+/* stem, DownsamplerBlock(Cin, 16) on the NCHW fp32 image (N,Cin,H,W), Cin 1..4, H and W even: cat (N,H/2,W/2,16) = [Conv2d(Cin, 16 - Cin,
+ * 3, stride 2, pad 1) | maxpool2x2]; w (16 - Cin,Cin,3,3), b [16 - Cin].
+ *   sc = sh = NULL  training form: rows [2][16][ld] (or NULL) receives RAW partial rows (sum v, sum v^2) of the values before rounding to
+ *                   the storage type, one per 256 output pixels; returns that count, ceil(N * H/2 * W/2 / 256) <= ld (lf_stem_rows)
+ *   sc, sh [16]     inference form (lf_stem_fwd_infer): cat = relu(v * sc + sh), after the max for the pooled channels; rows and ld are
+ *                   ignored; returns 0 */
+int lf_debug_stem_fwd(const float* img, int N, int Cin, int H, int W, const float* w, const float* b, const float* sc, const float* sh, float* cat,
+                      float* rows, int ld, int s16, void* stream);
+/* head, ConvTranspose2d(16, K, 2, stride 2), K 1..8: x (N,h,w,16) NHWC -> out (N,K,2h,2w) NCHW fp32; w (16,K,2,2), b [K].  Returns 0. */
+int lf_debug_head_fwd(const float* x, const float* w, const float* b, float* out, int N, int h, int w_, int K, int s16, void* stream);
+/* its data gradient: gout (N,K,2h,2w) NCHW fp32 -> gx (N,h,w,16) NHWC.  Returns 0. */
+int lf_debug_head_bwd_data(const float* gout, const float* w, float* gx, int N, int h, int w_, int K, int s16, void* stream);
 /* tap-GEMM launches that took a compiled-in bias + residual + ReLU epilogue (the inference engine's block tail) since the process
  * started: which kernel form a launch selected (tests/test_infer_gpu.py) */
 long lf_debug_bias_residual_launches(void);

@@ -394,6 +394,169 @@ int lf_debug_head_wgrad(int reduce, const float* x, const float* gout, float* gw
     return debug_row_sums(reduce, wrows, brows, rows, nw, gw, K, gb, st);
 }
 
+// ---- one launch of a bandwidth-bound backbone kernel (lf_eltwise.h): pass-throughs to the launchers the plan calls, with the
+// host checks the plan's own geometry makes unnecessary there (lf_debug.h has the contracts)
+namespace {
+bool al16(const void* p) { return ((size_t)p & 15) == 0; }
+// channel counts the row-writing kernels take: quads that divide a 256-thread workgroup
+bool quads_ok(int C) { return C >= 4 && C % 4 == 0 && 256 % (C / 4) == 0; }
+// builds parts[] from the flat source arguments (a null rows pointer = no such source); the number of sources, -1 on a bad one
+int debug_stat_parts(const char* who, const float* const rows[2], const int nrows[2], const int ld[2], const int Cs[2], const int ch_off[2],
+                     const int tile_pix[2], const int seg_rows[2], const long seg_pix[2], int C, LfStatPart parts[2]) {
+    int n = 0;
+    for (int i = 0; i < 2; ++i) {
+        if (!rows[i]) continue;
+        if (nrows[i] < 1 || ld[i] < nrows[i] || ld[i] % 4 != 0 || !al16(rows[i])) {
+            lf_fail("%s: source %d needs a 16-byte aligned base and a leading dimension >= nrows, multiple of 4 (ld=%d nrows=%d)", who, i, ld[i], nrows[i]);
+            return -1;
+        }
+        if (Cs[i] < 4 || Cs[i] % 4 != 0 || ch_off[i] < 0 || ch_off[i] % 4 != 0 || ch_off[i] + Cs[i] > C) {
+            lf_fail("%s: source %d covers channels [%d, %d) of %d: multiples of 4 inside the layer", who, i, ch_off[i], ch_off[i] + Cs[i], C);
+            return -1;
+        }
+        if (tile_pix[i] < 0 || (tile_pix[i] > 0 && (seg_rows[i] < 1 || nrows[i] % seg_rows[i] != 0 || seg_pix[i] > (long)seg_rows[i] * tile_pix[i] ||
+                                                    seg_pix[i] <= (long)(seg_rows[i] - 1) * tile_pix[i]))) {
+            lf_fail("%s: source %d: centred rows need the launch geometry (nrows=%d seg_rows=%d seg_pix=%ld tile_pix=%d)", who, i, nrows[i],
+                    seg_rows[i], seg_pix[i], tile_pix[i]);
+            return -1;
+        }
+        parts[n] = {rows[i], nrows[i], Cs[i], ch_off[i], ld[i]};
+        parts[n].tile_pix = tile_pix[i]; parts[n].seg_rows = seg_rows[i]; parts[n].seg_pix = seg_pix[i];
+        ++n;
+    }
+    return n;
+}
+bool stream_ok(const char* who, long npix, int C, long pix_per_image, const float* dm) {
+    if (npix < 1 || C < 4 || C % 4 != 0 || pix_per_image < 1 || (dm && npix % pix_per_image != 0)) {
+        lf_fail("%s: bad arguments (npix %ld C %d pix_per_image %ld)", who, npix, C, pix_per_image);
+        return false;
+    }
+    return true;
+}
+bool pool_ok(const char* who, int N, int H, int W, int Cin, int cat_pix, int choff) {
+    if (N < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || !quads_ok(Cin) || choff < 0 || choff % 4 != 0 || cat_pix % 4 != 0 || choff + Cin > cat_pix) {
+        lf_fail("%s: bad arguments (N %d H %d W %d Cin %d cat_pix %d choff %d)", who, N, H, W, Cin, cat_pix, choff);
+        return false;
+    }
+    return true;
+}
+}  // namespace
+
+int lf_debug_bn_finalize_fwd(const float* rows0, int nrows0, int ld0, int C0, int ch_off0, int tile_pix0, int seg_rows0, long seg_pix0,
+                             const float* rows1, int nrows1, int ld1, int C1, int ch_off1, int tile_pix1, int seg_rows1, long seg_pix1,
+                             int C, double count, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                             float momentum, float eps, int training, float* scale, float* shift, float* asc, float* ash, void* stream) {
+    if (!(gamma && beta && running_mean && running_var && scale && shift && asc && ash)) { lf_fail("lf_debug_bn_finalize_fwd: null pointer"); return -1; }
+    if (C < 4 || C % 4 != 0 || !(count >= 1.0)) { lf_fail("lf_debug_bn_finalize_fwd: bad arguments (C %d count %g)", C, count); return -1; }
+    const float* const rows[2] = {rows0, rows1};
+    const int nrows[2] = {nrows0, nrows1}, ld[2] = {ld0, ld1}, Cs[2] = {C0, C1}, ch_off[2] = {ch_off0, ch_off1}, tile_pix[2] = {tile_pix0, tile_pix1},
+              seg_rows[2] = {seg_rows0, seg_rows1};
+    const long seg_pix[2] = {seg_pix0, seg_pix1};
+    LfStatPart parts[2];
+    const int n = debug_stat_parts("lf_debug_bn_finalize_fwd", rows, nrows, ld, Cs, ch_off, tile_pix, seg_rows, seg_pix, C, parts);
+    if (n < 0) return -1;
+    if (training && n == 0) { lf_fail("lf_debug_bn_finalize_fwd: training mode needs a source of partial rows"); return -1; }
+    return lf_bn_finalize_fwd(parts, n, C, count, gamma, beta, running_mean, running_var, momentum, eps, training, scale, shift, asc, ash,
+                              (hipStream_t)stream) ? -1 : 0;
+}
+
+int lf_debug_bn_bwd_finalize(const float* rows0, int nrows0, int ld0, int C0, int ch_off0, int tile_pix0, int seg_rows0, long seg_pix0,
+                             const float* rows1, int nrows1, int ld1, int C1, int ch_off1, int tile_pix1, int seg_rows1, long seg_pix1,
+                             int C, double count, const float* asc, const float* ash, float* c1, float* c2, float* ggamma, float* gbeta,
+                             int training, void* stream) {
+    if (!(asc && ash && c1 && c2 && ggamma && gbeta)) { lf_fail("lf_debug_bn_bwd_finalize: null pointer"); return -1; }
+    if (C < 4 || C % 4 != 0 || !(count >= 1.0)) { lf_fail("lf_debug_bn_bwd_finalize: bad arguments (C %d count %g)", C, count); return -1; }
+    const float* const rows[2] = {rows0, rows1};
+    const int nrows[2] = {nrows0, nrows1}, ld[2] = {ld0, ld1}, Cs[2] = {C0, C1}, ch_off[2] = {ch_off0, ch_off1}, tile_pix[2] = {tile_pix0, tile_pix1},
+              seg_rows[2] = {seg_rows0, seg_rows1};
+    const long seg_pix[2] = {seg_pix0, seg_pix1};
+    LfStatPart parts[2];
+    const int n = debug_stat_parts("lf_debug_bn_bwd_finalize", rows, nrows, ld, Cs, ch_off, tile_pix, seg_rows, seg_pix, C, parts);
+    if (n < 0) return -1;
+    if (n == 0) { lf_fail("lf_debug_bn_bwd_finalize: no source of partial rows"); return -1; }
+    return lf_bn_bwd_finalize(parts, n, C, count, asc, ash, c1, c2, ggamma, gbeta, training, (hipStream_t)stream) ? -1 : 0;
+}
+
+int lf_debug_bn_act(const float* x, const float* sc, const float* sh, const float* dm, const float* res, float* y, long npix, int C,
+                    long pix_per_image, int s16, void* stream) {
+    if (!(x && sc && sh && y)) { lf_fail("lf_debug_bn_act: null pointer"); return -1; }
+    if (!(al16(x) && al16(sc) && al16(sh) && al16(dm) && al16(res) && al16(y))) { lf_fail("lf_debug_bn_act: pointers must be 16-byte aligned"); return -1; }
+    if (!stream_ok("lf_debug_bn_act", npix, C, pix_per_image, dm)) return -1;
+    return lf_bn_act(x, sc, sh, dm, res, y, npix, C, pix_per_image, s16 != 0, (hipStream_t)stream) ? -1 : 0;
+}
+
+int lf_debug_bn_bwd_reduce(const float* g, const float* y, const float* t, const float* asc, const float* ash, const float* dm, float* rows,
+                           int ld, long npix, int C, long pix_per_image, int s16, void* stream) {
+    if (!(g && t && asc && ash && rows)) { lf_fail("lf_debug_bn_bwd_reduce: null pointer"); return -1; }
+    if (!(al16(g) && al16(y) && al16(t) && al16(dm))) { lf_fail("lf_debug_bn_bwd_reduce: pointers must be 16-byte aligned"); return -1; }
+    if (!stream_ok("lf_debug_bn_bwd_reduce", npix, C, pix_per_image, dm)) return -1;
+    if (!quads_ok(C)) { lf_fail("lf_debug_bn_bwd_reduce: unsupported channel count %d", C); return -1; }
+    const int nrows = lf_bn_bwd_reduce_rows(npix);
+    if (ld < nrows) { lf_fail("lf_debug_bn_bwd_reduce: ld %d below the %d rows of the launch", ld, nrows); return -1; }
+    return lf_bn_bwd_reduce(g, y, t, asc, ash, dm, rows, ld, npix, C, pix_per_image, s16 != 0, (hipStream_t)stream) ? -1 : nrows;
+}
+
+int lf_debug_bn_bwd_apply(const float* g, const float* y, const float* t, const float* asc, const float* ash, const float* gamma,
+                          const float* c1, const float* c2, const float* dm, float* g_t, float* g_z, long npix, int C, long pix_per_image,
+                          int s16, void* stream) {
+    if (!(g && t && asc && ash && gamma && c1 && c2 && g_t)) { lf_fail("lf_debug_bn_bwd_apply: null pointer"); return -1; }
+    if (!(al16(g) && al16(y) && al16(t) && al16(asc) && al16(ash) && al16(gamma) && al16(c1) && al16(c2) && al16(dm) && al16(g_t) && al16(g_z))) {
+        lf_fail("lf_debug_bn_bwd_apply: pointers must be 16-byte aligned");
+        return -1;
+    }
+    if (!stream_ok("lf_debug_bn_bwd_apply", npix, C, pix_per_image, dm)) return -1;
+    return lf_bn_bwd_apply(g, y, t, asc, ash, gamma, c1, c2, dm, g_t, g_z, npix, C, pix_per_image, s16 != 0, (hipStream_t)stream) ? -1 : 0;
+}
+
+int lf_debug_pool_concat_fwd(const float* x, int N, int H, int W, int Cin, float* cat, int cat_pix, int choff, float* rows, int ld, int s16,
+                             void* stream) {
+    if (!(x && cat) || !al16(x) || !al16(cat)) { lf_fail("lf_debug_pool_concat_fwd: null or misaligned pointer"); return -1; }
+    if (!pool_ok("lf_debug_pool_concat_fwd", N, H, W, Cin, cat_pix, choff)) return -1;
+    const int nrows = lf_pool_rows((long)N * (H / 2) * (W / 2));
+    if (rows && ld < nrows) { lf_fail("lf_debug_pool_concat_fwd: ld %d below the %d rows of the launch", ld, nrows); return -1; }
+    return lf_pool_concat_fwd(x, N, H, W, Cin, cat, cat_pix, choff, rows, ld, s16 != 0, (hipStream_t)stream) ? -1 : nrows;
+}
+
+int lf_debug_pool_affine_fwd(const float* x, int N, int H, int W, int Cin, float* cat, int cat_pix, int choff, const float* sc, const float* sh,
+                             int s16, void* stream) {
+    if (!(x && cat && sc && sh) || !al16(x) || !al16(cat) || !al16(sc) || !al16(sh)) { lf_fail("lf_debug_pool_affine_fwd: null or misaligned pointer"); return -1; }
+    if (!pool_ok("lf_debug_pool_affine_fwd", N, H, W, Cin, cat_pix, choff)) return -1;
+    return lf_pool_affine_fwd(x, N, H, W, Cin, cat, cat_pix, choff, sc, sh, s16 != 0, (hipStream_t)stream) ? -1 : 0;
+}
+
+int lf_debug_pool_bwd(const float* x, const float* gcat, int N, int H, int W, int Cin, int cat_pix, int choff, float* gx, int s16, void* stream) {
+    if (!(x && gcat && gx) || !al16(x) || !al16(gcat) || !al16(gx)) { lf_fail("lf_debug_pool_bwd: null or misaligned pointer"); return -1; }
+    if (!pool_ok("lf_debug_pool_bwd", N, H, W, Cin, cat_pix, choff)) return -1;
+    return lf_pool_bwd(x, gcat, N, H, W, Cin, cat_pix, choff, gx, s16 != 0, (hipStream_t)stream) ? -1 : 0;
+}
+
+int lf_debug_stem_fwd(const float* img, int N, int Cin, int H, int W, const float* w, const float* b, const float* sc, const float* sh, float* cat,
+                      float* rows, int ld, int s16, void* stream) {
+    if (!(img && w && b && cat) || !al16(cat)) { lf_fail("lf_debug_stem_fwd: null or misaligned pointer"); return -1; }
+    if (N < 1 || Cin < 1 || Cin > 4 || H < 2 || W < 2 || (H & 1) || (W & 1)) {
+        lf_fail("lf_debug_stem_fwd: bad arguments (N %d Cin %d H %d W %d)", N, Cin, H, W);
+        return -1;
+    }
+    if ((sc == nullptr) != (sh == nullptr)) { lf_fail("lf_debug_stem_fwd: scale and shift come together"); return -1; }
+    hipStream_t st = (hipStream_t)stream;
+    if (sc) return lf_stem_fwd_infer(img, N, Cin, H, W, w, b, sc, sh, cat, s16 != 0, st) ? -1 : 0;
+    const int nrows = lf_stem_rows(N, H, W);
+    if (rows && ld < nrows) { lf_fail("lf_debug_stem_fwd: ld %d below the %d rows of the launch", ld, nrows); return -1; }
+    return lf_stem_fwd(img, N, Cin, H, W, w, b, cat, rows, ld, s16 != 0, st) ? -1 : nrows;
+}
+
+int lf_debug_head_fwd(const float* x, const float* w, const float* b, float* out, int N, int h, int w_, int K, int s16, void* stream) {
+    if (!(x && w && b && out) || !al16(x) || ((size_t)out & 7)) { lf_fail("lf_debug_head_fwd: null or misaligned pointer"); return -1; }
+    if (N < 1 || h < 1 || w_ < 1 || K < 1 || K > 8) { lf_fail("lf_debug_head_fwd: bad arguments (N %d h %d w %d K %d)", N, h, w_, K); return -1; }
+    return lf_head_fwd(x, w, b, out, N, h, w_, K, s16 != 0, (hipStream_t)stream) ? -1 : 0;
+}
+
+int lf_debug_head_bwd_data(const float* gout, const float* w, float* gx, int N, int h, int w_, int K, int s16, void* stream) {
+    if (!(gout && w && gx) || !al16(gx) || ((size_t)gout & 7)) { lf_fail("lf_debug_head_bwd_data: null or misaligned pointer"); return -1; }
+    if (N < 1 || h < 1 || w_ < 1 || K < 1 || K > 8) { lf_fail("lf_debug_head_bwd_data: bad arguments (N %d h %d w %d K %d)", N, h, w_, K); return -1; }
+    return lf_head_bwd_data(gout, w, gx, N, h, w_, K, s16 != 0, (hipStream_t)stream) ? -1 : 0;
+}
+
 namespace {
 int conv1d_bwd_weight(const float* x, const float* gy, const float* sc, const float* sh, float* gw, float* gb, int N, int H, int W, int C,
                       int axis, int dilation, float* scratch, hipStream_t st) {
