@@ -160,6 +160,8 @@ def _declare(lib):
         "lf_debug_set_wgrad_ro": (None, [I, I, I]),
         "lf_debug_set_fp32_stream": (None, [I, I]),
         "lf_debug_set_bwd16_fused": (None, [I]),
+        "lf_debug_set_fwd_pair": (None, [I, I]),
+        "lf_debug_conv1d_fwd_pair": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P]),
         "lf_debug_conv1d_bwd_pair_scratch_floats": (L, [I, I, I, I]),
         "lf_debug_conv1d_bwd_pair": (I, [P, P, P, I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P]),
         "lf_debug_conv1d_bwd_data_epi3": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P, P]),

@@ -77,6 +77,17 @@ bool lf_tapgemm_split_ok(const LfTapGeom& g);
 long lf_tapgemm_bias_residual_launches();
 extern std::atomic<long> g_bres_launches;           // ... the counter itself: ONE object, which both routes increment
 
+// ---- lf_conv_pair.hip: a non_bottleneck_1d block's 3x1 -> 1x3 forward pair in one launch (tappair_kernel; fp32 tensors) ----
+// ga / aa: the convolution along H with the ReLU epilogue (pro: its operand prologue), gb / ab: the one along W with the BatchNorm
+// statistics epilogue, ab.src == aa.dst.  Takes: precision mode 0, C -> C at a compiled channel count (64), 3 taps each, dense
+// stride-1 tensors, Wl % 64 == 0 and 256 % Wl == 0 (a 256-pixel tile is whole image rows), epi_a == LF_EPI_RELU and epi_b ==
+// LF_EPI_STATS_SQ (training).  Both tensors and the statistics rows are the two launches' bit for bit.  False too where the runtime
+// refuses the kernel's LDS budget on this device; the caller then takes the two launches.
+bool lf_tappair_ok(const LfTapGeom& ga, const LfTapGeom& gb, const LfTapArgs& aa, const LfTapArgs& ab, int pro, int epi_a, int epi_b);
+int lf_tappair_launch(const LfTapGeom& ga, const LfTapGeom& gb, const LfTapArgs& aa, const LfTapArgs& ab, int pro, hipStream_t st);
+void lf_tappair_set(int mode, int max_workgroups);   // lf_debug_set_fwd_pair (lf_debug.h)
+bool lf_tappair_routed(int C, int pro);              // the network takes the fused launch for this form (the forms that lowered the step)
+
 // ---- lf_conv_bf16.hip: the kernels on bf16 tensors, their route, routing switches and counters ----
 // lf_tapgemm_launch's route for a launch with packed bf16 weights (a.wp16), after its checks: epis, npix, nt and grid are its values
 int lf_tapgemm_bf16_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, int epis, long npix, int nt, dim3 grid, hipStream_t st);

@@ -1,8 +1,8 @@
 // Device helpers and launch state shared by the convolution kernel files lf_conv.hip and lf_conv_bf16.hip (tap-GEMM forward / data
-// gradient on fp32 and on bf16 tensors), lf_wgrad.hip (weight gradients) and lf_bwd16.hip (both gradients of the 16-channel
-// layers): the vector types, buffer-addressed loads and stores,
+// gradient on fp32 and on bf16 tensors), lf_conv_pair.hip (the fused 3x1 -> 1x3 forward pairs), lf_wgrad.hip (weight gradients) and
+// lf_bwd16.hip (both gradients of the 16-channel layers): the vector types, buffer-addressed loads and stores,
 // the DPP row sums, the tile constants, the per-(device, kernel) LDS attribute and occupancy cache with the launch that uses them,
-// the epilogue-set dispatchers and the dynamic-LDS symbol.  Internal: included by those four files only, everything in an
+// the epilogue-set dispatchers and the dynamic-LDS symbol.  Internal: included by those five files only, everything in an
 // anonymous namespace.  (lf_wgrad_ro.hip and lf_stem.hip keep private copies of zero4 and the typedefs.)
 #pragma once
 #include <stdlib.h>

@@ -1,6 +1,6 @@
-// The epilogue the tap-GEMM kernels of lf_conv.hip, lf_conv_bf16.hip and lf_bwd16.hip share (bias, ReLU, masks, residual, BatchNorm sums), as
+// The epilogue the tap-GEMM kernels of lf_conv.hip, lf_conv_pair.hip, lf_conv_bf16.hip and lf_bwd16.hip share (bias, ReLU, masks, residual, BatchNorm sums), as
 // macros expanded inside the kernel body: they use the kernel's own names (g, a, epi, npix, bx, cob, wave, pl, kq, pn / pi / pj /
-// pv, acc, and the constants NT, EPIC, S16, HOISTV).  Internal: included after lf_conv_dev.h by those three files only.
+// pv, acc, and the constants NT, EPIC, S16, HOISTV).  Internal: included after lf_conv_dev.h by those four files only.
 //
 // Protocol of the LF_EPI_* parameters.  The values defined in this header are the DEFAULTS, and they hold at every point of a file
 // outside a kernel that differs: such a kernel #undef's and redefines a parameter directly before the lines that expand the
@@ -10,6 +10,8 @@
 //   lf_conv.hip       tapgemm_kernel         LF_EPI_ONE_TILE, LF_EPI_TID, LF_EPI_ROW1
 //                     tapstream_kernel       LF_EPI_GROUPS, LF_EPI_ROW1, LF_EPI_ACC, LF_EPI_FIRST, LF_EPI_ROW_OK
 //                     tapgemm_split_kernel   LF_EPI_GROUPS (around the whole kernel), LF_EPI_PIVOT
+//   lf_conv_pair.hip  tappair_kernel         tapstream_kernel's five (in pair_phase, its tile body)
+//                     tappair128_kernel      LF_EPI_GROUPS, LF_EPI_TID, LF_EPI_ROW1, LF_EPI_TILE_OF (in pair128_phase)
 //   lf_conv_bf16.hip  tapgemm_bf16_kernel, tapgemm_bf16_ring_kernel   LF_EPI_PIVOT
 //   lf_bwd16.hip      tapbwd16_kernel        LF_EPI_ACC, LF_EPI_ROW1, LF_EPI_LDADD, LF_EPI_LDMSK, LF_EPI_LDAUX, LF_EPI_HOIST_ALL
 // tapgemm_lean_kernel and tapgemm_bf16_lean_kernel expand the defaults; the whole-line and wave-private bf16 kernels have epilogues
@@ -25,6 +27,9 @@
 #define LF_EPI_ACC(n, m) acc[n][m]   /* the finished sum of channel tile n, pixel tile m (tapstream_kernel: its one live pixel tile) */
 #define LF_EPI_FIRST(m) ((m) == 0)   /* the pixel tile whose first pixel is the pivot of the BN forward sums */
 #define LF_EPI_ROW_OK(tg) true       /* 4-wave group tg owns a tile of the launch (tapstream_kernel: the last pair of tiles may be half empty) */
+/* the 256-pixel tile (= statistics row) of 4-wave group tg: the groups of a workgroup own consecutive tiles (tappair128_kernel: ONE
+ * tile, its two groups produce the two 64-channel halves) */
+#define LF_EPI_TILE_OF(tg) (bx * (unsigned)LF_EPI_GROUPS + (unsigned)(tg))
 /* the lane's four elements of the residual / mask / BN operand at element offset o (tapbwd16_kernel: its LDS-staged tiles) */
 #define LF_EPI_LDADD(o) epi_ld<S16>(r_add, o)
 #define LF_EPI_LDMSK(o) epi_ld<S16>(r_msk, o)
@@ -127,7 +132,7 @@ _Pragma("unroll") \
             r1.x = sum16(s1[n].x); r1.y = sum16(s1[n].y); r1.z = sum16(s1[n].z); r1.w = sum16(s1[n].w); \
             r2.x = sum16(s2[n].x); r2.y = sum16(s2[n].y); r2.z = sum16(s2[n].z); r2.w = sum16(s2[n].w); \
             if (epi & LF_EPI_STATS_SQ) {      /* pivot sums -> (sum v, M2 about the wave's own mean) of the wave's nw valid pixels */ \
-                const unsigned lf_t0 = (bx * (unsigned)(WG_WAVES * LF_EPI_GROUPS) + (unsigned)wave) * 64u; \
+                const unsigned lf_t0 = (LF_EPI_TILE_OF(EG) * (unsigned)WG_WAVES + (unsigned)EW) * 64u; \
                 const float nw = lf_t0 < npix ? (float)min(npix - lf_t0, 64u) : 0.f; \
                 const float rn = nw > 0.f ? 1.f / nw : 0.f; \
                 r2 = r2 - r1 * r1 * rn; \
@@ -145,7 +150,7 @@ _Pragma("unroll") \
             const int j = tt & 7, q = (tt >> 3) & 3, n = tt >> 5; \
             float v = sred[tg][0][n][q][j] + sred[tg][1][n][q][j] + sred[tg][2][n][q][j] + sred[tg][3][n][q][j]; \
             if ((epi & LF_EPI_STATS_SQ) && j >= 4) {      /* Chan: M2 = sum_w M2_w + sum_w n_w (mean_w - mean)^2 */ \
-                const unsigned lf_tb = (bx * (unsigned)LF_EPI_GROUPS + (unsigned)tg) * (unsigned)(WG_WAVES * 64); \
+                const unsigned lf_tb = LF_EPI_TILE_OF(tg) * (unsigned)(WG_WAVES * 64); \
                 float nwv[4], sw[4], nt = 0.f, st = 0.f; \
 _Pragma("unroll") \
                 for (int w = 0; w < 4; ++w) { \
@@ -160,7 +165,7 @@ _Pragma("unroll") \
                     if (nwv[w] > 0.f) { const float dmw = sw[w] / nwv[w] - mg; v += nwv[w] * dmw * dmw; } \
             } \
             const int co = cob + n * 16 + q * 4 + (j & 3); \
-            a.stats[((long)(j >> 2) * g.Cd + co) * a.stats_ld + ((long)bx * LF_EPI_GROUPS + tg)] = v;      /* channel-major rows */ \
+            a.stats[((long)(j >> 2) * g.Cd + co) * a.stats_ld + (long)LF_EPI_TILE_OF(tg)] = v;      /* channel-major rows */ \
         } \
     }
 #define LF_TAPGEMM_EPILOGUE \

@@ -37,6 +37,19 @@ void lf_debug_set_wgrad_ro(int mode, int cap64, int cap128);
  * tapgemm_kernel takes every launch, 1 = the shipped routing, 2 = every variant tapstream_kernel is compiled for; max_workgroups > 0
  * caps the grid, so that one workgroup walks several tiles at small shapes.  The kernels agree bit for bit (tests/test_fp32_stream_gpu.py) */
 void lf_debug_set_fp32_stream(int mode, int max_workgroups);
+/* the 3x1 -> 1x3 forward pairs of the non_bottleneck_1d blocks on fp32 tensors (tappair_kernel, csrc/lf_conv_pair.hip): mode 0 = two
+ * launches, 1 = the shipped routing (the forms that lowered the step), 2 = every compiled form, 4 * m = the compiled forms of bit mask m
+ * (1 / 2: 64 channels without / with the BN+ReLU prologue, 4 / 8: 128 channels; A/B runs in the step); max_workgroups > 0 caps the grid, so
+ * that one workgroup walks several tiles at small shapes.  One launch and two agree bit for bit (tests/test_fwd_pair_gpu.py) */
+void lf_debug_set_fwd_pair(int mode, int max_workgroups);
+/* One pair on caller tensors, routed as the network routes it (lf_debug_set_fwd_pair; a pair the fused kernel does not take runs as
+ * two launches):  t = relu(conv3x1(pro(x)) + ba),  y = conv1x3(t) + bb, both with the dilation given; pro = relu(x * sc + sh) when sc
+ * and sh ([C] fp32) are given, else the identity.  x, t, y (N,H,W,C) NHWC fp32; wa, wb (C,C,3).  stats: [2][C][rows] BatchNorm forward
+ * rows of y (sum, M2 about the row's own mean), rows = ceil(N * H * W / 256).  scratch: lf_conv1d_scratch_floats floats.  Returns 1
+ * where the pair ran as one launch, 0 as two, -1 on error. */
+int lf_debug_conv1d_fwd_pair(const float* x, const float* wa, const float* ba, const float* wb, const float* bb, const float* sc,
+                             const float* sh, float* t, float* y, float* stats, int N, int H, int W, int C, int dilation, float* scratch,
+                             void* stream);
 /* fp32 16-channel 3-tap convolutions in backward: 0 = weight gradient and data gradient as two launches, 1 = the shipped routing
  * (tapbwd16_kernel, csrc/lf_bwd16.hip, takes the pairs it is routed for in one launch), 2 * m = exactly the forms of bit mask m
  * (1 mask, 2 recomputed-BN mask + sums with the prologue, 4 residual + mask + sums, 8 residual: A/B runs in the step) */

@@ -504,6 +504,27 @@ int run_gemm(const Ctx& c, const GemmOp& op, const float* src, float* dst, const
     return lf_tapgemm_launch(op.geom, extra, pro, epi, c.st);
 }
 
+// A non_bottleneck_1d block's 3x1 -> 1x3 pair: mid = relu(conv_a(pro(src)) + bias_a), dst = conv_b(mid) + bias_b with the BatchNorm
+// rows of extra_b -- as ONE launch where tappair_kernel (lf_conv_pair.hip) is routed for the form and takes the geometry, else as the
+// two run_gemm launches; bit-identical either way.  c.last_rows as run_gemm leaves it for conv_b.
+int run_gemm_pair(const Ctx& c, const ConvRef& cva, const ConvRef& cvb, const float* src, float* mid, float* dst, int pro,
+                  const LfTapArgs& extra_a, const LfTapArgs& extra_b) {
+    const GemmOp &opa = cva.fwd, &opb = cvb.fwd;
+    const int epi_b = c.training ? LF_EPI_STATS_SQ : 0;
+    if (c.P->precision == 0 && !c.s16 && c.training && lf_tappair_routed(opa.geom.Cs, pro)) {
+        LfTapArgs aa = extra_a, ab = extra_b;
+        aa.src = src; aa.dst = mid; aa.bias = c.params[cva.p_b]; aa.wp = c.packed(opa.pack);
+        ab.src = mid; ab.dst = dst; ab.bias = c.params[cvb.p_b]; ab.wp = c.packed(opb.pack);
+        if (lf_tappair_ok(opa.geom, opb.geom, aa, ab, pro, LF_EPI_RELU, epi_b)) {
+            c.last_rows = lf_tapgemm_stat_rows_for(opb.geom, ab);
+            ProfScope ps(c, 0, opb.geom, epi_b | (pro << 8), c.st, 2);
+            return lf_tappair_launch(opa.geom, opb.geom, aa, ab, pro, c.st);
+        }
+    }
+    LF_TRY(run_gemm(c, opa, src, mid, c.params[cva.p_b], pro, LF_EPI_RELU, extra_a));
+    return run_gemm(c, opb, mid, dst, c.params[cvb.p_b], LF_PRO_NONE, epi_b, extra_b);
+}
+
 int bn_finalize(const Ctx& c, const BNRef& b, const LfStatPart* parts, int nparts, double count) {
     return lf_bn_finalize_fwd(parts, nparts, b.C, count, c.params[b.p_g], c.params[b.p_b], c.running[2 * b.idx],
                               c.running[2 * b.idx + 1], BN_MOM, BN_EPS, c.training, c.at(b.sc), c.at(b.sh), c.at(b.asc),
@@ -551,20 +572,16 @@ int forward_layers(const Ctx& c, const float* img, int nlayers, int first = 0) {
             LF_TRY(lf_bn_act(c.at(L.b[0]), c.at(L.bn[0].sc), c.at(L.bn[0].sh), nullptr, nullptr, c.at(L.b[1]), npo, L.Cout,
                              (long)L.Hout * L.Wout, c.s16, c.st));
         } else if (L.kind == K_NB) {
-            LfTapArgs a = lf_no_args();
-            LF_TRY(run_gemm(c, L.cv[0].fwd, c.at(L.x), c.at(L.b[0]), c.params[L.cv[0].p_b], LF_PRO_NONE, LF_EPI_RELU, a));
+            // the two 3x1 -> 1x3 pairs have no BatchNorm between their halves: one launch each where tappair_kernel takes them
+            LfTapArgs a = lf_no_args(), ap = lf_no_args();
             a.stats = stat0; a.stats_ld = lf_stat_ld(lf_tapgemm_stat_rows(L.cv[1].fwd.geom));
-            LF_TRY(run_gemm(c, L.cv[1].fwd, c.at(L.b[0]), c.at(L.b[1]), c.params[L.cv[1].p_b], LF_PRO_NONE,
-                            c.training ? LF_EPI_STATS_SQ : 0, a));
+            LF_TRY(run_gemm_pair(c, L.cv[0], L.cv[1], c.at(L.x), c.at(L.b[0]), c.at(L.b[1]), LF_PRO_NONE, ap, a));
             LfStatPart p0 = lf_stat_part_tiles(stat0, c.last_rows, a.stats_ld, L.Cout, 0, c.last_rows, npo);
             LF_TRY(bn_finalize(c, L.bn[0], &p0, 1, (double)npo));
-            a = lf_no_args();
-            a.pro_sc = c.at(L.bn[0].sc); a.pro_sh = c.at(L.bn[0].sh);
-            LF_TRY(run_gemm(c, L.cv[2].fwd, c.at(L.b[1]), c.at(L.b[2]), c.params[L.cv[2].p_b], LF_PRO_BNRELU, LF_EPI_RELU, a));
+            ap.pro_sc = c.at(L.bn[0].sc); ap.pro_sh = c.at(L.bn[0].sh);
             a = lf_no_args();
             a.stats = stat0; a.stats_ld = lf_stat_ld(lf_tapgemm_stat_rows(L.cv[3].fwd.geom));
-            LF_TRY(run_gemm(c, L.cv[3].fwd, c.at(L.b[2]), c.at(L.b[3]), c.params[L.cv[3].p_b], LF_PRO_NONE,
-                            c.training ? LF_EPI_STATS_SQ : 0, a));
+            LF_TRY(run_gemm_pair(c, L.cv[2], L.cv[3], c.at(L.b[1]), c.at(L.b[2]), c.at(L.b[3]), LF_PRO_BNRELU, ap, a));
             p0.nrows = p0.seg_rows = c.last_rows; p0.ld = a.stats_ld;
             LF_TRY(bn_finalize(c, L.bn[1], &p0, 1, (double)npo));
             const float* dm = (c.training && L.drop_idx >= 0 && c.dropmask) ? c.dropmask + P->drop_off[L.drop_idx] : nullptr;

@@ -114,6 +114,7 @@ void lf_debug_set_ops_precision(int mode) { g_ops_bf16 = (mode == 2 || mode == 9
 void lf_debug_set_wgrad_ro(int mode, int cap64, int cap128) { lf_tapwgrad_ro_set(mode, cap64, cap128); }
 void lf_debug_set_fp32_stream(int mode, int max_workgroups) { lf_tapgemm_set_fp32_stream(mode, max_workgroups); }
 void lf_debug_set_bwd16_fused(int mode) { lf_tapbwd16_set(mode); }
+void lf_debug_set_fwd_pair(int mode, int max_workgroups) { lf_tappair_set(mode, max_workgroups); }
 long lf_debug_bias_residual_launches(void) { return lf_tapgemm_bias_residual_launches(); }
 long lf_debug_partial_fast_launches(void) { return lf_tapgemm_partial_fast_launches(); }
 
@@ -140,6 +141,30 @@ int lf_debug_conv1d_fwd_pro(const float* x, const float* w, const float* bias, c
     pack_conv1d(a, w, scratch, C, 3L, 3L * C, 0, st);
     a.src = x; a.bias = bias; a.dst = y; a.pro_sc = sc; a.pro_sh = sh;
     return lf_tapgemm_launch(g, a, LF_PRO_BNRELU, LF_EPI_RELU, st);
+}
+
+// one 3x1 -> 1x3 forward pair, routed as forward_layers (lf_erfnet.hip) routes it; scratch: [packed wa 3 C C][packed wb 3 C C]
+int lf_debug_conv1d_fwd_pair(const float* x, const float* wa, const float* ba, const float* wb, const float* bb, const float* sc,
+                             const float* sh, float* t, float* y, float* stats, int N, int H, int W, int C, int dilation, float* scratch,
+                             void* stream) {
+    if (!(x && wa && wb && t && y && stats && scratch) || (sc != nullptr) != (sh != nullptr)) { lf_fail("lf_debug_conv1d_fwd_pair: null pointer"); return -1; }
+    if (N < 1 || H < 1 || W < 1 || C < 16 || C % 16 != 0 || dilation < 1) { lf_fail("lf_debug_conv1d_fwd_pair: bad arguments"); return -1; }
+    if (g_ops_bf16 != 0) { lf_fail("lf_debug_conv1d_fwd_pair: fp32 tensors in precision mode 0 only"); return -1; }
+    hipStream_t st = (hipStream_t)stream;
+    const LfTapGeom ga = conv1d_geom(N, H, W, C, 0, dilation), gb = conv1d_geom(N, H, W, C, 1, dilation);
+    LfTapArgs aa, ab;
+    memset(&aa, 0, sizeof(aa));
+    memset(&ab, 0, sizeof(ab));
+    pack_conv1d(aa, wa, scratch, C, 3L, 3L * C, 0, st);
+    pack_conv1d(ab, wb, scratch + 3L * C * C, C, 3L, 3L * C, 0, st);
+    aa.src = x; aa.bias = ba; aa.dst = t; aa.pro_sc = sc; aa.pro_sh = sh;
+    ab.src = t; ab.bias = bb; ab.dst = y; ab.stats = stats;
+    ab.stats_ld = lf_tapgemm_stat_rows(gb);        // the caller's buffer: [2][C][rows], rows = ceil(N * H * W / 256)
+    const int pro = sc ? LF_PRO_BNRELU : LF_PRO_NONE;
+    if (lf_tappair_routed(C, pro) && lf_tappair_ok(ga, gb, aa, ab, pro, LF_EPI_RELU, LF_EPI_STATS_SQ))
+        return lf_tappair_launch(ga, gb, aa, ab, pro, st) ? -1 : 1;
+    if (lf_tapgemm_launch(ga, aa, pro, LF_EPI_RELU, st) || lf_tapgemm_launch(gb, ab, LF_PRO_NONE, LF_EPI_STATS_SQ, st)) return -1;
+    return 0;
 }
 
 // the weight gradient of lf_conv1d_bwd_weight (no reduction) with per-wave phase timestamps; returns the number of waves

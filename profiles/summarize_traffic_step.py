@@ -14,7 +14,7 @@ import re
 import sqlite3
 import sys
 
-FAMILIES = (("conv forward + data gradient (tap-GEMM kernels)", r"^tapgemm|^tapstream"), ("weight gradient (+ its reductions)", r"^tapwgrad|^wgrad_reduce|^rows_reduce|stem_wgrad|head_wgrad"),
+FAMILIES = (("conv forward + data gradient (tap-GEMM kernels)", r"^tapgemm|^tapstream|^tappair"), ("weight gradient (+ its reductions)", r"^tapwgrad|^wgrad_reduce|^rows_reduce|stem_wgrad|head_wgrad"),
             ("BatchNorm / element-wise passes", r"bn_|pool_|stem_fwd|head_fwd|head_bwd|pack_weights"), ("fit + losses", r"wls_|area_loss|backproj|ce_|mse_|seg_maps|trapezoid"))
 
 
