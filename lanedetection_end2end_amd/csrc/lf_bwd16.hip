@@ -74,13 +74,7 @@ __global__ __launch_bounds__(256, 2) void tapbwd16_kernel(const LfTapGeom g, con
     // load cursor: (image, row, column) of the next 16-pixel group (wave-uniform; Wl % 64 == 0: a group lies in one row)
     long p_ld = p_begin;
     int pj_, pi_, pn_;
-    {
-        const unsigned q = niter ? (unsigned)p_begin : 0u;
-        const unsigned r = q / (unsigned)g.Wl;
-        pj_ = __builtin_amdgcn_readfirstlane((int)(q - r * (unsigned)g.Wl));
-        pn_ = __builtin_amdgcn_readfirstlane((int)(r / (unsigned)g.Hl));
-        pi_ = __builtin_amdgcn_readfirstlane((int)r) - pn_ * g.Hl;
-    }
+    row1_coords(g, niter ? (unsigned)p_begin : 0u, pn_, pi_, pj_);
     int cj = pj_, ci = pi_, cn = pn_;                         // compute cursor: the group being multiplied and stored
     const int px = lane >> 2, chunk = lane & 3;
     int slot_ld = 0;

@@ -24,8 +24,10 @@
 // split-K reductions in lf_wgrad.hip, the weight-packing and BatchNorm-fold kernels in lf_pack.hip; the device helpers and launch
 // helpers shared with lf_conv_bf16.hip and lf_wgrad.hip are in lf_conv_dev.h.
 // The tap-GEMM kernels of both files share one epilogue (LF_TAPGEMM_EPILOGUE, lf_conv_epi.h: bias, ReLU, masks, residual, BN sums).
+// tapstream_kernel's tile body is stream_tile in lf_conv_stream.h, which the fused forward pair (lf_conv_pair.hip) runs too.
 #include "lf_conv_dev.h"
 #include "lf_conv_epi.h"
+#include "lf_conv_stream.h"
 
 namespace {
 
@@ -307,164 +309,44 @@ __global__ __launch_bounds__(256, (EPIC >= 0 || NT < 4) ? 2 : 1) void tapgemm_ke
 // tapstream_kernel: the fp32 3-tap C -> C convolutions and data gradients (C = CS = 64 or 128, Wl % 64 == 0) with the weights
 // RESIDENT IN LDS and the pixels streamed past them.  Ownership is tapgemm_kernel's -- a 4-wave group owns a 256-pixel tile, a wave
 // 64 pixels x 64 output channels, tiles walked inside the XCD's contiguous range, one statistics row per tile -- but a wave computes
-// its 64 pixels as FOUR 16-pixel sub-tiles in turn (16 + 16 accumulator registers instead of 64 + 64): per K-step one dwordx4 X
-// load per lane, four lane-contiguous ds_read_b128 of the weights ([K-step][channel tile][lane] float4, copied once per workgroup:
-// 48 KB at 64 channels, 96 KB at 128) and 16 MFMAs.  X runs through a register ring filled R K-steps ahead with buffer loads; the
-// ring wraps across sub-tiles and across the workgroup's tiles, so the operands of the next sub-tile (or tile) are in flight while
-// this one's epilogue runs, and the stores of a tile leave in four pieces spread over its life instead of in one burst at its end.
-// A prefetch past the last tile reads the out-of-range offset (zeros; with the operand prologue: pixel 0 of the tensor, masked).
-// Results are tapgemm_kernel's bit for bit: the same K order, the same 32-product segments flushed into accl, the same epilogue
-// text (LF_EPI_HEAD / LF_EPI_TILE / LF_EPI_TAIL) over the sub-tiles in the order 0, 1, 2, 3.
+// its 64 pixels as FOUR 16-pixel sub-tiles in turn (16 + 16 accumulator registers instead of 64 + 64) against weights copied once
+// per workgroup (48 KB at 64 channels, 96 KB at 128): the tile body is stream_tile (lf_conv_stream.h), shared with tappair_kernel.
+// This kernel is the walk around it: X runs through a register ring filled R K-steps ahead with buffer loads, and the ring wraps
+// across the workgroup's tiles -- the tail of a tile requests the first K-steps of the next, so they are in flight while this
+// tile's last epilogue runs.  A prefetch past the last tile reads the out-of-range offset (zeros; with the operand prologue: pixel
+// 0 of the tensor, masked).  Results are tapgemm_kernel's bit for bit (tests/test_fp32_stream_gpu.py).
 // G: 4-wave groups per workgroup (128 channels: one 512-thread workgroup per CU, its two groups own tiles 2u and 2u + 1).
 template <int CS, int PROC, int EPIC, int G>
 __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void tapstream_kernel(const LfTapGeom g, const LfTapArgs a) {
-    constexpr int NT = 4, NCG = CS / 16, NS = 3 * NCG, R = 8;
-    constexpr int epi = EPIC;
-    constexpr bool S16 = false, HOISTV = true;
-    static_assert((4 * NS) % R == 0 && R <= NS && NS % 2 == 0, "ring positions and K-step pairs must be compile-time");
+    constexpr int NS = 3 * (CS / 16), R = STREAM_R;
+    constexpr bool stats = (EPIC & (LF_EPI_STATS_SQ | LF_EPI_STATS_XHAT)) != 0;
     const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl);
     const int cob = blockIdx.y * 64;
     const unsigned ntiles = (npix + PIX_PER_WG - 1) / PIX_PER_WG, nunits = (ntiles + G - 1) / G;
-    unsigned u_first = blockIdx.x, u_stride = gridDim.x, u_end = nunits;      // (see tapgemm_kernel: XCD-contiguous ranges)
-    if ((gridDim.x & 7u) == 0 && (nunits & 7u) == 0) {
-        const unsigned per = nunits >> 3;
-        u_first = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); u_stride = gridDim.x >> 3; u_end = (blockIdx.x & 7u) * per + per;
-    }
+    const XcdRange u = xcd_range(nunits);      // (see tapgemm_kernel: XCD-contiguous ranges)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pl = lane & 15, kq = lane >> 4;
-    const unsigned wtile = (unsigned)__builtin_amdgcn_readfirstlane(wave);    // tile (u * G + wave / 4), wave % 4 of it: pixels from (u * 4G + wave) * 64
-
-
+    const unsigned wtile = (unsigned)__builtin_amdgcn_readfirstlane(wave);
     f32x4* const wl = reinterpret_cast<f32x4*>(lf_tap_lds);
     float* const pvec = reinterpret_cast<float*>(wl + NS * 256);              // BN+ReLU operand prologue: scale [CS], shift [CS]
-    // a wave's 64 pixels lie in one image row: (image, row, first column) are wave-uniform
-    struct WT { int n0, i0, j0; bool v; };
-    auto coords = [&](unsigned u, bool live) -> WT {
-        const unsigned tile0 = (u * (unsigned)(4 * G) + wtile) * 64u;
-        WT c;
-        c.v = live && tile0 < npix;
-        const unsigned q = c.v ? tile0 : 0u;
-        const unsigned r = q / (unsigned)g.Wl;
-        c.j0 = __builtin_amdgcn_readfirstlane((int)(q - r * (unsigned)g.Wl));
-        c.n0 = __builtin_amdgcn_readfirstlane((int)(r / (unsigned)g.Hl));
-        c.i0 = __builtin_amdgcn_readfirstlane((int)r) - c.n0 * g.Hl;
-        return c;
-    };
-    // byte offset of this lane's four source channels of (sub-tile, tap) -- tapgemm_kernel's tap table, computed where it is used
-    auto xoff = [&](const WT& c, int sub, int t, bool& in) -> unsigned {
-        const int sy = c.i0 * g.ssh + g.tdh[t], sx = (c.j0 + sub * 16 + pl) * g.ssw + g.tdw[t];
-        in = c.v && sy >= 0 && sy < g.Hs && sx >= 0 && sx < g.Ws;
-        const int syc = min(max(sy, 0), g.Hs - 1), sxc = min(max(sx, 0), g.Ws - 1);
-        const unsigned o = (unsigned)(((c.n0 * g.Hs + syc) * g.Ws + sxc) * g.s_pix + g.s_choff + kq * 4) * 4u;
-        return (PROC == 0 && !in) ? LF_OOB : o;
-    };
     const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.src, (unsigned)min((long)g.N * g.Hs * g.Ws * g.s_pix * 4, (long)LF_OOB));
-    // position p of a tile's K sequence: sub-tile p / NS, then tap-major, then 16-channel groups
-    auto xload = [&](const WT& c, int p) -> f32x4 {
-        const int k = p % NS;
-        bool in;
-        const unsigned o = xoff(c, p / NS, k / NCG, in);
-        return ldb4(rx, o, (unsigned)(k % NCG) * 64u);
-    };
 
     // the first R K-steps of X are requested BEFORE the weights are copied: their latency runs under the copy
-    f32x4 ring[R], wn[NT];
-    WT cur = coords(u_first, u_first < u_end);
+    f32x4 ring[R];
+    StreamWT cur = stream_coords<G>(g, npix, wtile, u.first, u.first < u.end);
 #pragma unroll
-    for (int p = 0; p < R; ++p) ring[p] = xload(cur, p);
-    // the workgroup's 64-output-channel slice of the packed weights [tap][CS/4][Cd][4] -> LDS [K-step][channel tile n][kq][pl] float4
-    {
-        const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.wp, (unsigned)(3 * CS * CS * 4));
-        for (int idx = threadIdx.x; idx < NS * 256; idx += 256 * G) {
-            const int col = idx & 63, row = idx >> 6;                          // row = tap * (CS / 4) + 4 * channel group + kq
-            wl[((row >> 2) * 4 + (col >> 4)) * 64 + (row & 3) * 16 + (col & 15)] = ldb4(rw, (unsigned)(row * CS + cob + col) * 16u, 0u);
-        }
-        if constexpr (PROC == LF_PRO_BNRELU) {
-            const __amdgpu_buffer_rsrc_t rsc = make_rsrc(a.pro_sc, CS * 4u), rsh = make_rsrc(a.pro_sh, CS * 4u);
-            for (int i = threadIdx.x; i < 2 * CS; i += 256 * G)
-                pvec[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(i < CS ? rsc : rsh, (i < CS ? i : i - CS) * 4, 0, 0));
-        }
-    }
+    for (int p = 0; p < R; ++p) ring[p] = stream_xload<CS, PROC>(g, rx, cur, p, pl, kq);
+    stream_copy_weights<CS, 256 * G>(wl, a.wp, cob);
+    if constexpr (PROC == LF_PRO_BNRELU) stream_copy_prologue<CS, 256 * G>(pvec, a);
     __syncthreads();
-#pragma unroll
-    for (int n = 0; n < NT; ++n) wn[n] = wl[n * 64 + lane];
 
-#undef LF_EPI_GROUPS
-#define LF_EPI_GROUPS G
-#undef LF_EPI_ROW1
-#define LF_EPI_ROW1 true
-#undef LF_EPI_ACC
-#define LF_EPI_ACC(n, m) acc[n]
-#undef LF_EPI_FIRST
-#define LF_EPI_FIRST(m) (sub == 0)
-#undef LF_EPI_ROW_OK
-#define LF_EPI_ROW_OK(tg) (bx * (unsigned)G + (unsigned)(tg) < ntiles)
-    LF_EPI_HEAD
-    for (unsigned bx = u_first; bx < u_end; bx += u_stride) {
-        const WT nxt = coords(bx + u_stride, bx + u_stride < u_end);
-        const int pn[1] = {cur.n0}, pi[1] = {cur.i0};
-        const bool pv[1] = {cur.v};
-#pragma unroll
-        for (int sub = 0; sub < 4; ++sub) {
-            f32x4 acc[NT], accl[NT];
-#pragma unroll
-            for (int k = 0; k < NS; ++k) {
-                const int p = sub * NS + k, cg = k % NCG;
-                f32x4 w[NT];
-#pragma unroll
-                for (int n = 0; n < NT; ++n) w[n] = wn[n];
-#pragma unroll
-                for (int n = 0; n < NT; ++n) wn[n] = wl[(((k + 1) % NS) * 4 + n) * 64 + lane];    // the next K-step's weights
-                f32x4 x = ring[p % R];
-                if constexpr (PROC == LF_PRO_BNRELU) {
-                    bool in;
-                    (void)xoff(cur, sub, k / NCG, in);
-                    const f32x4 sc = *reinterpret_cast<const f32x4*>(pvec + cg * 16 + kq * 4);
-                    const f32x4 sh = *reinterpret_cast<const f32x4*>(pvec + CS + cg * 16 + kq * 4);
-                    f32x4 v = max0(x * sc + sh);
-                    v.x = in ? v.x : 0.f; v.y = in ? v.y : 0.f; v.z = in ? v.z : 0.f; v.w = in ? v.w : 0.f;
-                    x = v;
-                }
-                if (k % 2 == 0) {       // a pair of K-steps = one 32-product chain: flush the finished one, restart from C = 0
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) {
-                        if (k == 0) accl[n] = zero4();
-                        else { accl[n] += acc[n]; asm volatile("" : "+v"(accl[n])); }
-                        acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[n][0], x[0], zero4(), 0, 0, 0);
-                    }
-                }
-#pragma unroll
-                for (int s = (k % 2 == 0) ? 1 : 0; s < 4; ++s)
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[n][s], x[s], acc[n], 0, 0, 0);
-                // this ring slot's next occupant, R K-steps ahead: this tile's, or the first of the workgroup's next tile
-                if (p + R < 4 * NS) ring[p % R] = xload(cur, p + R);
-                else ring[p % R] = xload(nxt, p + R - 4 * NS);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] += accl[n];
-            const int pj[1] = {cur.j0 + sub * 16 + pl};
-            LF_EPI_TILE(0)
-        }
-        LF_EPI_TAIL
-        if (stats) {
-#pragma unroll
-            for (int n = 0; n < NT; ++n) { s1[n] = zero4(); s2[n] = zero4(); }
-            if (bx + u_stride < u_end) __syncthreads();      // the statistics staging area is reused by the next tile
-        }
+    for (unsigned bx = u.first; bx < u.end; bx += u.stride) {
+        const StreamWT nxt = stream_coords<G>(g, npix, wtile, bx + u.stride, bx + u.stride < u.end);
+        stream_tile<CS, PROC, EPIC, G, true>(g, a, wl, pvec, bx, ntiles, npix, cob, cur, rx, ring,
+                                             [&](int p) { return stream_xload<CS, PROC>(g, rx, nxt, p, pl, kq); });
+        if (stats && bx + u.stride < u.end) __syncthreads();      // the statistics staging area is reused by the next tile
         cur = nxt;
     }
-#undef LF_EPI_GROUPS
-#define LF_EPI_GROUPS 1
-#undef LF_EPI_ROW1
-#define LF_EPI_ROW1 false
-#undef LF_EPI_ACC
-#define LF_EPI_ACC(n, m) acc[n][m]
-#undef LF_EPI_FIRST
-#define LF_EPI_FIRST(m) ((m) == 0)
-#undef LF_EPI_ROW_OK
-#define LF_EPI_ROW_OK(tg) true
 }
 
 // ---------------------------------------------------------------------------------------
@@ -517,8 +399,7 @@ __global__ __launch_bounds__(512, 2) void tapgemm_split_kernel(const LfTapGeom g
     if constexpr (DBG) tstamp[0] = __builtin_amdgcn_s_memrealtime();
     const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl);
     const int cob = blockIdx.y * NT * 16;
-    unsigned bx = blockIdx.x;
-    if ((gridDim.x & 7u) == 0) bx = (bx & 7u) * (gridDim.x >> 3) + (bx >> 3);
+    const unsigned bx = xcd_swizzle(blockIdx.x);
     const unsigned tile0 = (bx * WAVES + wave) * (MT * 16);
 
     int pn[MT], pi[MT], pj[MT];
@@ -899,7 +780,7 @@ void launch_tapgemm(K kernel, dim3 grid, size_t lds, hipStream_t st, const LfTap
 std::atomic<int> g_stream_mode{1}, g_stream_cap{0};
 enum { LF_STREAM_RELU = 1, LF_STREAM_STATS = 2, LF_STREAM_MASK = 4, LF_STREAM_PRO = 8, LF_STREAM_X48 = 16, LF_STREAM_X38 = 32 };   // X48, X38: 64 channels only
 constexpr int g_stream_routed[2] = {LF_STREAM_RELU | LF_STREAM_STATS | LF_STREAM_MASK | LF_STREAM_PRO | LF_STREAM_X48 | LF_STREAM_X38,      // 64 channels
-                                    0};     // 128 channels: one tile per wave at batch 32 -- the 96 KB copy is never amortised: +2 us alone, +2..5 in the step
+                                    0};     // 128 channels: one tile per wave at batch 32 -- the 96 KB copy is never amortised: +2 us alone, +2..5 in the step (with the per-tile epilogue head of stream_tile: level alone, the step not re-measured)
 // false: the runtime refused the kernel's LDS budget on this device (nothing launched: the caller takes tapgemm_kernel)
 template <int CS, int PROV, int EPIV>
 bool launch_tapstream(hipStream_t st, const LfTapGeom& g, const LfTapArgs& a) {

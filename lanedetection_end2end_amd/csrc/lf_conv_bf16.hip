@@ -48,8 +48,7 @@ __global__ __launch_bounds__(256, 2) void tapgemm_bf16_kernel(const LfTapGeom g,
     const int pl = lane & 15, kq = lane >> 4;
     const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl);
     const int cob = blockIdx.y * NT * 16;
-    unsigned bx = blockIdx.x;
-    if ((gridDim.x & 7u) == 0) bx = (bx & 7u) * (gridDim.x >> 3) + (bx >> 3);
+    const unsigned bx = xcd_swizzle(blockIdx.x);
     const unsigned tile0 = (bx * WG_WAVES + wave) * (MT * 16);
 
     int pn[MT], pi[MT], pj[MT];
@@ -471,11 +470,8 @@ __global__ __launch_bounds__(256, 2) void tapgemm_bf16_wl_kernel(const LfTapGeom
     const int cobw = wave * 16 * NT;                        // this wave's output channels
     const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl), ngroups = npix >> 4, GR = (unsigned)g.Wl >> 4;
     const unsigned nitems = (npix + PIX_PER_WG - 1) / PIX_PER_WG;
-    unsigned it_first = blockIdx.x, it_stride = gridDim.x, it_end = nitems;
-    if ((gridDim.x & 7u) == 0 && (nitems & 7u) == 0) {
-        const unsigned per = nitems >> 3;
-        it_first = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); it_stride = gridDim.x >> 3; it_end = (blockIdx.x & 7u) * per + per;
-    }
+    const XcdRange itr = xcd_range(nitems);
+    const unsigned it_first = itr.first, it_stride = itr.stride, it_end = itr.end;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lf_tap_lds;
     unsigned char* const ring = lf_tap_lds;
     unsigned char* const otile = lf_tap_lds + S * WL_STAGE;
@@ -838,11 +834,8 @@ __global__ __launch_bounds__(256, (EPIC >= 0 && WvCfg<EPIC>::NBUF < 2) ? 2 : 1) 
     const int pl = lane & 15, kq = lane >> 4;
     const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl), ngroups = npix >> 4, GR = (unsigned)g.Wl >> 4;
     const unsigned ntiles = (npix + PIX_PER_WG - 1) / PIX_PER_WG;
-    unsigned it_first = blockIdx.x, it_stride = gridDim.x, it_end = ntiles;
-    if ((gridDim.x & 7u) == 0 && (ntiles & 7u) == 0) {
-        const unsigned per = ntiles >> 3;
-        it_first = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); it_stride = gridDim.x >> 3; it_end = (blockIdx.x & 7u) * per + per;
-    }
+    const XcdRange itr = xcd_range(ntiles);
+    const unsigned it_first = itr.first, it_stride = itr.stride, it_end = itr.end;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lf_tap_lds + (unsigned)(wave * C::WAVE_LDS);
     unsigned char* const ring = lf_tap_lds + wave * C::WAVE_LDS;
     unsigned char* const otile = ring + R * WV_STAGE;
@@ -1153,8 +1146,7 @@ __global__ __launch_bounds__(256, 4) void tapgemm_bf16_lean_kernel(const LfTapGe
     const int pl = lane & 15, kq = lane >> 4;
     const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl), ngroups = npix >> 4, GR = (unsigned)g.Wl >> 4;
     const int cob = 0;
-    unsigned bx = blockIdx.x;
-    if ((gridDim.x & 7u) == 0) bx = (bx & 7u) * (gridDim.x >> 3) + (bx >> 3);
+    const unsigned bx = xcd_swizzle(blockIdx.x);
     RingGroups G;
     ring_groups(bx, wave, g.Hl, GR, ngroups, G);
     const int hi = kq >> 1, c8 = (kq & 1) * 8;              // which tap of the pair, which half of the pixel

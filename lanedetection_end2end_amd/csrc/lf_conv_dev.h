@@ -2,8 +2,8 @@
 // gradient on fp32 and on bf16 tensors), lf_conv_pair.hip (the fused 3x1 -> 1x3 forward pairs), lf_wgrad.hip (weight gradients) and
 // lf_bwd16.hip (both gradients of the 16-channel layers): the vector types, buffer-addressed loads and stores,
 // the DPP row sums, the tile constants, the per-(device, kernel) LDS attribute and occupancy cache with the launch that uses them,
-// the epilogue-set dispatchers and the dynamic-LDS symbol.  Internal: included by those five files only, everything in an
-// anonymous namespace.  (lf_wgrad_ro.hip and lf_stem.hip keep private copies of zero4 and the typedefs.)
+// the epilogue-set dispatchers and the dynamic-LDS symbol.  Internal: included by those five files (and by lf_conv_stream.h, the
+// stream tile body of the first and the third) only, everything in an anonymous namespace.  (lf_wgrad_ro.hip and lf_stem.hip keep private copies of zero4 and the typedefs.)
 #pragma once
 #include <stdlib.h>
 #include <string.h>
@@ -121,6 +121,37 @@ __device__ __forceinline__ float sum16(float v) {
     v += dpp_mov<0x124>(v);     // row_ror:4
     v += dpp_mov<0x128>(v);     // row_ror:8
     return v;
+}
+
+// Index arithmetic the tap-GEMM kernels share.  Each is used only where the kernel's instruction text stays what the inline
+// form gave (tools/kernel_asm_diff.py); the kernels it would have changed keep their own lines: tapgemm_kernel, tapgemm_lean_kernel,
+// tapgemm_bf16_ring_kernel, tappair128_kernel.  Scalar inputs are taken by const reference on purpose: by value, the callee is
+// simplified before it is inlined and most callers' register allocation moves.  (The clamped source-offset block -- sy, sx, in,
+// syc, sxc, offset -- has no helper: as a function it changed every kernel it was tried in.)
+// Workgroup b runs on XCD b % 8 (observed dispatch order): the block index remapped so that every XCD owns a CONTIGUOUS range of
+// tiles -- the halo rows neighbouring tiles share meet in one L2
+__device__ __forceinline__ unsigned xcd_swizzle(const unsigned& b) {
+    unsigned bx = b;
+    if ((gridDim.x & 7u) == 0) bx = (bx & 7u) * (gridDim.x >> 3) + (bx >> 3);
+    return bx;
+}
+// ... and for a workgroup that walks several units (first, first + stride, ... < end): the walk stays inside its XCD's range
+struct XcdRange { unsigned first, stride, end; };
+__device__ __forceinline__ XcdRange xcd_range(const unsigned& nunits) {
+    XcdRange r = {blockIdx.x, gridDim.x, nunits};
+    if ((gridDim.x & 7u) == 0 && (nunits & 7u) == 0) {
+        const unsigned per = nunits >> 3;
+        r.first = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); r.stride = gridDim.x >> 3; r.end = (blockIdx.x & 7u) * per + per;
+    }
+    return r;
+}
+// (image, row, first column) of a wave whose 64 pixels from logical pixel q on lie in one image row (Wl % 64 == 0, q wave-uniform):
+// two divisions, the results in scalar registers
+__device__ __forceinline__ void row1_coords(const LfTapGeom& g, const unsigned& q, int& n0, int& i0, int& j0) {
+    const unsigned r = q / (unsigned)g.Wl;
+    j0 = __builtin_amdgcn_readfirstlane((int)(q - r * (unsigned)g.Wl));
+    n0 = __builtin_amdgcn_readfirstlane((int)(r / (unsigned)g.Hl));
+    i0 = __builtin_amdgcn_readfirstlane((int)r) - n0 * g.Hl;
 }
 
 // Per-(device, kernel) launch state shared by the host threads of a process (one process may drive several GPUs): the "dynamic

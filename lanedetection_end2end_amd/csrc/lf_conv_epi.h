@@ -1,6 +1,7 @@
 // The epilogue the tap-GEMM kernels of lf_conv.hip, lf_conv_pair.hip, lf_conv_bf16.hip and lf_bwd16.hip share (bias, ReLU, masks, residual, BatchNorm sums), as
 // macros expanded inside the kernel body: they use the kernel's own names (g, a, epi, npix, bx, cob, wave, pl, kq, pn / pi / pj /
-// pv, acc, and the constants NT, EPIC, S16, HOISTV).  Internal: included after lf_conv_dev.h by those four files only.
+// pv, acc, and the constants NT, EPIC, S16, HOISTV).  Internal: included after lf_conv_dev.h by those four files and by
+// lf_conv_stream.h (the stream tile body the first two share) only.
 //
 // Protocol of the LF_EPI_* parameters.  The values defined in this header are the DEFAULTS, and they hold at every point of a file
 // outside a kernel that differs: such a kernel #undef's and redefines a parameter directly before the lines that expand the
@@ -8,10 +9,11 @@
 // kernel behind it in the file without a diagnostic, so a redefinition and its restore are kept within sight of each other.
 // The kernels that redefine:
 //   lf_conv.hip       tapgemm_kernel         LF_EPI_ONE_TILE, LF_EPI_TID, LF_EPI_ROW1
-//                     tapstream_kernel       LF_EPI_GROUPS, LF_EPI_ROW1, LF_EPI_ACC, LF_EPI_FIRST, LF_EPI_ROW_OK
 //                     tapgemm_split_kernel   LF_EPI_GROUPS (around the whole kernel), LF_EPI_PIVOT
-//   lf_conv_pair.hip  tappair_kernel         tapstream_kernel's five (in pair_phase, its tile body)
-//                     tappair128_kernel      LF_EPI_GROUPS, LF_EPI_TID, LF_EPI_ROW1, LF_EPI_TILE_OF (in pair128_phase)
+//   lf_conv_stream.h  stream_tile            LF_EPI_GROUPS, LF_EPI_ROW1, LF_EPI_ACC, LF_EPI_FIRST, LF_EPI_ROW_OK -- the tile body of
+//                                            tapstream_kernel (lf_conv.hip) and tappair_kernel (lf_conv_pair.hip): the stream
+//                                            family's only redefinitions
+//   lf_conv_pair.hip  tappair128_kernel      LF_EPI_GROUPS, LF_EPI_TID, LF_EPI_ROW1, LF_EPI_TILE_OF (in pair128_phase)
 //   lf_conv_bf16.hip  tapgemm_bf16_kernel, tapgemm_bf16_ring_kernel   LF_EPI_PIVOT
 //   lf_bwd16.hip      tapbwd16_kernel        LF_EPI_ACC, LF_EPI_ROW1, LF_EPI_LDADD, LF_EPI_LDMSK, LF_EPI_LDAUX, LF_EPI_HOIST_ALL
 // tapgemm_lean_kernel and tapgemm_bf16_lean_kernel expand the defaults; the whole-line and wave-private bf16 kernels have epilogues
@@ -35,7 +37,7 @@
 #define LF_EPI_LDMSK(o) epi_ld<S16>(r_msk, o)
 #define LF_EPI_LDAUX(o) epi_ld<S16>(r_aux, o)
 #define LF_EPI_HOIST_ALL false       /* tapbwd16_kernel: the MASKBN vectors held in registers beside the BN-backward sums too */
-/* The epilogue in three parts, so that a kernel can run the per-pixel-tile part one tile at a time (tapstream_kernel); LF_TAPGEMM_EPILOGUE
+/* The epilogue in three parts, so that a kernel can run the per-pixel-tile part one tile at a time (stream_tile); LF_TAPGEMM_EPILOGUE
  * below is the three in a row, the form every other kernel expands. */
 #define LF_EPI_HEAD \
     /* Pixel-tile outer, channel-tile inner: the loads of one operand tensor issued back to back cover one pixel's     \

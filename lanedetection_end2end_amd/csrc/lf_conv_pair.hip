@@ -13,202 +13,75 @@
 // order, the same 32-product segments flushed into the second accumulator set, the same epilogue text (lf_conv_epi.h), the same
 // tile ownership and hence the same statistics rows: t, y and the rows are bit-identical (tests/test_fwd_pair_gpu.py).
 //
-// 64 channels: tapstream_kernel's body twice per tile.  Both convolutions' weights stay resident in LDS (2 x 48 KB), which leaves
-// room for one workgroup per CU: 512 threads, its two 4-wave groups own tiles 2u and 2u + 1 -- the same two waves per SIMD as two
-// 256-thread tapstream workgroups.  Tile-major (conv_a, barrier, conv_b, next tile): t in flight between its store and its
-// read is one tile per group, 4 MB per XCD at batch 32, half of what the phase-major order would hold against a 4 MB L2.  The X
-// ring is filled afresh behind the barrier (conv_b) and, for the next tile's conv_a, during the tail of conv_b.
-#include "lf_conv_dev.h"
-#include "lf_conv_epi.h"
+// This file holds what is the pair's own: the two kernels' outer loops, the hand-over, pair128_phase, routing and launch.
+//
+// 64 channels: the stream tile body (stream_tile, lf_conv_stream.h: the one tapstream_kernel runs) twice per tile.  Both
+// convolutions' weights stay resident in LDS (2 x 48 KB), which leaves room for one workgroup per CU: 512 threads, its two
+// 4-wave groups own tiles 2u and 2u + 1 -- the same two waves per SIMD as two 256-thread tapstream workgroups.  Tile-major
+// (conv_a, barrier, conv_b, next tile): t in flight between its store and its read is one tile per group, 4 MB per XCD at batch
+// 32, half of what the phase-major order would hold against a 4 MB L2.  The X ring is filled afresh behind the barrier (conv_b)
+// and, for the next tile's conv_a, during the tail of conv_b.
+#include "lf_conv_stream.h"
 
 namespace {
 
-constexpr int PAIR_R = 8;       // K-steps of X in flight per wave (tapstream_kernel's ring)
-
-struct PairWT { int n0, i0, j0; bool v; };      // a wave's 64 pixels lie in one image row: (image, row, first column), wave-uniform
-
-// byte offset of this lane's four source channels of (sub-tile, tap) -- tapstream_kernel's
-template <int PROC>
-__device__ __forceinline__ unsigned pair_xoff(const LfTapGeom& g, const PairWT& c, int sub, int t, int pl, int kq, bool& in) {
-    const int sy = c.i0 * g.ssh + g.tdh[t], sx = (c.j0 + sub * 16 + pl) * g.ssw + g.tdw[t];
-    in = c.v && sy >= 0 && sy < g.Hs && sx >= 0 && sx < g.Ws;
-    const int syc = min(max(sy, 0), g.Hs - 1), sxc = min(max(sx, 0), g.Ws - 1);
-    const unsigned o = (unsigned)(((c.n0 * g.Hs + syc) * g.Ws + sxc) * g.s_pix + g.s_choff + kq * 4) * 4u;
-    return (PROC == 0 && !in) ? LF_OOB : o;
-}
-// position p of a tile's K sequence: sub-tile p / NS, then tap-major, then 16-channel groups
-template <int CS, int PROC>
-__device__ __forceinline__ f32x4 pair_xload(const LfTapGeom& g, __amdgpu_buffer_rsrc_t rx, const PairWT& c, int p, int pl, int kq) {
-    constexpr int NCG = CS / 16, NS = 3 * NCG;
-    const int k = p % NS;
-    bool in;
-    const unsigned o = pair_xoff<PROC>(g, c, p / NS, k / NCG, pl, kq, in);
-    return ldb4(rx, o, (unsigned)(k % NCG) * 64u);
-}
-// the workgroup's 64-output-channel slice of the packed weights [tap][CS/4][Cd][4] -> LDS [K-step][channel tile n][kq][pl] float4
-template <int CS, int THREADS>
-__device__ __forceinline__ void pair_copy_weights(f32x4* wl, const float* wp, int cob) {
-    constexpr int NS = 3 * (CS / 16);
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(wp, (unsigned)(3 * CS * CS * 4));
-    for (int idx = threadIdx.x; idx < NS * 256; idx += THREADS) {
-        const int col = idx & 63, row = idx >> 6;                          // row = tap * (CS / 4) + 4 * channel group + kq
-        wl[((row >> 2) * 4 + (col >> 4)) * 64 + (row & 3) * 16 + (col & 15)] = ldb4(rw, (unsigned)(row * CS + cob + col) * 16u, 0u);
-    }
-}
-
-// One convolution over one tile per 4-wave group (unit bx: tiles bx * G ..): tapstream_kernel's tile body.  ring holds the first
-// PAIR_R K-steps of X on entry; TAIL: the last PAIR_R slots are refilled from tail(p), p = 0 .. PAIR_R - 1 (the next tile's
-// conv_a), else they are left alone.
-template <int CS, int PROC, int EPIC, int G, bool TAIL, typename Tail>
-__device__ __forceinline__ void pair_phase(const LfTapGeom& g, const LfTapArgs& a, const f32x4* wl, const float* pvec, const unsigned bx,
-                                           const unsigned ntiles, const unsigned npix, const int cob, const PairWT& cur,
-                                           const __amdgpu_buffer_rsrc_t rx, f32x4 (&ring)[PAIR_R], Tail&& tail) {
-    constexpr int NT = 4, NCG = CS / 16, NS = 3 * NCG, R = PAIR_R;
-    constexpr int epi = EPIC;
-    constexpr bool S16 = false, HOISTV = true;
-    static_assert((4 * NS) % R == 0 && R <= NS && NS % 2 == 0, "ring positions and K-step pairs must be compile-time");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pl = lane & 15, kq = lane >> 4;
-    f32x4 wn[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) wn[n] = wl[n * 64 + lane];
-#undef LF_EPI_GROUPS
-#define LF_EPI_GROUPS G
-#undef LF_EPI_ROW1
-#define LF_EPI_ROW1 true
-#undef LF_EPI_ACC
-#define LF_EPI_ACC(n, m) acc[n]
-#undef LF_EPI_FIRST
-#define LF_EPI_FIRST(m) (sub == 0)
-#undef LF_EPI_ROW_OK
-#define LF_EPI_ROW_OK(tg) (bx * (unsigned)G + (unsigned)(tg) < ntiles)
-    LF_EPI_HEAD
-    const int pn[1] = {cur.n0}, pi[1] = {cur.i0};
-    const bool pv[1] = {cur.v};
-#pragma unroll
-    for (int sub = 0; sub < 4; ++sub) {
-        f32x4 acc[NT], accl[NT];
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            const int p = sub * NS + k, cg = k % NCG;
-            f32x4 w[NT];
-#pragma unroll
-            for (int n = 0; n < NT; ++n) w[n] = wn[n];
-#pragma unroll
-            for (int n = 0; n < NT; ++n) wn[n] = wl[(((k + 1) % NS) * 4 + n) * 64 + lane];    // the next K-step's weights
-            f32x4 x = ring[p % R];
-            if constexpr (PROC == LF_PRO_BNRELU) {
-                bool in;
-                (void)pair_xoff<PROC>(g, cur, sub, k / NCG, pl, kq, in);
-                const f32x4 sc = *reinterpret_cast<const f32x4*>(pvec + cg * 16 + kq * 4);
-                const f32x4 sh = *reinterpret_cast<const f32x4*>(pvec + CS + cg * 16 + kq * 4);
-                f32x4 v = max0(x * sc + sh);
-                v.x = in ? v.x : 0.f; v.y = in ? v.y : 0.f; v.z = in ? v.z : 0.f; v.w = in ? v.w : 0.f;
-                x = v;
-            }
-            if (k % 2 == 0) {       // a pair of K-steps = one 32-product chain: flush the finished one, restart from C = 0
-#pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    if (k == 0) accl[n] = zero4();
-                    else { accl[n] += acc[n]; asm volatile("" : "+v"(accl[n])); }
-                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[n][0], x[0], zero4(), 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int s = (k % 2 == 0) ? 1 : 0; s < 4; ++s)
-#pragma unroll
-                for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[n][s], x[s], acc[n], 0, 0, 0);
-            // this ring slot's next occupant, R K-steps ahead: this tile's, or what the caller wants in flight behind this phase
-            if (p + R < 4 * NS) ring[p % R] = pair_xload<CS, PROC>(g, rx, cur, p + R, pl, kq);
-            else if constexpr (TAIL) ring[p % R] = tail(p + R - 4 * NS);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int n = 0; n < NT; ++n) acc[n] += accl[n];
-        const int pj[1] = {cur.j0 + sub * 16 + pl};
-        LF_EPI_TILE(0)
-    }
-    LF_EPI_TAIL
-#undef LF_EPI_GROUPS
-#define LF_EPI_GROUPS 1
-#undef LF_EPI_ROW1
-#define LF_EPI_ROW1 false
-#undef LF_EPI_ACC
-#define LF_EPI_ACC(n, m) acc[n][m]
-#undef LF_EPI_FIRST
-#define LF_EPI_FIRST(m) ((m) == 0)
-#undef LF_EPI_ROW_OK
-#define LF_EPI_ROW_OK(tg) true
+// lf_tappair_ok admits dense stride-1 CS -> CS tensors of the logical size only: with those fields written as constants the two
+// geometries share (N, H, W) and differ in their three tap offsets -- the index arithmetic folds and the scalar registers hold six
+// tap offsets instead of two whole descriptors (which spilled 40 of them).  The shared fields are set here; the tap offsets stay one
+// line in each kernel (set in here too, tappair128_kernel's register allocation moves).
+template <int CS>
+__device__ __forceinline__ void pair_geoms(const LfTapGeom& ga_in, LfTapGeom& ga, LfTapGeom& gb) {
+    ga.N = ga_in.N; ga.Hl = ga.Hs = ga.Hd = ga_in.Hl; ga.Wl = ga.Ws = ga.Wd = ga_in.Wl;
+    ga.s_pix = ga.d_pix = ga.Cs = ga.Cd = CS; ga.s_choff = ga.d_choff = 0; ga.ntaps = 3;
+    ga.ssh = ga.ssw = ga.dsh = ga.dsw = 1; ga.dah = ga.daw = 0;
+    gb = ga;
 }
 
 // ga / aa: conv_a (along H, LF_EPI_RELU, PROC its operand prologue), gb / ab: conv_b (along W, LF_EPI_STATS_SQ); ab.src == aa.dst.
 // G 4-wave groups per workgroup, group q of unit u owns tile u * G + q; units are walked as tapstream_kernel walks them.
 template <int CS, int PROC, int G>
 __global__ __launch_bounds__(256 * G, 1) void tappair_kernel(const LfTapGeom ga_in, const LfTapArgs aa, const LfTapGeom gb_in, const LfTapArgs ab) {
-    constexpr int NS = 3 * (CS / 16), R = PAIR_R;
-    // lf_tappair_ok admits dense stride-1 CS -> CS tensors of the logical size only: with those fields written as constants the
-    // two geometries share (N, H, W) and differ in their three tap offsets -- the index arithmetic folds and the scalar registers
-    // hold six tap offsets instead of two whole descriptors (which spilled 40 of them)
+    constexpr int NS = 3 * (CS / 16), R = STREAM_R;
     LfTapGeom ga, gb;
-    ga.N = ga_in.N; ga.Hl = ga.Hs = ga.Hd = ga_in.Hl; ga.Wl = ga.Ws = ga.Wd = ga_in.Wl;
-    ga.s_pix = ga.d_pix = ga.Cs = ga.Cd = CS; ga.s_choff = ga.d_choff = 0; ga.ntaps = 3;
-    ga.ssh = ga.ssw = ga.dsh = ga.dsw = 1; ga.dah = ga.daw = 0;
-    gb = ga;
+    pair_geoms<CS>(ga_in, ga, gb);
 #pragma unroll
     for (int t = 0; t < 3; ++t) { ga.tdh[t] = ga_in.tdh[t]; ga.tdw[t] = 0; gb.tdh[t] = 0; gb.tdw[t] = gb_in.tdw[t]; }
     const unsigned npix = (unsigned)(ga.N * ga.Hl * ga.Wl);
     const int cob = 0;
     const unsigned ntiles = (npix + PIX_PER_WG - 1) / PIX_PER_WG, nunits = (ntiles + G - 1) / G;
-    unsigned u_first = blockIdx.x, u_stride = gridDim.x, u_end = nunits;      // (see tapgemm_kernel: XCD-contiguous ranges)
-    if ((gridDim.x & 7u) == 0 && (nunits & 7u) == 0) {
-        const unsigned per = nunits >> 3;
-        u_first = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); u_stride = gridDim.x >> 3; u_end = (blockIdx.x & 7u) * per + per;
-    }
+    const XcdRange u = xcd_range(nunits);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pl = lane & 15, kq = lane >> 4;
-    const unsigned wtile = (unsigned)__builtin_amdgcn_readfirstlane(wave);    // tile (u * G + wave / 4), wave % 4 of it: pixels from (u * 4G + wave) * 64
+    const unsigned wtile = (unsigned)__builtin_amdgcn_readfirstlane(wave);
     f32x4* const wla = reinterpret_cast<f32x4*>(lf_tap_lds);
     f32x4* const wlb = wla + NS * 256;
-    float* const pvec = reinterpret_cast<float*>(wlb + NS * 256);             // BN+ReLU operand prologue of conv_a: scale [CS], shift [CS]
-    auto coords = [&](unsigned u, bool live) -> PairWT {      // the logical grids of the two convolutions are one (lf_tappair_ok)
-        const unsigned tile0 = (u * (unsigned)(4 * G) + wtile) * 64u;
-        PairWT c;
-        c.v = live && tile0 < npix;
-        const unsigned q = c.v ? tile0 : 0u;
-        const unsigned r = q / (unsigned)ga.Wl;
-        c.j0 = __builtin_amdgcn_readfirstlane((int)(q - r * (unsigned)ga.Wl));
-        c.n0 = __builtin_amdgcn_readfirstlane((int)(r / (unsigned)ga.Hl));
-        c.i0 = __builtin_amdgcn_readfirstlane((int)r) - c.n0 * ga.Hl;
-        return c;
-    };
+    float* const pvec = reinterpret_cast<float*>(wlb + NS * 256);             // BN+ReLU operand prologue of conv_a
     const __amdgpu_buffer_rsrc_t rxa = make_rsrc(aa.src, (unsigned)min((long)ga.N * ga.Hs * ga.Ws * ga.s_pix * 4, (long)LF_OOB));
     const __amdgpu_buffer_rsrc_t rxb = make_rsrc(ab.src, (unsigned)min((long)gb.N * gb.Hs * gb.Ws * gb.s_pix * 4, (long)LF_OOB));
 
     // the first R K-steps of conv_a's X are requested BEFORE the weights are copied: their latency runs under the copy
+    // (the logical grids of the two convolutions are one, lf_tappair_ok: a wave's coordinates serve both)
     f32x4 ring[R];
-    PairWT cur = coords(u_first, u_first < u_end);
+    StreamWT cur = stream_coords<G>(ga, npix, wtile, u.first, u.first < u.end);
 #pragma unroll
-    for (int p = 0; p < R; ++p) ring[p] = pair_xload<CS, PROC>(ga, rxa, cur, p, pl, kq);
-    pair_copy_weights<CS, 256 * G>(wla, aa.wp, cob);
-    pair_copy_weights<CS, 256 * G>(wlb, ab.wp, cob);
-    if constexpr (PROC == LF_PRO_BNRELU) {
-        const __amdgpu_buffer_rsrc_t rsc = make_rsrc(aa.pro_sc, CS * 4u), rsh = make_rsrc(aa.pro_sh, CS * 4u);
-        for (int i = threadIdx.x; i < 2 * CS; i += 256 * G)
-            pvec[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(i < CS ? rsc : rsh, (i < CS ? i : i - CS) * 4, 0, 0));
-    }
+    for (int p = 0; p < R; ++p) ring[p] = stream_xload<CS, PROC>(ga, rxa, cur, p, pl, kq);
+    stream_copy_weights<CS, 256 * G>(wla, aa.wp, cob);
+    stream_copy_weights<CS, 256 * G>(wlb, ab.wp, cob);
+    if constexpr (PROC == LF_PRO_BNRELU) stream_copy_prologue<CS, 256 * G>(pvec, aa);
     __syncthreads();
 
-    for (unsigned bx = u_first; bx < u_end; bx += u_stride) {
-        const PairWT nxt = coords(bx + u_stride, bx + u_stride < u_end);
-        pair_phase<CS, PROC, LF_EPI_RELU, G, false>(ga, aa, wla, pvec, bx, ntiles, npix, cob, cur, rxa, ring, [](int) { return zero4(); });
+    for (unsigned bx = u.first; bx < u.end; bx += u.stride) {
+        const StreamWT nxt = stream_coords<G>(ga, npix, wtile, bx + u.stride, bx + u.stride < u.end);
+        stream_tile<CS, PROC, LF_EPI_RELU, G, false>(ga, aa, wla, pvec, bx, ntiles, npix, cob, cur, rxa, ring, [](int) { return zero4(); });
         // the hand-over: my stores of t have left, then everybody's have -- only now may any wave of the workgroup read t.  (It also
         // separates the previous tile's reads of the statistics staging area from this tile's writes.)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        // the X ring is filled afresh behind the barrier (conv_b) and, for the next tile's conv_a, during the tail of conv_b
 #pragma unroll
-        for (int p = 0; p < R; ++p) ring[p] = pair_xload<CS, 0>(gb, rxb, cur, p, pl, kq);
-        pair_phase<CS, 0, LF_EPI_STATS_SQ, G, true>(gb, ab, wlb, pvec, bx, ntiles, npix, cob, cur, rxb, ring,
-                                                     [&](int p) { return pair_xload<CS, PROC>(ga, rxa, nxt, p, pl, kq); });
+        for (int p = 0; p < R; ++p) ring[p] = stream_xload<CS, 0>(gb, rxb, cur, p, pl, kq);
+        stream_tile<CS, 0, LF_EPI_STATS_SQ, G, true>(gb, ab, wlb, pvec, bx, ntiles, npix, cob, cur, rxb, ring,
+                                                      [&](int p) { return stream_xload<CS, PROC>(ga, rxa, nxt, p, pl, kq); });
         cur = nxt;
     }
 }
@@ -219,6 +92,11 @@ __global__ __launch_bounds__(256 * G, 1) void tappair_kernel(const LfTapGeom ga_
 // (192 KB per convolution) do not fit LDS: operands are streamed L1 / L2 -> VGPR as tapgemm_kernel streams them, whose tile body
 // (ROW1 form: tap table in LDS, two operand sets, two accumulator sets, the compiled-in epilogue) this is, twice per tile.  One
 // workgroup per CU = the two waves per SIMD of tapgemm_kernel's two 256-thread workgroups.
+//
+// pair128_phase is a DELIBERATE COPY of tapgemm_kernel's ROW1 tile body (lf_conv.hip), not a shared function: called from both
+// kernels as one __forceinline__ template, the body moved the register allocation of every tapgemm_kernel instantiation (228 ->
+// 216-232 VGPRs, <3,0,-1> from 31 to 150 spilled SGPRs) and gave tappair128_kernel 308 bytes of scratch.  Any edit to either copy
+// must be mirrored in the other (tests/test_fwd_pair_gpu.py compares them bit for bit).
 constexpr size_t PAIR128_LDS = (size_t)2 * WG_WAVES * 3 * 64 * (sizeof(uint4) + sizeof(unsigned));      // tap tables of 8 waves
 
 template <int PROC, int EPIC>
@@ -383,17 +261,13 @@ __device__ __forceinline__ void pair128_phase(const LfTapGeom& g, const LfTapArg
 
 template <int PROC>
 __global__ __launch_bounds__(512, 1) void tappair128_kernel(const LfTapGeom ga_in, const LfTapArgs aa, const LfTapGeom gb_in, const LfTapArgs ab) {
-    constexpr int CS = 128;
-    LfTapGeom ga, gb;      // (the constant fields written as constants: see tappair_kernel)
-    ga.N = ga_in.N; ga.Hl = ga.Hs = ga.Hd = ga_in.Hl; ga.Wl = ga.Ws = ga.Wd = ga_in.Wl;
-    ga.s_pix = ga.d_pix = ga.Cs = ga.Cd = CS; ga.s_choff = ga.d_choff = 0; ga.ntaps = 3;
-    ga.ssh = ga.ssw = ga.dsh = ga.dsw = 1; ga.dah = ga.daw = 0;
-    gb = ga;
+    LfTapGeom ga, gb;
+    pair_geoms<128>(ga_in, ga, gb);
 #pragma unroll
     for (int t = 0; t < 3; ++t) { ga.tdh[t] = ga_in.tdh[t]; ga.tdw[t] = 0; gb.tdh[t] = 0; gb.tdw[t] = gb_in.tdw[t]; }
     const unsigned npix = (unsigned)(ga.N * ga.Hl * ga.Wl);
     const unsigned ntiles = (npix + PIX_PER_WG - 1) / PIX_PER_WG;
-    unsigned t_first = blockIdx.x, t_stride = gridDim.x, t_end = ntiles;      // (see tapgemm_kernel: XCD-contiguous ranges)
+    unsigned t_first = blockIdx.x, t_stride = gridDim.x, t_end = ntiles;      // (xcd_range written out: with the call the kernel's text moves)
     if ((gridDim.x & 7u) == 0 && (ntiles & 7u) == 0) {
         const unsigned per = ntiles >> 3;
         t_first = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); t_stride = gridDim.x >> 3; t_end = (blockIdx.x & 7u) * per + per;

@@ -59,8 +59,7 @@ __global__ __launch_bounds__(256, 2) void tapwgrad_kernel(const LfTapGeom g, con
     // one pixel range -- which read the same G rows and overlapping X rows -- follow each other through ONE L2
     // instead of streaming both tensors from HBM once per tap (FETCH_SIZE 177 MB -> see profiles/).
     const int ncob = g.Cd / GB;
-    unsigned ord = blockIdx.x;
-    if ((gridDim.x & 7u) == 0) ord = (ord & 7u) * (gridDim.x >> 3) + (ord >> 3);
+    const unsigned ord = xcd_swizzle(blockIdx.x);
     const unsigned nz = (unsigned)((g.Cs / XB) * ncob);
     const int t = (int)(ord % (unsigned)g.ntaps);
     const int bz = (int)((ord / (unsigned)g.ntaps) % nz);                 // channel-block pair: next fastest
@@ -520,13 +519,7 @@ __global__ __launch_bounds__(256) void tapwgrad16_tr_kernel(const LfTapGeom g, c
     // load cursor: (image, row, column) of the next 16-pixel group (wave-uniform; Wl % 16 == 0: a group lies in one row)
     long p_ld = p_begin;
     int pj, pi, pn;
-    {
-        const unsigned q = niter ? (unsigned)p_begin : 0u;
-        const unsigned r = q / (unsigned)g.Wl;
-        pj = __builtin_amdgcn_readfirstlane((int)(q - r * (unsigned)g.Wl));
-        pn = __builtin_amdgcn_readfirstlane((int)(r / (unsigned)g.Hl));
-        pi = __builtin_amdgcn_readfirstlane((int)r) - pn * g.Hl;
-    }
+    row1_coords(g, niter ? (unsigned)p_begin : 0u, pn, pi, pj);
     const int px = (lane >> 1) & 15, half = lane & 1;         // lanes 0-31: first group of the stage, 32-63: second
     int st_ld = 0;
     auto issue = [&]() __attribute__((always_inline)) {
@@ -682,13 +675,7 @@ __global__ __launch_bounds__(256) void tapwgrad16_f32_kernel(const LfTapGeom g, 
     // load cursor: (image, row, column) of the next 16-pixel group (wave-uniform; Wl % 16 == 0: a group lies in one row)
     long p_ld = p_begin;
     int pj, pi, pn;
-    {
-        const unsigned q = niter ? (unsigned)p_begin : 0u;
-        const unsigned r = q / (unsigned)g.Wl;
-        pj = __builtin_amdgcn_readfirstlane((int)(q - r * (unsigned)g.Wl));
-        pn = __builtin_amdgcn_readfirstlane((int)(r / (unsigned)g.Hl));
-        pi = __builtin_amdgcn_readfirstlane((int)r) - pn * g.Hl;
-    }
+    row1_coords(g, niter ? (unsigned)p_begin : 0u, pn, pi, pj);
     int cj = pj, ci = pi;                                     // compute cursor (PRO: the padding tests)
     const int px = lane >> 2, chunk = lane & 3;
     auto issue = [&](const int slot) __attribute__((always_inline)) {
