@@ -52,7 +52,9 @@ extern "C" {
                                  additions since 5 (segmentation-mode detect): lf_head_fit_seg, lf_lane_infer_seg_workspace_bytes,
                                  lf_lane_infer_seg;
                                  additions since 5 (input-image gradient): lf_stem_bwd_data, lf_erfnet_backward_input (and
-                                 lf_erfnet_backward_range writes a non-NULL gx for first = 0) */
+                                 lf_erfnet_backward_range writes a non-NULL gx for first = 0);
+                                 additions since 5 (frozen single-frame detector): lf_erfnet_infer_fold, lf_lane_infer_folded,
+                                 lf_lane_infer_seg_folded */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -669,6 +671,32 @@ int lf_conv1d_bwd_data(const float* gy, const float* w, const float* mask_src, f
                        int C, int axis, int dilation, float* scratch, void* stream);
 int lf_conv1d_bwd_weight(const float* x, const float* gy, float* gw, float* gb, int N, int H, int W, int C,
                          int axis, int dilation, float* scratch, void* stream);
+
+/* additions since 5 -- frozen single-frame detector: at deployment the weights and running statistics do not change between
+ * frames, so the BatchNorm fold of the inference engine is done ONCE into a persistent workspace and every call after it is the
+ * kernels alone.
+ * lf_erfnet_infer_fold: the fold-table upload and the one fold-and-pack launch that lf_erfnet_infer / lf_lane_infer /
+ *   lf_lane_infer_seg do on every call, in the plan's current precision mode (lf_erfnet_set_precision), into `workspace`.  The
+ *   folded region is the common prefix of the workspaces of lf_erfnet_infer_workspace_bytes, lf_lane_infer_workspace_bytes and
+ *   lf_lane_infer_seg_workspace_bytes: a workspace sized by any of them can be folded and then handed to the matching call.
+ *   Fold again after any change of a parameter, a running statistic or the plan's precision mode.
+ * lf_lane_infer_folded / lf_lane_infer_seg_folded: lf_lane_infer / lf_lane_infer_seg on such a workspace -- the same schedule and
+ *   the same results bit for bit, nothing uploaded, nothing folded.  params_host is still read (the stem and head kernels take
+ *   their raw weights from it); params_dev and running_host are not.  flags: LF_INFER_THIN routes the fp32 tap-GEMM launches whose
+ *   regular grid cannot fill the device (one camera frame) to a thin tiling with the same bits; 0 in the other precision modes. */
+enum { LF_INFER_THIN = 1 };
+int lf_erfnet_infer_fold(const lf_erfnet_plan* plan, const float* const* params_host, const float* const* params_dev,
+                         float* const* running_host, void* workspace, size_t workspace_bytes, void* stream);
+int lf_lane_infer_folded(const lf_erfnet_plan* plan, const float* img, const float* const* params_host,
+                         const float* const* params_dev, float* const* running_host, const float* grid_xy, long grid_batch_stride,
+                         int zero_rows, int order, double reg_ls, double y_offset, int act_kind, int use_cholesky,
+                         float* logits_or_null, double* beta, int32_t* status, void* workspace, size_t workspace_bytes, int flags,
+                         void* stream);
+int lf_lane_infer_seg_folded(const lf_erfnet_plan* plan, const float* img, const float* const* params_host,
+                             const float* const* params_dev, float* const* running_host, const float* grid_xy,
+                             long grid_batch_stride, const float* gt_line_or_null, int L, int zero_rows, int order, double reg_ls,
+                             double y_offset, int use_cholesky, uint8_t* classes_or_null, double* beta, int32_t* status,
+                             void* workspace, size_t workspace_bytes, int flags, void* stream);
 
 /* additions since 5 -- input-image gradient: d loss / d input of Net.forward, what `input.requires_grad_()` before the forward and
  * `loss.backward()` (BEV/main.py:264-266) give in the reference -- the data gradient of the stem DownsamplerBlock's

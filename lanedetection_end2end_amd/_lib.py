@@ -140,6 +140,9 @@ def _declare(lib):
         "lf_lane_infer_seg": (I, [P, P, P, P, P, P, L, P, I, I, I, D, D, I, P, P, P, P, c_size_t, P]),
         "lf_stem_bwd_data": (I, [P, P, P, I, I, I, I, I, P, P]),
         "lf_erfnet_backward_input": (I, [P, P, P, P, P, P, P, I, I, P, P, c_size_t, P]),
+        "lf_erfnet_infer_fold": (I, [P, P, P, P, P, c_size_t, P]),
+        "lf_lane_infer_folded": (I, [P, P, P, P, P, P, L, I, I, D, D, I, I, P, P, P, P, c_size_t, I, P]),
+        "lf_lane_infer_seg_folded": (I, [P, P, P, P, P, P, L, P, I, I, I, D, D, I, P, P, P, P, c_size_t, I, P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {
@@ -169,6 +172,9 @@ def _declare(lib):
         "lf_debug_conv1d_wgrad_pro": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P, P]),
         "lf_debug_bias_residual_launches": (L, []),
         "lf_debug_partial_fast_launches": (L, []),
+        "lf_debug_set_thin": (None, [I, I]),
+        "lf_debug_thin_launches": (L, []),
+        "lf_debug_fold_pack_launches": (L, []),
         # one launch of a bandwidth-bound backbone kernel; a source of partial rows = (rows, nrows, ld, C, ch_off, tile_pix, seg_rows, seg_pix)
         "lf_debug_bn_finalize_fwd": (I, [P, I, I, I, I, I, I, L] * 2 + [I, D, P, P, P, P, ctypes.c_float, ctypes.c_float, I, P, P, P, P, P]),
         "lf_debug_bn_bwd_finalize": (I, [P, I, I, I, I, I, I, L] * 2 + [I, D, P, P, P, P, P, P, I, P]),
@@ -195,7 +201,8 @@ def exported_symbols():
     return list(_declare(load()).keys()) + list(_extra_symbols)
 
 
-_extra_symbols = []
+# ... and the csrc/lf_debug.h hooks the frozen detector's tests and tools/detector_latency.py count launches with
+_extra_symbols = ["lf_debug_set_thin", "lf_debug_thin_launches", "lf_debug_fold_pack_launches"]
 
 
 def load():

@@ -61,11 +61,16 @@ struct LfTapArgs {
     float* stats;           // per-workgroup partial sums, channel-major: [2][Cd][stats_ld], row r = 256-pixel tile r of the launch
     int stats_ld;           //   (rows = lf_tapgemm_stat_rows(); stats_ld >= rows: lf_eltwise.h, LfStatPart)
     unsigned long long* dbg;  // optional: per-wave phase timestamps (s_memtime), 8 words per wave (tools/kbench.py --phases)
+    int thin;               // host-side routing flag (no kernel reads it): a launch whose regular grid cannot fill the device takes
+                            //   tapgemm_thin_kernel where that kernel is compiled for it (lf_conv.hip, launch_fp32_route); 0 everywhere
+                            //   but the frozen detector's calls (LF_INFER_THIN)
 };
 
 // ---- lf_conv.hip: forward and data-gradient launches, the fp32 kernels' routing switches and the counters of both routes ----
 void lf_tapgemm_set_split_any_size(int v);
 void lf_tapgemm_set_fp32_stream(int mode, int max_workgroups);   // tapstream_kernel routing (lf_debug_set_fp32_stream, lf_debug.h)
+void lf_tapgemm_set_thin(int mode, int nt);          // tapgemm_thin_kernel routing (lf_debug_set_thin, lf_debug.h)
+long lf_tapgemm_thin_launches();                     // launches tapgemm_thin_kernel took since the process started
 int lf_tapgemm_stat_rows(const LfTapGeom& g);                          // upper bound over the kernels (buffer sizing)
 int lf_tapgemm_stat_rows_for(const LfTapGeom& g, const LfTapArgs& a);  // rows the launch with these arguments writes
 int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, hipStream_t st);
@@ -188,5 +193,6 @@ struct LfFoldEntry {
 // arenas: fp32 [pk.dst_off], bf16 [pk.dst16_off] and split [3 * pk.dst16_off]; a null arena is not written; vec: the vector region
 int lf_fold_pack_launch(const LfFoldEntry* entries_dev, int nentries, const float* const* params_dev, float eps, float* vec, float* arena,
                         void* arena16, void* arena48, hipStream_t st);
+long lf_fold_pack_launches();       // lf_fold_pack_launch calls that launched since the process started (lf_debug_fold_pack_launches)
 int lf_pack_weights_bf16_launch(const LfPackEntry* entries_dev, int nentries, const float* const* params_dev, void* arena16,
                                 hipStream_t st);

@@ -17,9 +17,10 @@
 // Kernels in this file:
 //   tapgemm_kernel            fp32 matrix cores, operands streamed L2 -> VGPR: the 64- / 128-channel launches of the network
 //   tapstream_kernel          fp32, the 3-tap convolutions at 64 / 128 channels: weights resident in LDS, pixels streamed past them
+//   tapgemm_thin_kernel       tapgemm_kernel re-tiled (one 16-pixel tile per wave) for launches that cannot fill the device: one frame
 //   tapgemm_lean_kernel       16-channel layers in fp32 (HBM-bound)
 //   tapgemm_split_kernel      precision mode fp32x9: fp32 results from exact 3-way bf16 splits on the bf16 matrix cores
-// All four take fp32 tensors; lf_tapgemm_launch, at the end of the file, routes a launch to one of them or, for bf16 tensors, to
+// All five take fp32 tensors; lf_tapgemm_launch, at the end of the file, routes a launch to one of them or, for bf16 tensors, to
 // lf_tapgemm_bf16_route.  The kernels on bf16 tensors and that route are in lf_conv_bf16.hip, the weight gradients with their
 // split-K reductions in lf_wgrad.hip, the weight-packing and BatchNorm-fold kernels in lf_pack.hip; the device helpers and launch
 // helpers shared with lf_conv_bf16.hip and lf_wgrad.hip are in lf_conv_dev.h.
@@ -347,6 +348,140 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void tapstream_kernel(cons
         if (stats && bx + u.stride < u.end) __syncthreads();      // the statistics staging area is reused by the next tile
         cur = nxt;
     }
+}
+
+// ---------------------------------------------------------------------------------------
+// tapgemm_thin_kernel: tapgemm_kernel re-tiled for launches whose regular grid (256 pixels x 64 channels per workgroup) cannot
+// fill the device -- one camera frame: 8 to 32 workgroups on 256 CUs.  A wave owns ONE 16-pixel tile and NT 16-channel slabs, a
+// workgroup 64 consecutive logical pixels, blockIdx.y walks the slab groups, one workgroup per tile (no walk).  The general
+// LfTapGeom (any tap count, strides, sub-pixel destination offsets, ragged Wl); no operand prologue, no statistics; the epilogues
+// the inference schedules issue: bias + ReLU and bias + residual + ReLU (BRES).
+// Every output element is tapgemm_kernel's bit for bit (tests/test_thin_conv_gpu.py): the same MFMA with the same operand roles
+// and k-slot permutation, K-steps tap-major then 16-channel group, the chain restarted from a zero C operand at every pair of
+// K-steps with accl += acc in front of it and acc + accl at the end, the zero-operand dead step of an odd step count (the last
+// live weights against zeros), the shared epilogue text.  K is not split.
+// A thin wave is alone on its SIMD, so nothing hides a load but the wave's own MFMAs: a ring of R K-steps of operands (4 * (NT + 1)
+// registers per step) is in flight, R = LF_THIN_DEPTH / NT rounded to whole pairs of K-steps -- about the same bytes in flight
+// whatever NT, a step's MFMA time growing with NT.  Depths 4, 8 and 16 were measured: 8.  The ring changes
+// which registers a step's operands arrive in, not the order of the MFMAs: scheduling fences pin it.
+#ifndef LF_THIN_DEPTH
+#define LF_THIN_DEPTH 8
+#endif
+constexpr int thin_ring(int nt) {
+    const int r = (LF_THIN_DEPTH / nt + 1) / 2 * 2;
+    return r < 2 ? 2 : r;
+}
+template <int NT, int EPIC>
+__global__ __launch_bounds__(256, 2) void tapgemm_thin_kernel(const LfTapGeom g, const LfTapArgs a) {
+    constexpr int epi = EPIC, R = thin_ring(NT);
+    constexpr bool S16 = false, HOISTV = true;
+    static_assert(R % 2 == 0 && (EPIC == LF_EPI_RELU || EPIC == BRES), "the ring holds whole pairs of K-steps");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pl = lane & 15, kq = lane >> 4;
+    const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl);
+    const int cob = blockIdx.y * NT * 16;
+    const unsigned bx = xcd_swizzle(blockIdx.x);       // (see tapgemm_kernel: XCD-contiguous ranges)
+    int pn[1], pi[1], pj[1];
+    bool pv[1];
+    {
+        const unsigned p = (bx * WG_WAVES + wave) * 16 + pl;
+        pv[0] = p < npix;
+        const unsigned q = pv[0] ? p : 0u;
+        const unsigned r = q / (unsigned)g.Wl;
+        pj[0] = (int)(q - r * (unsigned)g.Wl);
+        pn[0] = (int)(r / (unsigned)g.Hl);
+        pi[0] = (int)(r - (unsigned)pn[0] * (unsigned)g.Hl);
+    }
+    // tapgemm_kernel's tap table, one pixel tile wide: this lane's source byte offset per tap, LF_OOB (reads as zeros) for padding
+    __shared__ unsigned tab[WG_WAVES][LF_MAX_TAPS][64];
+    for (int t = 0; t < g.ntaps; ++t) {
+        const int sy = pi[0] * g.ssh + g.tdh[t], sx = pj[0] * g.ssw + g.tdw[t];
+        const bool in = pv[0] && sy >= 0 && sy < g.Hs && sx >= 0 && sx < g.Ws;
+        const int syc = min(max(sy, 0), g.Hs - 1), sxc = min(max(sx, 0), g.Ws - 1);
+        const unsigned o = (unsigned)(((pn[0] * g.Hs + syc) * g.Ws + sxc) * g.s_pix + g.s_choff + kq * 4) * 4u;
+        tab[wave][t][lane] = in ? o : LF_OOB;
+    }
+    // (each lane reads back only what it wrote: no barrier needed)
+    f32x4 acc[NT][1], accl[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) { acc[n][0] = zero4(); accl[n] = zero4(); }
+    // (both ahead of the loop: the round trips of the bias vector and of the residual run under it -- behind it, nothing would hide them)
+    LF_EPI_HEAD
+    f32x4 addv[NT];
+    if constexpr ((EPIC & LF_EPI_ADD) != 0) {
+        const unsigned db = (unsigned)(((pn[0] * g.Hd + pi[0] * g.dsh + g.dah) * g.Wd + pj[0] * g.dsw + g.daw) * g.d_pix + g.d_choff + cob + kq * 4);
+#pragma unroll
+        for (int n = 0; n < NT; ++n) addv[n] = epi_ld<S16>(r_add, db + n * 16);
+    }
+    {
+        struct Step { f32x4 w[NT]; f32x4 x; };
+        const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.src, (unsigned)min((long)g.N * g.Hs * g.Ws * g.s_pix * 4, (long)LF_OOB));
+        const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.wp, 0xffffffffu);
+        const unsigned wlane = (unsigned)(kq * g.Cd + cob + pl) * 16u;      // bytes
+        const int ncg = g.Cs >> 4, ntaps = g.ntaps, nsteps = ntaps * ncg;
+        const int wstep = g.Cd * 64, wlast = (nsteps - 1) * wstep;          // bytes per 16-channel step
+        const int npad = (nsteps + 1) & ~1;                                 // an odd step count ends with a dead step
+        int t_ld = 0, cg_ld = 0, wofs = 0;
+        // the next K-step's operands -> S; past the last live step: the last live weights against zeros (tapgemm_kernel's dead step)
+        auto issue = [&](Step& S) {
+            const bool live = t_ld < ntaps;
+            const unsigned o = tab[wave][live ? t_ld : ntaps - 1][lane] | (live ? 0u : LF_OOB);
+#pragma unroll
+            for (int n = 0; n < NT; ++n) S.w[n] = ldb4(rw, wlane + n * 256, (unsigned)wofs);
+            S.x = ldb4(rx, o, (unsigned)cg_ld * 64u);
+            const int cgn = cg_ld + 1;
+            const bool wrap = cgn == ncg;
+            wofs = min(wofs + wstep, wlast);
+            cg_ld = live ? (wrap ? 0 : cgn) : cg_ld;
+            t_ld = (live && wrap) ? t_ld + 1 : t_ld;
+        };
+        Step ring[R];
+#pragma unroll
+        for (int p = 0; p < R; ++p) issue(ring[p]);
+        // one pair of K-steps = one 32-product chain; refill: each slot's next occupant, R K-steps ahead, behind its last MFMA
+        auto pair = [&](Step& A, Step& B, auto refill) {
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {    // the finished pair's chain joins the long-term sum, the next starts from C = 0
+                accl[n] += acc[n][0];
+                asm volatile("" : "+v"(accl[n]));
+                acc[n][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A.w[n][0], A.x[0], zero4(), 0, 0, 0);
+            }
+#pragma unroll
+            for (int s = 1; s < 4; ++s)
+#pragma unroll
+                for (int n = 0; n < NT; ++n) acc[n][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A.w[n][s], A.x[s], acc[n][0], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (decltype(refill)::value) issue(A);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int n = 0; n < NT; ++n) acc[n][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(B.w[n][s], B.x[s], acc[n][0], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (decltype(refill)::value) issue(B);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        // whole turns of the ring in a loop without an early exit (one that joins the latch makes the compiler's wait counts at
+        // the loop head assume the youngest load of every path: the ring drained once per turn), then the last, partial turn
+        int base = 0;
+        for (; base + R <= npad; base += R) {
+#pragma unroll
+            for (int j = 0; j < R; j += 2) pair(ring[j], ring[j + 1], std::true_type{});
+        }
+#pragma unroll
+        for (int j = 0; j < R - 2; j += 2) {
+            if (base + j >= npad) break;          // (wave-uniform)
+            pair(ring[j], ring[j + 1], std::false_type{});
+        }
+    }
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[n][0] += accl[n];
+#undef LF_EPI_LDADD
+#define LF_EPI_LDADD(o) addv[((o) - dbase) >> 4]      /* the residual of channel tile n, loaded ahead of the loop */
+    LF_EPI_TILE(0)
+#undef LF_EPI_LDADD
+#define LF_EPI_LDADD(o) epi_ld<S16>(r_add, o)
+    LF_EPI_TAIL
 }
 
 // ---------------------------------------------------------------------------------------
@@ -803,6 +938,47 @@ bool route_tapstream(int variant, hipStream_t st, const LfTapGeom& g, const LfTa
     }
 }
 
+// tapgemm_thin_kernel (see there).  lf_debug_set_thin: mode 0 = LfTapArgs::thin and the grid size decide, 2 = every launch the
+// kernel is compiled for takes it; nt = 0: the launcher's choice, 1..4: that many slabs per wave where it divides Cd / 16.
+std::atomic<int> g_thin_mode{0}, g_thin_nt{0};
+std::atomic<long> g_thin_launches{0};
+int device_cus() {
+    static std::map<int, int> cache;
+    const int dev = current_device();
+    std::lock_guard<std::mutex> lock(g_launch_state_mutex);
+    auto it = cache.find(dev);
+    if (it != cache.end()) return it->second;
+    int cus = 0;
+    if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
+    return cache[dev] = cus;
+}
+// the forms the thin kernel is compiled for: no prologue, bias + ReLU or bias + residual + ReLU
+bool thin_compiled(const LfTapArgs& a, int pro, int epis) {
+    return pro == LF_PRO_NONE && ((epis == LF_EPI_RELU && a.bias) || epis == BRES);
+}
+// slabs per wave: the largest of 4, 3, 2, 1 dividing Cd / 16 that still gives one workgroup per CU, else 1
+int thin_pick_nt(const LfTapGeom& g) {
+    const int slabs = g.Cd / 16, forced = g_thin_nt.load();
+    if (forced >= 1 && forced <= 4 && slabs % forced == 0) return forced;
+    const long tiles = lf_cdiv((long)g.N * g.Hl * g.Wl, WG_WAVES * 16);
+    for (int nt = 4; nt > 1; --nt)
+        if (slabs % nt == 0 && tiles * (slabs / nt) >= device_cus()) return nt;
+    return 1;
+}
+template <int EPIV>
+void launch_thin(const LfTapGeom& g, const LfTapArgs& a, hipStream_t st) {
+    const int nt = thin_pick_nt(g);
+    const dim3 grid((unsigned)lf_cdiv((long)g.N * g.Hl * g.Wl, WG_WAVES * 16), g.Cd / (16 * nt));
+    switch (nt) {
+        case 4: hipLaunchKernelGGL((tapgemm_thin_kernel<4, EPIV>), grid, dim3(256), 0, st, g, a); break;
+        case 3: hipLaunchKernelGGL((tapgemm_thin_kernel<3, EPIV>), grid, dim3(256), 0, st, g, a); break;
+        case 2: hipLaunchKernelGGL((tapgemm_thin_kernel<2, EPIV>), grid, dim3(256), 0, st, g, a); break;
+        default: hipLaunchKernelGGL((tapgemm_thin_kernel<1, EPIV>), grid, dim3(256), 0, st, g, a); break;
+    }
+    ++g_thin_launches;
+    if (EPIV == BRES) ++g_bres_launches;
+}
+
 // precision mode fp32x9: fp32 tensors, the weights packed as three bf16 terms (tapgemm_split_kernel)
 int launch_split_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, int epis, long npix, hipStream_t st) {
     LF_REQUIRE(a.split == 9, "tapgemm: split must be 9 (got %d; the 6-term form was removed in round 6)", a.split);
@@ -836,6 +1012,16 @@ int launch_fp32_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
         if ((g.Wl & 63) == 0) hipLaunchKernelGGL((tapgemm_kernel<4, 0, 0, true, true>), grid, dim3(256), tap_lds, st, g, a, pro, epi);
         else hipLaunchKernelGGL((tapgemm_kernel<4, 0, 0, false, true>), grid, dim3(256), tap_lds, st, g, a, pro, epi);
         LF_CHECK_LAUNCH("tapgemm (stamps)");
+        return 0;
+    }
+    // a launch of tapgemm_kernel's (64- / 128-channel slabs, the stride-2 layers, the up-sampler phases) that cannot put one
+    // workgroup on every CU: the thin tiling, where the caller asks for it
+    const int thin_mode = g_thin_mode.load();
+    if ((a.thin || thin_mode == 2) && nt >= 2 && thin_compiled(a, pro, epis) &&
+        (thin_mode == 2 || (long)grid.x * grid.y < device_cus())) {
+        if (epis == BRES) launch_thin<BRES>(g, a, st);
+        else launch_thin<LF_EPI_RELU>(g, a, st);
+        LF_CHECK_LAUNCH("tapgemm_thin");
         return 0;
     }
     if (g_stream_mode.load() != 0 && nt == 4 && g.ntaps == 3 && g.Cs == g.Cd && (g.Cs == 64 || g.Cs == 128) && (g.Wl & 63) == 0) {
@@ -874,6 +1060,9 @@ int launch_fp32_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
 }  // namespace
 
 void lf_tapgemm_set_fp32_stream(int mode, int max_workgroups) { g_stream_mode = mode; g_stream_cap = max_workgroups > 0 ? max_workgroups : 0; }
+
+void lf_tapgemm_set_thin(int mode, int nt) { g_thin_mode = mode == 2 ? 2 : 0; g_thin_nt = (nt >= 1 && nt <= 4) ? nt : 0; }
+long lf_tapgemm_thin_launches() { return g_thin_launches.load(); }
 
 int lf_tapgemm_launch_unordered(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, hipStream_t st) {
     g_launch_flags = hipExtAnyOrderLaunch;

@@ -9,6 +9,7 @@
 // kernel behind it in the file without a diagnostic, so a redefinition and its restore are kept within sight of each other.
 // The kernels that redefine:
 //   lf_conv.hip       tapgemm_kernel         LF_EPI_ONE_TILE, LF_EPI_TID, LF_EPI_ROW1
+//                     tapgemm_thin_kernel    LF_EPI_LDADD (expands LF_EPI_HEAD / LF_EPI_TILE(0) / LF_EPI_TAIL: one pixel tile per wave)
 //                     tapgemm_split_kernel   LF_EPI_GROUPS (around the whole kernel), LF_EPI_PIVOT
 //   lf_conv_stream.h  stream_tile            LF_EPI_GROUPS, LF_EPI_ROW1, LF_EPI_ACC, LF_EPI_FIRST, LF_EPI_ROW_OK -- the tile body of
 //                                            tapstream_kernel (lf_conv.hip) and tappair_kernel (lf_conv_pair.hip): the stream

@@ -196,6 +196,17 @@ int lf_debug_head_bwd_data(const float* gout, const float* w, float* gx, int N, 
 /* tap-GEMM launches that took a compiled-in bias + residual + ReLU epilogue (the inference engine's block tail) since the process
  * started: which kernel form a launch selected (tests/test_infer_gpu.py) */
 long lf_debug_bias_residual_launches(void);
+/* the thin fp32 tap-GEMM (tapgemm_thin_kernel, csrc/lf_conv.hip: one 16-pixel tile per wave, for launches that cannot fill the device).
+ * mode 0 (shipped): LfTapArgs::thin -- set by the frozen detector's calls only -- and the grid size decide; 2: every launch the kernel is
+ * compiled for (fp32 tensors, an output slab of 32 channels or more, no prologue, bias + ReLU or bias + residual + ReLU) takes it, whatever
+ * the flag and the grid.  nt 0: the launcher picks the 16-channel slabs per wave; 1..4: forced where it divides Cd / 16.  The kernels agree
+ * bit for bit (tests/test_thin_conv_gpu.py) */
+void lf_debug_set_thin(int mode, int nt);
+/* launches that kernel took since the process started */
+long lf_debug_thin_launches(void);
+/* fold-and-pack launches (lf_fold_pack_launch: the inference engine's per-call fold, lf_erfnet_infer_fold, the --clas heads' chains)
+ * since the process started */
+long lf_debug_fold_pack_launches(void);
 int lf_debug_conv1d_wgrad_phases(const float* x, const float* gy, int N, int H, int W, int C, int axis, int dilation,
                                  float* scratch, unsigned long long* dbg, void* stream);
 #ifdef __cplusplus

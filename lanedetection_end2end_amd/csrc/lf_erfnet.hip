@@ -1211,6 +1211,7 @@ struct InferCtx {
     InferLayout L;
     int mode, s16;
     hipStream_t st;
+    int thin = 0;       // LF_INFER_THIN: every infer_gemm of the call carries LfTapArgs::thin
     float* vec(int fi, int which = 0) const {     // folded bias (which = 0) / scale (0) and shift (1) of a vector-only entry
         return reinterpret_cast<float*>(ws + L.vec) + P->fold_src[fi].out_off + (which ? P->fold[fi].C : 0);
     }
@@ -1219,7 +1220,7 @@ struct InferCtx {
 int infer_gemm(const InferCtx& c, const GemmOp& op, int fi, const float* src, float* dst, int epi, const float* add) {
     const LfPackEntry& e = c.P->fold[fi].pk;
     LfTapArgs a = lf_no_args();
-    a.src = src; a.dst = dst; a.bias = c.vec(fi); a.add_src = add; a.s16 = c.s16;
+    a.src = src; a.dst = dst; a.bias = c.vec(fi); a.add_src = add; a.s16 = c.s16; a.thin = c.thin;
     if (c.L.a32 >= 0) a.wp = reinterpret_cast<const float*>(c.ws + c.L.a32) + e.dst_off;
     if (c.L.a16 >= 0) a.wp16 = reinterpret_cast<const unsigned short*>(c.ws + c.L.a16) + e.dst16_off;
     if (c.L.a48 >= 0) {
@@ -1317,10 +1318,14 @@ int lf_erfnet_infer(const lf_erfnet_plan* P, const float* img, const float* cons
 // ---------------------------------------------------------------------------------------
 namespace {
 
-int infer_begin(InferCtx& c, const lf_erfnet_plan* P, void* workspace, const float* const* params_host, const float* const* params_dev,
-                float* const* running_host, void* stream) {
+// the call's context over a workspace; nothing is launched (a workspace lf_erfnet_infer_fold has filled needs no more)
+void infer_open(InferCtx& c, const lf_erfnet_plan* P, void* workspace, void* stream) {
     c.P = P; c.ws = (char*)workspace; c.mode = P->precision; c.s16 = P->precision == 2; c.st = (hipStream_t)stream;
     c.L = infer_layout(P, c.mode);
+}
+int infer_begin(InferCtx& c, const lf_erfnet_plan* P, void* workspace, const float* const* params_host, const float* const* params_dev,
+                float* const* running_host, void* stream) {
+    infer_open(c, P, workspace, stream);
     LF_TRY(infer_fold_table(P, c.ws, c.L, params_host, running_host, c.st));
     return lf_fold_pack_launch(reinterpret_cast<const LfFoldEntry*>(c.ws + c.L.table), (int)P->fold.size(), params_dev, BN_EPS,
                                reinterpret_cast<float*>(c.ws + c.L.vec), c.L.a32 >= 0 ? reinterpret_cast<float*>(c.ws + c.L.a32) : nullptr,
@@ -1337,6 +1342,45 @@ LaneLayout lane_layout(const lf_erfnet_plan* P, int mode, int K, int order) {
     L.zinv = cur; cur += al((long)P->N * K * (order + 1) * (order + 1) * (long)sizeof(double));
     L.total = cur;
     return L;
+}
+
+// The schedule of lf_lane_infer (fold = true: the per-call fold-table upload and fold-and-pack launch first) and of
+// lf_lane_infer_folded (fold = false: the workspace holds what lf_erfnet_infer_fold wrote; flags: LF_INFER_*) -- one body.
+int lane_infer_run(const char* who, bool fold, int flags, const lf_erfnet_plan* P, const float* img, const float* const* params_host,
+                   const float* const* params_dev, float* const* running_host, const float* grid_xy, long grid_batch_stride,
+                   int zero_rows, int order, double reg_ls, double y_offset, int act_kind, int use_cholesky, float* logits_or_null,
+                   double* beta, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    const int K = P->Cout;
+    const LaneLayout LL = lane_layout(P, P->precision, K, order);
+    LF_REQUIRE(workspace_bytes >= (size_t)LL.total, "%s: workspace too small (%zu < %ld)", who, workspace_bytes, LL.total);
+    InferCtx c;
+    if (fold) LF_TRY(infer_begin(c, P, workspace, params_host, params_dev, running_host, stream));
+    else infer_open(c, P, workspace, stream);
+    c.thin = (flags & LF_INFER_THIN) != 0;
+    float* last = nullptr;
+    LF_TRY(forward_infer(c, img, params_host, (int)P->layers.size(), &last));
+    return lf_head_fit(last, c.s16, params_host[P->p_head_w[0]], params_host[P->p_head_b[0]], grid_xy, grid_batch_stride, P->N,
+                       P->H / 2, P->W / 2, K, zero_rows, order, reg_ls, y_offset, act_kind,
+                       use_cholesky ? LF_SOLVE_CHOLESKY : LF_SOLVE_LU, logits_or_null, beta,
+                       reinterpret_cast<double*>(c.ws + LL.zinv), c.ws + LL.partials, status, stream);
+}
+// ... and of lf_lane_infer_seg / lf_lane_infer_seg_folded
+int lane_infer_seg_run(const char* who, bool fold, int flags, const lf_erfnet_plan* P, const float* img, const float* const* params_host,
+                       const float* const* params_dev, float* const* running_host, const float* grid_xy, long grid_batch_stride,
+                       const float* gt_line_or_null, int L, int zero_rows, int order, double reg_ls, double y_offset, int use_cholesky,
+                       uint8_t* classes_or_null, double* beta, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    const LaneLayout LL = lane_layout(P, P->precision, L, order);
+    LF_REQUIRE(workspace_bytes >= (size_t)LL.total, "%s: workspace too small (%zu < %ld)", who, workspace_bytes, LL.total);
+    InferCtx c;
+    if (fold) LF_TRY(infer_begin(c, P, workspace, params_host, params_dev, running_host, stream));
+    else infer_open(c, P, workspace, stream);
+    c.thin = (flags & LF_INFER_THIN) != 0;
+    float* last = nullptr;
+    LF_TRY(forward_infer(c, img, params_host, (int)P->layers.size(), &last));
+    return lf_head_fit_seg(last, c.s16, params_host[P->p_head_w[0]], params_host[P->p_head_b[0]], grid_xy, grid_batch_stride,
+                           gt_line_or_null, P->N, P->H / 2, P->W / 2, P->Cout, L, zero_rows, order, reg_ls, y_offset,
+                           use_cholesky ? LF_SOLVE_CHOLESKY : LF_SOLVE_LU, classes_or_null, beta,
+                           reinterpret_cast<double*>(c.ws + LL.zinv), c.ws + LL.partials, status, stream);
 }
 
 }  // namespace
@@ -1393,17 +1437,9 @@ int lf_lane_infer(const lf_erfnet_plan* P, const float* img, const float* const*
     LF_REQUIRE(P && img && params_host && params_dev && running_host && grid_xy && beta && status && workspace,
                "lf_lane_infer: null pointer");
     LF_REQUIRE(order >= 0 && order <= 3, "lf_lane_infer: order %d not in 0..3", order);
-    const int K = P->Cout;
-    const LaneLayout LL = lane_layout(P, P->precision, K, order);
-    LF_REQUIRE(workspace_bytes >= (size_t)LL.total, "lf_lane_infer: workspace too small (%zu < %ld)", workspace_bytes, LL.total);
-    InferCtx c;
-    LF_TRY(infer_begin(c, P, workspace, params_host, params_dev, running_host, stream));
-    float* last = nullptr;
-    LF_TRY(forward_infer(c, img, params_host, (int)P->layers.size(), &last));
-    return lf_head_fit(last, c.s16, params_host[P->p_head_w[0]], params_host[P->p_head_b[0]], grid_xy, grid_batch_stride, P->N,
-                       P->H / 2, P->W / 2, K, zero_rows, order, reg_ls, y_offset, act_kind,
-                       use_cholesky ? LF_SOLVE_CHOLESKY : LF_SOLVE_LU, logits_or_null, beta,
-                       reinterpret_cast<double*>(c.ws + LL.zinv), c.ws + LL.partials, status, stream);
+    return lane_infer_run("lf_lane_infer", true, 0, P, img, params_host, params_dev, running_host, grid_xy, grid_batch_stride, zero_rows,
+                          order, reg_ls, y_offset, act_kind, use_cholesky, logits_or_null, beta, status, workspace, workspace_bytes,
+                          stream);
 }
 
 // The same for a segmentation-mode model (out_channels = classes, background first): image -> the L lane polynomials of the arg-max
@@ -1420,16 +1456,52 @@ int lf_lane_infer_seg(const lf_erfnet_plan* P, const float* img, const float* co
     LF_REQUIRE(P && img && params_host && params_dev && running_host && grid_xy && beta && status && workspace,
                "lf_lane_infer_seg: null pointer");
     LF_REQUIRE(order >= 0 && order <= 3 && L >= 1 && L <= 4, "lf_lane_infer_seg: order %d not in 0..3 or L = %d not in 1..4", order, L);
-    const LaneLayout LL = lane_layout(P, P->precision, L, order);
-    LF_REQUIRE(workspace_bytes >= (size_t)LL.total, "lf_lane_infer_seg: workspace too small (%zu < %ld)", workspace_bytes, LL.total);
+    return lane_infer_seg_run("lf_lane_infer_seg", true, 0, P, img, params_host, params_dev, running_host, grid_xy, grid_batch_stride,
+                              gt_line_or_null, L, zero_rows, order, reg_ls, y_offset, use_cholesky, classes_or_null, beta, status,
+                              workspace, workspace_bytes, stream);
+}
+
+// The frozen detector's entries: the fold done ONCE into a persistent workspace, then calls that upload nothing and fold nothing.
+// lf_erfnet_infer_fold: the fold-table upload and the one fold-and-pack launch of the calls above, in the plan's current precision
+// mode, into a workspace laid out by infer_layout -- the common prefix of lf_erfnet_infer_workspace_bytes,
+// lf_lane_infer_workspace_bytes and lf_lane_infer_seg_workspace_bytes.  What it read (weights, running statistics) and the plan's
+// precision mode must stay as they were until the next fold.
+int lf_erfnet_infer_fold(const lf_erfnet_plan* P, const float* const* params_host, const float* const* params_dev,
+                         float* const* running_host, void* workspace, size_t workspace_bytes, void* stream) {
+    LF_REQUIRE(P && params_host && params_dev && running_host && workspace, "lf_erfnet_infer_fold: null pointer");
+    const long need = infer_layout(P, P->precision).total;
+    LF_REQUIRE(workspace_bytes >= (size_t)need, "lf_erfnet_infer_fold: workspace too small (%zu < %ld)", workspace_bytes, need);
     InferCtx c;
-    LF_TRY(infer_begin(c, P, workspace, params_host, params_dev, running_host, stream));
-    float* last = nullptr;
-    LF_TRY(forward_infer(c, img, params_host, (int)P->layers.size(), &last));
-    return lf_head_fit_seg(last, c.s16, params_host[P->p_head_w[0]], params_host[P->p_head_b[0]], grid_xy, grid_batch_stride,
-                           gt_line_or_null, P->N, P->H / 2, P->W / 2, P->Cout, L, zero_rows, order, reg_ls, y_offset,
-                           use_cholesky ? LF_SOLVE_CHOLESKY : LF_SOLVE_LU, classes_or_null, beta,
-                           reinterpret_cast<double*>(c.ws + LL.zinv), c.ws + LL.partials, status, stream);
+    return infer_begin(c, P, workspace, params_host, params_dev, running_host, stream);
+}
+
+// lf_lane_infer / lf_lane_infer_seg on a workspace lf_erfnet_infer_fold has filled: the same schedule (lane_infer_run), nothing
+// uploaded, nothing folded.  The stem and head kernels read their raw weights from params_host, as in the unfolded calls;
+// params_dev and running_host are not read.  flags: LF_INFER_THIN sets LfTapArgs::thin on every tap-GEMM of the call.
+int lf_lane_infer_folded(const lf_erfnet_plan* P, const float* img, const float* const* params_host, const float* const* params_dev,
+                         float* const* running_host, const float* grid_xy, long grid_batch_stride, int zero_rows, int order,
+                         double reg_ls, double y_offset, int act_kind, int use_cholesky, float* logits_or_null, double* beta,
+                         int32_t* status, void* workspace, size_t workspace_bytes, int flags, void* stream) {
+    LF_REQUIRE(P && img && params_host && grid_xy && beta && status && workspace, "lf_lane_infer_folded: null pointer");
+    LF_REQUIRE(order >= 0 && order <= 3, "lf_lane_infer_folded: order %d not in 0..3", order);
+    LF_REQUIRE((flags & ~LF_INFER_THIN) == 0, "lf_lane_infer_folded: unknown flags %d", flags);
+    return lane_infer_run("lf_lane_infer_folded", false, flags, P, img, params_host, params_dev, running_host, grid_xy,
+                          grid_batch_stride, zero_rows, order, reg_ls, y_offset, act_kind, use_cholesky, logits_or_null, beta, status,
+                          workspace, workspace_bytes, stream);
+}
+
+int lf_lane_infer_seg_folded(const lf_erfnet_plan* P, const float* img, const float* const* params_host, const float* const* params_dev,
+                             float* const* running_host, const float* grid_xy, long grid_batch_stride, const float* gt_line_or_null,
+                             int L, int zero_rows, int order, double reg_ls, double y_offset, int use_cholesky,
+                             uint8_t* classes_or_null, double* beta, int32_t* status, void* workspace, size_t workspace_bytes,
+                             int flags, void* stream) {
+    LF_REQUIRE(P && img && params_host && grid_xy && beta && status && workspace, "lf_lane_infer_seg_folded: null pointer");
+    LF_REQUIRE(order >= 0 && order <= 3 && L >= 1 && L <= 4, "lf_lane_infer_seg_folded: order %d not in 0..3 or L = %d not in 1..4",
+               order, L);
+    LF_REQUIRE((flags & ~LF_INFER_THIN) == 0, "lf_lane_infer_seg_folded: unknown flags %d", flags);
+    return lane_infer_seg_run("lf_lane_infer_seg_folded", false, flags, P, img, params_host, params_dev, running_host, grid_xy,
+                              grid_batch_stride, gt_line_or_null, L, zero_rows, order, reg_ls, y_offset, use_cholesky, classes_or_null,
+                              beta, status, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

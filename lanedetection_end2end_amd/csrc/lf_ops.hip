@@ -116,6 +116,9 @@ void lf_debug_set_fp32_stream(int mode, int max_workgroups) { lf_tapgemm_set_fp3
 void lf_debug_set_bwd16_fused(int mode) { lf_tapbwd16_set(mode); }
 void lf_debug_set_fwd_pair(int mode, int max_workgroups) { lf_tappair_set(mode, max_workgroups); }
 long lf_debug_bias_residual_launches(void) { return lf_tapgemm_bias_residual_launches(); }
+void lf_debug_set_thin(int mode, int nt) { lf_tapgemm_set_thin(mode, nt); }
+long lf_debug_thin_launches(void) { return lf_tapgemm_thin_launches(); }
+long lf_debug_fold_pack_launches(void) { return lf_fold_pack_launches(); }
 long lf_debug_partial_fast_launches(void) { return lf_tapgemm_partial_fast_launches(); }
 
 // same as lf_conv1d_fwd with per-wave phase timestamps: dbg receives 8 uint64 per wave

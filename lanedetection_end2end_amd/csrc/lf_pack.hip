@@ -130,6 +130,8 @@ __global__ __launch_bounds__(256) void fold_pack_kernel(const LfFoldEntry* __res
     }
 }
 
+std::atomic<long> g_fold_pack_launches{0};      // (the backbone's engine and the --clas heads' chains both fold through here)
+
 }  // namespace
 
 int lf_fold_pack_launch(const LfFoldEntry* entries_dev, int nentries, const float* const* params_dev, float eps, float* vec, float* arena,
@@ -139,8 +141,10 @@ int lf_fold_pack_launch(const LfFoldEntry* entries_dev, int nentries, const floa
     hipLaunchKernelGGL(fold_pack_kernel, dim3(nentries, 16), dim3(256), 0, st, entries_dev, params_dev, eps, vec, arena,
                        reinterpret_cast<__bf16*>(arena16), reinterpret_cast<__bf16*>(arena48));
     LF_CHECK_LAUNCH("fold_pack");
+    ++g_fold_pack_launches;
     return 0;
 }
+long lf_fold_pack_launches() { return g_fold_pack_launches.load(); }
 
 int lf_pack_weights_launch(const LfPackEntry* entries_dev, int nentries, const float* const* params_dev, float* arena,
                            hipStream_t st) {

@@ -185,6 +185,12 @@ class _LaneFitNet(nn.Module):
                                "head 0 has no class channels")
         return self._seg_infer(input, None, True, check=False)[1]
 
+    def detector(self, batch=1, height=None, width=None, thin="auto"):
+        """A frozen ``LaneDetector`` of this model for inputs of ``(batch, channels_in, height, width)`` (``height`` / ``width``
+        default to ``resize`` / ``2 * resize``): ``det(frame)`` returns ``detect(frame)``'s results bit for bit with the BatchNorm
+        fold done once, at construction.  Eval mode only.  See ``LaneDetector``."""
+        return LaneDetector(self, batch, self.resize if height is None else height, 2 * self.resize if width is None else width, thin)
+
     def _require_eval_on_device(self, input, what):
         # (the wrapper, the backbone and the heads: four flags, not a walk over ~300 modules on every call)
         parts = (self, self.net) + ((self.line_classification, self.horizon_estimation) if self.classification_branch else ())
@@ -211,6 +217,178 @@ class _LaneFitNet(nn.Module):
         self.last_status = status
         if self.check_singular if check is None else check:
             ops._raise_if_singular(status, 1 if self.use_cholesky else 0)
+        return beta, classes
+
+
+# detector(thin="auto"): the largest batch at which the thin fp32 tap-GEMM route measured faster in-stream than fold-once alone,
+# beyond the min-max ranges of both, at 256 x 512 and at 320 x 640 (profiles/detector_latency.json, key thin_auto_max_batch;
+# tools/detector_latency.py): it won at 1, 2, 4 and 8, and batch 32 has no launch left for it to take.  0 would mean "auto" = off
+THIN_AUTO_MAX_BATCH = 8
+
+
+class LaneDetector:
+    """``model.detector(batch, height, width, thin)``: the model frozen for one input shape -- what a deployment loop calls once
+    per camera frame.  ``det(input, gt_line=None)`` returns ``model.detect(input, gt_line)``'s 6-tuple bit for bit (same dtypes,
+    shapes and ``None``s; ``model.last_status`` and ``det.last_status`` are set, ``model.check_singular`` raises as in ``detect``),
+    ``det.segment(input)`` returns ``model.segment(input)``'s class map for a segmentation-mode model.
+
+    What is done ONCE, at construction and in ``refresh()``, instead of on every call: the engine plan and its precision mode
+    (``model.net.precision`` at that time; the detector owns its plan), ONE persistent workspace with every BatchNorm folded into
+    the convolution that feeds it (``lf_erfnet_infer_fold``: the fold-table upload and the fold-and-pack launch), the parameter
+    and running-buffer pointer tables, and the grid table (the constant grid, or the ``lf_theta_grid`` table of a homography set
+    with ``set_homography``).  A call validates the input's shape, allocates ``beta`` and ``status`` and makes one C call
+    (``lf_lane_infer_folded``; segmentation-mode models: ``lf_lane_infer_seg_folded`` at every batch size, the bits of
+    ``detect``'s three-step path at batch 1 too).  The ``--clas`` heads run as in ``detect``, on the encoder output inside the
+    detector's workspace; their own per-call fold stays.
+
+    ``refresh()`` MUST be called after any change of a parameter, a running statistic, the homography or ``model.net.precision``
+    (``load_state_dict``, a training step, ``set_homography``, ``.to()``): nothing is checked per call, and what an un-refreshed
+    detector returns after such a change is NOT DEFINED (stale weights, or pointers to freed memory).
+
+    ``thin``: ``True`` / ``False`` route / do not route the fp32 tap-GEMM launches whose regular grid cannot fill the device to
+    ``tapgemm_thin_kernel`` (one 16-pixel tile per wave; the same bits); ``"auto"``: on in precision mode ``fp32`` for batches up
+    to ``THIN_AUTO_MAX_BATCH``.  The thin kernel exists for fp32 tensors on the fp32 matrix cores only: in ``bf16`` and ``fp32x9``
+    the detector gives fold-once only, whatever ``thin`` says.
+
+    The results of a call live in fresh tensors; the workspace is the detector's, so calls of ONE detector must be issued on one
+    stream (or ordered by the caller).  Detectors of one model are independent of each other and of ``detect``."""
+
+    def __init__(self, model, batch, height, width, thin="auto"):
+        if thin not in (True, False, "auto"):
+            raise ValueError("detector(thin=...) takes True, False or \"auto\"")
+        if not model.end_to_end and model.pretrained:
+            raise RuntimeError("lanefit detector() does not take a pretrained segmentation-mode model (its segmentation head is the "
+                               "decoder's second one, which the one-call path does not run): use detect()")
+        self.model = model
+        self.shape = (int(batch), int(model.net.in_channels), int(height), int(width))
+        self.thin = thin
+        self.last_status = None
+        self._plan = erfnet._Plan(self.shape[0], self.shape[2], self.shape[3], model.net.in_channels, model.net.out_channels,
+                                  2 if model.net.pretrained else 1)
+        self.refresh()
+
+    @torch.no_grad()
+    def refresh(self):
+        """Fold again and rebuild the pointer tables and the grid table: after ANY change of the model's parameters, running
+        statistics, homography or precision mode (see the class docstring: an un-refreshed detector is not defined)."""
+        model, net, lib = self.model, self.model.net, erfnet._lib.load()
+        self._require_eval()
+        N, _, H, W = self.shape
+        self._params = [p.detach() for p in net._ordered_params()]
+        for p in self._params:
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                raise erfnet._lib.LaneFitLibraryError("lanefit detector() needs the model's parameters as contiguous fp32 tensors on "
+                                                      "the MI355X; there is no CPU path")
+        dev = self._params[0].device
+        self._running = net._running_buffers()
+        self._params_host = erfnet._ptr_array(self._params)
+        self._running_host = erfnet._ptr_array(self._running)
+        self._params_dev = torch.tensor([p.data_ptr() for p in self._params], dtype=torch.int64, device=dev)
+        self.precision = net.precision
+        self._mode = erfnet._PRECISIONS[self.precision]
+        erfnet._lib.check(lib.lf_erfnet_set_precision(self._plan.handle, self._mode), "lf_erfnet_set_precision")
+        self._seg = not model.end_to_end
+        self._lanes = 2 if model.nclasses < 3 else 4
+        self._order = int(model.order)
+        if self._seg:
+            self._nbytes = lib.lf_lane_infer_seg_workspace_bytes(self._plan.handle, self._mode, self._lanes, self._order)
+        else:
+            self._nbytes = lib.lf_lane_infer_workspace_bytes(self._plan.handle, self._mode, net.out_channels, self._order)
+        if self._nbytes == 0:
+            raise erfnet._lib.LaneFitLibraryError("lanefit detector(): unsupported mode / lanes / order (%s, %d)"
+                                                  % (self.precision, self._order))
+        ws = self.__dict__.get("_ws")
+        if ws is None or ws.numel() != self._nbytes or ws.device != dev:
+            self._ws = torch.empty(self._nbytes, dtype=torch.uint8, device=dev)
+        erfnet._lib.check(lib.lf_erfnet_infer_fold(self._plan.handle, self._params_host, erfnet._lib.ptr(self._params_dev),
+                                                   self._running_host, erfnet._lib.ptr(self._ws), self._nbytes,
+                                                   erfnet._lib.stream()), "lf_erfnet_infer_fold")
+        # the grid table of the fused head + fit kernel: the constant grid, or the per-image grid of the homography (_detect_grid)
+        if model._homography() is None:
+            grid = model.grid_on(dev)
+        else:
+            grid = ops.theta_grid(model._geometry(dev)["theta"], H, W, model.normalised).detach()
+        grid = grid.contiguous()
+        if grid.dtype != torch.float32 or tuple(grid.shape[-2:]) != (H * W, 2):
+            raise ValueError("lanefit detector(): the model's grid is %s, the detector's shape needs (%d, 2)"
+                             % (tuple(grid.shape), H * W))
+        self._grid = grid
+        self._gstride = H * W * 2 if grid.dim() == 3 and grid.shape[0] > 1 else 0      # (as ops.WLSFit)
+        self._reg = 0.0 if (model.use_cholesky and model.cholesky_drops_reg) else float(model.reg_ls)
+        self._zero_rows, self._y_offset = int(model.zero_rows), float(model.y_offset)
+        self._act, self._chol = int(ops.ACT_KINDS[model.activation_name]), int(bool(model.use_cholesky))
+        thin_on = self.thin is True or (self.thin == "auto" and N <= THIN_AUTO_MAX_BATCH)
+        self._flags = 1 if (thin_on and self.precision == "fp32") else 0          # LF_INFER_THIN
+        self._enc = None
+        if model.classification_branch and not self._seg:
+            # logical NCHW, channels-last memory (as Net.forward hands it out): a view of the detector's own workspace
+            self._enc = net._infer_encoder_view(self._plan, self._ws, self._mode).permute(0, 3, 1, 2)
+        self._dev = dev
+        self._ptrs = (erfnet._lib.ptr(self._params_dev), erfnet._lib.ptr(self._grid), erfnet._lib.ptr(self._ws))
+
+    def _require_eval(self):
+        model = self.model
+        parts = (model, model.net) + ((model.line_classification, model.horizon_estimation) if model.classification_branch else ())
+        if any(m.training for m in parts):
+            raise RuntimeError("lanefit detector() needs the model, its backbone and its heads in eval mode (model.eval()): it folds "
+                               "the BatchNorm running statistics into the convolutions")
+
+    def _input(self, input):
+        self._require_eval()
+        if tuple(input.shape) != self.shape:
+            raise ValueError("this detector was built for inputs of shape %s, got %s" % (self.shape, tuple(input.shape)))
+        if not input.is_cuda:
+            raise erfnet._lib.LaneFitLibraryError("lanefit detector needs its input on the MI355X; there is no CPU path")
+        if input.dtype != torch.float32 or not input.is_contiguous():
+            input = input.contiguous().float()
+        return input
+
+    def _finish(self, status, check):
+        self.last_status = self.model.last_status = status
+        if check:
+            ops._raise_if_singular(status, self._chol)
+
+    @torch.no_grad()
+    def __call__(self, input, gt_line=None):
+        x = self._input(input)
+        model, lib, N = self.model, erfnet._lib.load(), self.shape[0]
+        params_dev, grid, ws = self._ptrs
+        if self._seg:
+            beta, _ = self._seg_call(x, ops.seg_flags(gt_line, N, self._lanes, self._dev), False, model.check_singular)
+            return fit.split_lanes(beta, model.nclasses, model.beta_dtype) + (None, None)
+        K = model.net.out_channels
+        beta = torch.empty(N, K, self._order + 1, dtype=torch.float64, device=self._dev)
+        status = torch.empty(N * K, dtype=torch.int32, device=self._dev)
+        erfnet._lib.check(lib.lf_lane_infer_folded(self._plan.handle, x.data_ptr(), self._params_host, params_dev, self._running_host,
+                                                   grid, self._gstride, self._zero_rows, self._order, self._reg, self._y_offset,
+                                                   self._act, self._chol, None, beta.data_ptr(), status.data_ptr(), ws, self._nbytes,
+                                                   self._flags, erfnet._lib.stream()), "lf_lane_infer_folded")
+        self._finish(status, model.check_singular)
+        line = horizon = None
+        if self._enc is not None:
+            line, horizon = model.line_classification(self._enc, folded=True), model.horizon_estimation(self._enc, folded=True)
+        return fit.split_lanes(beta, model.nclasses, model.beta_dtype) + (line, horizon)
+
+    @torch.no_grad()
+    def segment(self, input):
+        """``model.segment(input)``: the (N, H, W) uint8 arg-max class map of a segmentation-mode model, from the folded call."""
+        if not self._seg:
+            raise RuntimeError("lanefit segment() is for segmentation-mode models (end_to_end=False, not pretrained): this model's "
+                               "head 0 has no class channels")
+        return self._seg_call(self._input(input), None, True, False)[1]
+
+    def _seg_call(self, x, flags, want_classes, check):
+        lib, (N, _, H, W) = erfnet._lib.load(), self.shape
+        params_dev, grid, ws = self._ptrs
+        beta = torch.empty(N, self._lanes, self._order + 1, dtype=torch.float64, device=self._dev)
+        status = torch.empty(N * self._lanes, dtype=torch.int32, device=self._dev)
+        classes = torch.empty(N, H, W, dtype=torch.uint8, device=self._dev) if want_classes else None
+        erfnet._lib.check(lib.lf_lane_infer_seg_folded(self._plan.handle, x.data_ptr(), self._params_host, params_dev,
+                                                       self._running_host, grid, self._gstride, erfnet._lib.ptr(flags), self._lanes,
+                                                       self._zero_rows, self._order, self._reg, self._y_offset, self._chol,
+                                                       erfnet._lib.ptr(classes), beta.data_ptr(), status.data_ptr(), ws,
+                                                       self._nbytes, self._flags, erfnet._lib.stream()), "lf_lane_infer_seg_folded")
+        self._finish(status, check)
         return beta, classes
 
 

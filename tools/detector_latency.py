@@ -1,0 +1,207 @@
+"""Latency of one call, image -> lane coefficients, at small batch: ``model.detect`` against the frozen detector.
+
+    python tools/detector_latency.py [--out profiles/detector_latency.json] [--batches 1,2,4,8,32] [--configs bev,bp] [--precisions fp32,bf16]
+
+Three paths alternated in one process: (A) ``model.detect`` (the fold on every call), (B) ``model.detector(thin=False)`` (fold
+once), (C) ``model.detector(thin=True)`` (fold once + the thin fp32 tap-GEMM route; precision mode fp32 only).  Geometries: BEV
+2 lanes 256 x 512 and BP 4 lanes order 3 320 x 640, each in fp32 (A, B, C) and in bf16 (A, B).  ``check_singular`` is off on every
+path (its status read would synchronise every call).  Protocol: per repeat and path --warmup untimed calls, then --calls
+back-to-back calls between two in-stream events and two host clock reads, the second behind one final synchronise; --repeats
+repeats; reported: median and min-max of both times per call (ms).  Where the host issues slower than the device runs, the two
+agree and the host is the limit.  ``thin_auto_max_batch``: the largest batch among 1, 2, 4, 8 at which (C)'s in-stream time is below
+(B)'s beyond the min-max ranges of both, in every fp32 geometry measured (0: nowhere) -- lsq.THIN_AUTO_MAX_BATCH.
+
+    rocprofv3 --kernel-trace --stats -d DIR -o trace -- python tools/detector_latency.py --trace A|C
+    python tools/detector_latency.py --launches DB_A DB_C [--out profiles/detector_launches.md]
+
+The launch table: ten batch-1 calls at 1 x 256 x 512 fp32 of path (A) / (C) under the profiler (no counters), then per-kernel count
+and duration of the two runs side by side from their rocpd databases.
+"""
+import argparse
+import json
+import os
+import re
+import statistics
+import subprocess
+import sys
+import time
+from argparse import Namespace
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+CONFIGS = {
+    "bev": dict(name="bev_2lanes_256x512", tree="bev", K=2, order=2, H=256, W=512, mask=0.3),
+    "bp": dict(name="bp_4lanes_order3_320x640", tree="bp", K=4, order=3, H=320, W=640, mask=0.2),
+}
+
+
+def commit_stamp():
+    """The commit the tree is at, as the other profiles carry it: .git_head (tools/stamp_head.sh; where there is no .git) or git."""
+    try:
+        return open(os.path.join(ROOT, ".git_head")).read().strip()
+    except OSError:
+        pass
+    try:
+        return subprocess.check_output(["git", "rev-parse", "HEAD"], cwd=ROOT, text=True).strip()
+    except Exception:
+        return "unknown"
+
+
+def make_model(cfg, precision, N):
+    import torch
+    from oracle import erfnet_oracle
+    if cfg["tree"] == "bev":
+        from lanedetection_end2end_amd.bev.Networks.LSQ_layer import Net
+    else:
+        from lanedetection_end2end_amd.bp.Networks.LSQ_layer import Net
+    args = Namespace(batch_size=N, nclasses=cfg["K"], resize=cfg["H"], end_to_end=True, mod="erfnet", layers=18, channels_in=3,
+                     pretrained=False, pool=True, activation_layer="square", no_cuda=False, order=cfg["order"], reg_ls=0.0,
+                     use_cholesky=False, mask_percentage=cfg["mask"], clas=False, no_mapping=False, loss_policy="backproject",
+                     weight_seg=30, weight_funct="none", precision=precision)
+    model = Net(args)
+    model.net.load_state_dict(erfnet_oracle.make_params(seed=3, out_channels=cfg["K"]))
+    g = torch.Generator().manual_seed(5)
+    with torch.no_grad():           # non-trivial running statistics (the cost does not depend on them)
+        for m in model.net.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.running_mean.copy_(torch.rand(m.num_features, generator=g) - 0.5)
+                m.running_var.copy_(torch.rand(m.num_features, generator=g) + 0.5)
+    model = model.cuda().eval()
+    model.check_singular = False
+    return model
+
+
+def timed(fn, x, calls):
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    a.record()
+    for _ in range(calls):
+        fn(x)
+    b.record()
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    return a.elapsed_time(b) / calls, (t1 - t0) * 1e3 / calls
+
+
+def stats(v):
+    return {"median": round(statistics.median(v), 5), "min": round(min(v), 5), "max": round(max(v), 5)}
+
+
+def measure(cfg, precision, N, warmup, calls, repeats):
+    import torch
+    from oracle import inputs
+    model = make_model(cfg, precision, N)
+    x = torch.from_numpy(inputs.images(N, cfg["H"], cfg["W"], seed=1)).cuda()
+    paths = {"A_detect": model.detect, "B_detector": model.detector(batch=N, height=cfg["H"], width=cfg["W"], thin=False)}
+    if precision == "fp32":
+        paths["C_detector_thin"] = model.detector(batch=N, height=cfg["H"], width=cfg["W"], thin=True)
+    ref = model.detect(x)
+    for name, fn in paths.items():      # the three paths give the same bits
+        got = fn(x)
+        assert all((u is None and v is None) or torch.equal(u, v) for u, v in zip(got, ref)), name
+    ev = {k: [] for k in paths}
+    wall = {k: [] for k in paths}
+    for _ in range(repeats):
+        for name, fn in paths.items():      # alternated: every path sees the same clocks and neighbours
+            for _ in range(warmup):
+                fn(x)
+            e, w = timed(fn, x, calls)
+            ev[name].append(e)
+            wall[name].append(w)
+    row = {"config": cfg["name"], "precision": precision, "batch": N}
+    for name in paths:
+        row[name] = {"in_stream_ms": stats(ev[name]), "wall_ms": stats(wall[name])}
+    if "C_detector_thin" in paths:
+        row["thin_wins"] = row["C_detector_thin"]["in_stream_ms"]["max"] < row["B_detector"]["in_stream_ms"]["min"]
+    del model, paths, x
+    torch.cuda.empty_cache()
+    return row
+
+
+def run(args):
+    import torch
+    rows = []
+    for key in args.configs.split(","):
+        for precision in args.precisions.split(","):
+            for N in [int(b) for b in args.batches.split(",")]:
+                rows.append(measure(CONFIGS[key], precision, N, args.warmup, args.calls, args.repeats))
+                print(json.dumps(rows[-1]), flush=True)
+    bound = 0
+    for N in (1, 2, 4, 8):
+        at = [r for r in rows if r["precision"] == "fp32" and r["batch"] == N]
+        if at and all(r["thin_wins"] for r in at):
+            bound = N
+    res = {"tool": "detector_latency", "commit": commit_stamp(), "device": torch.cuda.get_device_name(0), "warmup": args.warmup,
+           "calls": args.calls, "repeats": args.repeats, "check_singular": False, "thin_auto_max_batch": bound, "results": rows}
+    with open(args.out or os.path.join(ROOT, "profiles", "detector_latency.json"), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"thin_auto_max_batch": bound}))
+
+
+def trace(path):
+    """ten batch-1 calls of one path at 1 x 256 x 512 fp32 (run under rocprofv3 --kernel-trace --stats)"""
+    import torch
+    from oracle import inputs
+    cfg = CONFIGS["bev"]
+    model = make_model(cfg, "fp32", 1)
+    x = torch.from_numpy(inputs.images(1, cfg["H"], cfg["W"], seed=1)).cuda()
+    fn = model.detect if path == "A" else model.detector(thin=True)
+    for _ in range(10):
+        fn(x)
+    torch.cuda.synchronize()
+
+
+def launches(db_a, db_c, out):
+    import sqlite3
+
+    def table(path):
+        cur = sqlite3.connect(path).cursor()
+        cols = [r[1] for r in cur.execute("pragma table_info(kernels)")]
+        name_col = "name" if "name" in cols else [c for c in cols if "name" in c][0]
+        agg = {}
+        for n, s, e in cur.execute("select %s, start, end from kernels" % name_col).fetchall():
+            k = re.sub(r"\(.*$", "", re.sub(r"\(anonymous namespace\)::", "", n)).replace("void ", "")[:80]
+            a = agg.setdefault(k, [0, 0])
+            a[0] += 1
+            a[1] += e - s
+        return agg
+    ta, tc = table(db_a), table(db_c)
+    lines = ["# Launches of ten single-frame calls, 1 x 3 x 256 x 512, fp32", "",
+             "commit: `%s`" % commit_stamp(), "",
+             "`rocprofv3 --kernel-trace --stats` (no counters) of one process each: the model's set-up, then ten calls of (A) `model.detect`",
+             "/ (C) `model.detector(thin=True)`; the first call carries first-launch costs.  Per kernel: launches and summed duration (us)",
+             "over the whole process (torch's set-up kernels included), sorted by (A)'s time.", "",
+             "| kernel | (A) launches | (A) us | (C) launches | (C) us |", "|---|---:|---:|---:|---:|"]
+    for k in sorted(set(ta) | set(tc), key=lambda k: -(ta.get(k, [0, 0])[1] + tc.get(k, [0, 0])[1])):
+        a, c = ta.get(k, [0, 0]), tc.get(k, [0, 0])
+        lines.append("| `%s` | %d | %.1f | %d | %.1f |" % (k, a[0], a[1] / 1e3, c[0], c[1] / 1e3))
+    lines += ["", "total: (A) %d launches, %.1f us; (C) %d launches, %.1f us" %
+              (sum(v[0] for v in ta.values()), sum(v[1] for v in ta.values()) / 1e3,
+               sum(v[0] for v in tc.values()), sum(v[1] for v in tc.values()) / 1e3), ""]
+    with open(out or os.path.join(ROOT, "profiles", "detector_launches.md"), "w") as f:
+        f.write("\n".join(lines))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--configs", default="bev,bp")
+    ap.add_argument("--precisions", default="fp32,bf16")
+    ap.add_argument("--batches", default="1,2,4,8,32")
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--trace", choices=["A", "C"])
+    ap.add_argument("--launches", nargs=2, metavar=("DB_A", "DB_C"))
+    args = ap.parse_args()
+    if args.trace:
+        trace(args.trace)
+    elif args.launches:
+        launches(args.launches[0], args.launches[1], args.out)
+    else:
+        run(args)
