@@ -427,6 +427,14 @@ int lf_rmsprop_step_clipped(const void* tensors_dev, const void* work_dev, int n
  * parameters, running statistics and parameter gradients stay fp32.  lf_convchain_workspace_bytes follows the mode the plan
  * is set to; lf_convchain_workspace_bytes_for(plan, mode) names it (0 bytes for a mode other than 0 and 2), and a workspace
  * sized for mode 2 serves mode 0 too.
+ * Limits of lf_convchain_backward (lf_convchain_plan_create, _forward and _infer take every multiple of 16 and every W; the backward
+ * call then returns < 0 with lf_last_error set, having written no parameter gradient of the refused block or of any block below
+ * it, and the plan and its workspace stay usable for further forward calls):
+ *   - the weight gradient is compiled for (C_in, C_out) channel pairs in which each side is a multiple of 64, 16 or 48 -- a side of
+ *     32, 80, 96, ... that is no multiple of 64 is refused, and so is the pair (48, 48);
+ *   - W must be a multiple of 4;
+ *   - the LAST block's channel count must be a power of two (its BatchNorm backward reduces whole pixels per lane group;
+ *     with any other count the call fails before it writes anything).
  * ---------------------------------------------------------------------------------- */
 typedef struct lf_convchain_plan lf_convchain_plan;
 lf_convchain_plan* lf_convchain_plan_create(int N, int H, int W, int nlayers, const int* channels_host,

@@ -187,6 +187,7 @@ def _declare(lib):
         "lf_debug_stem_fwd": (I, [P, I, I, I, I, P, P, P, P, P, P, I, I, P]),
         "lf_debug_head_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
         "lf_debug_head_bwd_data": (I, [P, P, P, I, I, I, I, I, P]),
+        "lf_debug_convchain_offset": (L, [P, I, I]),
     }
     for table in (sig, dbg):
         for name, (res, args) in table.items():

@@ -238,7 +238,10 @@ __device__ __forceinline__ void groups_at(unsigned G0, int Hl, unsigned GR, unsi
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         o.ok[m] = G0 + m < ngroups;
-        o.n[m] = n; o.i[m] = i; o.j[m] = jg * 16;
+        // a group past the last pixel takes the position of group 0 (tapgemm_bf16_kernel's `q = pv ? p : 0`): nothing of it is stored or
+        // summed, but the epilogues still LOAD its operand tensors -- past the tensor's end otherwise, and 0 * (a NaN found there) is a
+        // NaN in the BN-backward sum of the tile (tests/test_convchain_shapes_gpu.py: 800 pixels, three and an eighth tiles)
+        o.n[m] = o.ok[m] ? n : 0; o.i[m] = o.ok[m] ? i : 0; o.j[m] = o.ok[m] ? jg * 16 : 0;
         if (++jg == (int)GR) { jg = 0; if (++i == Hl) { i = 0; ++n; } }
     }
 }

@@ -221,6 +221,12 @@ lf_convchain_plan* lf_convchain_plan_create(int N, int H, int W, int nlayers, co
 }
 
 void lf_convchain_plan_destroy(lf_convchain_plan* P) { delete P; }
+// test hook (csrc/lf_debug.h): float offset of a block's saved region in the training workspace
+long lf_debug_convchain_offset(const lf_convchain_plan* P, int block, int which) {
+    if (!P || block < 0 || block >= P->L || which < 0 || which > 4) return -1;
+    const long* region[5] = {P->z, P->sc, P->sh, P->asc, P->ash};
+    return region[which][block];
+}
 // follows the precision mode: call it after lf_convchain_set_precision
 size_t lf_convchain_workspace_bytes(const lf_convchain_plan* P) {
     return (size_t)(P->precision == 2 ? P->total16_floats : P->total_floats) * sizeof(float);

@@ -209,6 +209,12 @@ long lf_debug_thin_launches(void);
 long lf_debug_fold_pack_launches(void);
 int lf_debug_conv1d_wgrad_phases(const float* x, const float* gy, int N, int H, int W, int C, int axis, int dilation,
                                  float* scratch, unsigned long long* dbg, void* stream);
+/* where lf_convchain_forward leaves block `block`'s saved state in its training workspace, as a FLOAT offset (the same in both
+ * precision modes: in mode 2 the region of z holds bf16 elements from that offset on): which 0 = z, the pre-BatchNorm tensor
+ * (N,H,W,C_block+1) NHWC; 1 = sc, 2 = sh (the folded scale and shift the next block's prologue and the ReLU masks use); 3 = asc (rstd),
+ * 4 = ash (-mean * rstd) -- [C] fp32 each.  -1 for a null plan or a block / which out of range.  (tests/test_convchain_shapes_gpu.py) */
+struct lf_convchain_plan;
+long lf_debug_convchain_offset(const struct lf_convchain_plan* plan, int block, int which);
 #ifdef __cplusplus
 }
 #endif

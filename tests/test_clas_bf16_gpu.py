@@ -162,7 +162,7 @@ def test_trunk_bf16_against_fp64(tree):
         xt = x.cuda().permute(0, 2, 3, 1).contiguous().to(torch.bfloat16).permute(0, 3, 1, 2).requires_grad_(True)
         y = m.trunk(xt)
         assert y.dtype == torch.bfloat16 and y.shape == (x.shape[0], 32, 64, 64)
-        state = _chain_state(y.grad_fn.ws, N, H, W, m._channels)
+        state = _chain_state(y.grad_fn.ws, N, H, W, m._channels, m._plans[(N, H, W)])
         (y.float() * g.cuda()).sum().backward()
         assert xt.grad.dtype == torch.bfloat16
         with torch.no_grad():
@@ -190,18 +190,19 @@ def test_trunk_bf16_against_fp64(tree):
             assert int(sd["conv4_bn.num_batches_tracked"]) == 1
 
 
-def _chain_state(ws, N, H, W, channels):
-    """The conv chain's saved forward state in its workspace (lf_convchain.hip, lf_convchain_plan_create's layout: per block the
-    pre-BN tensor z, then the folded BatchNorm scale, shift and four more per-channel vectors, each region rounded up to 64
-    floats): per block (z as stored -- bf16 in mode 2 --, scale, shift) in fp64."""
-    r64 = lambda n: (n + 63) // 64 * 64
-    npix, off, out = N * H * W, 0, []
-    for co in channels[1:]:
-        z = ws.view(torch.bfloat16)[2 * off: 2 * off + npix * co].view(N, H, W, co).permute(0, 3, 1, 2).double().cpu()
-        off += r64(npix * co)
-        sc = ws.view(torch.float32)[off: off + co].double().cpu()
-        sh = ws.view(torch.float32)[off + r64(co): off + r64(co) + co].double().cpu()
-        off += 6 * r64(co)
+def _chain_state(ws, N, H, W, channels, plan):
+    """The conv chain's saved forward state in its workspace, found with lf_debug_convchain_offset (csrc/lf_debug.h: float offsets
+    of block i's pre-BN tensor z and of its folded BatchNorm scale and shift): per block (z as stored -- bf16 in mode 2 --, scale,
+    shift) in fp64."""
+    from lanedetection_end2end_amd import _lib
+    lib = _lib.load()
+    npix, out = N * H * W, []
+    for i, co in enumerate(channels[1:]):
+        oz, osc, osh = (lib.lf_debug_convchain_offset(plan.handle, i, which) for which in (0, 1, 2))
+        assert min(oz, osc, osh) >= 0
+        z = ws.view(torch.bfloat16)[2 * oz: 2 * oz + npix * co].view(N, H, W, co).permute(0, 3, 1, 2).double().cpu()
+        sc = ws.view(torch.float32)[osc: osc + co].double().cpu()
+        sh = ws.view(torch.float32)[osh: osh + co].double().cpu()
         out.append((z, sc, sh))
     return out
 
