@@ -172,6 +172,8 @@ def _declare(lib):
         "lf_debug_conv1d_wgrad_pro": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P, P]),
         "lf_debug_bias_residual_launches": (L, []),
         "lf_debug_partial_fast_launches": (L, []),
+        "lf_debug_bf16_ring_launches": (L, []),
+        "lf_debug_set_bf16_max_workgroups": (None, [I]),
         "lf_debug_set_thin": (None, [I, I]),
         "lf_debug_thin_launches": (L, []),
         "lf_debug_fold_pack_launches": (L, []),

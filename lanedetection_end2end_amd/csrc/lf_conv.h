@@ -100,6 +100,8 @@ void lf_tapgemm_set_bf16_lds(int v);
 int lf_tapgemm_bf16_lds();                          // the value set (the 16-channel weight gradient's LDS rings follow it: lf_wgrad.hip)
 void lf_tapgemm_set_bf16_no_partial_fast(int v);   // 1: launches with Cs % 32 != 0 decline the compiled-in whole-step forms (tests)
 long lf_tapgemm_partial_fast_launches();            // launches with Cs % 32 != 0 that took a compiled-in whole-step form since the process started (tests)
+long lf_tapgemm_bf16_ring_launches();               // launches tapgemm_bf16_ring_kernel took since the process started (tests)
+void lf_tapgemm_set_bf16_max_workgroups(int v);     // > 0: caps grid.x of the resident bf16 launches (ring, whole-line, wave-private); 0: shipped (tests)
 
 // ---- lf_wgrad.hip: weight gradients and their split-K reductions (lf_tapwgrad_ro_*: lf_wgrad_ro.hip) ----
 struct LfWgradArgs {

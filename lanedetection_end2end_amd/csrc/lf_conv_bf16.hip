@@ -1216,6 +1216,9 @@ int g_bf16_lds = 4;            // tools / A-B runs only: 4 = wave-private (64 ch
                                // for every launch it takes; 0 = the streaming bf16 kernel only
 std::atomic<long> g_part_fast_launches{0};   // launches with Cs % 32 != 0 that took a compiled-in whole-step form (lf_tapgemm_partial_fast_launches)
 int g_bf16_no_partial_fast = 0; // kernel-level tests only: launches with Cs % 32 != 0 decline the compiled-in whole-step forms of tapgemm_bf16_kernel
+std::atomic<long> g_ring_launches{0};        // launches tapgemm_bf16_ring_kernel took (lf_tapgemm_bf16_ring_launches)
+std::atomic<int> g_bf16_cap{0};              // kernel-level tests only: > 0 caps grid.x of the resident launches below, so that one workgroup
+                                             // walks several items at small shapes; 0 (shipped): launch_resident's own size
 
 }  // namespace
 
@@ -1223,22 +1226,27 @@ void lf_tapgemm_set_bf16_lds(int v) { g_bf16_lds = v; }
 int lf_tapgemm_bf16_lds() { return g_bf16_lds; }
 void lf_tapgemm_set_bf16_no_partial_fast(int v) { g_bf16_no_partial_fast = v; }
 long lf_tapgemm_partial_fast_launches() { return g_part_fast_launches.load(); }
+long lf_tapgemm_bf16_ring_launches() { return g_ring_launches.load(); }
+void lf_tapgemm_set_bf16_max_workgroups(int v) { g_bf16_cap = v > 0 ? v : 0; }
 
 namespace {
 // tapgemm_bf16_ring_kernel: persistent
 template <int EPIV, bool DBGV = false>
 void launch_bf16_ring(unsigned nitems, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
-    launch_resident(tapgemm_bf16_ring_kernel<EPIV, DBGV>, dim3(nitems), 256, (size_t)LB_STAGES * LB_STAGE_BYTES, 0, 0, 0, st, g, a, pro, epi);
+    launch_resident(tapgemm_bf16_ring_kernel<EPIV, DBGV>, dim3(nitems), 256, (size_t)LB_STAGES * LB_STAGE_BYTES, 0, (unsigned)g_bf16_cap.load(), 0, st, g, a,
+                    pro, epi);
+    ++g_ring_launches;
 }
 // false: the runtime refused the kernel's LDS budget on this device (nothing launched: the caller takes the ring / streaming kernel)
 template <int CBV, int EPIV, int PROV = 0>
 bool launch_bf16_wl(unsigned nitems, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
-    return launch_resident(tapgemm_bf16_wl_kernel<CBV, EPIV, PROV>, dim3(nitems), 256, WlCfg<CBV, EPIV, PROV>::LDS, BIG_LDS, 0, 0, st, g, a, pro, epi);
+    return launch_resident(tapgemm_bf16_wl_kernel<CBV, EPIV, PROV>, dim3(nitems), 256, WlCfg<CBV, EPIV, PROV>::LDS, BIG_LDS, (unsigned)g_bf16_cap.load(), 0, st, g, a,
+                           pro, epi);
 }
 // tapgemm_bf16_wv_kernel (64 channels): same contract
 template <int EPIV>
 bool launch_bf16_wv(unsigned ntiles, hipStream_t st, const LfTapGeom& g, const LfTapArgs& a, int pro, int epi) {
-    return launch_resident(tapgemm_bf16_wv_kernel<EPIV>, dim3(ntiles), 256, WvCfg<EPIV>::LDS, BIG_LDS, 0, 0, st, g, a, pro, epi);
+    return launch_resident(tapgemm_bf16_wv_kernel<EPIV>, dim3(ntiles), 256, WvCfg<EPIV>::LDS, BIG_LDS, (unsigned)g_bf16_cap.load(), 0, st, g, a, pro, epi);
 }
 
 // the streaming tapgemm_bf16_kernel (FAST: its whole-step forms, see there); _rt: the run-time-flag form of an output slab width

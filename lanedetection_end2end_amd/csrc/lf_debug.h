@@ -17,6 +17,12 @@ void lf_debug_set_bf16_lds(int v);
 void lf_debug_set_bf16_no_partial_fast(int v);
 /* launches with Cs % 32 != 0 that took one of those compiled-in forms since the process started: which form a launch selected */
 long lf_debug_partial_fast_launches(void);
+/* launches tapgemm_bf16_ring_kernel (the persistent LDS-DMA ring) took since the process started: which bf16 kernel a launch selected */
+long lf_debug_bf16_ring_launches(void);
+/* v > 0 caps grid.x of the resident bf16-tensor launches (ring, whole-line, wave-private kernels), so that one workgroup walks several
+   items -- across tiles and output slabs -- at small shapes; 0 (shipped) leaves every launch as it is.  Capped and uncapped runs agree
+   bit for bit (tests/test_bf16_stride2_kernels_gpu.py, tests/test_bf16_kernels_gpu.py) */
+void lf_debug_set_bf16_max_workgroups(int v);
 /* precision mode of the lf_conv1d_* calls: 0 fp32, 2 bf16 matrix cores on bf16 tensors (x, y, gx, gy, mask_src hold bf16; w, bias,
  * gw, gb stay fp32), 9 fp32 from 9-term split operands (modes 1 and 6 were removed in round 6 and select 0) */
 void lf_debug_set_ops_precision(int mode);

@@ -120,6 +120,8 @@ void lf_debug_set_thin(int mode, int nt) { lf_tapgemm_set_thin(mode, nt); }
 long lf_debug_thin_launches(void) { return lf_tapgemm_thin_launches(); }
 long lf_debug_fold_pack_launches(void) { return lf_fold_pack_launches(); }
 long lf_debug_partial_fast_launches(void) { return lf_tapgemm_partial_fast_launches(); }
+long lf_debug_bf16_ring_launches(void) { return lf_tapgemm_bf16_ring_launches(); }
+void lf_debug_set_bf16_max_workgroups(int v) { lf_tapgemm_set_bf16_max_workgroups(v); }
 
 // same as lf_conv1d_fwd with per-wave phase timestamps: dbg receives 8 uint64 per wave
 // (start, tap table built, main loop done, stores retired); waves = ceil(N*H*W/256)*4*(C/64)

@@ -5,7 +5,9 @@ memory load, not as a failing refcheck.  Every launch of a repeat loop must equa
 K order: the same MFMA sequence per accumulator), forward (+bias, ReLU) and data gradient (+ReLU mask of a staged tensor), at the
 shapes that failed during bring-up: row width 80 (16-pixel groups straddle rows), dilation 8 (a padding tap empties a whole DMA
 instruction: it returns without a memory round trip and overtook pending fragment reads before the lgkmcnt(0) in front of the
-barrier -- 1 launch in 3 wrong), two workgroups per CU with one or two work items each."""
+barrier -- 1 launch in 3 wrong), two workgroups per CU with one or two work items each.  lf_debug_set_bf16_lds selects the kernel;
+lf_debug_set_bf16_max_workgroups(v > 0) caps the grid of the ring, whole-line and wave-private launches, so that one workgroup walks
+several items at a small shape too (0, the shipped value, leaves every launch as it is; the tests restore it)."""
 import ctypes
 
 import pytest
@@ -66,9 +68,19 @@ def test_lds_dma_kernels_equal_the_streaming_kernel_on_every_launch(shape):
                     px = ((y != ref[0]) | (gx != ref[1]) | (yp != ref[2])).reshape(-1, C).any(1).nonzero().flatten()
                     bad.append((it, len(px), int(px[0])))
             assert not bad, "%s kernel, shape %r: launches that differ from the streaming kernel (launch, pixels, first pixel): %r" % (name, shape, bad[:6])
+            # ONE more run with the grid capped to a single workgroup (lf_debug_set_bf16_max_workgroups; 0 is the shipped value, the
+            # product caps at the resident workgroups only): it walks every item of the launch, its ring running across the item
+            # boundaries -- at the smallest shape (one item: the cap must change nothing) and at the smallest with several items
+            if shape in ((2, 64, 8, 16, 0, 1), (5, 64, 12, 32, 0, 2)):
+                lib.lf_debug_set_bf16_max_workgroups(1)
+                y, gx, yp = run(mode)
+                lib.lf_debug_set_bf16_max_workgroups(0)
+                assert torch.equal(y, ref[0]) and torch.equal(gx, ref[1]) and torch.equal(yp, ref[2]), \
+                    "%s kernel, shape %r: one workgroup walking every item differs from the streaming kernel" % (name, shape)
     finally:
         lib.lf_debug_set_ops_precision(0)
         lib.lf_debug_set_bf16_lds(4)
+        lib.lf_debug_set_bf16_max_workgroups(0)
 
 
 @pytest.mark.parametrize("shape", [(64, 64, 80, 160, 1, 1), (64, 64, 80, 160, 0, 1), (16, 128, 40, 80, 0, 8), (3, 64, 20, 48, 1, 2), (5, 64, 12, 32, 0, 1)])

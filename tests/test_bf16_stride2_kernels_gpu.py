@@ -10,9 +10,23 @@ test reaches) and on the fp32 kernels, against torch fp64 convolutions of the op
   C     down data gradient, 4 phases  Cs 48 at pixel stride 64 -> 16   <1, 0, EPI, FAST>: two 32-channel steps per tap
   D     up forward, 4 phases          64 -> 16                         <1, 0, EPI, FAST>: whole steps
 
+and the same four launches of the 64 <-> 128 pair, DownsamplerBlock(64, 128) and UpsamplerBlock(128, 64), which select other kernels:
+on fp32 tensors tapgemm_kernel<4, 0, E> in its rectangular forms (two 64-channel output slabs, a 128-channel source, 64 channels read
+at pixel stride 128; both row-arithmetic variants), on bf16 tensors the persistent LDS-DMA ring (tapgemm_bf16_ring_kernel) where
+Wl % 16 == 0 and tapgemm_bf16_kernel<4, 0, E, true> at ragged widths:
+
+  E     down forward                  Cin 64 -> Cc 64 of Ccat 128      9 taps x 2 steps
+  F     up data gradient              Co 64 -> Cin 128                 9 taps x 2 steps, two output slabs
+  G     down data gradient, 4 phases  Cs 64 at pixel stride 128 -> 64  channels [64, 128) of every source pixel hold NaN
+  H     up forward, 4 phases          128 -> 64                        1 / 2 / 2 / 4 taps x 4 steps
+
+lf_debug_bf16_ring_launches pins which bf16 kernel ran; lf_debug_set_bf16_max_workgroups caps the ring's grid so that ONE workgroup walks
+every item of a small launch, across tiles and output slabs (the product launches cap the grid at the resident workgroups only, which
+no small shape exceeds).
+
 Every tensor is carved out of the middle of a larger allocation: sources lie between NaN guard bands, destinations are pre-filled with
-a canary bit pattern which the guard bands, the pooled channels [48, 64) of case A and the other phases' pixels of cases C and D must
-still hold afterwards.
+a canary bit pattern which the guard bands, the pooled channels [48, 64) of case A ([64, 128) of case E) and the other phases' pixels
+of cases C, D, G and H must still hold afterwards.
 
 Per-element gate (derived, not measured): with K = taps * Cs + 2 terms and S the same convolution of |x| with |w| plus |bias| and
 |add|, any fp32 accumulation order is within K * 2^-24 * S of the exact sum, and a bf16 store adds half a bf16 ulp:
@@ -42,13 +56,31 @@ CANARY = {torch.bfloat16: (torch.int16, 0x5A5B), torch.float32: (torch.int32, 0x
 # image boundary, two workgroups with a ragged tail (10x22); width 24, reachable in the network (16x24); gridDim.x == 8, the
 # smallest launch that takes the (gridDim.x & 7) == 0 workgroup remap (32x32)
 SHAPES = [(3, 6, 10), (2, 20, 44), (1, 32, 48), (2, 64, 64)]
+# ... of cases E-H, Wl = W / 2: Wl 5, 45 pixels, one partial workgroup on the streaming kernels; Wl 16, 192 pixels: the ring, one partial
+# item with the image boundary inside it; Wl 48, 720 pixels = three tiles, the last partial, tiles straddling images (240 pixels each);
+# Wl 128, two full tiles: the fp32 wave-uniform row variant ((Wl & 63) == 0); Wl 32, eight tiles: the (gridDim.x & 7) == 0 remap
+WIDE_SHAPES = [(3, 6, 10), (2, 12, 32), (3, 10, 96), (1, 8, 256), (2, 64, 64)]
 
 #        kind, phases, Cin, Cout, source channels (pixel stride), contracted, destination channels (pixel stride), produced, bias
 CASES = {"A": dict(kind=0, nph=1, Cin=16, Cout=48, s_pix=16, Cs=16, d_pix=64, Cd=48, bias=True, src_large=True),
          "B": dict(kind=3, nph=1, Cin=64, Cout=16, s_pix=16, Cs=16, d_pix=64, Cd=64, bias=False, src_large=True),
          "C": dict(kind=1, nph=4, Cin=16, Cout=48, s_pix=64, Cs=48, d_pix=16, Cd=16, bias=False, src_large=False),
-         "D": dict(kind=2, nph=4, Cin=64, Cout=16, s_pix=64, Cs=64, d_pix=16, Cd=16, bias=True, src_large=False)}
-EPIS = {"A": (0, RELU, STATS_SQ), "B": (0, MASK | STATS_XHAT), "C": (0, ADD), "D": (0, STATS_SQ, RELU)}
+         "D": dict(kind=2, nph=4, Cin=64, Cout=16, s_pix=64, Cs=64, d_pix=16, Cd=16, bias=True, src_large=False),
+         "E": dict(kind=0, nph=1, Cin=64, Cout=64, s_pix=64, Cs=64, d_pix=128, Cd=64, bias=True, src_large=True),
+         "F": dict(kind=3, nph=1, Cin=128, Cout=64, s_pix=64, Cs=64, d_pix=128, Cd=128, bias=False, src_large=True),
+         "G": dict(kind=1, nph=4, Cin=64, Cout=64, s_pix=128, Cs=64, d_pix=64, Cd=64, bias=False, src_large=False, nan_tail=True),
+         "H": dict(kind=2, nph=4, Cin=128, Cout=64, s_pix=128, Cs=128, d_pix=64, Cd=64, bias=True, src_large=False)}
+EPIS = {"A": (0, RELU, STATS_SQ), "B": (0, MASK | STATS_XHAT), "C": (0, ADD), "D": (0, STATS_SQ, RELU),
+        "E": (0, RELU, STATS_SQ), "F": (0, MASK | STATS_XHAT), "G": (0, ADD), "H": (0, STATS_SQ, RELU)}
+WIDE = "EFGH"
+CASE_SHAPES = [(case, shape) for case in "ABCD" for shape in SHAPES] + [(case, shape) for case in WIDE for shape in WIDE_SHAPES]
+shape_id = lambda s: "%dx%dx%d" % s
+
+
+def scratch_floats(case):
+    """9 * roundup(Kc, 32) * Nc floats (csrc/lf_debug.h; 73728 for case F), no less than the 9 * 64 * 64 cases A-D ran with, plus slack"""
+    c = CASES[case]
+    return max(9 * 64 * 64, 9 * ((c["Cs"] + 31) // 32 * 32) * c["Cd"]) + 4096
 
 
 def P(t):
@@ -91,12 +123,13 @@ def problem(case, shape, mode):
     c = CASES[case]
     N, H, W = shape
     dt = torch.bfloat16 if mode == 2 else torch.float32
-    gen = torch.Generator().manual_seed(1000 * "ABCD".index(case) + H * W + mode)
+    gen = torch.Generator().manual_seed(1000 * "ABCDEFGH".index(case) + H * W + mode)
     sshape, dshape = sizes(case, shape)
     rnd = lambda *s: torch.randn(*s, generator=gen).to(dt)
     src = rnd(*sshape)
     taps = 9 if c["nph"] == 1 else 4
-    wshape = (48, 16, 3, 3) if c["kind"] <= 1 else (64, 16, 3, 3)      # Conv2d(16, 48) / ConvTranspose2d(64, 16) layouts
+    # Conv2d(Cin, Cout) / ConvTranspose2d(Cin, Cout) layouts
+    wshape = (c["Cout"], c["Cin"], 3, 3) if c["kind"] <= 1 else (c["Cin"], c["Cout"], 3, 3)
     w = torch.randn(*wshape, generator=gen) * (2.0 / (taps * c["Cs"])) ** 0.5
     bias = torch.randn(c["Cd"], generator=gen) if c["bias"] else None
     oshape = dshape[:3] + (c["Cd"],)
@@ -111,12 +144,14 @@ def problem(case, shape, mode):
         if c["kind"] == 3:          # the adjoint of conv_transpose2d(., w) is conv2d(., w)
             return F.conv2d(x, wt, None, stride=2, padding=1)
         if c["kind"] == 1:
-            return torch.nn.grad.conv2d_input((N, 16, H, W), wt, x, stride=2, padding=1)
+            return torch.nn.grad.conv2d_input((N, c["Cin"], H, W), wt, x, stride=2, padding=1)
         return F.conv_transpose2d(x, wt, b, stride=2, padding=1, output_padding=1)
     bd = bias.double() if bias is not None else None
     want = op(xs, wk, bd).permute(0, 2, 3, 1).contiguous()
     S = op(xs.abs(), wk.abs(), bd.abs() if bd is not None else None).permute(0, 2, 3, 1).contiguous()
     assert want.shape == oshape
+    if c.get("nan_tail"):           # the other slice of the concat gradient: the launch must not read it (xs above is taken without it)
+        src[..., c["Cs"]:] = float("nan")
     # terms per destination pixel: 9 taps, or the phase's 1, 2, 2, 4
     K = torch.full(oshape[1:3], 9.0 * c["Cs"] + 2, dtype=torch.float64)
     if c["nph"] == 4:
@@ -145,7 +180,7 @@ class Launcher:
             _, t = carve(self.dshape, p["dt"], float("nan"))
             t[..., :self.c["Cd"]] = p[k].cuda()
             self.epi_t[k] = t
-        self.scratch = torch.empty(9 * 64 * 64 + 4096, device="cuda")
+        self.scratch = torch.empty(scratch_floats(case), device="cuda")
         N, H, W = shape
         self.npix = N * (H // 2) * (W // 2)          # logical pixels of every launch here
         self.rows = (self.npix + 255) // 256
@@ -191,6 +226,8 @@ def set_mode(lib, mode, no_partial_fast=0):
 def reset(lib):
     lib.lf_debug_set_ops_precision(0)
     lib.lf_debug_set_bf16_no_partial_fast(0)
+    lib.lf_debug_set_bf16_lds(4)
+    lib.lf_debug_set_bf16_max_workgroups(0)
 
 
 def check_stats(L, epi, dst, stats, tag):
@@ -222,19 +259,25 @@ def check_stats(L, epi, dst, stats, tag):
 
 
 @pytest.mark.parametrize("mode", [2, 0], ids=["bf16", "fp32"])
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%dx%d" % s)
-@pytest.mark.parametrize("case", "ABCD")
+@pytest.mark.parametrize("case,shape", CASE_SHAPES, ids=["%s-%s" % (c, shape_id(s)) for c, s in CASE_SHAPES])
 def test_stride2_launch_against_fp64(case, shape, mode):
     """Every element of every launch inside its derived gate, the statistics rows against fp64 sums, guards and canaries intact.
     (fp32: lf_tapgemm_launch takes every epilogue set for these geometries -- tapgemm_kernel<3> and tapgemm_lean_kernel<1> in their
-    run-time-flag or compiled-in forms, tapgemm_kernel<4> compiled-in -- so the bf16 mode's sets are used there too.)"""
+    run-time-flag or compiled-in forms, tapgemm_kernel<4> compiled-in -- so the bf16 mode's sets are used there too.)  Cases E-H
+    run at WIDE_SHAPES; in the bf16 mode the ring kernel takes their launches wherever Wl % 16 == 0 (the shipped routing), which
+    lf_debug_bf16_ring_launches pins."""
     L = Launcher(case, shape, mode)
     p, c = L.p, L.c
+    ring = L.lib.lf_debug_bf16_ring_launches
+    on_ring = c["nph"] if case in WIDE and mode == 2 and (shape[2] // 2) % 16 == 0 else 0
     try:
         set_mode(L.lib, mode)
         for epi in EPIS[case]:
             tag = "case %s %r mode %d epi %d" % (case, shape, mode, epi)
+            n0 = ring()
             _, dst, stats = L(epi)
+            if case in WIDE:
+                assert ring() - n0 == on_ring, "%s: %d launches on the ring kernel, expected %d" % (tag, ring() - n0, on_ring)
             want, S = p["want"], p["S"]
             if epi & ADD:
                 want, S = want + p["add"].double(), S + p["add"].double().abs()
@@ -281,21 +324,67 @@ def test_compiled_in_forms_equal_the_run_time_flag_form_bit_for_bit(case, shape)
         reset(L.lib)
 
 
+@pytest.mark.parametrize("shape", WIDE_SHAPES, ids=shape_id)
+@pytest.mark.parametrize("case", WIDE)
+def test_ring_kernel_equals_the_streaming_kernel_bit_for_bit(case, shape):
+    """Cases E-H on bf16 tensors, every epilogue set of the case, five runs per launch: lf_debug_set_bf16_lds(4) (the shipped routing:
+    the ring wherever Wl % 16 == 0), the same again (ONE determinism comparison, not a retry), (4) with the grid capped to 1 and to 2
+    workgroups (lf_debug_set_bf16_max_workgroups: one workgroup then walks every item of the launch -- with case F 2 * ntiles of
+    them, changing the output slab at every other one -- with its load cursor running ahead across the item boundaries), and
+    lf_debug_set_bf16_lds(0), the streaming kernel.  lf_debug_bf16_ring_launches rises by the launches of the case (1, or 4 phases) in
+    each of the first four runs and by 0 in the last; at (3, 6, 10), Wl = 5, it does not rise at all.  Stored values AND statistics
+    rows are equal in bits across all five runs ("K order = tapgemm_bf16_kernel's: results bit-identical", lf_conv_bf16.hip; both
+    kernels end in LF_TAPGEMM_EPILOGUE on the same accumulator layout, so the rows are summed in the same order too)."""
+    L = Launcher(case, shape, 2)
+    lib, c = L.lib, L.c
+    ring = lib.lf_debug_bf16_ring_launches
+    on_ring = c["nph"] if (shape[2] // 2) % 16 == 0 else 0
+    runs = (("ring", 4, 0), ("ring again", 4, 0), ("ring, 1 workgroup", 4, 1), ("ring, 2 workgroups", 4, 2), ("streaming", 0, 0))
+    try:
+        set_mode(lib, 2)
+        for epi in EPIS[case]:
+            tag = "case %s %r epi %d" % (case, shape, epi)
+            first, counts = None, []
+            for name, lds, cap in runs:
+                lib.lf_debug_set_bf16_lds(lds)
+                lib.lf_debug_set_bf16_max_workgroups(cap)
+                n0 = ring()
+                _, dst, stats = L(epi)
+                counts.append(ring() - n0)
+                assert torch.isfinite(dst[..., :c["Cd"]].float()).all(), (tag, name)
+                if first is None:
+                    first = (dst, stats)
+                    continue
+                diff = (bits(dst) != bits(first[0])).reshape(-1, c["d_pix"]).any(1)
+                assert not diff.any(), "%s, %s: %d pixels differ from the first run (first at %d)" % (tag, name, int(diff.sum()),
+                                                                                                   int(diff.nonzero()[0]))
+                for ph, (x, y) in enumerate(zip(stats, first[1])):
+                    assert (x is None and y is None) or torch.equal(x, y), "%s, %s: statistics rows of phase %d differ" % (tag, name, ph)
+            print("%s: ring launches per run %r" % (tag, counts))
+            assert counts == [on_ring] * 4 + [0], "%s: ring launches per run %r, expected %r" % (tag, counts, [on_ring] * 4 + [0])
+    finally:
+        reset(lib)
+
+
 def planted_positions(case, sshape):
     """(name, (n, y, x, channel)) in the source tensor: (a) an interior pixel at an even column, (b) column 0 of a row -- the pixel in
     front of it in memory is the previous row's last --, (c) pixel (0, 0) of image 1 -- ... image 0's last --, and for case C (d) one
-    of the channels 48..63 of a source pixel, which the Cs = 48 launch must not read as data."""
+    of the channels 48..63 of a source pixel, which the Cs = 48 launch must not read as data (case G: one of [64, 128))."""
     N, Hs, Ws, _ = sshape
     pos = [("a", (0, Hs // 2, 2 * (Ws // 4), 5)), ("b", (0, Hs // 2 + 1, 0, 9)), ("c", (1, 0, 0, 3))]
     if case == "C":
         pos.append(("d", (0, Hs // 2, 2 * (Ws // 4), 53)))
+    if case == "G":
+        pos.append(("d", (0, Hs // 2, 2 * (Ws // 4), 117)))
     return pos
 
 
 def window_pixels(case, shape, pos):
     """Destination pixels (bool (N, Hd, Wd)) whose tap window contains source pixel pos, from the layer's definition: the 3x3
     stride-2 pad-1 window of small pixel (i, j) covers large rows 2i-1..2i+1 and columns 2j-1..2j+1 -- cases A, B gather along
-    it (large -> small), case C scatters back along it (small -> large)."""
+    it (large -> small), case C scatters back along it (small -> large).  E, F: as A, B; G and H: as C -- large pixel (Y, X) of the
+    transposed convolution H receives small pixel (i, j) exactly where |Y - 2i| <= 1 and |X - 2j| <= 1 too.  A channel the launch does
+    not contract (>= Cs) has an empty window.  (tests/test_stride2_ref_cpu.py: equal to the support of the modules' autograd gradient.)"""
     N, H, W = shape
     n, y, x, ch = pos
     c = CASES[case]
@@ -314,12 +403,15 @@ def window_pixels(case, shape, pos):
     return out
 
 
-CONTAINMENT = [(case, epi) for case, epis in (("A", (0, RELU)), ("B", (0, RELU)), ("C", (0,))) for epi in epis]
+# position c needs two images.  E-H: the streaming shape, then the ring at one partial item, at tiles straddling images, at eight tiles
+CONTAINMENT = [(case, epi, shape) for case, epis in (("A", (0, RELU)), ("B", (0, RELU)), ("C", (0,))) for epi in epis
+               for shape in SHAPES[:2] + SHAPES[3:]] + \
+              [(case, epi, shape) for case, epis in (("E", (0, RELU)), ("F", (0,)), ("G", (0,)), ("H", (0, RELU))) for epi in epis
+               for shape in (WIDE_SHAPES[1], WIDE_SHAPES[2], WIDE_SHAPES[4], WIDE_SHAPES[0])]
 
 
 @pytest.mark.parametrize("value", [float("inf"), float("-inf"), float("nan")], ids=["+inf", "-inf", "nan"])
-@pytest.mark.parametrize("shape", SHAPES[:2] + SHAPES[3:], ids=lambda s: "%dx%dx%d" % s)   # position c needs two images
-@pytest.mark.parametrize("case,epi", CONTAINMENT, ids=["%s-epi%d" % ce for ce in CONTAINMENT])
+@pytest.mark.parametrize("case,epi,shape", CONTAINMENT, ids=["%s-epi%d-%s" % (c, e, shape_id(s)) for c, e, s in CONTAINMENT])
 def test_a_non_finite_value_stays_inside_its_tap_windows(case, epi, shape, value):
     """One +Inf, -Inf or NaN in the source (no STATS flag: through the sums it legitimately reaches the whole channel): the
     non-finite output pixels are EXACTLY those whose tap window contains the planted pixel, every other element keeps the clean
@@ -338,13 +430,24 @@ def test_a_non_finite_value_stays_inside_its_tap_windows(case, epi, shape, value
     maximum stores as 0 where torch.relu keeps the NaN -- 0 non-finite pixels where 1-2 are expected, with a planted NaN at every
     position and with +-Inf at position b (channel 9) on the run-time-flag form, whose clamped lanes re-read channels 8..15 of the
     SAME pixel against zero weights (0 * Inf = NaN in every channel of the window pixels).  The bf16 kernels' epilogues now take
-    relu_keep_nan (v <= 0 ? 0 : v), which differs from max0 on a sign-set NaN only."""
+    relu_keep_nan (v <= 0 ? 0 : v), which differs from max0 on a sign-set NaN only.
+
+    Cases E-H have Cs % 32 == 0 and no partial step: their two forms are the shipped routing (lf_debug_set_bf16_lds(4): the ring
+    kernel wherever Wl % 16 == 0, pinned by lf_debug_bf16_ring_launches; its padding is the DMA's out-of-range offset) and the
+    streaming kernel alone (lf_debug_set_bf16_lds(0)).  E, F gather like A, B; G, H scatter like C, and G's position d lies in the
+    channels [64, 128) the launch does not contract -- which hold NaN in the clean run already."""
     L = Launcher(case, shape, 2)
     c = L.c
     sshape, _ = sizes(case, shape)
     bad = []
-    count = L.lib.lf_debug_partial_fast_launches
-    compiled_in = 0 if (case, epi) == ("B", RELU) else c["nph"]
+    wide = case in WIDE
+    count = L.lib.lf_debug_bf16_ring_launches if wide else L.lib.lf_debug_partial_fast_launches
+    if wide:
+        compiled_in = c["nph"] if (shape[2] // 2) % 16 == 0 else 0       # launches on the ring kernel under the shipped routing
+        forms = ("shipped routing", "streaming")
+    else:
+        compiled_in = 0 if (case, epi) == ("B", RELU) else c["nph"]
+        forms = ("compiled-in", "run-time-flag")
     try:
         set_mode(L.lib, 2, 0)
         _, clean, _ = L(epi)
@@ -357,7 +460,9 @@ def test_a_non_finite_value_stays_inside_its_tap_windows(case, epi, shape, value
             src[pos] = value
             L.src.copy_(src)
             for flagform in (0, 1):
-                set_mode(L.lib, 2, flagform)
+                set_mode(L.lib, 2, 0 if wide else flagform)
+                if wide:
+                    L.lib.lf_debug_set_bf16_lds(0 if flagform else 4)
                 n0 = count()
                 _, got, _ = L(epi)
                 assert count() - n0 == (0 if flagform else compiled_in), (name, flagform, count() - n0)
@@ -368,7 +473,7 @@ def test_a_non_finite_value_stays_inside_its_tap_windows(case, epi, shape, value
                 if not (got_set == want_set).all() or not same:
                     extra = np.argwhere(got_set & ~want_set)
                     bad.append("position %s, %s form: %d non-finite pixels, %d expected, %d outside the windows (first %s)%s"
-                               % (name, "run-time-flag" if flagform else "compiled-in", got_set.sum(), want_set.sum(), len(extra),
+                               % (name, forms[flagform], got_set.sum(), want_set.sum(), len(extra),
                                   extra[0].tolist() if len(extra) else None, "" if same else "; finite elements changed"))
         assert not bad, "case %s epi %d %r value %s:\n" % (case, epi, shape, value) + "\n".join(bad)
     finally:
