@@ -690,8 +690,9 @@ int lf_conv1d_bwd_weight(const float* x, const float* gy, float* gw, float* gb, 
  *   Fold again after any change of a parameter, a running statistic or the plan's precision mode.
  * lf_lane_infer_folded / lf_lane_infer_seg_folded: lf_lane_infer / lf_lane_infer_seg on such a workspace -- the same schedule and
  *   the same results bit for bit, nothing uploaded, nothing folded.  params_host is still read (the stem and head kernels take
- *   their raw weights from it); params_dev and running_host are not.  flags: LF_INFER_THIN routes the fp32 tap-GEMM launches whose
- *   regular grid cannot fill the device (one camera frame) to a thin tiling with the same bits; 0 in the other precision modes. */
+ *   their raw weights from it); params_dev and running_host are not.  flags: LF_INFER_THIN routes the tap-GEMM launches whose
+ *   regular grid cannot fill the device (one camera frame) to a thin tiling with the same bits, in precision mode fp32 (fp32 tensors,
+ *   fp32 matrix cores) and bf16 (bf16 tensors, bf16 matrix cores); 0 in the split-operand mode, which has no thin kernel. */
 enum { LF_INFER_THIN = 1 };
 int lf_erfnet_infer_fold(const lf_erfnet_plan* plan, const float* const* params_host, const float* const* params_dev,
                          float* const* running_host, void* workspace, size_t workspace_bytes, void* stream);

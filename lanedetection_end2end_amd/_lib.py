@@ -176,6 +176,8 @@ def _declare(lib):
         "lf_debug_set_bf16_max_workgroups": (None, [I]),
         "lf_debug_set_thin": (None, [I, I]),
         "lf_debug_thin_launches": (L, []),
+        "lf_debug_set_thin_bf16": (None, [I, I]),
+        "lf_debug_thin_bf16_launches": (L, []),
         "lf_debug_fold_pack_launches": (L, []),
         # one launch of a bandwidth-bound backbone kernel; a source of partial rows = (rows, nrows, ld, C, ch_off, tile_pix, seg_rows, seg_pix)
         "lf_debug_bn_finalize_fwd": (I, [P, I, I, I, I, I, I, L] * 2 + [I, D, P, P, P, P, ctypes.c_float, ctypes.c_float, I, P, P, P, P, P]),
@@ -205,7 +207,8 @@ def exported_symbols():
 
 
 # ... and the csrc/lf_debug.h hooks the frozen detector's tests and tools/detector_latency.py count launches with
-_extra_symbols = ["lf_debug_set_thin", "lf_debug_thin_launches", "lf_debug_fold_pack_launches"]
+_extra_symbols = ["lf_debug_set_thin", "lf_debug_thin_launches", "lf_debug_fold_pack_launches", "lf_debug_set_thin_bf16",
+                  "lf_debug_thin_bf16_launches"]
 
 
 def load():

@@ -62,8 +62,9 @@ struct LfTapArgs {
     int stats_ld;           //   (rows = lf_tapgemm_stat_rows(); stats_ld >= rows: lf_eltwise.h, LfStatPart)
     unsigned long long* dbg;  // optional: per-wave phase timestamps (s_memtime), 8 words per wave (tools/kbench.py --phases)
     int thin;               // host-side routing flag (no kernel reads it): a launch whose regular grid cannot fill the device takes
-                            //   tapgemm_thin_kernel where that kernel is compiled for it (lf_conv.hip, launch_fp32_route); 0 everywhere
-                            //   but the frozen detector's calls (LF_INFER_THIN)
+                            //   tapgemm_thin_kernel (fp32 tensors: lf_conv.hip, launch_fp32_route) / tapgemm_bf16_thin_kernel (bf16 tensors:
+                            //   lf_conv_bf16.hip, lf_tapgemm_bf16_route) where that kernel is compiled for it; 0 everywhere but the frozen
+                            //   detector's calls (LF_INFER_THIN)
 };
 
 // ---- lf_conv.hip: forward and data-gradient launches, the fp32 kernels' routing switches and the counters of both routes ----
@@ -71,6 +72,11 @@ void lf_tapgemm_set_split_any_size(int v);
 void lf_tapgemm_set_fp32_stream(int mode, int max_workgroups);   // tapstream_kernel routing (lf_debug_set_fp32_stream, lf_debug.h)
 void lf_tapgemm_set_thin(int mode, int nt);          // tapgemm_thin_kernel routing (lf_debug_set_thin, lf_debug.h)
 long lf_tapgemm_thin_launches();                     // launches tapgemm_thin_kernel took since the process started
+// what the two thin routes (fp32 here, bf16 in lf_conv_bf16.hip) share: the CU count of the current device (cached), and the 16-channel
+// slabs per wave of a thin launch -- `forced` (1..4) where it divides Cd / 16, else the largest of 4, 3, 2, 1 dividing Cd / 16 that
+// still gives one workgroup (64 pixels x nt slabs) per CU, else 1
+int lf_tapgemm_device_cus();
+int lf_tapgemm_thin_pick_nt(const LfTapGeom& g, int forced);
 int lf_tapgemm_stat_rows(const LfTapGeom& g);                          // upper bound over the kernels (buffer sizing)
 int lf_tapgemm_stat_rows_for(const LfTapGeom& g, const LfTapArgs& a);  // rows the launch with these arguments writes
 int lf_tapgemm_launch(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, hipStream_t st);
@@ -102,6 +108,8 @@ void lf_tapgemm_set_bf16_no_partial_fast(int v);   // 1: launches with Cs % 32 !
 long lf_tapgemm_partial_fast_launches();            // launches with Cs % 32 != 0 that took a compiled-in whole-step form since the process started (tests)
 long lf_tapgemm_bf16_ring_launches();               // launches tapgemm_bf16_ring_kernel took since the process started (tests)
 void lf_tapgemm_set_bf16_max_workgroups(int v);     // > 0: caps grid.x of the resident bf16 launches (ring, whole-line, wave-private); 0: shipped (tests)
+void lf_tapgemm_set_thin_bf16(int mode, int nt);    // tapgemm_bf16_thin_kernel routing (lf_debug_set_thin_bf16, lf_debug.h)
+long lf_tapgemm_thin_bf16_launches();               // launches tapgemm_bf16_thin_kernel took since the process started
 
 // ---- lf_wgrad.hip: weight gradients and their split-K reductions (lf_tapwgrad_ro_*: lf_wgrad_ro.hip) ----
 struct LfWgradArgs {

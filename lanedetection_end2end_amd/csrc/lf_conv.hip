@@ -942,29 +942,12 @@ bool route_tapstream(int variant, hipStream_t st, const LfTapGeom& g, const LfTa
 // kernel is compiled for takes it; nt = 0: the launcher's choice, 1..4: that many slabs per wave where it divides Cd / 16.
 std::atomic<int> g_thin_mode{0}, g_thin_nt{0};
 std::atomic<long> g_thin_launches{0};
-int device_cus() {
-    static std::map<int, int> cache;
-    const int dev = current_device();
-    std::lock_guard<std::mutex> lock(g_launch_state_mutex);
-    auto it = cache.find(dev);
-    if (it != cache.end()) return it->second;
-    int cus = 0;
-    if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
-    return cache[dev] = cus;
-}
+int device_cus() { return lf_tapgemm_device_cus(); }
 // the forms the thin kernel is compiled for: no prologue, bias + ReLU or bias + residual + ReLU
 bool thin_compiled(const LfTapArgs& a, int pro, int epis) {
     return pro == LF_PRO_NONE && ((epis == LF_EPI_RELU && a.bias) || epis == BRES);
 }
-// slabs per wave: the largest of 4, 3, 2, 1 dividing Cd / 16 that still gives one workgroup per CU, else 1
-int thin_pick_nt(const LfTapGeom& g) {
-    const int slabs = g.Cd / 16, forced = g_thin_nt.load();
-    if (forced >= 1 && forced <= 4 && slabs % forced == 0) return forced;
-    const long tiles = lf_cdiv((long)g.N * g.Hl * g.Wl, WG_WAVES * 16);
-    for (int nt = 4; nt > 1; --nt)
-        if (slabs % nt == 0 && tiles * (slabs / nt) >= device_cus()) return nt;
-    return 1;
-}
+int thin_pick_nt(const LfTapGeom& g) { return lf_tapgemm_thin_pick_nt(g, g_thin_nt.load()); }
 template <int EPIV>
 void launch_thin(const LfTapGeom& g, const LfTapArgs& a, hipStream_t st) {
     const int nt = thin_pick_nt(g);
@@ -1060,6 +1043,26 @@ int launch_fp32_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int epi, 
 }  // namespace
 
 void lf_tapgemm_set_fp32_stream(int mode, int max_workgroups) { g_stream_mode = mode; g_stream_cap = max_workgroups > 0 ? max_workgroups : 0; }
+
+int lf_tapgemm_device_cus() {
+    static std::map<int, int> cache;
+    const int dev = current_device();
+    std::lock_guard<std::mutex> lock(g_launch_state_mutex);
+    auto it = cache.find(dev);
+    if (it != cache.end()) return it->second;
+    int cus = 0;
+    if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
+    return cache[dev] = cus;
+}
+// slabs per wave: the largest of 4, 3, 2, 1 dividing Cd / 16 that still gives one workgroup per CU, else 1
+int lf_tapgemm_thin_pick_nt(const LfTapGeom& g, int forced) {
+    const int slabs = g.Cd / 16;
+    if (forced >= 1 && forced <= 4 && slabs % forced == 0) return forced;
+    const long tiles = lf_cdiv((long)g.N * g.Hl * g.Wl, WG_WAVES * 16);
+    for (int nt = 4; nt > 1; --nt)
+        if (slabs % nt == 0 && tiles * (slabs / nt) >= lf_tapgemm_device_cus()) return nt;
+    return 1;
+}
 
 void lf_tapgemm_set_thin(int mode, int nt) { g_thin_mode = mode == 2 ? 2 : 0; g_thin_nt = (nt >= 1 && nt <= 4) ? nt : 0; }
 long lf_tapgemm_thin_launches() { return g_thin_launches.load(); }

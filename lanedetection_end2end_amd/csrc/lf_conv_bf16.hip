@@ -9,7 +9,9 @@
 //                             (LDS-DMA operand ring, weights in registers, LDS-transposed stores)
 //   tapgemm_bf16_wv_kernel    the 3-tap convolutions at 64 channels: a wave owns its pixels and all 64 output channels
 //   tapgemm_bf16_lean_kernel  16 -> 16 channels (two taps per K = 32 MFMA)
-// The streaming, ring and lean kernels expand the epilogue they share with the fp32 kernels (LF_TAPGEMM_EPILOGUE, lf_conv_epi.h);
+//   tapgemm_bf16_thin_kernel  one 16-pixel tile per wave, for launches that cannot fill the device: one frame (the frozen detector)
+// The streaming, ring and lean kernels expand the epilogue they share with the fp32 kernels (LF_TAPGEMM_EPILOGUE, lf_conv_epi.h), the
+// thin kernel its three parts (one pixel tile);
 // the whole-line and wave-private kernels have their own (same arithmetic, output and operand tensors through LDS tiles).
 // The device and launch helpers shared with lf_conv.hip and lf_wgrad.hip are in lf_conv_dev.h, the LDS-DMA helpers in lf_ldsdma.h.
 #include "lf_conv_dev.h"
@@ -1211,12 +1213,149 @@ __global__ __launch_bounds__(256, 4) void tapgemm_bf16_lean_kernel(const LfTapGe
     LF_TAPGEMM_EPILOGUE
 }
 
+// ---------------------------------------------------------------------------------------
+// tapgemm_bf16_thin_kernel: tapgemm_thin_kernel's tiling (lf_conv.hip) on bf16 tensors and the bf16 matrix cores, for the launches of
+// one camera frame -- 8 to 32 workgroups of the kernels above on 256 CUs.  A wave owns ONE 16-pixel tile and NT 16-channel slabs, a
+// workgroup 64 consecutive logical pixels, blockIdx.y walks the slab groups, one workgroup per tile: no walk, no workgroup barrier.
+// The general LfTapGeom (any tap count, strides, sub-pixel destination offsets, ragged Wl); no operand prologue, no statistics; the
+// epilogues the inference schedule issues: bias + ReLU and bias + residual + ReLU (BRES), the shared text (LF_EPI_HEAD / TILE / TAIL).
+// Every output element is tapgemm_bf16_kernel's bit for bit (tests/test_thin_bf16_conv_gpu.py), and so the wave-private, whole-line
+// and ring kernels': K-steps tap-major then 32-channel step, ONE fp32 MFMA chain per accumulator, a lane supplies the 8 channels
+// kq * 8 .. of its pixel in the step, padding is zero bits (the out-of-range offset), an odd step count ends with the streaming
+// kernel's dead step (the last live weights against zeros).  K is not split.
+// Source channels: whole 32-channel steps, or 16 (DownsamplerBlock(16, 64)'s convolution: one half-filled step per tap) -- there the
+// lanes kq = 2, 3, whose channels the pixel does not have, hold the out-of-range offset in every tap-table row: they read the buffer
+// bound's zeros, not the next pixel (whose Inf / NaN against the zero-padded weights would be NaN in every output channel).
+// A thin wave is alone on its SIMD and a step's MFMAs take NT x 8 passes, so nothing hides a load but the depth of the wave's own
+// queue: a ring of R K-steps of operands (4 * (NT + 1) registers per step) is in flight.  The steps a turn of the ring requests
+// beyond the K loop carry the out-of-range offset for BOTH operands: returned as zeros without a memory round trip, never used.
+// Operand budgets of 80, 120, 160 and 200 registers per lane (R = the even step count a budget holds, at most 18: the longest K
+// loop of the network) were measured in the detector, DESIGN.md section 9: within 4 % at one frame and 7 % at eight, the deepest the
+// slowest; R = 14 / 10 / 6 at NT = 1 / 2 / 3 (the 120-register build's, fastest at one frame, where NT is 1 and 2) and 4 at NT = 4
+// (the 80-register build's, fastest at 8 frames, where NT is 4) ship.
+// ---------------------------------------------------------------------------------------
+constexpr int thin16_ring(int nt) { return nt == 1 ? 14 : nt == 2 ? 10 : nt == 3 ? 6 : 4; }
+__device__ __forceinline__ f32x4 widen_bf16x4(u32x2v q) {
+    f32x4 v;
+    v.x = __uint_as_float(q[0] << 16); v.y = __uint_as_float(q[0] & 0xffff0000u);
+    v.z = __uint_as_float(q[1] << 16); v.w = __uint_as_float(q[1] & 0xffff0000u);
+    return v;
+}
+template <int NT, int EPIC>
+__global__ __launch_bounds__(256, 2) void tapgemm_bf16_thin_kernel(const LfTapGeom g, const LfTapArgs a) {
+    constexpr int epi = EPIC, R = thin16_ring(NT);
+    constexpr bool S16 = true, HOISTV = true;
+    static_assert(R % 2 == 0 && (EPIC == LF_EPI_RELU || EPIC == BRES), "the ring holds whole pairs of K-steps");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pl = lane & 15, kq = lane >> 4;
+    const unsigned npix = (unsigned)(g.N * g.Hl * g.Wl);
+    const int cob = blockIdx.y * NT * 16;
+    const unsigned bx = xcd_swizzle(blockIdx.x);       // (see tapgemm_kernel: XCD-contiguous ranges)
+    int pn[1], pi[1], pj[1];
+    bool pv[1];
+    {
+        const unsigned p = (bx * WG_WAVES + wave) * 16 + pl;
+        pv[0] = p < npix;
+        const unsigned q = pv[0] ? p : 0u;
+        const unsigned r = q / (unsigned)g.Wl;
+        pj[0] = (int)(q - r * (unsigned)g.Wl);
+        pn[0] = (int)(r / (unsigned)g.Hl);
+        pi[0] = (int)(r - (unsigned)pn[0] * (unsigned)g.Hl);
+    }
+    // tapgemm_bf16_kernel's tap table (FAST form), one pixel tile wide: this lane's source byte offset per tap -- its 8 channels of
+    // the first 32-channel step --, LF_OOB (reads as zeros) for padding and for channels the pixel does not have (Cs = 16)
+    __shared__ unsigned tab[WG_WAVES][LF_MAX_TAPS][64];
+    for (int t = 0; t < g.ntaps; ++t) {
+        const int sy = pi[0] * g.ssh + g.tdh[t], sx = pj[0] * g.ssw + g.tdw[t];
+        const bool in = pv[0] && sy >= 0 && sy < g.Hs && sx >= 0 && sx < g.Ws && kq * 8 < g.Cs;
+        const int syc = min(max(sy, 0), g.Hs - 1), sxc = min(max(sx, 0), g.Ws - 1);
+        const unsigned o = (unsigned)(((pn[0] * g.Hs + syc) * g.Ws + sxc) * g.s_pix + g.s_choff + kq * 8) * 2u;
+        tab[wave][t][lane] = in ? o : LF_OOB;
+    }
+    // (each lane reads back only what it wrote: no barrier needed)
+    f32x4 acc[NT][1];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[n][0] = zero4();
+    // (both ahead of the loop: the round trips of the bias vector and of the residual run under it -- behind it, nothing would hide
+    // them; the residual stays as loaded -- widening it here would wait for it in front of the first operand request)
+    LF_EPI_HEAD
+    u32x2v addv[NT];
+    if constexpr ((EPIC & LF_EPI_ADD) != 0) {
+        const unsigned db = (unsigned)(((pn[0] * g.Hd + pi[0] * g.dsh + g.dah) * g.Wd + pj[0] * g.dsw + g.daw) * g.d_pix + g.d_choff + cob + kq * 4);
+#pragma unroll
+        for (int n = 0; n < NT; ++n) addv[n] = __builtin_amdgcn_raw_buffer_load_b64(r_add, (int)((db + n * 16) * 2u), 0, 0);
+    }
+    {
+        struct Step { u32x4v w[NT]; u32x4v x; };
+        const int ncb = (g.Cs + 31) >> 5, ntaps = g.ntaps, nsteps = ntaps * ncb;      // 32-channel steps per tap (Cs = 16: one, half filled)
+        const int wstep = g.Cd * 64;                                        // bytes per 32-channel step (4 k-blocks x Cd x 16)
+        const int npad = (nsteps + 1) & ~1;                                 // an odd step count ends with a dead step
+        const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.src, (unsigned)min((long)g.N * g.Hs * g.Ws * g.s_pix * 2, (long)LF_OOB));
+        const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.wp16, (unsigned)(nsteps * wstep));
+        const unsigned wlane = (unsigned)(kq * g.Cd + cob + pl) * 16u;      // bytes (8 bf16 per lane and slab)
+        const int wlast = (nsteps - 1) * wstep;
+        int s_ld = 0, t_ld = 0, cb_ld = 0, wofs = 0;
+        // the next K-step's operands -> S.  Step nsteps of an odd count: the last live weights against zeros (tapgemm_bf16_kernel's dead
+        // step); from npad on -- the ring's turn reaches beyond the loop -- both operands out of range
+        auto issue = [&](Step& S) {
+            const bool live = t_ld < ntaps;
+            const unsigned beyond = s_ld < npad ? 0u : LF_OOB;
+            const unsigned o = tab[wave][live ? t_ld : ntaps - 1][lane] | (live ? 0u : LF_OOB);
+#pragma unroll
+            for (int n = 0; n < NT; ++n) S.w[n] = __builtin_amdgcn_raw_buffer_load_b128(rw, (int)((wlane + n * 256) | beyond), wofs, 0);
+            S.x = __builtin_amdgcn_raw_buffer_load_b128(rx, (int)o, cb_ld * 64, 0);
+            const int cbn = cb_ld + 1;
+            const bool wrap = cbn == ncb;
+            wofs = min(wofs + wstep, wlast);
+            cb_ld = live ? (wrap ? 0 : cbn) : cb_ld;
+            t_ld = (live && wrap) ? t_ld + 1 : t_ld;
+            ++s_ld;
+        };
+        Step ring[R];
+#pragma unroll
+        for (int p = 0; p < R; ++p) issue(ring[p]);
+        // one K-step: NT MFMAs, each continuing its accumulator's chain; refill: the slot's next occupant, R K-steps ahead
+        auto step = [&](Step& S, auto refill) {
+            const bf16x8 xb = __builtin_bit_cast(bf16x8, S.x);
+#pragma unroll
+            for (int n = 0; n < NT; ++n)
+                acc[n][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, S.w[n]), xb, acc[n][0], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (decltype(refill)::value) issue(S);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        // whole turns of the ring in a loop without an early exit (see tapgemm_thin_kernel), then the last, partial turn
+        int base = 0;
+        for (; base + R <= npad; base += R) {
+#pragma unroll
+            for (int j = 0; j < R; ++j) step(ring[j], std::true_type{});
+        }
+#pragma unroll
+        for (int j = 0; j < R - 2; j += 2) {
+            if (base + j >= npad) break;          // (wave-uniform; npad and R are even)
+            step(ring[j], std::false_type{});
+            step(ring[j + 1], std::false_type{});
+        }
+    }
+#undef LF_EPI_LDADD
+#define LF_EPI_LDADD(o) widen_bf16x4(addv[((o) - dbase) >> 4])      /* the residual of channel tile n, loaded ahead of the loop */
+    LF_EPI_TILE(0)
+#undef LF_EPI_LDADD
+#define LF_EPI_LDADD(o) epi_ld<S16>(r_add, o)
+    LF_EPI_TAIL
+}
+
 int g_bf16_lds = 4;            // tools / A-B runs only: 4 = wave-private (64 ch) / whole-line (128 ch) + 16-channel kernels where they apply, else the ring (shipped);
                                // 3 = the whole-line kernel at 64 channels too (round 5's routing); 2 = the ring
                                // for every launch it takes; 0 = the streaming bf16 kernel only
 std::atomic<long> g_part_fast_launches{0};   // launches with Cs % 32 != 0 that took a compiled-in whole-step form (lf_tapgemm_partial_fast_launches)
 int g_bf16_no_partial_fast = 0; // kernel-level tests only: launches with Cs % 32 != 0 decline the compiled-in whole-step forms of tapgemm_bf16_kernel
 std::atomic<long> g_ring_launches{0};        // launches tapgemm_bf16_ring_kernel took (lf_tapgemm_bf16_ring_launches)
+// tapgemm_bf16_thin_kernel (see there).  lf_debug_set_thin_bf16: mode 0 = LfTapArgs::thin and the grid size decide, 2 = every launch the
+// kernel is compiled for takes it; nt = 0: the launcher's choice, 1..4: that many slabs per wave where it divides Cd / 16.  Its own
+// switch and counter: lf_debug_set_thin / lf_debug_thin_launches (the fp32 kernel's, lf_conv.hip) do not touch bf16 launches.
+std::atomic<int> g_thin16_mode{0}, g_thin16_nt{0};
+std::atomic<long> g_thin16_launches{0};
 std::atomic<int> g_bf16_cap{0};              // kernel-level tests only: > 0 caps grid.x of the resident launches below, so that one workgroup
                                              // walks several items at small shapes; 0 (shipped): launch_resident's own size
 
@@ -1228,6 +1367,8 @@ void lf_tapgemm_set_bf16_no_partial_fast(int v) { g_bf16_no_partial_fast = v; }
 long lf_tapgemm_partial_fast_launches() { return g_part_fast_launches.load(); }
 long lf_tapgemm_bf16_ring_launches() { return g_ring_launches.load(); }
 void lf_tapgemm_set_bf16_max_workgroups(int v) { g_bf16_cap = v > 0 ? v : 0; }
+void lf_tapgemm_set_thin_bf16(int mode, int nt) { g_thin16_mode = mode == 2 ? 2 : 0; g_thin16_nt = (nt >= 1 && nt <= 4) ? nt : 0; }
+long lf_tapgemm_thin_bf16_launches() { return g_thin16_launches.load(); }
 
 namespace {
 // tapgemm_bf16_ring_kernel: persistent
@@ -1259,6 +1400,20 @@ void launch_bf16_stream_rt(dim3 grid, hipStream_t st, const LfTapGeom& g, const 
     if (pro == LF_PRO_BNRELU) launch_bf16_stream<NTV, 1>(grid, st, g, a, pro, epi);
     else launch_bf16_stream<NTV, 0>(grid, st, g, a, pro, epi);
 }
+// tapgemm_bf16_thin_kernel: one workgroup per 64 pixels and group of nt slabs (lf_tapgemm_thin_pick_nt: shared with the fp32 route)
+template <int EPIV>
+void launch_bf16_thin(const LfTapGeom& g, const LfTapArgs& a, hipStream_t st) {
+    const int nt = lf_tapgemm_thin_pick_nt(g, g_thin16_nt.load());
+    const dim3 grid((unsigned)lf_cdiv((long)g.N * g.Hl * g.Wl, WG_WAVES * 16), g.Cd / (16 * nt));
+    switch (nt) {
+        case 4: hipLaunchKernelGGL((tapgemm_bf16_thin_kernel<4, EPIV>), grid, dim3(256), 0, st, g, a); break;
+        case 3: hipLaunchKernelGGL((tapgemm_bf16_thin_kernel<3, EPIV>), grid, dim3(256), 0, st, g, a); break;
+        case 2: hipLaunchKernelGGL((tapgemm_bf16_thin_kernel<2, EPIV>), grid, dim3(256), 0, st, g, a); break;
+        default: hipLaunchKernelGGL((tapgemm_bf16_thin_kernel<1, EPIV>), grid, dim3(256), 0, st, g, a); break;
+    }
+    ++g_thin16_launches;
+    if (EPIV == BRES) ++g_bres_launches;
+}
 }  // namespace
 
 // precision mode bf16: bf16 tensors on the bf16 matrix cores (lf_tapgemm_launch's route for the launches with wp16)
@@ -1266,6 +1421,18 @@ int lf_tapgemm_bf16_route(const LfTapGeom& g, const LfTapArgs& a, int pro, int e
     LF_REQUIRE(a.s16, "tapgemm: the bf16 matrix-core kernels take bf16 tensors (s16); bf16 operands on fp32 tensors were removed in round 6");
     LF_REQUIRE(g.Cs >= 8 && g.s_pix >= g.s_choff + 8, "tapgemm bf16: needs at least 8 source channels");
     const bool in_offsets = (long)g.N * g.Hs * g.Ws * g.s_pix * 2 < (long)LF_OOB;    // the bf16 source inside 32-bit byte offsets
+    // a launch of an output slab of 32 channels or more (the 64- / 128-channel convolutions, the stride-2 layers, the up-sampler
+    // phases) that cannot put one workgroup on every CU: the thin tiling, where the caller asks for it (launch_fp32_route's rule).
+    // Whole 32-channel steps, or 16 source channels; everything else runs where it ran
+    const int thin_mode = g_thin16_mode.load();
+    if ((a.thin || thin_mode == 2) && nt >= 2 && !a.dbg && pro == LF_PRO_NONE && ((epis == LF_EPI_RELU && a.bias) || epis == BRES) &&
+        (g.Cs % 32 == 0 || g.Cs == 16) && g.s_pix >= g.s_choff + g.Cs && in_offsets &&
+        (thin_mode == 2 || (long)grid.x * grid.y < lf_tapgemm_device_cus())) {
+        if (epis == BRES) launch_bf16_thin<BRES>(g, a, st);
+        else launch_bf16_thin<LF_EPI_RELU>(g, a, st);
+        LF_CHECK_LAUNCH("tapgemm_bf16_thin");
+        return 0;
+    }
     // the 16 -> 16 channel 3-tap convolutions on bf16 tensors: tapgemm_bf16_lean_kernel
     if (a.s16 && g_bf16_lds >= 3 && !a.dbg && g.Cs == 16 && g.Cd == 16 && g.ntaps == 3 && g.Wl % 16 == 0 && g.s_pix % 8 == 0 && g.s_choff % 8 == 0 && in_offsets) {
         with_epi<true>(epis, [&](auto e) {

@@ -16,6 +16,7 @@
 //                                            family's only redefinitions
 //   lf_conv_pair.hip  tappair128_kernel      LF_EPI_GROUPS, LF_EPI_TID, LF_EPI_ROW1, LF_EPI_TILE_OF (in pair128_phase)
 //   lf_conv_bf16.hip  tapgemm_bf16_kernel, tapgemm_bf16_ring_kernel   LF_EPI_PIVOT
+//                     tapgemm_bf16_thin_kernel   LF_EPI_LDADD (expands LF_EPI_HEAD / LF_EPI_TILE(0) / LF_EPI_TAIL, as tapgemm_thin_kernel)
 //   lf_bwd16.hip      tapbwd16_kernel        LF_EPI_ACC, LF_EPI_ROW1, LF_EPI_LDADD, LF_EPI_LDMSK, LF_EPI_LDAUX, LF_EPI_HOIST_ALL
 // tapgemm_lean_kernel and tapgemm_bf16_lean_kernel expand the defaults; the whole-line and wave-private bf16 kernels have epilogues
 // of their own and expand nothing from here.

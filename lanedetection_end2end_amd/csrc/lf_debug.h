@@ -210,6 +210,14 @@ long lf_debug_bias_residual_launches(void);
 void lf_debug_set_thin(int mode, int nt);
 /* launches that kernel took since the process started */
 long lf_debug_thin_launches(void);
+/* the thin bf16 tap-GEMM (tapgemm_bf16_thin_kernel, csrc/lf_conv_bf16.hip: the same tiling on bf16 tensors and the bf16 matrix cores), with
+ * a switch and a counter of its own -- lf_debug_set_thin leaves bf16 launches alone, and this pair fp32 launches.  mode 0 (shipped):
+ * LfTapArgs::thin and the grid size decide; 2: every launch the kernel is compiled for (bf16 tensors, an output slab of 32 channels or
+ * more, source channels a multiple of 32 or 16, no prologue, bias + ReLU or bias + residual + ReLU) takes it.  nt as above.  The kernels
+ * agree bit for bit (tests/test_thin_bf16_conv_gpu.py) */
+void lf_debug_set_thin_bf16(int mode, int nt);
+/* launches that kernel took since the process started */
+long lf_debug_thin_bf16_launches(void);
 /* fold-and-pack launches (lf_fold_pack_launch: the inference engine's per-call fold, lf_erfnet_infer_fold, the --clas heads' chains)
  * since the process started */
 long lf_debug_fold_pack_launches(void);

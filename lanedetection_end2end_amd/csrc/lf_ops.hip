@@ -118,6 +118,8 @@ void lf_debug_set_fwd_pair(int mode, int max_workgroups) { lf_tappair_set(mode, 
 long lf_debug_bias_residual_launches(void) { return lf_tapgemm_bias_residual_launches(); }
 void lf_debug_set_thin(int mode, int nt) { lf_tapgemm_set_thin(mode, nt); }
 long lf_debug_thin_launches(void) { return lf_tapgemm_thin_launches(); }
+void lf_debug_set_thin_bf16(int mode, int nt) { lf_tapgemm_set_thin_bf16(mode, nt); }
+long lf_debug_thin_bf16_launches(void) { return lf_tapgemm_thin_bf16_launches(); }
 long lf_debug_fold_pack_launches(void) { return lf_fold_pack_launches(); }
 long lf_debug_partial_fast_launches(void) { return lf_tapgemm_partial_fast_launches(); }
 long lf_debug_bf16_ring_launches(void) { return lf_tapgemm_bf16_ring_launches(); }

@@ -224,6 +224,9 @@ class _LaneFitNet(nn.Module):
 # beyond the min-max ranges of both, at 256 x 512 and at 320 x 640 (profiles/detector_latency.json, key thin_auto_max_batch;
 # tools/detector_latency.py): it won at 1, 2, 4 and 8, and batch 32 has no launch left for it to take.  0 would mean "auto" = off
 THIN_AUTO_MAX_BATCH = 8
+# ... and of the thin bf16 route (tapgemm_bf16_thin_kernel) in precision mode bf16, by the same rule (profiles/detector_latency_bf16_thin.json):
+# it won at 1, 2 and 4 at both sizes; at 8 it won at 256 x 512 (0.723 against 0.842 ms) and lost at 320 x 640 (1.070 against 0.977 ms)
+THIN_AUTO_MAX_BATCH_BF16 = 4
 
 
 class LaneDetector:
@@ -245,10 +248,11 @@ class LaneDetector:
     (``load_state_dict``, a training step, ``set_homography``, ``.to()``): nothing is checked per call, and what an un-refreshed
     detector returns after such a change is NOT DEFINED (stale weights, or pointers to freed memory).
 
-    ``thin``: ``True`` / ``False`` route / do not route the fp32 tap-GEMM launches whose regular grid cannot fill the device to
-    ``tapgemm_thin_kernel`` (one 16-pixel tile per wave; the same bits); ``"auto"``: on in precision mode ``fp32`` for batches up
-    to ``THIN_AUTO_MAX_BATCH``.  The thin kernel exists for fp32 tensors on the fp32 matrix cores only: in ``bf16`` and ``fp32x9``
-    the detector gives fold-once only, whatever ``thin`` says.
+    ``thin``: ``True`` / ``False`` route / do not route the tap-GEMM launches whose regular grid cannot fill the device to the thin
+    kernel of the precision mode (one 16-pixel tile per wave; the same bits): ``tapgemm_thin_kernel`` in ``fp32``,
+    ``tapgemm_bf16_thin_kernel`` in ``bf16``; ``"auto"``: on for batches up to ``THIN_AUTO_MAX_BATCH`` (``fp32``) /
+    ``THIN_AUTO_MAX_BATCH_BF16`` (``bf16``).  There is no thin kernel for the split operands of ``fp32x9``: there the detector
+    gives fold-once only, whatever ``thin`` says.
 
     The results of a call live in fresh tensors; the workspace is the detector's, so calls of ONE detector must be issued on one
     stream (or ordered by the caller).  Detectors of one model are independent of each other and of ``detect``."""
@@ -317,8 +321,9 @@ class LaneDetector:
         self._reg = 0.0 if (model.use_cholesky and model.cholesky_drops_reg) else float(model.reg_ls)
         self._zero_rows, self._y_offset = int(model.zero_rows), float(model.y_offset)
         self._act, self._chol = int(ops.ACT_KINDS[model.activation_name]), int(bool(model.use_cholesky))
-        thin_on = self.thin is True or (self.thin == "auto" and N <= THIN_AUTO_MAX_BATCH)
-        self._flags = 1 if (thin_on and self.precision == "fp32") else 0          # LF_INFER_THIN
+        auto_max = {"fp32": THIN_AUTO_MAX_BATCH, "bf16": THIN_AUTO_MAX_BATCH_BF16}.get(self.precision)
+        thin_on = auto_max is not None and (self.thin is True or (self.thin == "auto" and N <= auto_max))
+        self._flags = 1 if thin_on else 0          # LF_INFER_THIN
         self._enc = None
         if model.classification_branch and not self._seg:
             # logical NCHW, channels-last memory (as Net.forward hands it out): a view of the detector's own workspace

@@ -1,15 +1,23 @@
 """Latency of one call, image -> lane coefficients, at small batch: ``model.detect`` against the frozen detector.
 
     python tools/detector_latency.py [--out profiles/detector_latency.json] [--batches 1,2,4,8,32] [--configs bev,bp] [--precisions fp32,bf16]
+    python tools/detector_latency.py --precisions bf16          (-> profiles/detector_latency_bf16_thin.json)
 
 Three paths alternated in one process: (A) ``model.detect`` (the fold on every call), (B) ``model.detector(thin=False)`` (fold
-once), (C) ``model.detector(thin=True)`` (fold once + the thin fp32 tap-GEMM route; precision mode fp32 only).  Geometries: BEV
-2 lanes 256 x 512 and BP 4 lanes order 3 320 x 640, each in fp32 (A, B, C) and in bf16 (A, B).  ``check_singular`` is off on every
-path (its status read would synchronise every call).  Protocol: per repeat and path --warmup untimed calls, then --calls
+once), (C) ``model.detector(thin=True)`` (fold once + the thin tap-GEMM route of the precision mode: tapgemm_thin_kernel in fp32,
+tapgemm_bf16_thin_kernel in bf16).  Geometries: BEV 2 lanes 256 x 512 and BP 4 lanes order 3 320 x 640, each in fp32 and in
+bf16.  Beside (C) the row records the thin launches of one call (``thin_launches_per_call``, the library's counter) and, where
+there are any, ``thin_nt_derived``: the slabs per wave of the network's thin launches by output channel count, DERIVED in this
+file from the launcher's rule at nt = 0 (lf_tapgemm_thin_pick_nt, csrc/lf_conv.hip), not read back from the launches.  A row
+whose (C) took no thin launch ran (B)'s code: it carries no ``thin_wins``.  ``check_singular`` is off on every path (its status
+read would synchronise every call).  Protocol: per repeat and path --warmup untimed calls, then --calls
 back-to-back calls between two in-stream events and two host clock reads, the second behind one final synchronise; --repeats
 repeats; reported: median and min-max of both times per call (ms).  Where the host issues slower than the device runs, the two
 agree and the host is the limit.  ``thin_auto_max_batch``: the largest batch among 1, 2, 4, 8 at which (C)'s in-stream time is below
-(B)'s beyond the min-max ranges of both, in every fp32 geometry measured (0: nowhere) -- lsq.THIN_AUTO_MAX_BATCH.
+(B)'s beyond the min-max ranges of both, in every geometry measured (0: nowhere), per precision mode -- lsq.THIN_AUTO_MAX_BATCH
+(fp32; the top-level key of a run that measured fp32) and lsq.THIN_AUTO_MAX_BATCH_BF16 (the top-level key of a bf16-only run);
+``thin_auto_max_batch_by_precision`` has both.  A run of --precisions bf16 alone writes profiles/detector_latency_bf16_thin.json
+and leaves the fp32 file as it is.
 
     rocprofv3 --kernel-trace --stats -d DIR -o trace -- python tools/detector_latency.py --trace A|C
     python tools/detector_latency.py --launches DB_A DB_C [--out profiles/detector_launches.md]
@@ -91,13 +99,34 @@ def stats(v):
     return {"median": round(statistics.median(v), 5), "min": round(min(v), 5), "max": round(max(v), 5)}
 
 
+def thin_launches(precision):
+    """the launch counter of the precision mode's thin kernel"""
+    from lanedetection_end2end_amd import _lib
+    lib = _lib.load()
+    return lib.lf_debug_thin_launches() if precision == "fp32" else lib.lf_debug_thin_bf16_launches()
+
+
+def derived_nt(cfg, N):
+    """slabs per wave of the network's thin launches by (stage pixels, output channels), DERIVED from the launcher's rule with no nt
+    forced (lf_tapgemm_thin_pick_nt, csrc/lf_conv.hip: the largest of 4, 3, 2, 1 dividing Cd / 16 that still gives one 64-pixel
+    workgroup per CU, else 1); which of these launches take the route at this batch is not derived"""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    out = {}
+    for name, div, cd in (("down_16_to_48", 4, 48), ("conv_64", 4, 64), ("down_64_to_64", 8, 64), ("conv_128", 8, 128), ("up_128_to_64_phase", 8, 64)):
+        tiles = -(-(N * (cfg["H"] // div) * (cfg["W"] // div)) // 64)
+        slabs = cd // 16
+        out[name] = next((nt for nt in (4, 3, 2) if slabs % nt == 0 and tiles * (slabs // nt) >= cus), 1)
+    return out
+
+
 def measure(cfg, precision, N, warmup, calls, repeats):
     import torch
     from oracle import inputs
     model = make_model(cfg, precision, N)
     x = torch.from_numpy(inputs.images(N, cfg["H"], cfg["W"], seed=1)).cuda()
     paths = {"A_detect": model.detect, "B_detector": model.detector(batch=N, height=cfg["H"], width=cfg["W"], thin=False)}
-    if precision == "fp32":
+    if precision in ("fp32", "bf16"):
         paths["C_detector_thin"] = model.detector(batch=N, height=cfg["H"], width=cfg["W"], thin=True)
     ref = model.detect(x)
     for name, fn in paths.items():      # the three paths give the same bits
@@ -116,7 +145,12 @@ def measure(cfg, precision, N, warmup, calls, repeats):
     for name in paths:
         row[name] = {"in_stream_ms": stats(ev[name]), "wall_ms": stats(wall[name])}
     if "C_detector_thin" in paths:
-        row["thin_wins"] = row["C_detector_thin"]["in_stream_ms"]["max"] < row["B_detector"]["in_stream_ms"]["min"]
+        c0 = thin_launches(precision)
+        paths["C_detector_thin"](x)
+        row["thin_launches_per_call"] = thin_launches(precision) - c0
+        if row["thin_launches_per_call"] > 0:      # (none: (C) ran (B)'s code, a difference is the order of the runs)
+            row["thin_wins"] = row["C_detector_thin"]["in_stream_ms"]["max"] < row["B_detector"]["in_stream_ms"]["min"]
+            row["thin_nt_derived"] = derived_nt(cfg, N)
     del model, paths, x
     torch.cuda.empty_cache()
     return row
@@ -130,17 +164,23 @@ def run(args):
             for N in [int(b) for b in args.batches.split(",")]:
                 rows.append(measure(CONFIGS[key], precision, N, args.warmup, args.calls, args.repeats))
                 print(json.dumps(rows[-1]), flush=True)
-    bound = 0
-    for N in (1, 2, 4, 8):
-        at = [r for r in rows if r["precision"] == "fp32" and r["batch"] == N]
-        if at and all(r["thin_wins"] for r in at):
-            bound = N
+    bounds = {}
+    for precision in args.precisions.split(","):
+        bounds[precision] = 0
+        for N in (1, 2, 4, 8):
+            at = [r for r in rows if r["precision"] == precision and r["batch"] == N]
+            if at and all(r.get("thin_wins", False) for r in at):
+                bounds[precision] = N
+    bf16_only = args.precisions == "bf16"
+    bound = bounds["bf16"] if bf16_only else bounds.get("fp32", 0)
     res = {"tool": "detector_latency", "commit": commit_stamp(), "device": torch.cuda.get_device_name(0), "warmup": args.warmup,
-           "calls": args.calls, "repeats": args.repeats, "check_singular": False, "thin_auto_max_batch": bound, "results": rows}
-    with open(args.out or os.path.join(ROOT, "profiles", "detector_latency.json"), "w") as f:
+           "calls": args.calls, "repeats": args.repeats, "check_singular": False, "thin_auto_max_batch": bound,
+           "thin_auto_max_batch_by_precision": bounds, "results": rows}
+    default = "detector_latency_bf16_thin.json" if bf16_only else "detector_latency.json"
+    with open(args.out or os.path.join(ROOT, "profiles", default), "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
-    print(json.dumps({"thin_auto_max_batch": bound}))
+    print(json.dumps({"thin_auto_max_batch": bound, "by_precision": bounds}))
 
 
 def trace(path):
