@@ -54,7 +54,9 @@ extern "C" {
                                  additions since 5 (input-image gradient): lf_stem_bwd_data, lf_erfnet_backward_input (and
                                  lf_erfnet_backward_range writes a non-NULL gx for first = 0);
                                  additions since 5 (frozen single-frame detector): lf_erfnet_infer_fold, lf_lane_infer_folded,
-                                 lf_lane_infer_seg_folded */
+                                 lf_lane_infer_seg_folded;
+                                 additions since 5 (frozen --clas heads): lf_convchain_infer_fold, lf_convchain_infer_folded,
+                                 lf_clas_tail_workspace_bytes, lf_clas_tail */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -706,6 +708,32 @@ int lf_lane_infer_seg_folded(const lf_erfnet_plan* plan, const float* img, const
                              long grid_batch_stride, const float* gt_line_or_null, int L, int zero_rows, int order, double reg_ls,
                              double y_offset, int use_cholesky, uint8_t* classes_or_null, double* beta, int32_t* status,
                              void* workspace, size_t workspace_bytes, int flags, void* stream);
+
+/* additions since 5 -- frozen --clas heads (the frozen single-frame detector carried through the line-type / horizon heads to the
+ * lanes of the frame):
+ * lf_convchain_infer_fold: the fold-table upload and the one fold-and-pack launch of lf_convchain_infer, in the plan's current
+ *   precision mode (lf_convchain_set_precision), into a workspace of lf_convchain_infer_workspace_bytes that the caller keeps.
+ *   Fold again after any change of a parameter, a running statistic or the plan's precision mode.
+ * lf_convchain_infer_folded: the convolution launches of lf_convchain_infer on such a workspace -- the same results bit for bit,
+ *   nothing uploaded, folded or allocated.  flags: LF_INFER_THIN, as for lf_lane_infer_folded.
+ * lf_clas_tail: everything behind the two trunks, three dependent launches.  y_line / y_hor (N,H,W,C) NHWC trunk outputs (fp32, or
+ *   bf16 elements with bf16 != 0; H and W even); w1 (O1, C*(H/2)*(W/2)), b1: fully_connected1 (+ReLU); wl (4, O1), bl:
+ *   fully_connected_line1; wh (R, C*H), bh: fully_connected_horizon; beta (N,L,order+1) fp64, L in 1..4; y_eval, y_prime (S), minv_host,
+ *   scale, lo, hi, fill as lf_lane_decode.  Outputs: line (N,4) and horizon (N,R) fp32 logits (the bits of lf_poolflat_* +
+ *   lf_linear_fwd), line_flags (N,4) fp32 = round(sigmoid(line)), horizon_row (N) int32 = round((sum sigmoid(horizon) * 2.5 + 80) /
+ *   10) * 10 (the sum in fp64, a fixed order), lanes (N,L,S) int32 = lf_lane_decode's x_int with line_flag[n][l] = line_flags[n][{1,2,0,3}[l]]
+ *   and bound[n] = trunc((horizon_row[n] - 160) / 10) (BP/test.py:60-88).  Workspace: lf_clas_tail_workspace_bytes; nothing persists
+ *   in it between calls. */
+int lf_convchain_infer_fold(const lf_convchain_plan* plan, const float* const* params_host, const float* const* params_dev,
+                            float* const* running_host, float eps, void* workspace, size_t workspace_bytes, void* stream);
+int lf_convchain_infer_folded(const lf_convchain_plan* plan, const float* x, float* y, void* workspace, size_t workspace_bytes,
+                              int flags, void* stream);
+size_t lf_clas_tail_workspace_bytes(int N, int H, int W, int C, int O1);
+int lf_clas_tail(const void* y_line, const void* y_hor, int bf16, int N, int H, int W, int C, const float* w1, const float* b1,
+                 int O1, const float* wl, const float* bl, const float* wh, const float* bh, int R, const double* beta, int L,
+                 int order, const double* y_eval, const double* y_prime, int S, const double* minv_host, double scale, double lo,
+                 double hi, double fill, float* line, float* horizon, float* line_flags, int32_t* horizon_row, int32_t* lanes,
+                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* additions since 5 -- input-image gradient: d loss / d input of Net.forward, what `input.requires_grad_()` before the forward and
  * `loss.backward()` (BEV/main.py:264-266) give in the reference -- the data gradient of the stem DownsamplerBlock's

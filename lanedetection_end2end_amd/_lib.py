@@ -143,6 +143,11 @@ def _declare(lib):
         "lf_erfnet_infer_fold": (I, [P, P, P, P, P, c_size_t, P]),
         "lf_lane_infer_folded": (I, [P, P, P, P, P, P, L, I, I, D, D, I, I, P, P, P, P, c_size_t, I, P]),
         "lf_lane_infer_seg_folded": (I, [P, P, P, P, P, P, L, P, I, I, I, D, D, I, P, P, P, P, c_size_t, I, P]),
+        "lf_convchain_infer_fold": (I, [P, P, P, P, ctypes.c_float, P, c_size_t, P]),
+        "lf_convchain_infer_folded": (I, [P, P, P, P, c_size_t, I, P]),
+        "lf_clas_tail_workspace_bytes": (c_size_t, [I, I, I, I, I]),
+        "lf_clas_tail": (I, [P, P, I, I, I, I, I, P, P, I, P, P, P, P, I, P, I, I, P, P, I, P, D, D, D, D, P, P, P, P, P, P,
+                             c_size_t, P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {

@@ -11,6 +11,10 @@ the backbone's ``precision = "bf16"`` it runs in the chain's precision mode 2 (b
 ``lf_convchain_set_precision``) and pooling reads bf16 (``lf_poolflat_bf16_*``); the features, the ``nn.Linear`` tails and
 the head outputs are fp32 in every mode.
 
+``FrozenHead`` is a head's trunk frozen for one input shape -- folded once into a persistent workspace, then the convolution launches
+alone per frame (``lf_convchain_infer_fold`` / ``lf_convchain_infer_folded``) -- which ``lsq.LaneDetector`` owns per head; its
+``lanes()`` runs everything behind the two trunks, down to the decoded lanes, as ``lf_clas_tail``.
+
 ``Projections`` mirrors BP/test.py:128-186 and ``decode_lanes`` fuses ``compute_coordinates`` for all lanes
 with the gating of ``test_model`` (BP/test.py:72-88) into one launch (``lf_lane_decode``).
 
@@ -230,13 +234,68 @@ class Classification(nn.Module):
         return y
 
     def forward(self, x, folded=None):
-        y = self.trunk(x, folded)
+        return self._tail(self.trunk(x, folded))
+
+    def frozen(self, N, H, W):
+        """This head frozen for (N, H, W, channels_in) NHWC encoder outputs: see ``FrozenHead`` (``lsq.LaneDetector`` owns one per
+        head)."""
+        return FrozenHead(self, N, H, W)
+
+    def _tail(self, y):
+        """Pooling + the fully connected layers on the trunk's NHWC output."""
         if self.class_type == 'line':
             f = _PoolFlatFn.apply(y, 0)
             f = ops.linear(f, self.fully_connected1.weight, self.fully_connected1.bias, relu=True)      # F.relu(fc1(f)), one launch
             return self._line_logits(f)
         f = _PoolFlatFn.apply(y, 1)
         return ops.linear(f, self.fully_connected_horizon.weight, self.fully_connected_horizon.bias)
+
+
+class FrozenHead:
+    """The conv trunk of one ``Classification`` head frozen for one input shape (``lf_convchain_infer_fold`` /
+    ``lf_convchain_infer_folded``): a chain plan of its own, ONE persistent workspace with every BatchNorm folded into its
+    convolution, the pointer tables and the trunk's output buffer.  ``fold(mode, device)`` does the fold-table upload and the
+    fold-and-pack launch (after any change of a parameter, a running statistic or the precision mode); ``run(xh, flags)`` is the
+    four convolution launches alone -- no fold, no upload, no allocation -- and returns the NHWC output buffer, which the next
+    ``run`` overwrites.  The bits are ``Classification.trunk(folded=True)``'s."""
+
+    def __init__(self, head, N, H, W):
+        self.head = head
+        self.plan = _ChainPlan(N, H, W, head._channels, (1, 3, 3, 3))
+        self.mode = None
+        self._ws = self.y = None
+
+    @torch.no_grad()
+    def fold(self, mode, device):
+        lib, head, plan = _lib.load(), self.head, self.plan
+        N, H, W = plan.shape
+        self.mode = mode
+        _lib.check(lib.lf_convchain_set_precision(plan.handle, mode), "lf_convchain_set_precision")
+        self.nbytes = lib.lf_convchain_infer_workspace_bytes(plan.handle, mode)
+        dtype = torch.bfloat16 if mode == 2 else torch.float32
+        if self._ws is None or self._ws.numel() != self.nbytes or self._ws.device != device:
+            self._ws = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
+        if self.y is None or self.y.dtype != dtype or self.y.device != device:
+            self.y = torch.empty(N, H, W, plan.channels[-1], dtype=dtype, device=device)
+        self._params = [p.detach() for p in head._trunk_params()]
+        for p in self._params:
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                raise _lib.LaneFitLibraryError("lanefit detector() needs the heads' parameters as contiguous fp32 tensors on the "
+                                               "MI355X; there is no CPU path")
+        bns = head._batchnorms()
+        self._running = [b for bn in bns for b in (bn.running_mean, bn.running_var)]
+        self._params_dev = torch.tensor([p.data_ptr() for p in self._params], dtype=torch.int64, device=device)
+        _lib.check(lib.lf_convchain_infer_fold(plan.handle, _ptr_array(self._params), _lib.ptr(self._params_dev),
+                                               _ptr_array(self._running), float(bns[0].eps), _lib.ptr(self._ws), self.nbytes,
+                                               _lib.stream()), "lf_convchain_infer_fold")
+        self._ptrs = (self.y.data_ptr(), self._ws.data_ptr())
+
+    def run(self, xh, flags):
+        """``xh``: the contiguous NHWC input of the plan's shape, fp32 (mode 0) or bf16 (mode 2); ``flags``: LF_INFER_THIN or 0."""
+        y, ws = self._ptrs
+        _lib.check(_lib.load().lf_convchain_infer_folded(self.plan.handle, xh.data_ptr(), y, ws, self.nbytes, flags, _lib.stream()),
+                   "lf_convchain_infer_folded")
+        return self.y
 
 
 class ClassificationBEV(Classification):

@@ -14,6 +14,7 @@
 
 #include <vector>
 
+#include "lf_clas_dev.h"
 #include "lf_conv.h"
 #include "lf_eltwise.h"
 #include "lf_plan.h"
@@ -63,20 +64,12 @@ int add_pack(lf_convchain_plan* P, int param, int Kc, int Nc, long sk, long sn, 
 // mode 0 ('line'):    MaxPool2d(2, 2)        NHWC (N,H,W,C) -> NCHW-flat (N, C*(H/2)*(W/2))
 // mode 1 ('horizon'): AvgPool2d((1, W))      NHWC (N,H,W,C) -> NCHW-flat (N, C*H)
 // T = the storage type of the NHWC tensor (float, or lf_bf16 in precision mode 2); the flat features and their gradient are fp32
+// (the forward bodies are lf_poolflat_*_at, lf_clas_dev.h: the fused --clas tail runs the same text)
 template <typename T>
 __global__ __launch_bounds__(256) void poolflat_max_fwd_kernel(const T* __restrict__ y, int N, int H, int W, int C,
                                                               float* __restrict__ out) {
-    const int Ho = H / 2, Wo = W / 2;
-    const long total = (long)N * C * Ho * Wo;
-    for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < total; u += (long)gridDim.x * 256) {
-        const int j = (int)(u % Wo);
-        long r = u / Wo;
-        const int i = (int)(r % Ho);
-        r /= Ho;
-        const int c = (int)(r % C), n = (int)(r / C);
-        const T* b = y + (((long)n * H + 2 * i) * W + 2 * j) * C + c;
-        out[u] = fmaxf(fmaxf(lf_ld1(b), lf_ld1(b + C)), fmaxf(lf_ld1(b + (long)W * C), lf_ld1(b + (long)W * C + C)));
-    }
+    const long total = (long)N * C * (H / 2) * (W / 2);
+    for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < total; u += (long)gridDim.x * 256) out[u] = lf_poolflat_max_at(y, u, H, W, C);
 }
 template <typename T>
 __global__ __launch_bounds__(256) void poolflat_max_bwd_kernel(const T* __restrict__ y, const float* __restrict__ g,
@@ -108,13 +101,9 @@ __global__ __launch_bounds__(256) void poolflat_avg_fwd_kernel(const T* __restri
                                                               float* __restrict__ out) {
     const long total = (long)N * H * C;
     for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < total; u += (long)gridDim.x * 256) {
-        const int c = (int)(u % C);
-        const long r = u / C;
-        const int i = (int)(r % H), n = (int)(r / H);
-        const T* b = y + ((long)n * H + i) * W * C + c;
-        float s = 0.f;
-        for (int j = 0; j < W; ++j) s += lf_ld1(b + (long)j * C);
-        out[((long)n * C + c) * H + i] = s / (float)W;
+        long o;
+        const float v = lf_poolflat_avg_at(y, u, H, W, C, &o);
+        out[o] = v;
     }
 }
 template <typename T>
@@ -309,21 +298,18 @@ size_t lf_convchain_infer_workspace_bytes(const lf_convchain_plan* P, int mode) 
     return (size_t)chain_infer_layout(P, mode).total;
 }
 
-// x, y as lf_convchain_forward (bf16 elements in mode 2, x read in place); running statistics are read, never written.
-int lf_convchain_infer(const lf_convchain_plan* P, const float* x, const float* const* params_host, const float* const* params_dev,
-                       float* const* running_host, float eps, float* y, void* workspace, size_t workspace_bytes, void* stream) {
-    LF_REQUIRE(P && x && params_host && params_dev && running_host && y && workspace, "lf_convchain_infer: null pointer");
-    const int mode = P->precision, s16 = mode == 2;
-    const ChainInferLayout L = chain_infer_layout(P, mode);
-    LF_REQUIRE(workspace_bytes >= (size_t)L.total, "lf_convchain_infer: workspace too small (%zu < %ld)", workspace_bytes, L.total);
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
+}  // extern "C"
+namespace {
+// the fold of one call: the fold table with this call's pointers uploaded, then the one fold-and-pack launch into the workspace
+int chain_fold(const char* what, const lf_convchain_plan* P, const ChainInferLayout& L, const float* const* params_host,
+               const float* const* params_dev, float* const* running_host, float eps, char* ws, hipStream_t st) {
+    const int s16 = P->precision == 2;
     std::vector<const void*> key;
     for (int i = 0; i < 4 * P->L; ++i) key.push_back(params_host[i]);
     for (int i = 0; i < 2 * P->L; ++i) key.push_back(running_host[i]);
     if (key != P->fold_key) {
         // (the table is uploaded from this vector: let an earlier upload of it finish before it is rewritten)
-        if (!P->fold_key.empty() && hipStreamSynchronize(st) != hipSuccess) return lf_fail("lf_convchain_infer: stream synchronisation failed");
+        if (!P->fold_key.empty() && hipStreamSynchronize(st) != hipSuccess) return lf_fail("%s: stream synchronisation failed", what);
         P->fold_call = P->fold;
         for (int i = 0; i < P->L; ++i) {
             LfFoldEntry& f = P->fold_call[i];
@@ -333,10 +319,16 @@ int lf_convchain_infer(const lf_convchain_plan* P, const float* x, const float* 
         P->fold_key = key;
     }
     if (hipMemcpyAsync(ws + L.table, P->fold_call.data(), P->fold_call.size() * sizeof(LfFoldEntry), hipMemcpyHostToDevice, st) != hipSuccess)
-        return lf_fail("lf_convchain_infer: upload of the fold table failed");
+        return lf_fail("%s: upload of the fold table failed", what);
     float* vec = reinterpret_cast<float*>(ws + L.vec);
     LF_TRY(lf_fold_pack_launch(reinterpret_cast<const LfFoldEntry*>(ws + L.table), P->L, params_dev, eps, vec,
                                s16 ? nullptr : reinterpret_cast<float*>(ws + L.arena), s16 ? ws + L.arena : nullptr, nullptr, st));
+    return 0;
+}
+// the per-block tap-GEMM launches on a folded workspace; thin: LfTapArgs::thin of every launch (the routers decide)
+int chain_run(const lf_convchain_plan* P, const ChainInferLayout& L, const float* x, float* y, char* ws, int thin, hipStream_t st) {
+    const int s16 = P->precision == 2;
+    const float* vec = reinterpret_cast<const float*>(ws + L.vec);
     const float* src = x;
     for (int i = 0; i < P->L; ++i) {
         const LfFoldEntry& f = P->fold[i];
@@ -345,12 +337,46 @@ int lf_convchain_infer(const lf_convchain_plan* P, const float* x, const float* 
         a.dst = i == P->L - 1 ? y : reinterpret_cast<float*>(ws + L.buf[i & 1]);
         a.bias = vec + f.out_off;
         a.s16 = s16;
+        a.thin = thin;
         if (s16) a.wp16 = reinterpret_cast<const unsigned short*>(ws + L.arena) + f.pk.dst16_off;
         else a.wp = reinterpret_cast<const float*>(ws + L.arena) + f.pk.dst_off;
         LF_TRY(lf_tapgemm_launch(P->fwd[i], a, LF_PRO_NONE, LF_EPI_RELU, st));
         src = a.dst;
     }
     return 0;
+}
+}  // namespace
+extern "C" {
+
+// x, y as lf_convchain_forward (bf16 elements in mode 2, x read in place); running statistics are read, never written.
+int lf_convchain_infer(const lf_convchain_plan* P, const float* x, const float* const* params_host, const float* const* params_dev,
+                       float* const* running_host, float eps, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    LF_REQUIRE(P && x && params_host && params_dev && running_host && y && workspace, "lf_convchain_infer: null pointer");
+    const ChainInferLayout L = chain_infer_layout(P, P->precision);
+    LF_REQUIRE(workspace_bytes >= (size_t)L.total, "lf_convchain_infer: workspace too small (%zu < %ld)", workspace_bytes, L.total);
+    hipStream_t st = (hipStream_t)stream;
+    LF_TRY(chain_fold("lf_convchain_infer", P, L, params_host, params_dev, running_host, eps, (char*)workspace, st));
+    return chain_run(P, L, x, y, (char*)workspace, 0, st);
+}
+
+// include/lanefit.h, "additions since 5 -- frozen --clas heads": the fold of lf_convchain_infer alone, into a workspace the caller
+// keeps (the plan's current precision mode) ...
+int lf_convchain_infer_fold(const lf_convchain_plan* P, const float* const* params_host, const float* const* params_dev,
+                            float* const* running_host, float eps, void* workspace, size_t workspace_bytes, void* stream) {
+    LF_REQUIRE(P && params_host && params_dev && running_host && workspace, "lf_convchain_infer_fold: null pointer");
+    const ChainInferLayout L = chain_infer_layout(P, P->precision);
+    LF_REQUIRE(workspace_bytes >= (size_t)L.total, "lf_convchain_infer_fold: workspace too small (%zu < %ld)", workspace_bytes, L.total);
+    return chain_fold("lf_convchain_infer_fold", P, L, params_host, params_dev, running_host, eps, (char*)workspace, (hipStream_t)stream);
+}
+
+// ... and its convolution launches alone on such a workspace: nothing uploaded, folded or allocated.  flags: LF_INFER_THIN.
+int lf_convchain_infer_folded(const lf_convchain_plan* P, const float* x, float* y, void* workspace, size_t workspace_bytes, int flags,
+                              void* stream) {
+    LF_REQUIRE(P && x && y && workspace, "lf_convchain_infer_folded: null pointer");
+    LF_REQUIRE((flags & ~LF_INFER_THIN) == 0, "lf_convchain_infer_folded: unknown flags %d", flags);
+    const ChainInferLayout L = chain_infer_layout(P, P->precision);
+    LF_REQUIRE(workspace_bytes >= (size_t)L.total, "lf_convchain_infer_folded: workspace too small (%zu < %ld)", workspace_bytes, L.total);
+    return chain_run(P, L, x, y, (char*)workspace, (flags & LF_INFER_THIN) != 0, (hipStream_t)stream);
 }
 
 // Backward of the forward that last used `workspace`.  gy (N,H,W,C_L) NHWC; grads_host: 4*L device pointers

@@ -12,6 +12,7 @@
 // per (image, lane).  One pass over the logits (4 B/pixel) + the shared L2-resident grid;
 // masked rows are never read.  Accumulation is fp64 (the reference's fp32 bmm over 131k
 // pixels is the source of its 5e-5..1e-4 noise floor); HBM-bound.
+#include "lf_clas_dev.h"
 #include "lf_common.h"
 #include "lf_solve.h"
 #include "lf_types.h"
@@ -1398,24 +1399,14 @@ __global__ __launch_bounds__(256) void lane_decode_kernel(const double* __restri
                                                          double lo, double hi, double fill, int N, int L, int S, int order,
                                                          double* __restrict__ x_out, int* __restrict__ x_int) {
     const long total = (long)N * L * S;
+    const LfDecodeConsts c = {m0, m1, m2, m6, m7, m8, scale, lo, hi, fill};
     for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < total; u += (long)gridDim.x * 256) {
         const int s = (int)(u % S);
         const long nl = u / S;
         const int n = (int)(nl / L);
-        const double* b = beta + nl * (order + 1);
-        const double ye = y_eval[s];
-        double xp = b[0];
-        for (int k = 1; k <= order; ++k) xp = xp * ye + b[k];          // highest power first, as Projections.Y
-        const double yp = y_prime[s];
-        double x = (m0 * xp + m1 * yp + m2) / (m6 * xp + m7 * yp + m8) * scale;
-        if (line_flag && line_flag[nl] == 0.f) x = fill;
-        if (bound) {
-            int bd = bound[n];                                          // python slice [:bd]
-            if (bd < 0) bd = S + bd < 0 ? 0 : S + bd;
-            if (s < bd) x = fill;
-        }
-        if (x > hi) x = fill;
-        if (x < lo) x = fill;
+        // (the arithmetic and the gates: lf_lane_decode_at, lf_clas_dev.h -- the fused --clas tail runs the same text)
+        const double x = lf_lane_decode_at(beta + nl * (order + 1), order, y_eval[s], y_prime[s], c, line_flag && line_flag[nl] == 0.f,
+                                           bound != nullptr, bound ? bound[n] : 0, s, S);
         if (x_out) x_out[u] = x;
         if (x_int) x_int[u] = (int)rint(x);                             // np.round: half to even
     }

@@ -9,62 +9,23 @@
 //    per-lane maps valued k where the arg-max is k, the masked top rows zeroed, and the BP tree's "prevent singular matrix"
 //    overwrite of flagged lanes with map [0, 0] (BEV/Networks/LSQ_layer.py:302-308, BP/Networks/LSQ_layer.py:279-293,308-311)
 //    -- one elementwise launch instead of argmax / compare / stack / index_put, and no host read of gt_line.sum().
+#include "lf_clas_dev.h"
 #include "lf_common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int NB = 8;      // batch rows per workgroup (forward, data gradient)
+constexpr int NB = LF_LINEAR_NB;      // batch rows per workgroup (forward, data gradient)
 constexpr int OB = 4;      // output features per thread (weight gradient)
 
-__device__ __forceinline__ float block_sum_256(float v, float* sm) {      // sum over 256 threads, fixed order
-    v = lf_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-    __syncthreads();
-    return r;
-}
-
 // y[n][o] = act(b[o] + sum_k x[n][k] * w[o][k]); grid (O, ceil(N / NB)); the weight row is read once per workgroup
+// (the body is lf_linear_rows, lf_clas_dev.h: the fused --clas tail runs the same text)
 __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ b, float* __restrict__ y, int N, int K, int O,
                                                         int relu) {
-    const int o = blockIdx.x, n0 = blockIdx.y * NB;
-    float acc[NB];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) acc[j] = 0.f;
-    const float* wr = w + (long)o * K;
-    if ((K & 3) == 0) {
-        for (int k = threadIdx.x * 4; k < K; k += 1024) {
-            const f32x4 wv = *reinterpret_cast<const f32x4*>(wr + k);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                if (n0 + j < N) {
-                    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (long)(n0 + j) * K + k);
-                    acc[j] = fmaf(xv.x, wv.x, fmaf(xv.y, wv.y, fmaf(xv.z, wv.z, fmaf(xv.w, wv.w, acc[j]))));
-                }
-            }
-        }
-    } else {
-        for (int k = threadIdx.x; k < K; k += 256) {
-            const float wv = wr[k];
-#pragma unroll
-            for (int j = 0; j < NB; ++j)
-                if (n0 + j < N) acc[j] = fmaf(x[(long)(n0 + j) * K + k], wv, acc[j]);
-        }
-    }
     __shared__ float sm[4];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const float s = block_sum_256(acc[j], sm);
-        if (threadIdx.x == 0 && n0 + j < N) {
-            float v = s + (b ? b[o] : 0.f);
-            if (relu) v = fmaxf(v, 0.f);
-            y[(long)(n0 + j) * O + o] = v;
-        }
-    }
+    lf_linear_rows(x, w, b, y, N, K, O, relu, blockIdx.x, blockIdx.y * NB, sm);
 }
 
 // gym[n][o] = gy[n][o] * [y[n][o] > 0] (relu) -- applied on the fly below

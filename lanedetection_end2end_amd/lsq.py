@@ -3,14 +3,16 @@ BEV flavour (normalised coordinates, fp32 betas) and BP flavour (pixel coordinat
 
 Reference: BEV/Networks/LSQ_layer.py:231-326, BP/Networks/LSQ_layer.py:210-315.
 """
+from collections import namedtuple
 from math import ceil
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import erfnet, fit, geometry, ops
-from .clas import Classification, ClassificationBEV
+from .clas import Classification, ClassificationBEV, Projections
 
 
 def activation_layer(activation='square', no_cuda=False):
@@ -227,6 +229,16 @@ THIN_AUTO_MAX_BATCH = 8
 # ... and of the thin bf16 route (tapgemm_bf16_thin_kernel) in precision mode bf16, by the same rule (profiles/detector_latency_bf16_thin.json):
 # it won at 1, 2 and 4 at both sizes; at 8 it won at 256 x 512 (0.723 against 0.842 ms) and lost at 320 x 640 (1.070 against 0.977 ms)
 THIN_AUTO_MAX_BATCH_BF16 = 4
+# ... and of the --clas heads' conv trunks inside the detector (lf_convchain_infer_folded with LF_INFER_THIN), per precision mode, by the
+# same rule at batch 1, 2, 4 and 8 on the BP recipe at 256 x 512 (tools/detector_latency.py --lanes, profiles/detector_lanes_latency.json,
+# key heads_thin_auto_max_batch_by_precision): thin heads won at all four batches in both modes, behind the hand-written tail and
+# behind lf_clas_tail alike (fp32 batch 1: 0.665 against 1.025 ms; bf16 batch 8: 1.071 against 1.118 ms).  None would mean "not
+# measured": the heads follow the backbone's flag; 0: "auto" never routes them.  thin=True always asks for it
+THIN_AUTO_MAX_BATCH_HEADS = 8
+THIN_AUTO_MAX_BATCH_HEADS_BF16 = 8
+
+# what LaneDetector.lanes returns
+FrameLanes = namedtuple("FrameLanes", ["lanes", "betas", "line", "horizon", "line_flags", "horizon_row"])
 
 
 class LaneDetector:
@@ -242,7 +254,14 @@ class LaneDetector:
     with ``set_homography``).  A call validates the input's shape, allocates ``beta`` and ``status`` and makes one C call
     (``lf_lane_infer_folded``; segmentation-mode models: ``lf_lane_infer_seg_folded`` at every batch size, the bits of
     ``detect``'s three-step path at batch 1 too).  The ``--clas`` heads run as in ``detect``, on the encoder output inside the
-    detector's workspace; their own per-call fold stays.
+    detector's workspace, frozen too: per head the detector owns a chain plan, a persistent workspace folded in ``refresh()``
+    (``lf_convchain_infer_fold``), the pointer tables and the trunk's output buffer, and a call runs the four convolution launches
+    alone (``lf_convchain_infer_folded``) -- no fold, no upload, no workspace allocation -- with the detector's thin flag.
+
+    ``det.lanes(input, out=None)`` (BP tree, end-to-end, ``--clas``) goes on to what ``BP/test.py`` writes per frame: the 56
+    x-coordinates of every lane in the 1280 x 720 frame, gated by the line-type and horizon heads -- the backbone call, the two
+    trunks and ONE fused tail (``lf_clas_tail``: pooling, the fully connected layers, ``horizon_row``, ``line_flags`` and
+    ``Projections.decode_lanes`` in three launches).
 
     ``refresh()`` MUST be called after any change of a parameter, a running statistic, the homography or ``model.net.precision``
     (``load_state_dict``, a training step, ``set_homography``, ``.to()``): nothing is checked per call, and what an un-refreshed
@@ -251,8 +270,9 @@ class LaneDetector:
     ``thin``: ``True`` / ``False`` route / do not route the tap-GEMM launches whose regular grid cannot fill the device to the thin
     kernel of the precision mode (one 16-pixel tile per wave; the same bits): ``tapgemm_thin_kernel`` in ``fp32``,
     ``tapgemm_bf16_thin_kernel`` in ``bf16``; ``"auto"``: on for batches up to ``THIN_AUTO_MAX_BATCH`` (``fp32``) /
-    ``THIN_AUTO_MAX_BATCH_BF16`` (``bf16``).  There is no thin kernel for the split operands of ``fp32x9``: there the detector
-    gives fold-once only, whatever ``thin`` says.
+    ``THIN_AUTO_MAX_BATCH_BF16`` (``bf16``); the ``--clas`` heads' trunks follow ``thin`` too, ``"auto"`` up to
+    ``THIN_AUTO_MAX_BATCH_HEADS`` / ``THIN_AUTO_MAX_BATCH_HEADS_BF16``.  There is no thin kernel for the split operands of
+    ``fp32x9``: there the detector gives fold-once only, whatever ``thin`` says.
 
     The results of a call live in fresh tensors; the workspace is the detector's, so calls of ONE detector must be issued on one
     stream (or ordered by the caller).  Detectors of one model are independent of each other and of ``detect``."""
@@ -267,6 +287,9 @@ class LaneDetector:
         self.shape = (int(batch), int(model.net.in_channels), int(height), int(width))
         self.thin = thin
         self.last_status = None
+        # False: det(frame) runs the --clas heads as model.detect does (their fold, upload and workspace on every call) -- the same
+        # bits; tests and tools/detector_latency.py --lanes alternate the two in one process
+        self.frozen_heads = True
         self._plan = erfnet._Plan(self.shape[0], self.shape[2], self.shape[3], model.net.in_channels, model.net.out_channels,
                                   2 if model.net.pretrained else 1)
         self.refresh()
@@ -324,10 +347,22 @@ class LaneDetector:
         auto_max = {"fp32": THIN_AUTO_MAX_BATCH, "bf16": THIN_AUTO_MAX_BATCH_BF16}.get(self.precision)
         thin_on = auto_max is not None and (self.thin is True or (self.thin == "auto" and N <= auto_max))
         self._flags = 1 if thin_on else 0          # LF_INFER_THIN
-        self._enc = None
+        self._enc = self._heads = self._lanes_state = None
         if model.classification_branch and not self._seg:
-            # logical NCHW, channels-last memory (as Net.forward hands it out): a view of the detector's own workspace
-            self._enc = net._infer_encoder_view(self._plan, self._ws, self._mode).permute(0, 3, 1, 2)
+            # the NHWC encoder output: a view of the detector's own workspace; _enc is its logical-NCHW form (as Net.forward hands it out)
+            self._enc_nhwc = net._infer_encoder_view(self._plan, self._ws, self._mode)
+            self._enc = self._enc_nhwc.permute(0, 3, 1, 2)
+            auto_heads = {"fp32": THIN_AUTO_MAX_BATCH_HEADS, "bf16": THIN_AUTO_MAX_BATCH_HEADS_BF16}.get(self.precision)
+            if self.thin == "auto" and auto_heads is not None:
+                self._head_flags = 1 if N <= auto_heads else 0
+            else:
+                self._head_flags = self._flags        # (thin=True always asks; an unmeasured "auto" follows the backbone)
+            if self.__dict__.get("_frozen") is None:
+                eh, ew = self._enc_nhwc.shape[1:3]
+                self._frozen = tuple(h.frozen(N, eh, ew) for h in (model.line_classification, model.horizon_estimation))
+            for f in self._frozen:
+                f.fold(2 if self._enc_nhwc.dtype == torch.bfloat16 else 0, dev)
+            self._heads = (model.line_classification, model.horizon_estimation)
         self._dev = dev
         self._ptrs = (erfnet._lib.ptr(self._params_dev), erfnet._lib.ptr(self._grid), erfnet._lib.ptr(self._ws))
 
@@ -356,11 +391,23 @@ class LaneDetector:
     @torch.no_grad()
     def __call__(self, input, gt_line=None):
         x = self._input(input)
-        model, lib, N = self.model, erfnet._lib.load(), self.shape[0]
-        params_dev, grid, ws = self._ptrs
+        model, N = self.model, self.shape[0]
         if self._seg:
             beta, _ = self._seg_call(x, ops.seg_flags(gt_line, N, self._lanes, self._dev), False, model.check_singular)
             return fit.split_lanes(beta, model.nclasses, model.beta_dtype) + (None, None)
+        beta, status = self._backbone(x)
+        self._finish(status, model.check_singular)
+        line = horizon = None
+        if self._enc is not None and not self.frozen_heads:
+            line, horizon = model.line_classification(self._enc, folded=True), model.horizon_estimation(self._enc, folded=True)
+        elif self._enc is not None:
+            line, horizon = (h._tail(f.run(self._enc_nhwc, self._head_flags)) for h, f in zip(self._heads, self._frozen))
+        return fit.split_lanes(beta, model.nclasses, model.beta_dtype) + (line, horizon)
+
+    def _backbone(self, x):
+        """The backbone call of one frame: -> (beta (N,K,order+1) fp64, status); the encoder output is left in the workspace."""
+        model, lib, N = self.model, erfnet._lib.load(), self.shape[0]
+        params_dev, grid, ws = self._ptrs
         K = model.net.out_channels
         beta = torch.empty(N, K, self._order + 1, dtype=torch.float64, device=self._dev)
         status = torch.empty(N * K, dtype=torch.int32, device=self._dev)
@@ -368,11 +415,73 @@ class LaneDetector:
                                                    grid, self._gstride, self._zero_rows, self._order, self._reg, self._y_offset,
                                                    self._act, self._chol, None, beta.data_ptr(), status.data_ptr(), ws, self._nbytes,
                                                    self._flags, erfnet._lib.stream()), "lf_lane_infer_folded")
+        return beta, status
+
+    def _lanes_setup(self):
+        """What ``lanes`` needs beside the heads, built on its first call after a ``refresh()``: the fully connected layers'
+        tensors, the sample heights and M_inv of ``Projections``, the fused tail's workspace."""
+        model, lib = self.model, erfnet._lib.load()
+        if self._enc is None:
+            why = ("a segmentation-mode model (end_to_end=False) has no line-type / horizon heads to gate the lanes with" if self._seg
+                   else "the model was built without --clas: there are no line-type / horizon heads to gate the lanes with")
+            raise RuntimeError("lanefit detector.lanes(): " + why)
+        if model.normalised:
+            raise RuntimeError("lanefit detector.lanes() is for the BP tree: the BEV tree's lane decoding is gated by ground-truth "
+                               "labels (ProjectionsBEV.decode_lanes)")
+        line, hor = self._heads
+        fc = [t.detach() for t in (line.fully_connected1.weight, line.fully_connected1.bias, line.fully_connected_line1.weight,
+                                   line.fully_connected_line1.bias, hor.fully_connected_horizon.weight, hor.fully_connected_horizon.bias)]
+        for t in fc:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise erfnet._lib.LaneFitLibraryError("lanefit detector.lanes() needs the heads' parameters as contiguous fp32 tensors "
+                                                      "on the MI355X; there is no CPU path")
+        proj = Projections(SimpleNamespace(resize=model.resize, order=model.order))
+        y_eval, y_prime = proj._device_consts(self._dev)
+        N, eh, ew, C = self._frozen[0].y.shape
+        O1, R = fc[0].shape[0], fc[4].shape[0]
+        nbytes = lib.lf_clas_tail_workspace_bytes(N, eh, ew, C, O1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self._dev)
+        self._lanes_state = dict(fc=fc, proj=proj, y_eval=y_eval, y_prime=y_prime, ws=ws, nbytes=nbytes, dims=(N, eh, ew, C, O1, R),
+                                 S=proj.num_heights)
+        return self._lanes_state
+
+    @torch.no_grad()
+    def lanes(self, input, out=None):
+        """One frame -> ``FrameLanes(lanes, betas, line, horizon, line_flags, horizon_row)``: what ``BP/test.py`` writes per frame.
+        ``lanes`` (N, L, 56) int32: the x-coordinates of every lane at the heights 160, 170, .. 710 of the 1280 x 720 frame, -2 where
+        ``test_model`` writes -2 (line-type flag 0, above the horizon row, outside the frame); ``out``: a contiguous (N, L, 56) int32
+        device tensor of the caller's (a slice of a buffer for the whole test set, say) that receives them in place.  ``betas``
+        (the four per-lane tensors), ``line`` (N, 4) and ``horizon`` (N, resize) are ``det(input)``'s, bit for bit;
+        ``line_flags`` (N, 4) fp32 is ``clas.line_flags(line)``, ``horizon_row`` (N) int32 ``clas.horizon_row(horizon)`` with the
+        sum of sigmoids taken in fp64.  BP-tree end-to-end ``--clas`` models only (``RuntimeError`` otherwise).  ``last_status``
+        and ``check_singular`` behave as in ``det(input)``.  The call: ``lf_lane_infer_folded``, two ``lf_convchain_infer_folded``
+        and ``lf_clas_tail``."""
+        x = self._input(input)
+        st = self._lanes_state or self._lanes_setup()
+        model, lib = self.model, erfnet._lib.load()
+        beta, status = self._backbone(x)
         self._finish(status, model.check_singular)
-        line = horizon = None
-        if self._enc is not None:
-            line, horizon = model.line_classification(self._enc, folded=True), model.horizon_estimation(self._enc, folded=True)
-        return fit.split_lanes(beta, model.nclasses, model.beta_dtype) + (line, horizon)
+        y_line, y_hor = (f.run(self._enc_nhwc, self._head_flags) for f in self._frozen)
+        N, eh, ew, C, O1, R = st["dims"]
+        L, S, dev = beta.shape[1], st["S"], self._dev
+        if L > 4:
+            raise RuntimeError("lanefit detector.lanes(): %d lanes, the line-type head flags 4" % L)
+        line = torch.empty(N, 4, dtype=torch.float32, device=dev)
+        horizon = torch.empty(N, R, dtype=torch.float32, device=dev)
+        flags = torch.empty(N, 4, dtype=torch.float32, device=dev)
+        row = torch.empty(N, dtype=torch.int32, device=dev)
+        if out is None:
+            out = torch.empty(N, L, S, dtype=torch.int32, device=dev)
+        elif not (out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (N, L, S) and out.is_contiguous()):
+            raise ValueError("detector.lanes(out=...) takes a contiguous (%d, %d, %d) int32 tensor on the device" % (N, L, S))
+        w1, b1, wl, bl, wh, bh = st["fc"]
+        erfnet._lib.check(lib.lf_clas_tail(y_line.data_ptr(), y_hor.data_ptr(), int(y_line.dtype == torch.bfloat16), N, eh, ew, C,
+                                           w1.data_ptr(), b1.data_ptr(), O1, wl.data_ptr(), bl.data_ptr(), wh.data_ptr(), bh.data_ptr(),
+                                           R, beta.data_ptr(), L, self._order, st["y_eval"].data_ptr(), st["y_prime"].data_ptr(), S,
+                                           st["proj"]._minv, 2.5, 0.0, 1279.0, -2.0, line.data_ptr(), horizon.data_ptr(),
+                                           flags.data_ptr(), row.data_ptr(), out.data_ptr(), st["ws"].data_ptr(), st["nbytes"],
+                                           erfnet._lib.stream()), "lf_clas_tail")
+        return FrameLanes(out, fit.split_lanes(beta, model.nclasses, model.beta_dtype), line, horizon, flags, row)
 
     @torch.no_grad()
     def segment(self, input):

@@ -19,8 +19,18 @@ agree and the host is the limit.  ``thin_auto_max_batch``: the largest batch amo
 ``thin_auto_max_batch_by_precision`` has both.  A run of --precisions bf16 alone writes profiles/detector_latency_bf16_thin.json
 and leaves the fp32 file as it is.
 
-    rocprofv3 --kernel-trace --stats -d DIR -o trace -- python tools/detector_latency.py --trace A|C
+    python tools/detector_latency.py --lanes [--out profiles/detector_lanes_latency.json] [--precisions fp32,bf16] [--batches 1,2,4,8]
+
+--lanes: one frame -> the lanes BP/test.py writes, on the BP tree's deployment recipe (4 lanes, order 3, --clas, 1 x 256 x 512).  Three
+ways alternated in one process by the same protocol: (A) the detector with its --clas heads run as ``model.detect`` runs them (their
+fold, upload and workspace on every call: ``frozen_heads = False``), then ``horizon_row`` / ``line_flags`` / ``decode_lanes`` as
+``test_model`` issues them; (B) ``det(frame)`` with frozen heads, then the same hand-written tail; (C) ``det.lanes(frame)``.  (B) and
+(C) are measured with the heads' trunks on the regular tiling and on the thin route (the backbone is thin="auto" in all five), which
+decides lsq.THIN_AUTO_MAX_BATCH_HEADS / _BF16 by the rule above.  ``gain`` is stated only where the min-max ranges do not overlap.
+
+    rocprofv3 --kernel-trace --stats -d DIR -o trace -- python tools/detector_latency.py --trace A|C|L
     python tools/detector_latency.py --launches DB_A DB_C [--out profiles/detector_launches.md]
+    python tools/detector_latency.py --lanes-launches DB_L [--out profiles/detector_launches.md]      (appends the list of --trace L)
 
 The launch table: ten batch-1 calls at 1 x 256 x 512 fp32 of path (A) / (C) under the profiler (no counters), then per-kernel count
 and duration of the two runs side by side from their rocpd databases.
@@ -57,7 +67,10 @@ def commit_stamp():
         return "unknown"
 
 
-def make_model(cfg, precision, N):
+LANES_CFG = dict(name="bp_4lanes_order3_clas_256x512", tree="bp", K=4, order=3, H=256, W=512, mask=0.2)
+
+
+def make_model(cfg, precision, N, clas=False):
     import torch
     from oracle import erfnet_oracle
     if cfg["tree"] == "bev":
@@ -66,10 +79,14 @@ def make_model(cfg, precision, N):
         from lanedetection_end2end_amd.bp.Networks.LSQ_layer import Net
     args = Namespace(batch_size=N, nclasses=cfg["K"], resize=cfg["H"], end_to_end=True, mod="erfnet", layers=18, channels_in=3,
                      pretrained=False, pool=True, activation_layer="square", no_cuda=False, order=cfg["order"], reg_ls=0.0,
-                     use_cholesky=False, mask_percentage=cfg["mask"], clas=False, no_mapping=False, loss_policy="backproject",
+                     use_cholesky=False, mask_percentage=cfg["mask"], clas=clas, no_mapping=False, loss_policy="backproject",
                      weight_seg=30, weight_funct="none", precision=precision)
     model = Net(args)
     model.net.load_state_dict(erfnet_oracle.make_params(seed=3, out_channels=cfg["K"]))
+    if clas:
+        from oracle import clas_oracle
+        model.line_classification.load_state_dict(clas_oracle.make_clas_params("line", seed=11))
+        model.horizon_estimation.load_state_dict(clas_oracle.make_clas_params("horizon", seed=12))
     g = torch.Generator().manual_seed(5)
     with torch.no_grad():           # non-trivial running statistics (the cost does not depend on them)
         for m in model.net.modules():
@@ -183,10 +200,142 @@ def run(args):
     print(json.dumps({"thin_auto_max_batch": bound, "by_precision": bounds}))
 
 
+def lanes_paths(model, N):
+    """The five ways of --lanes, each frame -> (N, 4, 56) int32 lanes."""
+    import torch
+    from lanedetection_end2end_amd import clas
+    cfg = LANES_CFG
+    proj = clas.Projections(Namespace(resize=cfg["H"], order=cfg["order"]))
+    buf = torch.empty(N, cfg["K"], 56, dtype=torch.int32, device="cuda")
+
+    def detector(frozen, heads_thin):
+        det = model.detector(batch=N, height=cfg["H"], width=cfg["W"], thin="auto")
+        det.frozen_heads = frozen
+        det._head_flags = int(heads_thin)          # (tool only: the heads' LF_INFER_THIN apart from the backbone's)
+        return det
+
+    def hand_tail(det):
+        def call(x):      # the tail of bp/test.py::test_model
+            b0, b1, b2, b3, line, horizon = det(x)
+            row = clas.horizon_row(horizon)
+            flags = clas.line_flags(line)
+            proj.decode_lanes([b0, b1, b2, b3], flags, row, out_int=buf)
+            return buf
+        return call
+
+    def fused(det):
+        return lambda x: det.lanes(x, out=buf).lanes
+    return {"A_unfrozen_heads_hand_tail": hand_tail(detector(False, False)),
+            "B_frozen_heads_hand_tail": hand_tail(detector(True, False)),
+            "B_frozen_heads_thin_hand_tail": hand_tail(detector(True, True)),
+            "C_lanes": fused(detector(True, False)),
+            "C_lanes_heads_thin": fused(detector(True, True))}
+
+
+def measure_lanes(precision, N, warmup, calls, repeats):
+    import torch
+    from oracle import inputs
+    cfg = LANES_CFG
+    model = make_model(cfg, precision, N, clas=True)
+    x = torch.from_numpy(inputs.images(N, cfg["H"], cfg["W"], seed=1)).cuda()
+    paths = lanes_paths(model, N)
+    ref = paths["A_unfrozen_heads_hand_tail"](x).clone()
+    for name, fn in paths.items():      # the five ways give the same lanes
+        assert torch.equal(fn(x), ref), name
+    ev = {k: [] for k in paths}
+    wall = {k: [] for k in paths}
+    for _ in range(repeats):
+        for name, fn in paths.items():
+            for _ in range(warmup):
+                fn(x)
+            e, w = timed(fn, x, calls)
+            ev[name].append(e)
+            wall[name].append(w)
+    row = {"config": cfg["name"], "precision": precision, "batch": N}
+    for name in paths:
+        row[name] = {"in_stream_ms": stats(ev[name]), "wall_ms": stats(wall[name])}
+    a = row["A_unfrozen_heads_hand_tail"]["in_stream_ms"]
+    for name in paths:
+        if name[0] != "A":      # a gain only where the min-max ranges do not overlap
+            s = row[name]["in_stream_ms"]
+            row[name]["against_A"] = ("gain" if s["max"] < a["min"] else "loss" if s["min"] > a["max"] else "ranges overlap")
+            row[name]["median_ratio_to_A"] = round(s["median"] / a["median"], 4)
+    row["heads_thin_wins"] = all(row[t]["in_stream_ms"]["max"] < row[r]["in_stream_ms"]["min"] for r, t in
+                                 (("B_frozen_heads_hand_tail", "B_frozen_heads_thin_hand_tail"), ("C_lanes", "C_lanes_heads_thin")))
+    del model, paths, x
+    torch.cuda.empty_cache()
+    return row
+
+
+def run_lanes(args):
+    import torch
+    rows = []
+    precisions = args.precisions.split(",")
+    batches = [int(b) for b in args.batches.split(",") if int(b) <= 8]
+    for precision in precisions:
+        for N in batches:
+            rows.append(measure_lanes(precision, N, args.warmup, args.calls, args.repeats))
+            print(json.dumps(rows[-1]), flush=True)
+    bounds = {}
+    for precision in precisions:      # the rule of thin_auto_max_batch: the largest batch up to which the thin route won at every batch
+        bounds[precision] = 0
+        for N in (1, 2, 4, 8):
+            at = [r for r in rows if r["precision"] == precision and r["batch"] == N]
+            if not at or not all(r["heads_thin_wins"] for r in at):
+                break
+            bounds[precision] = N
+    res = {"tool": "detector_latency --lanes", "commit": commit_stamp(), "device": torch.cuda.get_device_name(0), "warmup": args.warmup,
+           "calls": args.calls, "repeats": args.repeats, "check_singular": False, "heads_thin_auto_max_batch_by_precision": bounds,
+           "results": rows}
+    with open(args.out or os.path.join(ROOT, "profiles", "detector_lanes_latency.json"), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"heads_thin_auto_max_batch_by_precision": bounds}))
+
+
+def trace_lanes():
+    """ten batch-1 det.lanes(frame) calls at 1 x 256 x 512 fp32, --clas (run under rocprofv3 --kernel-trace --stats)"""
+    import torch
+    from oracle import inputs
+    cfg = LANES_CFG
+    model = make_model(cfg, "fp32", 1, clas=True)
+    x = torch.from_numpy(inputs.images(1, cfg["H"], cfg["W"], seed=1)).cuda()
+    det = model.detector(thin=True)
+    for _ in range(10):
+        det.lanes(x)
+    torch.cuda.synchronize()
+
+
+def lanes_launches(db, out):
+    """append the kernels of --trace L to the launch table"""
+    import sqlite3
+    cur = sqlite3.connect(db).cursor()
+    cols = [r[1] for r in cur.execute("pragma table_info(kernels)")]
+    name_col = "name" if "name" in cols else [c for c in cols if "name" in c][0]
+    agg = {}
+    for n, s, e in cur.execute("select %s, start, end from kernels" % name_col).fetchall():
+        k = re.sub(r"\(.*$", "", re.sub(r"\(anonymous namespace\)::", "", n)).replace("void ", "")[:80]
+        a = agg.setdefault(k, [0, 0])
+        a[0] += 1
+        a[1] += e - s
+    lines = ["", "# Launches of ten `det.lanes(frame)` calls, 1 x 3 x 256 x 512, fp32, BP 4 lanes order 3 --clas", "",
+             "commit: `%s`" % commit_stamp(), "",
+             "`rocprofv3 --kernel-trace --stats` (no counters) of one process: the model's set-up and the detector's three folds, then ten",
+             "calls of `model.detector(thin=True).lanes(frame)`.  Per kernel: launches and summed duration (us) over the whole process.", "",
+             "| kernel | launches | us |", "|---|---:|---:|"]
+    for k in sorted(agg, key=lambda k: -agg[k][1]):
+        lines.append("| `%s` | %d | %.1f |" % (k, agg[k][0], agg[k][1] / 1e3))
+    lines += ["", "total: %d launches, %.1f us" % (sum(v[0] for v in agg.values()), sum(v[1] for v in agg.values()) / 1e3), ""]
+    with open(out or os.path.join(ROOT, "profiles", "detector_launches.md"), "a") as f:
+        f.write("\n".join(lines))
+
+
 def trace(path):
     """ten batch-1 calls of one path at 1 x 256 x 512 fp32 (run under rocprofv3 --kernel-trace --stats)"""
     import torch
     from oracle import inputs
+    if path == "L":
+        return trace_lanes()
     cfg = CONFIGS["bev"]
     model = make_model(cfg, "fp32", 1)
     x = torch.from_numpy(inputs.images(1, cfg["H"], cfg["W"], seed=1)).cuda()
@@ -236,12 +385,18 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--trace", choices=["A", "C"])
+    ap.add_argument("--trace", choices=["A", "C", "L"])
+    ap.add_argument("--lanes", action="store_true")
+    ap.add_argument("--lanes-launches", metavar="DB_L")
     ap.add_argument("--launches", nargs=2, metavar=("DB_A", "DB_C"))
     args = ap.parse_args()
     if args.trace:
         trace(args.trace)
     elif args.launches:
         launches(args.launches[0], args.launches[1], args.out)
+    elif args.lanes_launches:
+        lanes_launches(args.lanes_launches, args.out)
+    elif args.lanes:
+        run_lanes(args)
     else:
         run(args)
