@@ -1,5 +1,5 @@
 // Device bodies that the --clas tail shares between its one-purpose kernels (poolflat_*_fwd_kernel in lf_convchain.hip,
-// linear_fwd_kernel in lf_linear.hip, lane_decode_kernel in lf_fit.hip) and the fused tail of the frozen detector
+// linear_fwd_kernel in lf_linear.hip, lane_decode_kernel in lf_lanes.hip) and the fused tail of the frozen detector
 // (lf_clas_tail.hip): ONE text per body, so the fused launches give the composed path's bits.
 #pragma once
 #include "lf_common.h"

@@ -25,6 +25,24 @@ int lf_fail(const char* fmt, ...);
 
 static inline int lf_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+constexpr int CE_MAXC = 8;       // classes of the cross entropies (lf_ce2d_fwd / _bwd, lf_seg_step)
+
+// VEC = 4 (W % 4 == 0: one 16-byte access, the four pixels share a row) or 1
+template <int VEC>
+__device__ __forceinline__ void load_px(const float* __restrict__ p, float (&v)[VEC]) {
+    if constexpr (VEC == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+        v[0] = *p;
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void store_px(float* __restrict__ p, const float (&v)[VEC]) {
+    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else *p = v[0];
+}
+
 // wave64 all-lanes sum (butterfly), double and float
 __device__ __forceinline__ double lf_wave_sum(double v) {
 #pragma unroll

@@ -1,18 +1,20 @@
 // Whole-step criterion: every lane loss, the two --clas head losses, their gradients, the validation accuracies and the
 // weighted total of one training / validation step in ONE launch (lf_step_loss).
 //   Backprojection_Loss/main.py:296-326, :459-501 and Birds_Eye_View_Loss/main.py:223-253, :395-431 are the statements it replaces;
-//   the per-lane arithmetic is that of backproj_kernel / area_loss_kernel / mse_loss_kernel in lf_fit.hip (which keep serving the
-//   per-lane modules), the head losses are nn.BCEWithLogitsLoss / nn.CrossEntropyLoss in fp64.
+//   the back-projection lane body and the Area_Loss integrand with its gradient live in lf_loss_dev.h, which backproj_kernel and
+//   area_loss_kernel (lf_losses.hip, the per-lane modules) call too; the area mean and the MSE sums are each kernel's own; the head
+//   losses are nn.BCEWithLogitsLoss / nn.CrossEntropyLoss in fp64.
 // Grid: one 256-thread workgroup per task -- K lanes, then (with the heads) line and horizon.  Each workgroup reduces its task in a
 // fixed order, writes its gradient slice already multiplied by the task's static weight, publishes its scalars in a workspace slot
 // and draws a ticket; whoever draws the last ticket adds the slots up in the loop's order and writes the totals.  Nobody waits on
 // anybody, no value depends on which workgroup came last, and the ticket goes back to zero for the next call.
 #include "lf_common.h"
+#include "lf_loss_dev.h"
 
 namespace {
 
 constexpr int ST_MAXK = 4;
-constexpr int ST_THREADS = 256;
+constexpr int ST_THREADS = LF_LOSS_THREADS;
 // workspace: 9 fp64 slots (4 lane losses, line loss, horizon loss, line hits, horizon hits, bad labels) + the ticket
 constexpr int WS_LINE = 4, WS_HOR = 5, WS_LINE_HITS = 6, WS_HOR_HITS = 7, WS_BAD = 8, WS_TICKET = 9, WS_WORDS = 16;
 
@@ -38,104 +40,12 @@ struct StepArgs {
     double* ws;
 };
 
-// sum over the workgroup, the four wave sums added in wave order: the same order as the per-lane kernels
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    v = lf_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// Area_Loss integrand and its gradient in the coefficient differences (BEV/Loss_crit.py:103-126), as area_loss_kernel has them
-__device__ __forceinline__ double area_value(double a, double b, double c, int order, int wf) {
-    const double t = 0.7;
-    const double t2 = t * t, t3 = t2 * t, t4 = t3 * t, t5 = t4 * t, t6 = t5 * t;
-    if (order != 2) return b * b * t + a * b * t2 + (a * a * t3) / 3;
-    if (wf == LF_WF_NONE)
-        return a * a * t5 / 5 + 2 * a * b * t4 / 4 + (b * b + c * 2 * a) * t3 / 3 + 2 * b * c * t2 / 2 + c * c * t;
-    if (wf == LF_WF_LINEAR)
-        return c * c * t - t5 * ((2 * a * b) / 5 - a * a / 5) + t2 * (b * c - c * c / 2) - (a * a * t6) / 6 -
-               t4 * (b * b / 4 - (a * b) / 2 + (a * c) / 2) + t3 * (b * b / 3 - (2 * c * b) / 3 + (2 * a * c) / 3);
-    const double t15 = pow(t, 1.5), t25 = pow(t, 2.5), t35 = pow(t, 3.5), t45 = pow(t, 4.5), t55 = pow(t, 5.5);
-    return t3 * (b * b / 3 + 2.0 / 3 * a * c) - t35 * (2.0 / 7 * b * b + 4.0 / 7 * a * c) + c * c * t + 0.2 * a * a * t5 -
-           2.0 / 11 * a * a * t55 - 2.0 / 3 * c * c * t15 + 0.5 * a * b * t4 - 4.0 / 9 * a * b * t45 + b * c * t2 - 0.8 * b * c * t25;
-}
-
-__device__ __forceinline__ void area_grad(double a, double b, double c, int order, int wf, double* g) {
-    const double t = 0.7;
-    const double t2 = t * t, t3 = t2 * t, t4 = t3 * t, t5 = t4 * t, t6 = t5 * t;
-    g[2] = 0.0;
-    if (order != 2) {
-        g[0] = b * t2 + 2 * a * t3 / 3;
-        g[1] = 2 * b * t + a * t2;
-    } else if (wf == LF_WF_NONE) {
-        g[0] = 2 * a * t5 / 5 + b * t4 / 2 + 2 * c * t3 / 3;
-        g[1] = a * t4 / 2 + 2 * b * t3 / 3 + c * t2;
-        g[2] = 2 * a * t3 / 3 + b * t2 + 2 * c * t;
-    } else if (wf == LF_WF_LINEAR) {
-        g[0] = -t5 * (2 * b / 5 - 2 * a / 5) - a * t6 / 3 - t4 * (-b / 2 + c / 2) + t3 * (2 * c / 3);
-        g[1] = -t5 * (2 * a / 5) + t2 * c - t4 * (b / 2 - a / 2) + t3 * (2 * b / 3 - 2 * c / 3);
-        g[2] = 2 * c * t + t2 * (b - c) - t4 * (a / 2) + t3 * (-2 * b / 3 + 2 * a / 3);
-    } else {
-        const double t15 = pow(t, 1.5), t25 = pow(t, 2.5), t35 = pow(t, 3.5), t45 = pow(t, 4.5), t55 = pow(t, 5.5);
-        g[0] = t3 * (2.0 / 3 * c) - t35 * (4.0 / 7 * c) + 0.4 * a * t5 - 4.0 / 11 * a * t55 + 0.5 * b * t4 - 4.0 / 9 * b * t45;
-        g[1] = t3 * (2.0 / 3 * b) - t35 * (4.0 / 7 * b) + 0.5 * a * t4 - 4.0 / 9 * a * t45 + c * t2 - 0.8 * c * t25;
-        g[2] = t3 * (2.0 / 3 * a) - t35 * (4.0 / 7 * a) + 2 * c * t - 4.0 / 3 * c * t15 + b * t2 - 0.8 * b * t25;
-    }
-}
-
-// backprojection_loss of one lane (BP/Loss_crit.py:202-218): backproj_kernel's two phases on lane k of the (N, K, .) tensors
+// backprojection_loss of one lane (BP/Loss_crit.py:202-218): lane k of the (N, K, .) tensors, its gradient times the lane's weight
 template <typename T>
 __device__ double lane_backproject(const StepArgs& a, int k, double* sh) {
-    const int D = a.order + 1, N = a.N, S = a.S, K = a.K;
-    const T* beta = (const T*)a.beta[k];
-    const double* x_gt = (const double*)a.target + (long)k * S;
-    const double* valid = a.valid + (long)k * S;
-    const double *Y = a.Y, *yp = a.yp;
-    double e2 = 0.0, nv = 0.0;
-    for (long idx = threadIdx.x; idx < (long)N * S; idx += ST_THREADS) {
-        const int n = (int)(idx / S), j = (int)(idx % S);
-        double xp = 0.0;
-        for (int i = 0; i < D; ++i) xp = fma(Y[(long)j * D + i], (double)beta[(long)n * a.bstride + i], xp);
-        const double t0 = a.m00 * xp + a.m01 * yp[j] + a.m02;
-        const double t2 = a.m20 * xp + a.m21 * yp[j] + a.m22;
-        const double xc = t0 / t2;
-        const double v = valid[(long)n * a.tstride + j];
-        const double err = (x_gt[(long)n * a.tstride + j] - xc) * v;
-        a.xcal[((long)n * K + k) * S + j] = xc * v;
-        e2 = fma(err, err, e2);
-        nv += v;
-    }
-    const double te = block_sum(e2, sh), tv = block_sum(nv, sh);
-    const double inv = tv != 0.0 ? 1.0 / tv : 0.0;
-    T* grad = (T*)a.grad;
-    // four threads per image, each taking every fourth sample height, merged in a fixed order by two butterfly steps
-    for (int n0 = 0; n0 < N; n0 += 64) {
-        const int n = n0 + (int)(threadIdx.x >> 2), q = (int)(threadIdx.x & 3);
-        const bool live = n < N;
-        const int nn = live ? n : 0;
-        double g[4] = {0, 0, 0, 0};
-        for (int j = q; j < S && live; j += 4) {
-            double xp = 0.0;
-            for (int i = 0; i < D; ++i) xp = fma(Y[(long)j * D + i], (double)beta[(long)nn * a.bstride + i], xp);
-            const double t0 = a.m00 * xp + a.m01 * yp[j] + a.m02;
-            const double t2 = a.m20 * xp + a.m21 * yp[j] + a.m22;
-            const double v = valid[(long)nn * a.tstride + j];
-            const double err = (x_gt[(long)nn * a.tstride + j] - t0 / t2) * v;
-            const double dxc = (a.m00 * t2 - a.m20 * t0) / (t2 * t2);
-            const double gx = -2.0 * err * v * inv * dxc;
-            for (int i = 0; i < D; ++i) g[i] = fma(gx, Y[(long)j * D + i], g[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            g[i] += __shfl_xor(g[i], 1, 64);
-            g[i] += __shfl_xor(g[i], 2, 64);
-        }
-        if (live && q == 0)
-            for (int i = 0; i < D; ++i) grad[((long)n * K + k) * D + i] = (T)(g[i] * a.w_lane);
-    }
-    return tv != 0.0 ? te / tv : 0.0;
+    const LfBackprojConsts c = {a.Y, a.yp, a.m00, a.m01, a.m02, a.m20, a.m21, a.m22};
+    return lf_backproject_lane<T>((const T*)a.beta[k], a.bstride, (const double*)a.target + (long)k * a.S, a.valid + (long)k * a.S,
+                                  a.tstride, c, a.N, a.S, a.order, a.K, k, a.w_lane, a.xcal, (T*)a.grad, sh);
 }
 
 // Area_Loss (BEV/Loss_crit.py:98-134) or MSE_Loss of one lane.  An image whose ground truth has a zero coefficient is dropped
@@ -159,7 +69,7 @@ __device__ double lane_coeff(const StepArgs& a, int k, double* sh) {
         }
         for (int j = 0; j < D; ++j) d[j] = ((masked && !keep) ? 0.0 : (double)beta[(long)i * a.bstride + j]) - gj[j];
         if (area) {
-            if (keep) { Lsum += area_value(d[0], d[1], d[2], a.order, a.wf); cnt += 1.0; }
+            if (keep) { Lsum += lf_area_value(d[0], d[1], d[2], a.order, a.wf); cnt += 1.0; }
         } else {
             for (int j = 0; j < D; ++j) Lsum = fma(d[j], d[j], Lsum);
         }
@@ -177,7 +87,7 @@ __device__ double lane_coeff(const StepArgs& a, int k, double* sh) {
         for (int j = 0; j < D; ++j) d[j] = ((masked && !keep) ? 0.0 : (double)beta[(long)i * a.bstride + j]) - gj[j];
         bool live;
         if (area) {
-            area_grad(d[0], d[1], d[2], a.order, a.wf, g);
+            lf_area_grad(d[0], d[1], d[2], a.order, a.wf, g);
             live = keep;
         } else {
             for (int j = 0; j < D; ++j) g[j] = 2.0 * d[j];

@@ -18,7 +18,7 @@
 namespace {
 
 constexpr int SG_THREADS = 256;
-constexpr int SG_MAXC = 8;          // CE_MAXC of lf_ce2d_fwd
+constexpr int SG_MAXC = CE_MAXC;    // the class cap of lf_ce2d_fwd (lf_common.h)
 constexpr int SG_MAXL = 4;
 constexpr int SG_MAXCHUNKS = 128;   // workgroups per image at most
 constexpr int SG_COUNT_BYTES = 128; // SG_MAXC class counts + the out-of-range count, uint64, at the head of the workspace
@@ -74,21 +74,6 @@ struct SegArgs {
     double* momp;               // (N, L, CH, 3 * order + 2): wls_solve_kernel's layout with CH chunks
 };
 
-template <int VEC>
-__device__ __forceinline__ void seg_load(const float* __restrict__ p, float (&v)[VEC]) {
-    if constexpr (VEC == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-        v[0] = *p;
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void seg_store(float* __restrict__ p, const float (&v)[VEC]) {
-    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else *p = v[0];
-}
-
 // ORDER < 0: cross entropy only.  LMAX: lanes compiled in (2 or 4); a.L <= LMAX of them are live.  VEC = 4 wants W % 4 == 0 and
 // 16-byte aligned tensors.
 template <int ORDER, int LMAX, int VEC>
@@ -130,7 +115,7 @@ __global__ __launch_bounds__(SG_THREADS) void seg_step_kernel(const SegArgs a) {
         float v[SG_MAXC][VEC];
 #pragma unroll
         for (int c = 0; c < SG_MAXC; ++c)
-            if (c < C) seg_load<VEC>(z + ((unsigned)c * P32 + p32), v[c]);
+            if (c < C) load_px<VEC>(z + ((unsigned)c * P32 + p32), v[c]);
         int64_t t64[VEC];
         if constexpr (VEC == 4) {
             const longlong2 t0 = *reinterpret_cast<const longlong2*>(tg + p);
@@ -174,7 +159,7 @@ __global__ __launch_bounds__(SG_THREADS) void seg_step_kernel(const SegArgs a) {
         if (g) {
 #pragma unroll
             for (int c = 0; c < SG_MAXC; ++c)
-                if (c < C) seg_store<VEC>(g + ((unsigned)c * P32 + p32), v[c]);
+                if (c < C) store_px<VEC>(g + ((unsigned)c * P32 + p32), v[c]);
         }
         if constexpr (FIT) {
             bool any = false;
@@ -219,7 +204,7 @@ __global__ __launch_bounds__(SG_THREADS) void seg_step_kernel(const SegArgs a) {
                         float m[VEC];
 #pragma unroll
                         for (int e = 0; e < VEC; ++e) m[e] = (lane_of[e] == l + 1) ? (float)(l + 1) : 0.f;
-                        seg_store<VEC>(maps + ((unsigned)l * P32 + p32), m);
+                        store_px<VEC>(maps + ((unsigned)l * P32 + p32), m);
                     }
             }
         }
@@ -267,7 +252,7 @@ struct SegFinish {
     double* meters;
 };
 
-// workgroup 0: the loss; workgroups 1..: one thread per (image, lane), wls_solve_kernel's arithmetic without the Z^-1 output
+// workgroup 0: the loss; workgroups 1..: one thread per (image, lane), wls_solve_kernel's solve (lf_solve_moments) without the Z^-1 output
 template <int ORDER>
 __global__ __launch_bounds__(LF_WAVE) void seg_finish_kernel(const SegFinish f) {
     if (blockIdx.x == 0) {
@@ -285,7 +270,7 @@ __global__ __launch_bounds__(LF_WAVE) void seg_finish_kernel(const SegFinish f) 
         return;
     }
     if constexpr (ORDER >= 0) {
-        constexpr int D = ORDER + 1, NM = 2 * ORDER + 1, NMOM = 3 * ORDER + 2;
+        constexpr int D = ORDER + 1, NMOM = 3 * ORDER + 2;
         const int nk = ((int)blockIdx.x - 1) * LF_WAVE + (int)threadIdx.x;
         if (nk >= f.N * f.L) return;
         // "prevent singular matrix" (BP/Networks/LSQ_layer.py:308-311): a flagged lane fits map [0, 0]
@@ -296,21 +281,10 @@ __global__ __launch_bounds__(LF_WAVE) void seg_finish_kernel(const SegFinish f) 
         for (int c = 0; c < f.CH; ++c)
 #pragma unroll
             for (int j = 0; j < NMOM; ++j) mom[j] += f.momp[((long)src * f.CH + c) * NMOM + j];
-        double Z[D][D], Zi[D][D], X[D];
+        double b[D], Zi[D][D];
+        const int st = lf_solve_moments<ORDER>(mom, f.reg, f.solver, b, Zi);
 #pragma unroll
-        for (int i = 0; i < D; ++i) {
-#pragma unroll
-            for (int j = 0; j < D; ++j) Z[i][j] = mom[(ORDER - i) + (ORDER - j)] + (i == j ? f.reg : 0.0);
-            X[i] = mom[NM + (ORDER - i)];
-        }
-        const int st = (f.solver == LF_SOLVE_CHOLESKY) ? invert_chol<D>(Z, Zi) : invert_lu<D>(Z, Zi);
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            double b = 0.0;
-#pragma unroll
-            for (int j = 0; j < D; ++j) b = fma(Zi[i][j], X[j], b);
-            f.beta[(long)nk * D + i] = b;
-        }
+        for (int i = 0; i < D; ++i) f.beta[(long)nk * D + i] = b[i];
         f.status[nk] = st;
     }
 }

@@ -1,5 +1,6 @@
-// In-register inverses of the fit's (order + 1) x (order + 1) normal matrix: shared by the solve kernels of lf_fit.hip and the
-// segmentation-mode step criterion of lf_criterion.hip.
+// In-register inverses of the fit's (order + 1) x (order + 1) normal matrix and the solve from the summed moments: shared by the
+// solve kernels of lf_fit.hip (wls_solve_kernel, gels_solve_kernel) and the segmentation-mode step criterion's seg_finish_kernel
+// (lf_seg_step.hip): ONE text, so the two routes give the same bits.
 #pragma once
 #include "lf_common.h"
 
@@ -95,6 +96,31 @@ __device__ int invert_chol(double (&A)[D][D], double (&Ai)[D][D]) {
         for (int i = 0; i < D; ++i) Ai[i][c] = x[i];
     }
     return bad;
+}
+
+// The fit of one (image, lane) from its summed moments mom = [m_0 .. m_2d, q_0 .. q_d] (Moments<ORDER>'s layout): the Hankel normal
+// matrix Z (+ reg on the diagonal, both solvers: BEV/Networks/LSQ_layer.py:120-126), Zi = Z^-1 by `solver`, b = Zi X, highest power
+// first.  Returns the inverse's status.
+template <int ORDER>
+__device__ __forceinline__ int lf_solve_moments(const double* mom, double reg, int solver, double (&b)[ORDER + 1],
+                                                double (&Zi)[ORDER + 1][ORDER + 1]) {
+    constexpr int D = ORDER + 1, NM = 2 * ORDER + 1;
+    double Z[D][D], X[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+#pragma unroll
+        for (int j = 0; j < D; ++j) Z[i][j] = mom[(ORDER - i) + (ORDER - j)] + (i == j ? reg : 0.0);
+        X[i] = mom[NM + (ORDER - i)];
+    }
+    const int st = (solver == LF_SOLVE_CHOLESKY) ? invert_chol<D>(Z, Zi) : invert_lu<D>(Z, Zi);
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) s = fma(Zi[i][j], X[j], s);
+        b[i] = s;
+    }
+    return st;
 }
 
 }  // namespace

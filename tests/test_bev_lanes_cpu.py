@@ -110,8 +110,8 @@ def test_symbol_exported_and_declared():
 def test_lane_decode_bev_kernels_do_not_spill(tmp_path):
     from lanedetection_end2end_amd import build
     import isa_meta
-    src = os.path.join(build.CSRC, "lf_fit.hip")
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + build.FLAGS + ["-c", src, "-o", str(tmp_path / "lf_fit.o"), "-save-temps=obj"]
+    src = os.path.join(build.CSRC, "lf_lanes.hip")
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + build.FLAGS + ["-c", src, "-o", str(tmp_path / "lf_lanes.o"), "-save-temps=obj"]
     subprocess.check_call(cmd, cwd=str(tmp_path))
     asm = glob.glob(str(tmp_path / "*gfx950*.s"))
     assert asm, "no device assembly produced"
