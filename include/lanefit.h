@@ -56,7 +56,10 @@ extern "C" {
                                  additions since 5 (frozen single-frame detector): lf_erfnet_infer_fold, lf_lane_infer_folded,
                                  lf_lane_infer_seg_folded;
                                  additions since 5 (frozen --clas heads): lf_convchain_infer_fold, lf_convchain_infer_folded,
-                                 lf_clas_tail_workspace_bytes, lf_clas_tail */
+                                 lf_clas_tail_workspace_bytes, lf_clas_tail;
+                                 additions since 5 (camera frames): lf_pipeline_frame_stem_ok, lf_pipeline_frame_stem_lds_bytes,
+                                 lf_pipeline_frame_stem_tile, lf_lane_infer_u8_workspace_bytes, lf_lane_infer_seg_u8_workspace_bytes,
+                                 lf_lane_infer_folded_u8, lf_lane_infer_seg_folded_u8 */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -734,6 +737,39 @@ int lf_clas_tail(const void* y_line, const void* y_hor, int bf16, int N, int H, 
                  int order, const double* y_eval, const double* y_prime, int S, const double* minv_host, double scale, double lo,
                  double hi, double fill, float* line, float* horizon, float* line_flags, int32_t* horizon_row, int32_t* lanes,
                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* additions since 5 -- camera frames: the frozen detector's calls from decoded uint8 HWC camera frames (N,Hin,Win,3), what the
+ * reference's LaneTestSet.__getitem__ starts from (BP/Dataloader/Load_Data_new.py:55-65: crop, Pillow BILINEAR resize, ToTensor), in
+ * the place of the fp32 (N,3,H,W) image.  `pipe` is an lf_pipeline_plan whose output size is the network plan's H x W, tables_dev
+ * the buffer lf_pipeline_upload filled.  RGB only: the network plan has 3 input channels.
+ * lf_lane_infer_folded_u8 / lf_lane_infer_seg_folded_u8: lf_lane_infer_folded / lf_lane_infer_seg_folded with (pipe, tables_dev,
+ *   frames) for img; the results are those of lf_pipeline_image followed by the call on its output, bit for bit.  The resize and the
+ *   stem run as ONE launch (the resized image stays in LDS) where lf_pipeline_frame_stem_ok(pipe) is 1; where it is 0 (the source
+ *   window of a tile does not fit 64 KB of LDS: 640 x 1280 -> 64 x 128) or with LF_INFER_FRAME_TWO_LAUNCH in flags, as two launches
+ *   through an fp32 image slot at the end of the workspace.
+ * lf_lane_infer_u8_workspace_bytes / lf_lane_infer_seg_u8_workspace_bytes: lf_lane_infer_workspace_bytes /
+ *   lf_lane_infer_seg_workspace_bytes + that image slot, always: one workspace serves both forms.  The folded prefix is the same
+ *   (lf_erfnet_infer_fold).
+ * lf_pipeline_frame_stem_ok: 1 where the one-launch kernel takes the plan's geometry (even output size, a tile that fits), else 0;
+ *   lf_pipeline_frame_stem_lds_bytes: the LDS bytes of one of its workgroups (0 where it does not fit);
+ *   lf_pipeline_frame_stem_tile: its tile of stem output pixels (0 x 0 where it does not fit). */
+enum { LF_INFER_FRAME_TWO_LAUNCH = 2 };
+int lf_pipeline_frame_stem_ok(const lf_pipeline_plan* plan);
+size_t lf_pipeline_frame_stem_lds_bytes(const lf_pipeline_plan* plan);
+int lf_pipeline_frame_stem_tile(const lf_pipeline_plan* plan, int* tile_h, int* tile_w);
+size_t lf_lane_infer_u8_workspace_bytes(const lf_erfnet_plan* plan, int mode, int K, int order);
+size_t lf_lane_infer_seg_u8_workspace_bytes(const lf_erfnet_plan* plan, int mode, int L, int order);
+int lf_lane_infer_folded_u8(const lf_erfnet_plan* plan, const lf_pipeline_plan* pipe, const void* tables_dev, const uint8_t* frames,
+                            const float* const* params_host, const float* const* params_dev, float* const* running_host,
+                            const float* grid_xy, long grid_batch_stride, int zero_rows, int order, double reg_ls, double y_offset,
+                            int act_kind, int use_cholesky, float* logits_or_null, double* beta, int32_t* status, void* workspace,
+                            size_t workspace_bytes, int flags, void* stream);
+int lf_lane_infer_seg_folded_u8(const lf_erfnet_plan* plan, const lf_pipeline_plan* pipe, const void* tables_dev,
+                                const uint8_t* frames, const float* const* params_host, const float* const* params_dev,
+                                float* const* running_host, const float* grid_xy, long grid_batch_stride,
+                                const float* gt_line_or_null, int L, int zero_rows, int order, double reg_ls, double y_offset,
+                                int use_cholesky, uint8_t* classes_or_null, double* beta, int32_t* status, void* workspace,
+                                size_t workspace_bytes, int flags, void* stream);
 
 /* additions since 5 -- input-image gradient: d loss / d input of Net.forward, what `input.requires_grad_()` before the forward and
  * `loss.backward()` (BEV/main.py:264-266) give in the reference -- the data gradient of the stem DownsamplerBlock's

@@ -148,6 +148,13 @@ def _declare(lib):
         "lf_clas_tail_workspace_bytes": (c_size_t, [I, I, I, I, I]),
         "lf_clas_tail": (I, [P, P, I, I, I, I, I, P, P, I, P, P, P, P, I, P, I, I, P, P, I, P, D, D, D, D, P, P, P, P, P, P,
                              c_size_t, P]),
+        "lf_pipeline_frame_stem_ok": (I, [P]),
+        "lf_pipeline_frame_stem_lds_bytes": (c_size_t, [P]),
+        "lf_pipeline_frame_stem_tile": (I, [P, P, P]),
+        "lf_lane_infer_u8_workspace_bytes": (c_size_t, [P, I, I, I]),
+        "lf_lane_infer_seg_u8_workspace_bytes": (c_size_t, [P, I, I, I]),
+        "lf_lane_infer_folded_u8": (I, [P, P, P, P, P, P, P, P, L, I, I, D, D, I, I, P, P, P, P, c_size_t, I, P]),
+        "lf_lane_infer_seg_folded_u8": (I, [P, P, P, P, P, P, P, P, L, P, I, I, I, D, D, I, P, P, P, P, c_size_t, I, P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {
@@ -194,6 +201,7 @@ def _declare(lib):
         "lf_debug_pool_affine_fwd": (I, [P, I, I, I, I, P, I, I, P, P, I, P]),
         "lf_debug_pool_bwd": (I, [P, P, I, I, I, I, I, I, P, I, P]),
         "lf_debug_stem_fwd": (I, [P, I, I, I, I, P, P, P, P, P, P, I, I, P]),
+        "lf_debug_frame_stem": (I, [P, P, I, P, P, P, P, P, P, I, P]),
         "lf_debug_head_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
         "lf_debug_head_bwd_data": (I, [P, P, P, I, I, I, I, I, P]),
         "lf_debug_convchain_offset": (L, [P, I, I]),
@@ -213,7 +221,7 @@ def exported_symbols():
 
 # ... and the csrc/lf_debug.h hooks the frozen detector's tests and tools/detector_latency.py count launches with
 _extra_symbols = ["lf_debug_set_thin", "lf_debug_thin_launches", "lf_debug_fold_pack_launches", "lf_debug_set_thin_bf16",
-                  "lf_debug_thin_bf16_launches"]
+                  "lf_debug_thin_bf16_launches", "lf_debug_frame_stem"]
 
 
 def load():

@@ -195,6 +195,13 @@ int lf_debug_pool_bwd(const float* x, const float* gcat, int N, int H, int W, in
  *                   ignored; returns 0 */
 int lf_debug_stem_fwd(const float* img, int N, int Cin, int H, int W, const float* w, const float* b, const float* sc, const float* sh, float* cat,
                       float* rows, int ld, int s16, void* stream);
+/* frame_stem_kernel alone (csrc/lf_frame_stem.hip): frames (N,Hin,Win,3) uint8 HWC -> cat (N,out_h/2,out_w/2,16) = the inference form of
+ * lf_debug_stem_fwd (Cin = 3; sc, sh [16]) on lf_pipeline_image's output, bit for bit, in one launch.  plan / tables_dev: an
+ * lf_pipeline_plan and its uploaded tables.  Returns 0; -1 (lf_last_error) WITHOUT launching for a null pointer, a plan with an odd
+ * out_h / out_w or one whose geometry does not fit the kernel (lf_pipeline_frame_stem_ok = 0).  (tests/test_frame_stem_gpu.py) */
+struct lf_pipeline_plan;
+int lf_debug_frame_stem(const struct lf_pipeline_plan* plan, const unsigned char* frames, int N, const void* tables_dev, const float* w,
+                        const float* b, const float* sc, const float* sh, float* cat, int s16, void* stream);
 /* head, ConvTranspose2d(16, K, 2, stride 2), K 1..8: x (N,h,w,16) NHWC -> out (N,K,2h,2w) NCHW fp32; w (16,K,2,2), b [K].  Returns 0. */
 int lf_debug_head_fwd(const float* x, const float* w, const float* b, float* out, int N, int h, int w_, int K, int s16, void* stream);
 /* its data gradient: gout (N,K,2h,2w) NCHW fp32 -> gx (N,h,w,16) NHWC.  Returns 0. */

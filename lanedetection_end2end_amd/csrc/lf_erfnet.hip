@@ -16,6 +16,7 @@
 
 #include "lf_conv.h"
 #include "lf_eltwise.h"
+#include "lf_pipeline_dev.h"
 #include "lf_plan.h"
 #include "lf_types.h"
 
@@ -1230,9 +1231,21 @@ int infer_gemm(const InferCtx& c, const GemmOp& op, int fi, const float* src, fl
     return lf_tapgemm_launch(op.geom, a, LF_PRO_NONE, epi, c.st);
 }
 
+// Where the stem takes its image from: the fp32 NCHW tensor, or decoded uint8 camera frames + their pipeline plan and tables
+// (lf_lane_infer_folded_u8).  Frames run through frame_stem_kernel (fused) or through lf_pipeline_image into `slot` and the stem.
+struct ImgSrc {
+    const float* img = nullptr;
+    const lf_pipeline_plan* pipe = nullptr;
+    const void* tables = nullptr;
+    const uint8_t* frames = nullptr;
+    float* slot = nullptr;
+    bool fused = false;
+    ImgSrc(const float* p = nullptr) : img(p) {}
+};
+
 // layers [first, nlayers); the last encoder layer writes the encoder-output region; *out = the last layer's output.  xin: the NHWC
 // input of layer `first` when first > 0 (one of the three activation buffers, or the encoder-output region); unused for first = 0
-int forward_infer(const InferCtx& c, const float* img, const float* const* params_host, int nlayers, float** out, int first = 0,
+int forward_infer(const InferCtx& c, const ImgSrc& src, const float* const* params_host, int nlayers, float** out, int first = 0,
                   float* xin = nullptr) {
     const lf_erfnet_plan* P = c.P;
     const int N = P->N, ne = encoder_layers(P);
@@ -1248,6 +1261,17 @@ int forward_infer(const InferCtx& c, const float* img, const float* const* param
         const Layer& L = P->layers[li];
         if (L.kind == K_DOWN && L.x < 0) {
             float* y = bufs[0];
+            const float* img = src.img;
+            if (src.frames && src.fused) {
+                LF_TRY(lf_frame_stem_fwd_infer(src.pipe, src.frames, N, src.tables, params_host[L.cv[0].p_w], params_host[L.cv[0].p_b],
+                                               c.vec(L.fv, 0), c.vec(L.fv, 1), y, c.s16, c.st));
+                x = y;
+                continue;
+            }
+            if (src.frames) {
+                LF_TRY(lf_pipeline_image(src.pipe, src.frames, N, src.tables, nullptr, src.slot, c.st));
+                img = src.slot;
+            }
             LF_TRY(lf_stem_fwd_infer(img, N, L.Cin, L.Hin, L.Win, params_host[L.cv[0].p_w], params_host[L.cv[0].p_b], c.vec(L.fv, 0),
                                      c.vec(L.fv, 1), y, c.s16, c.st));
             x = y;
@@ -1344,15 +1368,36 @@ LaneLayout lane_layout(const lf_erfnet_plan* P, int mode, int K, int order) {
     return L;
 }
 
+// uint8 frames: the fp32 image slot of the two-launch form behind the lane layout (always part of the _u8 workspace), the checks of
+// the pipeline plan against the network plan, and which form the call runs
+size_t frame_slot_bytes(const lf_erfnet_plan* P, const ImgSrc& s) {
+    return s.frames ? ((size_t)P->N * 3 * P->H * P->W * sizeof(float) + 255) / 256 * 256 : 0;
+}
+int frame_source_open(const char* who, const lf_erfnet_plan* P, ImgSrc& s, int flags, char* slot) {
+    if (!s.frames) {
+        LF_REQUIRE(!(flags & LF_INFER_FRAME_TWO_LAUNCH), "%s: LF_INFER_FRAME_TWO_LAUNCH is a flag of the uint8-frame calls", who);
+        return 0;
+    }
+    LF_REQUIRE(s.pipe && s.tables, "%s: null pipeline plan or tables", who);
+    LF_REQUIRE(P->Cin == 3, "%s: uint8 frames are RGB, the network plan has %d input channels", who, P->Cin);
+    LF_REQUIRE(s.pipe->out_h == P->H && s.pipe->out_w == P->W, "%s: the pipeline plan resizes to %d x %d, the network plan takes %d x %d", who,
+               s.pipe->out_h, s.pipe->out_w, P->H, P->W);
+    s.slot = reinterpret_cast<float*>(slot);
+    s.fused = s.pipe->fs_ok && !(flags & LF_INFER_FRAME_TWO_LAUNCH);
+    return 0;
+}
+
 // The schedule of lf_lane_infer (fold = true: the per-call fold-table upload and fold-and-pack launch first) and of
 // lf_lane_infer_folded (fold = false: the workspace holds what lf_erfnet_infer_fold wrote; flags: LF_INFER_*) -- one body.
-int lane_infer_run(const char* who, bool fold, int flags, const lf_erfnet_plan* P, const float* img, const float* const* params_host,
+int lane_infer_run(const char* who, bool fold, int flags, const lf_erfnet_plan* P, ImgSrc img, const float* const* params_host,
                    const float* const* params_dev, float* const* running_host, const float* grid_xy, long grid_batch_stride,
                    int zero_rows, int order, double reg_ls, double y_offset, int act_kind, int use_cholesky, float* logits_or_null,
                    double* beta, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
     const int K = P->Cout;
     const LaneLayout LL = lane_layout(P, P->precision, K, order);
-    LF_REQUIRE(workspace_bytes >= (size_t)LL.total, "%s: workspace too small (%zu < %ld)", who, workspace_bytes, LL.total);
+    LF_REQUIRE(workspace_bytes >= (size_t)LL.total + frame_slot_bytes(P, img), "%s: workspace too small (%zu < %zu)", who, workspace_bytes,
+               (size_t)LL.total + frame_slot_bytes(P, img));
+    LF_TRY(frame_source_open(who, P, img, flags, (char*)workspace + LL.total));
     InferCtx c;
     if (fold) LF_TRY(infer_begin(c, P, workspace, params_host, params_dev, running_host, stream));
     else infer_open(c, P, workspace, stream);
@@ -1365,12 +1410,14 @@ int lane_infer_run(const char* who, bool fold, int flags, const lf_erfnet_plan* 
                        reinterpret_cast<double*>(c.ws + LL.zinv), c.ws + LL.partials, status, stream);
 }
 // ... and of lf_lane_infer_seg / lf_lane_infer_seg_folded
-int lane_infer_seg_run(const char* who, bool fold, int flags, const lf_erfnet_plan* P, const float* img, const float* const* params_host,
+int lane_infer_seg_run(const char* who, bool fold, int flags, const lf_erfnet_plan* P, ImgSrc img, const float* const* params_host,
                        const float* const* params_dev, float* const* running_host, const float* grid_xy, long grid_batch_stride,
                        const float* gt_line_or_null, int L, int zero_rows, int order, double reg_ls, double y_offset, int use_cholesky,
                        uint8_t* classes_or_null, double* beta, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
     const LaneLayout LL = lane_layout(P, P->precision, L, order);
-    LF_REQUIRE(workspace_bytes >= (size_t)LL.total, "%s: workspace too small (%zu < %ld)", who, workspace_bytes, LL.total);
+    LF_REQUIRE(workspace_bytes >= (size_t)LL.total + frame_slot_bytes(P, img), "%s: workspace too small (%zu < %zu)", who, workspace_bytes,
+               (size_t)LL.total + frame_slot_bytes(P, img));
+    LF_TRY(frame_source_open(who, P, img, flags, (char*)workspace + LL.total));
     InferCtx c;
     if (fold) LF_TRY(infer_begin(c, P, workspace, params_host, params_dev, running_host, stream));
     else infer_open(c, P, workspace, stream);
@@ -1500,6 +1547,52 @@ int lf_lane_infer_seg_folded(const lf_erfnet_plan* P, const float* img, const fl
                order, L);
     LF_REQUIRE((flags & ~LF_INFER_THIN) == 0, "lf_lane_infer_seg_folded: unknown flags %d", flags);
     return lane_infer_seg_run("lf_lane_infer_seg_folded", false, flags, P, img, params_host, params_dev, running_host, grid_xy,
+                              grid_batch_stride, gt_line_or_null, L, zero_rows, order, reg_ls, y_offset, use_cholesky, classes_or_null,
+                              beta, status, workspace, workspace_bytes, stream);
+}
+
+// include/lanefit.h, "additions since 5 -- camera frames": the two folded calls from decoded uint8 frames.  One body with the fp32
+// calls (lane_infer_run / lane_infer_seg_run): only the stem's image source differs.
+size_t lf_lane_infer_u8_workspace_bytes(const lf_erfnet_plan* P, int mode, int K, int order) {
+    const size_t base = lf_lane_infer_workspace_bytes(P, mode, K, order);
+    ImgSrc s; s.frames = reinterpret_cast<const uint8_t*>(P);      // (any non-null value: the slot's size depends on the plan alone)
+    return base ? base + frame_slot_bytes(P, s) : 0;
+}
+size_t lf_lane_infer_seg_u8_workspace_bytes(const lf_erfnet_plan* P, int mode, int L, int order) {
+    const size_t base = lf_lane_infer_seg_workspace_bytes(P, mode, L, order);
+    ImgSrc s; s.frames = reinterpret_cast<const uint8_t*>(P);
+    return base ? base + frame_slot_bytes(P, s) : 0;
+}
+
+int lf_lane_infer_folded_u8(const lf_erfnet_plan* P, const lf_pipeline_plan* pipe, const void* tables_dev, const uint8_t* frames,
+                            const float* const* params_host, const float* const* params_dev, float* const* running_host,
+                            const float* grid_xy, long grid_batch_stride, int zero_rows, int order, double reg_ls, double y_offset,
+                            int act_kind, int use_cholesky, float* logits_or_null, double* beta, int32_t* status, void* workspace,
+                            size_t workspace_bytes, int flags, void* stream) {
+    LF_REQUIRE(P && pipe && tables_dev && frames && params_host && grid_xy && beta && status && workspace,
+               "lf_lane_infer_folded_u8: null pointer");
+    LF_REQUIRE(order >= 0 && order <= 3, "lf_lane_infer_folded_u8: order %d not in 0..3", order);
+    LF_REQUIRE((flags & ~(LF_INFER_THIN | LF_INFER_FRAME_TWO_LAUNCH)) == 0, "lf_lane_infer_folded_u8: unknown flags %d", flags);
+    ImgSrc src;
+    src.pipe = pipe; src.tables = tables_dev; src.frames = frames;
+    return lane_infer_run("lf_lane_infer_folded_u8", false, flags, P, src, params_host, params_dev, running_host, grid_xy,
+                          grid_batch_stride, zero_rows, order, reg_ls, y_offset, act_kind, use_cholesky, logits_or_null, beta, status,
+                          workspace, workspace_bytes, stream);
+}
+
+int lf_lane_infer_seg_folded_u8(const lf_erfnet_plan* P, const lf_pipeline_plan* pipe, const void* tables_dev, const uint8_t* frames,
+                                const float* const* params_host, const float* const* params_dev, float* const* running_host,
+                                const float* grid_xy, long grid_batch_stride, const float* gt_line_or_null, int L, int zero_rows,
+                                int order, double reg_ls, double y_offset, int use_cholesky, uint8_t* classes_or_null, double* beta,
+                                int32_t* status, void* workspace, size_t workspace_bytes, int flags, void* stream) {
+    LF_REQUIRE(P && pipe && tables_dev && frames && params_host && grid_xy && beta && status && workspace,
+               "lf_lane_infer_seg_folded_u8: null pointer");
+    LF_REQUIRE(order >= 0 && order <= 3 && L >= 1 && L <= 4, "lf_lane_infer_seg_folded_u8: order %d not in 0..3 or L = %d not in 1..4",
+               order, L);
+    LF_REQUIRE((flags & ~(LF_INFER_THIN | LF_INFER_FRAME_TWO_LAUNCH)) == 0, "lf_lane_infer_seg_folded_u8: unknown flags %d", flags);
+    ImgSrc src;
+    src.pipe = pipe; src.tables = tables_dev; src.frames = frames;
+    return lane_infer_seg_run("lf_lane_infer_seg_folded_u8", false, flags, P, src, params_host, params_dev, running_host, grid_xy,
                               grid_batch_stride, gt_line_or_null, L, zero_rows, order, reg_ls, y_offset, use_cholesky, classes_or_null,
                               beta, status, workspace, workspace_bytes, stream);
 }

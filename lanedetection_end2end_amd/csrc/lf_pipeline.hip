@@ -17,24 +17,11 @@
 
 #include <vector>
 
-#include "lf_common.h"
+#include "lf_pipeline_dev.h"
 
-#define PIL_PRECISION_BITS 22
 #define TILE_H_MAX 16
 #define TILE_W_MAX 64
 #define LDS_BUDGET (48 * 1024)
-
-struct lf_pipeline_plan {
-    int Hin, Win, crop_top, crop_h, out_h, out_w;
-    int ksx, ksy;
-    std::vector<int> bx, kx, by, ky;     // bilinear: bounds (first, count) and fixed-point weights
-    std::vector<int> ntx, nty;           // nearest source index tables
-    int tile_h, tile_w;                  // output tile per workgroup (shrunk until its input window fits the LDS budget)
-    int max_rows, max_cols;              // largest input window of an output tile
-    size_t lds_bytes;
-    int in_stride;                       // LDS bytes per staged input row (dword aligned, + shift + tap over-read pad)
-    long table_ints;
-};
 
 namespace {
 
@@ -88,22 +75,6 @@ void pil_nearest_table(int in_size, int out_size, std::vector<int>& tab) {
     }
 }
 
-__device__ __forceinline__ int clip8(int acc) {
-    const int v = acc >> PIL_PRECISION_BITS;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
-
-// device table block layout (ints): bx[2*ow] kx[ow*ksx] by[2*oh] ky[oh*ksy] ntx[ow] nty[oh]
-struct Tables {
-    const int *bx, *kx, *by, *ky, *ntx, *nty;
-};
-__host__ __device__ inline Tables table_ptrs(const int* t, int oh, int ow, int ksx, int ksy) {
-    Tables r;
-    r.bx = t; r.kx = r.bx + 2 * ow; r.by = r.kx + (long)ow * ksx; r.ky = r.by + 2 * oh;
-    r.ntx = r.ky + (long)oh * ksy; r.nty = r.ntx + ow;
-    return r;
-}
-
 // KSX / KSY: compile-time tap counts (table rows are zero-padded to them); 0 = generic (runtime count).
 // Staging uses aligned dword loads with a per-row byte shift; the horizontal pass keeps a column's weights in
 // registers while it walks the rows; the vertical pass walks output rows with wave-uniform (scalar) weights.
@@ -132,28 +103,8 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const uint8_t* __r
         if (bad_index && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(bad_index, 1);
         frame = 0;
     }
-    for (int r = wave; r < nr; r += 4) {
-        // sel: batch element n reads frame sel[n] of a resident pool (the gather of a cached dataset's index batch happens here,
-        // not in a separate 88 MB copy)
-        const size_t g0 = (((size_t)frame * Hin + crop_top + r0 + r) * Win + c0) * 3;
-        const int sh = (int)(g0 & 3);
-        const size_t a0 = g0 - sh;
-        const int nd = (sh + ncb + 3) >> 2;
-        uint32_t* dst = reinterpret_cast<uint32_t*>(s_in + (size_t)r * in_stride);
-        for (int d = lane; d < nd; d += 64) {
-            const size_t byte = a0 + 4 * (size_t)d;
-            uint32_t v;
-            if (byte + 4 <= total_bytes) {
-                v = *reinterpret_cast<const uint32_t*>(frames + byte);
-            } else {
-                v = 0;
-                for (int e = 0; e < 4; ++e)
-                    if (byte + e < total_bytes) v |= (uint32_t)frames[byte + e] << (8 * e);
-            }
-            dst[d] = v;
-        }
-        if (lane == 0) s_shift[r] = sh;
-    }
+    // (the gather of a cached dataset's index batch happens here, not in a separate 88 MB copy)
+    lf_stage_window(frames, total_bytes, frame, Hin, Win, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave);
     __syncthreads();
     // horizontal pass: one (x, channel) column per thread, rows in sequence
     if ((int)threadIdx.x < tw * 3) {
@@ -257,7 +208,7 @@ __global__ __launch_bounds__(256) void horizon_kernel(const int64_t* __restrict_
 
 static size_t lf_pipeline_lds_bytes(lf_pipeline_plan* P) {
     // staged rows hold [shift <= 3][window][over-read of up to ksx taps], rounded to dwords; one spare row each
-    P->in_stride = (P->max_cols * 3 + 3 + P->ksx * 3 + 3) / 4 * 4;
+    P->in_stride = lf_pipeline_in_stride(P->max_cols, P->ksx);
     return ((size_t)(P->max_rows + 1) * sizeof(int) + 15) / 16 * 16 + (size_t)(P->max_rows + 1) * P->in_stride +
            (size_t)(P->max_rows + P->ksy) * P->tile_w * 3;
 }
@@ -291,7 +242,10 @@ lf_pipeline_plan* lf_pipeline_plan_create(int Hin, int Win, int crop_top, int cr
             if (n > P->max_cols) P->max_cols = n;
         }
         P->lds_bytes = lf_pipeline_lds_bytes(P);
-        if (P->lds_bytes <= LDS_BUDGET) return P;
+        if (P->lds_bytes <= LDS_BUDGET) {
+            lf_frame_stem_plan(P);
+            return P;
+        }
         if (P->tile_h == 1 && P->tile_w == 1) break;
         if (P->max_cols >= 2 * P->max_rows && P->tile_w > 1) P->tile_w /= 2;     // keep rows of >= 16 pixels while possible
         else if (P->tile_h > 1) P->tile_h /= 2;
@@ -303,6 +257,16 @@ lf_pipeline_plan* lf_pipeline_plan_create(int Hin, int Win, int crop_top, int cr
 }
 void lf_pipeline_plan_destroy(lf_pipeline_plan* P) { delete P; }
 size_t lf_pipeline_table_bytes(const lf_pipeline_plan* P) { return (size_t)P->table_ints * sizeof(int); }
+// include/lanefit.h, "additions since 5 -- camera frames": whether frame_stem_kernel (lf_frame_stem.hip) takes the plan's geometry,
+// the tile of stem output pixels it chose and the LDS bytes of one workgroup (0 where it does not fit)
+int lf_pipeline_frame_stem_ok(const lf_pipeline_plan* P) { return P && P->fs_ok ? 1 : 0; }
+size_t lf_pipeline_frame_stem_lds_bytes(const lf_pipeline_plan* P) { return P && P->fs_ok ? P->fs_lds_bytes : 0; }
+int lf_pipeline_frame_stem_tile(const lf_pipeline_plan* P, int* tile_h, int* tile_w) {
+    LF_REQUIRE(P, "lf_pipeline_frame_stem_tile: null plan");
+    if (tile_h) *tile_h = P->fs_ok ? P->fs_th : 0;
+    if (tile_w) *tile_w = P->fs_ok ? P->fs_tw : 0;
+    return 0;
+}
 
 // Copy the tables (bilinear bounds + weights, nearest indices) to a device buffer of lf_pipeline_table_bytes().
 int lf_pipeline_upload(const lf_pipeline_plan* P, void* tables_dev, void* stream) {

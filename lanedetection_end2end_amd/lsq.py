@@ -3,6 +3,8 @@ BEV flavour (normalised coordinates, fp32 betas) and BP flavour (pixel coordinat
 
 Reference: BEV/Networks/LSQ_layer.py:231-326, BP/Networks/LSQ_layer.py:210-315.
 """
+import ctypes
+import weakref
 from collections import namedtuple
 from math import ceil
 from types import SimpleNamespace
@@ -237,6 +239,18 @@ THIN_AUTO_MAX_BATCH_BF16 = 4
 THIN_AUTO_MAX_BATCH_HEADS = 8
 THIN_AUTO_MAX_BATCH_HEADS_BF16 = 8
 
+# camera(fused="auto"): the largest batch up to which the fused resize + stem launch (frame_stem_kernel, csrc/lf_frame_stem.hip) measured
+# faster in-stream than the two-launch form inside the same call, beyond the min-max ranges of both, at every batch below it too and in
+# both geometries, 720 x 1280 -> 256 x 512 (BP --clas, lanes) and -> 320 x 640 (BP 4 lanes, __call__), among 1, 2, 4, 8, 32
+# (tools/detector_latency.py --frames, profiles/detector_frames_latency.json, key frame_stem_auto_max_batch_by_precision).  fp32: it
+# won at 1, 2, 4 and 8 (one frame 0.684 -> 0.667 ms and 0.785 -> 0.772 ms); at 32 it won at 256 x 512 (5.037 -> 5.025 ms) and the
+# ranges overlap at 320 x 640 (7.601 (7.596 - 7.702) against 7.613 (7.607 - 7.617) ms).  0 would mean "auto" = the two-launch form.
+# fp32x9 runs the stem launches of fp32 and follows its constant
+FRAME_STEM_AUTO_MAX_BATCH = 8
+# ... in precision mode bf16 it won at all five batches in both geometries (one frame 0.523 -> 0.508 and 0.559 -> 0.544 ms; 32 frames
+# 1.872 -> 1.862 and 1.949 -> 1.898 ms)
+FRAME_STEM_AUTO_MAX_BATCH_BF16 = 32
+
 # what LaneDetector.lanes returns
 FrameLanes = namedtuple("FrameLanes", ["lanes", "betas", "line", "horizon", "line_flags", "horizon_row"])
 
@@ -292,7 +306,14 @@ class LaneDetector:
         self.frozen_heads = True
         self._plan = erfnet._Plan(self.shape[0], self.shape[2], self.shape[3], model.net.in_channels, model.net.out_channels,
                                   2 if model.net.pretrained else 1)
+        self._cameras = weakref.WeakSet()
         self.refresh()
+
+    def camera(self, frame_hw=(720, 1280), crop=640, fused="auto"):
+        """A ``CameraDetector`` on this detector: the same calls from decoded uint8 camera frames ``(batch, Hf, Wf, 3)`` -- the
+        reference's ``LaneTestSet`` pixel work (crop the bottom ``crop`` rows, Pillow BILINEAR resize to the detector's
+        ``(height, width)``, ``ToTensor``) inside the one backbone C call.  RGB models only.  See ``CameraDetector``."""
+        return CameraDetector(self, frame_hw, crop, fused)
 
     @torch.no_grad()
     def refresh(self):
@@ -365,6 +386,8 @@ class LaneDetector:
             self._heads = (model.line_classification, model.horizon_estimation)
         self._dev = dev
         self._ptrs = (erfnet._lib.ptr(self._params_dev), erfnet._lib.ptr(self._grid), erfnet._lib.ptr(self._ws))
+        for cam in list(self._cameras):
+            cam._refold()
 
     def _require_eval(self):
         model = self.model
@@ -502,6 +525,159 @@ class LaneDetector:
                                                        self._zero_rows, self._order, self._reg, self._y_offset, self._chol,
                                                        erfnet._lib.ptr(classes), beta.data_ptr(), status.data_ptr(), ws,
                                                        self._nbytes, self._flags, erfnet._lib.stream()), "lf_lane_infer_seg_folded")
+        self._finish(status, check)
+        return beta, classes
+
+
+class CameraDetector(LaneDetector):
+    """``det.camera(frame_hw=(720, 1280), crop=640, fused="auto")``: a view on a ``LaneDetector`` that starts from what a camera (and
+    the reference's ``LaneTestSet.__getitem__``, BP/Dataloader/Load_Data_new.py:55-65) delivers -- decoded uint8 HWC frames.
+    ``cam(frames_u8, gt_line=None)``, ``cam.lanes(frames_u8, out=None)`` and ``cam.segment(frames_u8)`` return exactly what
+    ``det(x)``, ``det.lanes(x)`` and ``det.segment(x)`` return for ``x = InputPipeline(resize, tree, frame_hw=frame_hw,
+    crop=crop)(frames_u8)[0]``: the same tuples and ``FrameLanes``, dtypes, ``None``s, ``last_status`` (on the camera and the model)
+    and ``check_singular`` behaviour.  Each is ONE backbone C call (``lf_lane_infer_folded_u8`` / ``lf_lane_infer_seg_folded_u8``);
+    no fp32 image tensor is allocated.
+
+    The camera owns its ``lf_pipeline_plan`` (``frame_hw``, ``crop`` -> the detector's ``(height, width)``), the uploaded tables and a
+    workspace of its own, folded once like the detector's; everything else (the engine plan, pointer tables, grid, the frozen
+    ``--clas`` heads, the thin flags) is the detector's.  ``det.refresh()`` refreshes its cameras too (``cam.refresh()`` is
+    ``det.refresh()``): the detector's contract -- refresh after ANY change of the model -- covers them.  Calls of a camera and of
+    its detector must be issued on one stream; cameras of one detector are independent of each other (own workspace, fresh results).
+
+    ``cam.fused``: ``True`` -- crop, resize, ``ToTensor`` and the stem in one launch (``frame_stem_kernel``: the resized image
+    stays in LDS); ``False`` -- ``resize_bilinear_kernel`` into an image slot of the workspace, then the stem, two launches inside the
+    same call; the same bits.  ``"auto"`` (default): fused for batches up to ``FRAME_STEM_AUTO_MAX_BATCH`` (``fp32``, ``fp32x9``) /
+    ``FRAME_STEM_AUTO_MAX_BATCH_BF16`` (``bf16``).  A geometry whose source window does not fit the kernel's LDS tile (1280 x 640 ->
+    128 x 64) raises ``ValueError`` for ``True`` and runs as two launches for ``"auto"``.
+
+    Input: a contiguous uint8 tensor ``(batch, Hf, Wf, 3)`` on the device (``ValueError`` otherwise; ``LaneFitLibraryError`` for a
+    CPU tensor).  Eval mode only, as the detector."""
+
+    def __init__(self, det, frame_hw=(720, 1280), crop=640, fused="auto"):
+        if type(det) is not LaneDetector:
+            raise TypeError("camera() is a method of a LaneDetector")
+        lib = erfnet._lib.load()
+        det._require_eval()
+        if det.shape[1] != 3:
+            raise RuntimeError("lanefit camera() needs an RGB model (channels_in = 3): camera frames are (batch, Hf, Wf, 3) uint8, this "
+                               "model takes %d channel(s)" % det.shape[1])
+        Hf, Wf = int(frame_hw[0]), int(frame_hw[1])
+        N, _, H, W = det.shape
+        self._det = det
+        self.frame_shape = (N, Hf, Wf, 3)
+        self.last_status = None
+        self._pipe = lib.lf_pipeline_plan_create(Hf, Wf, Hf - int(crop), int(crop), H, W)
+        if not self._pipe:
+            raise erfnet._lib.LaneFitLibraryError("lf_pipeline_plan_create failed: %s" % lib.lf_last_error().decode())
+        self._pipe = ctypes.c_void_p(self._pipe)
+        self.fits = bool(lib.lf_pipeline_frame_stem_ok(self._pipe))
+        self.fused = fused
+        self._tables = self._ws = None
+        self._refold()
+        det._cameras.add(self)
+
+    def __getattr__(self, name):
+        # what the camera does not own is the detector's (the engine plan, pointer tables, grid, heads, flags)
+        det = self.__dict__.get("_det")
+        if det is None or name.startswith("__"):
+            raise AttributeError(name)
+        return getattr(det, name)
+
+    def __del__(self):
+        try:
+            erfnet._lib.load().lf_pipeline_plan_destroy(self._pipe)
+        except Exception:
+            pass
+
+    @property
+    def fused(self):
+        return self._fused
+
+    @fused.setter
+    def fused(self, value):
+        if value not in (True, False, "auto"):
+            raise ValueError("camera(fused=...) takes True, False or \"auto\"")
+        if value is True and not self.fits:
+            raise ValueError("camera(fused=True): the source window of a tile does not fit the fused kernel's LDS budget at %s -> %s; "
+                             "use \"auto\" or False (two launches inside the call)" % (self.frame_shape[1:3], self._det.shape[2:]))
+        self._fused = value
+
+    def camera(self, *args, **kwargs):
+        raise RuntimeError("camera() is a method of the LaneDetector, not of one of its cameras")
+
+    def refresh(self):
+        """``det.refresh()``: the detector and every camera of it fold again."""
+        self._det.refresh()
+
+    @torch.no_grad()
+    def _refold(self):
+        det, lib = self._det, erfnet._lib.load()
+        dev = det._dev
+        K = det._lanes if det._seg else det.model.net.out_channels
+        query = lib.lf_lane_infer_seg_u8_workspace_bytes if det._seg else lib.lf_lane_infer_u8_workspace_bytes
+        self._nbytes = query(det._plan.handle, det._mode, K, det._order)
+        if self._nbytes == 0:
+            raise erfnet._lib.LaneFitLibraryError("lanefit camera(): unsupported mode / lanes / order (%s, %d)" % (det.precision, det._order))
+        if self._tables is None or self._tables.device != dev:
+            self._tables = torch.empty(lib.lf_pipeline_table_bytes(self._pipe), dtype=torch.uint8, device=dev)
+            erfnet._lib.check(lib.lf_pipeline_upload(self._pipe, erfnet._lib.ptr(self._tables), erfnet._lib.stream()), "lf_pipeline_upload")
+        if self._ws is None or self._ws.numel() != self._nbytes or self._ws.device != dev:
+            self._ws = torch.empty(self._nbytes, dtype=torch.uint8, device=dev)
+        erfnet._lib.check(lib.lf_erfnet_infer_fold(det._plan.handle, det._params_host, erfnet._lib.ptr(det._params_dev),
+                                                   det._running_host, erfnet._lib.ptr(self._ws), self._nbytes, erfnet._lib.stream()),
+                          "lf_erfnet_infer_fold")
+        self._enc = self._enc_nhwc = self._lanes_state = None
+        if det._enc is not None:
+            self._enc_nhwc = det.model.net._infer_encoder_view(det._plan, self._ws, det._mode)
+            self._enc = self._enc_nhwc.permute(0, 3, 1, 2)
+        self._ptrs = (erfnet._lib.ptr(det._params_dev), erfnet._lib.ptr(det._grid), erfnet._lib.ptr(self._ws))
+
+    def _u8_flags(self):
+        det = self._det
+        if self._fused == "auto":
+            auto_max = FRAME_STEM_AUTO_MAX_BATCH_BF16 if det.precision == "bf16" else FRAME_STEM_AUTO_MAX_BATCH
+            on = self.fits and det.shape[0] <= auto_max
+        else:
+            on = self._fused
+        return det._flags | (0 if on else 2)          # LF_INFER_FRAME_TWO_LAUNCH
+
+    def _input(self, frames):
+        self._det._require_eval()
+        if tuple(frames.shape) != self.frame_shape:
+            raise ValueError("this camera was built for frames of shape %s, got %s" % (self.frame_shape, tuple(frames.shape)))
+        if not frames.is_cuda:
+            raise erfnet._lib.LaneFitLibraryError("lanefit camera needs its frames on the MI355X; there is no CPU path")
+        if frames.dtype != torch.uint8 or not frames.is_contiguous():
+            raise ValueError("camera frames are contiguous uint8 (batch, Hf, Wf, 3) tensors, got %s%s"
+                             % (frames.dtype, "" if frames.is_contiguous() else ", not contiguous"))
+        return frames
+
+    def _backbone(self, x):
+        det, lib = self._det, erfnet._lib.load()
+        N, K = det.shape[0], det.model.net.out_channels
+        params_dev, grid, ws = self._ptrs
+        beta = torch.empty(N, K, det._order + 1, dtype=torch.float64, device=det._dev)
+        status = torch.empty(N * K, dtype=torch.int32, device=det._dev)
+        erfnet._lib.check(lib.lf_lane_infer_folded_u8(det._plan.handle, self._pipe, self._tables.data_ptr(), x.data_ptr(),
+                                                      det._params_host, params_dev, det._running_host, grid, det._gstride,
+                                                      det._zero_rows, det._order, det._reg, det._y_offset, det._act, det._chol, None,
+                                                      beta.data_ptr(), status.data_ptr(), ws, self._nbytes, self._u8_flags(),
+                                                      erfnet._lib.stream()), "lf_lane_infer_folded_u8")
+        return beta, status
+
+    def _seg_call(self, x, flags, want_classes, check):
+        det, lib = self._det, erfnet._lib.load()
+        N, _, H, W = det.shape
+        params_dev, grid, ws = self._ptrs
+        beta = torch.empty(N, det._lanes, det._order + 1, dtype=torch.float64, device=det._dev)
+        status = torch.empty(N * det._lanes, dtype=torch.int32, device=det._dev)
+        classes = torch.empty(N, H, W, dtype=torch.uint8, device=det._dev) if want_classes else None
+        erfnet._lib.check(lib.lf_lane_infer_seg_folded_u8(det._plan.handle, self._pipe, self._tables.data_ptr(), x.data_ptr(),
+                                                          det._params_host, params_dev, det._running_host, grid, det._gstride,
+                                                          erfnet._lib.ptr(flags), det._lanes, det._zero_rows, det._order, det._reg,
+                                                          det._y_offset, det._chol, erfnet._lib.ptr(classes), beta.data_ptr(),
+                                                          status.data_ptr(), ws, self._nbytes, self._u8_flags(), erfnet._lib.stream()),
+                          "lf_lane_infer_seg_folded_u8")
         self._finish(status, check)
         return beta, classes
 

@@ -32,6 +32,19 @@ decides lsq.THIN_AUTO_MAX_BATCH_HEADS / _BF16 by the rule above.  ``gain`` is st
     python tools/detector_latency.py --launches DB_A DB_C [--out profiles/detector_launches.md]
     python tools/detector_latency.py --lanes-launches DB_L [--out profiles/detector_launches.md]      (appends the list of --trace L)
 
+    python tools/detector_latency.py --frames [--out profiles/detector_frames_latency.json] [--precisions fp32,bf16] [--batches 1,2,4,8,32]
+
+--frames: decoded uint8 720 x 1280 camera frames -> results, three ways alternated in one process by the same protocol: (A)
+``InputPipeline`` + ``det(x)`` / ``det.lanes(x)`` (two Python calls, a fresh fp32 image per frame), (B) ``det.camera()`` with the
+two-launch form inside the call (``fused=False``), (C) the camera with the fused resize + stem launch (``fused=True``,
+frame_stem_kernel).  Geometries: -> 256 x 512 on the BP --clas recipe through ``lanes``, -> 320 x 640 on BP 4 lanes through
+``__call__``.  ``fused_wins``: (C)'s in-stream time is below (B)'s beyond the min-max ranges of both.
+``frame_stem_auto_max_batch_by_precision``: the largest batch up to which (C) won at every batch and in both geometries (0: nowhere)
+-- lsq.FRAME_STEM_AUTO_MAX_BATCH / _BF16.
+
+    rocprofv3 --kernel-trace --stats -d DIR -o trace -- python tools/detector_latency.py --trace F|G
+    python tools/detector_latency.py --frames-launches DB_F DB_G [--out profiles/detector_launches.md]   (appends; F fused, G two launches)
+
 The launch table: ten batch-1 calls at 1 x 256 x 512 fp32 of path (A) / (C) under the profiler (no counters), then per-kernel count
 and duration of the two runs side by side from their rocpd databases.
 """
@@ -293,6 +306,130 @@ def run_lanes(args):
     print(json.dumps({"heads_thin_auto_max_batch_by_precision": bounds}))
 
 
+FRAMES_HW, FRAMES_CROP = (720, 1280), 640
+
+
+def camera_frames(N):
+    import numpy as np
+    import torch
+    from oracle import pipeline_oracle
+    return torch.from_numpy(np.stack([pipeline_oracle.synthetic_frame(3 + n)[0] for n in range(min(N, 4))])[[n % 4 for n in range(N)]]).cuda()
+
+
+def measure_frames(cfg, through_lanes, precision, N, warmup, calls, repeats):
+    import torch
+    from lanedetection_end2end_amd.pipeline import InputPipeline
+    model = make_model(cfg, precision, N, clas=through_lanes)
+    f = camera_frames(N)
+    det = model.detector(batch=N, height=cfg["H"], width=cfg["W"], thin="auto")
+    pipe = InputPipeline(cfg["H"], "bp", frame_hw=FRAMES_HW, crop=FRAMES_CROP)
+    cams = {False: det.camera(FRAMES_HW, FRAMES_CROP, fused=False), True: det.camera(FRAMES_HW, FRAMES_CROP, fused=True)}
+    if through_lanes:
+        buf = torch.empty(N, cfg["K"], 56, dtype=torch.int32, device="cuda")
+        paths = {"A_pipeline_then_detector": lambda u: det.lanes(pipe(u)[0], out=buf).lanes,
+                 "B_camera_two_launches": lambda u: cams[False].lanes(u, out=buf).lanes,
+                 "C_camera_fused": lambda u: cams[True].lanes(u, out=buf).lanes}
+    else:
+        paths = {"A_pipeline_then_detector": lambda u: det(pipe(u)[0])[3],
+                 "B_camera_two_launches": lambda u: cams[False](u)[3],
+                 "C_camera_fused": lambda u: cams[True](u)[3]}
+    ref = paths["A_pipeline_then_detector"](f).clone()
+    for name, fn in paths.items():      # the three ways give the same bits
+        assert torch.equal(fn(f), ref), name
+    ev = {k: [] for k in paths}
+    wall = {k: [] for k in paths}
+    for _ in range(repeats):
+        for name, fn in paths.items():
+            for _ in range(warmup):
+                fn(f)
+            e, w = timed(fn, f, calls)
+            ev[name].append(e)
+            wall[name].append(w)
+    row = {"config": cfg["name"], "through": "lanes" if through_lanes else "__call__", "frames": "%dx%d crop %d" % (FRAMES_HW + (FRAMES_CROP,)),
+           "precision": precision, "batch": N}
+    for name in paths:
+        row[name] = {"in_stream_ms": stats(ev[name]), "wall_ms": stats(wall[name])}
+    b, c = row["B_camera_two_launches"]["in_stream_ms"], row["C_camera_fused"]["in_stream_ms"]
+    row["fused_wins"] = c["max"] < b["min"]
+    row["fused_against_two_launches"] = "gain" if c["max"] < b["min"] else "loss" if c["min"] > b["max"] else "ranges overlap"
+    row["median_ratio_C_to_B"] = round(c["median"] / b["median"], 4)
+    row["median_ratio_B_to_A"] = round(b["median"] / row["A_pipeline_then_detector"]["in_stream_ms"]["median"], 4)
+    del model, det, cams, paths, f
+    torch.cuda.empty_cache()
+    return row
+
+
+def run_frames(args):
+    import torch
+    rows = []
+    precisions = args.precisions.split(",")
+    batches = [int(b) for b in args.batches.split(",")]
+    for cfg, through_lanes in ((LANES_CFG, True), (CONFIGS["bp"], False)):
+        for precision in precisions:
+            for N in batches:
+                rows.append(measure_frames(cfg, through_lanes, precision, N, args.warmup, args.calls, args.repeats))
+                print(json.dumps(rows[-1]), flush=True)
+    bounds = {}
+    for precision in precisions:      # the largest batch up to which the fused launch won at every batch, in both geometries
+        bounds[precision] = 0
+        for N in sorted(set(batches)):
+            at = [r for r in rows if r["precision"] == precision and r["batch"] == N]
+            if not at or not all(r["fused_wins"] for r in at):
+                break
+            bounds[precision] = N
+    res = {"tool": "detector_latency --frames", "commit": commit_stamp(), "device": torch.cuda.get_device_name(0), "warmup": args.warmup,
+           "calls": args.calls, "repeats": args.repeats, "check_singular": False, "frame_stem_auto_max_batch_by_precision": bounds,
+           "results": rows}
+    with open(args.out or os.path.join(ROOT, "profiles", "detector_frames_latency.json"), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"frame_stem_auto_max_batch_by_precision": bounds}))
+
+
+def trace_frames(fused):
+    """ten batch-1 cam.lanes(frame) calls, 720 x 1280 -> 256 x 512 fp32, --clas (run under rocprofv3 --kernel-trace --stats)"""
+    import torch
+    cfg = LANES_CFG
+    model = make_model(cfg, "fp32", 1, clas=True)
+    cam = model.detector(thin=True).camera(FRAMES_HW, FRAMES_CROP, fused=fused)
+    f = camera_frames(1)
+    for _ in range(10):
+        cam.lanes(f)
+    torch.cuda.synchronize()
+
+
+def frames_launches(db_f, db_g, out):
+    """append the kernels of --trace F (fused) and --trace G (two launches) side by side to the launch table"""
+    import sqlite3
+
+    def table(path):
+        cur = sqlite3.connect(path).cursor()
+        cols = [r[1] for r in cur.execute("pragma table_info(kernels)")]
+        name_col = "name" if "name" in cols else [c for c in cols if "name" in c][0]
+        agg = {}
+        for n, s, e in cur.execute("select %s, start, end from kernels" % name_col).fetchall():
+            k = re.sub(r"\(.*$", "", re.sub(r"\(anonymous namespace\)::", "", n)).replace("void ", "")[:80]
+            a = agg.setdefault(k, [0, 0])
+            a[0] += 1
+            a[1] += e - s
+        return agg
+    tf, tg = table(db_f), table(db_g)
+    lines = ["", "# Launches of ten `det.camera().lanes(frame_u8)` calls, 1 x 720 x 1280 x 3 uint8 -> 256 x 512, fp32, BP 4 lanes order 3 --clas", "",
+             "commit: `%s`" % commit_stamp(), "",
+             "`rocprofv3 --kernel-trace --stats` (no counters) of one process each: the model's set-up and the folds, then ten calls with",
+             "(F) `fused=True` (frame_stem_kernel) / (G) `fused=False` (resize_bilinear_kernel + stem_fwd_kernel inside the call).",
+             "Per kernel: launches and summed duration (us) over the whole process, sorted by time.", "",
+             "| kernel | (F) launches | (F) us | (G) launches | (G) us |", "|---|---:|---:|---:|---:|"]
+    for k in sorted(set(tf) | set(tg), key=lambda k: -(tf.get(k, [0, 0])[1] + tg.get(k, [0, 0])[1])):
+        a, c = tf.get(k, [0, 0]), tg.get(k, [0, 0])
+        lines.append("| `%s` | %d | %.1f | %d | %.1f |" % (k, a[0], a[1] / 1e3, c[0], c[1] / 1e3))
+    lines += ["", "total: (F) %d launches, %.1f us; (G) %d launches, %.1f us" %
+              (sum(v[0] for v in tf.values()), sum(v[1] for v in tf.values()) / 1e3,
+               sum(v[0] for v in tg.values()), sum(v[1] for v in tg.values()) / 1e3), ""]
+    with open(out or os.path.join(ROOT, "profiles", "detector_launches.md"), "a") as f:
+        f.write("\n".join(lines))
+
+
 def trace_lanes():
     """ten batch-1 det.lanes(frame) calls at 1 x 256 x 512 fp32, --clas (run under rocprofv3 --kernel-trace --stats)"""
     import torch
@@ -336,6 +473,8 @@ def trace(path):
     from oracle import inputs
     if path == "L":
         return trace_lanes()
+    if path in ("F", "G"):
+        return trace_frames(path == "F")
     cfg = CONFIGS["bev"]
     model = make_model(cfg, "fp32", 1)
     x = torch.from_numpy(inputs.images(1, cfg["H"], cfg["W"], seed=1)).cuda()
@@ -385,8 +524,10 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--trace", choices=["A", "C", "L"])
+    ap.add_argument("--trace", choices=["A", "C", "L", "F", "G"])
     ap.add_argument("--lanes", action="store_true")
+    ap.add_argument("--frames", action="store_true")
+    ap.add_argument("--frames-launches", nargs=2, metavar=("DB_F", "DB_G"))
     ap.add_argument("--lanes-launches", metavar="DB_L")
     ap.add_argument("--launches", nargs=2, metavar=("DB_A", "DB_C"))
     args = ap.parse_args()
@@ -396,7 +537,11 @@ if __name__ == "__main__":
         launches(args.launches[0], args.launches[1], args.out)
     elif args.lanes_launches:
         lanes_launches(args.lanes_launches, args.out)
+    elif args.frames_launches:
+        frames_launches(args.frames_launches[0], args.frames_launches[1], args.out)
     elif args.lanes:
         run_lanes(args)
+    elif args.frames:
+        run_frames(args)
     else:
         run(args)
