@@ -59,7 +59,8 @@ extern "C" {
                                  lf_clas_tail_workspace_bytes, lf_clas_tail;
                                  additions since 5 (camera frames): lf_pipeline_frame_stem_ok, lf_pipeline_frame_stem_lds_bytes,
                                  lf_pipeline_frame_stem_tile, lf_lane_infer_u8_workspace_bytes, lf_lane_infer_seg_u8_workspace_bytes,
-                                 lf_lane_infer_folded_u8, lf_lane_infer_seg_folded_u8 */
+                                 lf_lane_infer_folded_u8, lf_lane_infer_seg_folded_u8;
+                                 additions since 5 (frame formats): lf_pipeline_plan_set_format, lf_pipeline_frame_bytes */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -741,7 +742,8 @@ int lf_clas_tail(const void* y_line, const void* y_hor, int bf16, int N, int H, 
 /* additions since 5 -- camera frames: the frozen detector's calls from decoded uint8 HWC camera frames (N,Hin,Win,3), what the
  * reference's LaneTestSet.__getitem__ starts from (BP/Dataloader/Load_Data_new.py:55-65: crop, Pillow BILINEAR resize, ToTensor), in
  * the place of the fp32 (N,3,H,W) image.  `pipe` is an lf_pipeline_plan whose output size is the network plan's H x W, tables_dev
- * the buffer lf_pipeline_upload filled.  RGB only: the network plan has 3 input channels.
+ * the buffer lf_pipeline_upload filled.  RGB only: the network plan has 3 input channels (frames in BGR, NV12 or YUYV become RGB in
+ * the staging: "additions since 5 -- frame formats" below).
  * lf_lane_infer_folded_u8 / lf_lane_infer_seg_folded_u8: lf_lane_infer_folded / lf_lane_infer_seg_folded with (pipe, tables_dev,
  *   frames) for img; the results are those of lf_pipeline_image followed by the call on its output, bit for bit.  The resize and the
  *   stem run as ONE launch (the resized image stays in LDS) where lf_pipeline_frame_stem_ok(pipe) is 1; where it is 0 (the source
@@ -770,6 +772,33 @@ int lf_lane_infer_seg_folded_u8(const lf_erfnet_plan* plan, const lf_pipeline_pl
                                 const float* gt_line_or_null, int L, int zero_rows, int order, double reg_ls, double y_offset,
                                 int use_cholesky, uint8_t* classes_or_null, double* beta, int32_t* status, void* workspace,
                                 size_t workspace_bytes, int flags, void* stream);
+
+/* additions since 5 -- frame formats: what the frames pointer of a plan holds.  Decoders write NV12, USB / CSI cameras deliver YUYV,
+ * OpenCV decodes to BGR; the staging of a source window converts to RGB in registers, and everything behind it (both resize passes,
+ * ToTensor, the fused stem) runs on those uint8 RGB values as on packed RGB frames.  Contiguous uint8, pitch = width:
+ *   LF_FRAME_RGB, LF_FRAME_BGR  (N,Hin,Win,3) packed;
+ *   LF_FRAME_NV12               (N,Hin*3/2,Win): Hin rows of Y, then Hin/2 rows of interleaved Cb Cr pairs; Hin and Win even;
+ *   LF_FRAME_YUYV               (N,Hin,Win,2): Y0 Cb Y1 Cr per pixel pair; Win even.
+ * The chroma of pixel (y, x) is the pair at chroma row y >> 1, column x >> 1 (NV12) / of pixel pair x >> 1 in row y (YUYV), y the row
+ * in the FULL frame (an odd crop_top is legal): replicated, not interpolated.  YCbCr -> RGB is this Q16 form, arithmetic shift:
+ *   y' = Y - y_off;  u = Cb - 128;  v = Cr - 128
+ *   R = clamp8((c_y y' + c_rv v + 32768) >> 16)
+ *   G = clamp8((c_y y' - c_gu u - c_gv v + 32768) >> 16)
+ *   B = clamp8((c_y y' + c_bu u + 32768) >> 16)
+ * with coef = {c_y, y_off, c_rv, c_gu, c_gv, c_bu}: {65536, 0, 91881, 22554, 46802, 116130} is full-range BT.601 as libjpeg's
+ * decoder computes it, bit for bit (the default); {76309, 16, 117489, 13975, 34925, 138438} is limited-range BT.709.
+ * Bit contract: every result of a call on frames in format F equals the same call on an LF_FRAME_RGB plan of the same geometry, fed the
+ * RGB frames this definition makes from them.
+ * lf_pipeline_plan_set_format: sets the format of a plan (host only, no device is touched).  coef may be NULL for LF_FRAME_RGB /
+ *   LF_FRAME_BGR (it is ignored there) and for the YCbCr formats (the default above).  Refuses an unknown format, an odd Hin or Win
+ *   for NV12, an odd Win for YUYV, and coefficients with which an intermediate could leave int32.  A plan that never gets this call
+ *   is an LF_FRAME_RGB plan.  Every entry point that takes a plan and a frames pointer (lf_pipeline_image, lf_pipeline_image_indexed,
+ *   lf_lane_infer_folded_u8, lf_lane_infer_seg_folded_u8) reads the format from the plan; labels know no format.
+ * lf_pipeline_frame_bytes: the bytes of one frame in the plan's format (Hin Win 3, Hin Win 3 / 2, Hin Win 2); 0 for a NULL plan.  No
+ *   load reaches past N (pool_frames) times this many bytes behind the frames pointer. */
+enum { LF_FRAME_RGB = 0, LF_FRAME_BGR = 1, LF_FRAME_NV12 = 2, LF_FRAME_YUYV = 3 };
+int lf_pipeline_plan_set_format(lf_pipeline_plan* plan, int format, const int coef[6]);
+size_t lf_pipeline_frame_bytes(const lf_pipeline_plan* plan);
 
 /* additions since 5 -- input-image gradient: d loss / d input of Net.forward, what `input.requires_grad_()` before the forward and
  * `loss.backward()` (BEV/main.py:264-266) give in the reference -- the data gradient of the stem DownsamplerBlock's

@@ -155,6 +155,8 @@ def _declare(lib):
         "lf_lane_infer_seg_u8_workspace_bytes": (c_size_t, [P, I, I, I]),
         "lf_lane_infer_folded_u8": (I, [P, P, P, P, P, P, P, P, L, I, I, D, D, I, I, P, P, P, P, c_size_t, I, P]),
         "lf_lane_infer_seg_folded_u8": (I, [P, P, P, P, P, P, P, P, L, P, I, I, I, D, D, I, P, P, P, P, c_size_t, I, P]),
+        "lf_pipeline_plan_set_format": (I, [P, I, P]),
+        "lf_pipeline_frame_bytes": (c_size_t, [P]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {

@@ -8,7 +8,9 @@
 //   - the resize passes are resize_bilinear_kernel's integer arithmetic on the same tables, and ToTensor is the same (float)v / 255.0f;
 //   - the MFMA sequence is stem_fwd_kernel's: 7 K-steps of v_mfma_f32_16x16x4_f32, k = 4 s + kq, the same A and B per step, zeros for
 //     the padding taps and the padded K-step; the pooled channels after the same permutes, bias / affine + ReLU in the same order.
-// The staging (and its guard against the end of the frames buffer) is SHARED with resize_bilinear_kernel (lf_pipeline_dev.h).  The
+// The staging (and its guard against the end of the frames buffer) is SHARED with resize_bilinear_kernel (lf_pipeline_dev.h), and it
+// is the only stage that knows the frame format: frame_stem_kernel is the packed-RGB kernel, frame_format_stem_kernel<.., FMT> the same
+// body behind lf_stage_window_format<FMT> (BGR, NV12, YUYV -> the same RGB triples in the same LDS rows; the same LDS budget).  The
 // two resize passes and the stem's per-tile arithmetic are LABELLED COPIES: the passes here walk a window
 // with a one-pixel zero border and write LDS, not NCHW rows, and stem_fwd_kernel interleaves its operand addressing with the MFMA
 // issue -- a common body would change the registers of both existing kernels.
@@ -41,11 +43,13 @@ inline FsLayout fs_layout(int th, int tw, int max_rows, int max_cols, int ksx, i
 }
 
 // KSX / KSY: compile-time tap counts (table rows are zero-padded to them); 0 = generic (runtime count), as resize_bilinear_kernel
-template <int KSX, int KSY, typename T>
-__global__ __launch_bounds__(256) void frame_stem_kernel(const uint8_t* __restrict__ frames, size_t total_bytes, int Hin, int Win, int crop_top,
-                                                        const int* __restrict__ tables, int oh, int ow, int ksx, int ksy, int TH, int TW,
-                                                        int max_rows, int in_stride, const float* __restrict__ w, const float* __restrict__ b,
-                                                        const float* __restrict__ sc, const float* __restrict__ sh, T* __restrict__ cat) {
+// FMT: the frame format (LF_FRAME_*), which only the staging knows; cf: its YCbCr coefficients (unused for RGB / BGR)
+template <int KSX, int KSY, typename T, int FMT>
+__device__ __forceinline__ void frame_stem_body(const uint8_t* __restrict__ frames, size_t total_bytes, int Hin, int Win, int crop_top,
+                                                const int* __restrict__ tables, int oh, int ow, int ksx, int ksy, int TH, int TW,
+                                                int max_rows, int in_stride, const float* __restrict__ w, const float* __restrict__ b,
+                                                const float* __restrict__ sc, const float* __restrict__ sh, T* __restrict__ cat,
+                                                const lf_yuv_coef cf) {
     constexpr int CIN = 3, Cc = 16 - CIN, KK = 9 * CIN, KS = (KK + 3) / 4;
     extern __shared__ uint8_t smem[];
     const int ncw = 2 * TW + 1, nrw = 2 * TH + 1;             // resized window: columns, rows
@@ -65,7 +69,10 @@ __global__ __launch_bounds__(256) void frame_stem_kernel(const uint8_t* __restri
     const int r0 = Tb.by[2 * ya], r1 = Tb.by[2 * yb] + Tb.by[2 * yb + 1];
     const int c0 = Tb.bx[2 * xa], c1 = Tb.bx[2 * xb] + Tb.bx[2 * xb + 1];
     const int nr = r1 - r0, ncb = (c1 - c0) * 3;
-    lf_stage_window(frames, total_bytes, n, Hin, Win, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave);
+    if constexpr (FMT == LF_FRAME_RGB)
+        lf_stage_window(frames, total_bytes, n, Hin, Win, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave);
+    else
+        lf_stage_window_format<FMT>(frames, total_bytes, n, Hin, Win, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave, cf);
     __syncthreads();
     // ---- horizontal pass (copy of resize_bilinear_kernel's): one (x, channel) column of the window per thread, rows in sequence
     const int nxc = (xb - xa + 1) * 3;
@@ -174,6 +181,26 @@ __global__ __launch_bounds__(256) void frame_stem_kernel(const uint8_t* __restri
     }
 }
 
+// packed RGB frames: the kernel every plan ran before there were formats, the same code
+template <int KSX, int KSY, typename T>
+__global__ __launch_bounds__(256) void frame_stem_kernel(const uint8_t* __restrict__ frames, size_t total_bytes, int Hin, int Win, int crop_top,
+                                                        const int* __restrict__ tables, int oh, int ow, int ksx, int ksy, int TH, int TW,
+                                                        int max_rows, int in_stride, const float* __restrict__ w, const float* __restrict__ b,
+                                                        const float* __restrict__ sc, const float* __restrict__ sh, T* __restrict__ cat) {
+    frame_stem_body<KSX, KSY, T, LF_FRAME_RGB>(frames, total_bytes, Hin, Win, crop_top, tables, oh, ow, ksx, ksy, TH, TW, max_rows, in_stride, w,
+                                               b, sc, sh, cat, lf_yuv_coef{});
+}
+// BGR, NV12 and YUYV frames: the staging converts (lf_stage_window_format), everything behind it is the same
+template <int KSX, int KSY, typename T, int FMT>
+__global__ __launch_bounds__(256) void frame_format_stem_kernel(const uint8_t* __restrict__ frames, size_t total_bytes, int Hin, int Win,
+                                                               int crop_top, const int* __restrict__ tables, int oh, int ow, int ksx, int ksy,
+                                                               int TH, int TW, int max_rows, int in_stride, const float* __restrict__ w,
+                                                               const float* __restrict__ b, const float* __restrict__ sc,
+                                                               const float* __restrict__ sh, T* __restrict__ cat, const lf_yuv_coef cf) {
+    frame_stem_body<KSX, KSY, T, FMT>(frames, total_bytes, Hin, Win, crop_top, tables, oh, ow, ksx, ksy, TH, TW, max_rows, in_stride, w, b, sc, sh,
+                                      cat, cf);
+}
+
 }  // namespace
 
 // Tile of stem pixels per workgroup: the first of the candidates whose workgroup stays inside the LDS budget.  Every candidate keeps a
@@ -212,11 +239,24 @@ int lf_frame_stem_fwd_infer(const lf_pipeline_plan* P, const uint8_t* frames, in
     LF_REQUIRE(P->fs_ok, "frame_stem: the source window of a tile does not fit the LDS budget (%d x %d from %d x %d)", P->out_h, P->out_w,
                P->crop_h, P->Win);
     const dim3 grid(lf_cdiv(P->out_w / 2, P->fs_tw), lf_cdiv(P->out_h / 2, P->fs_th), N);
-    const size_t total = (size_t)N * P->Hin * P->Win * 3;
-#define LF_FS_LAUNCH(KX, KY, TT)                                                                                                    \
-    hipLaunchKernelGGL((frame_stem_kernel<KX, KY, TT>), grid, dim3(256), P->fs_lds_bytes, st, frames, total, P->Hin, P->Win,        \
-                       P->crop_top, (const int*)tables_dev, P->out_h, P->out_w, P->ksx, P->ksy, P->fs_th, P->fs_tw, P->fs_max_rows, \
-                       P->fs_in_stride, w, b, sc, sh, reinterpret_cast<TT*>(cat))
+    const size_t total = (size_t)N * lf_plan_frame_bytes(P);
+#define LF_FS_ARGS(TT)                                                                                                                 \
+    frames, total, P->Hin, P->Win, P->crop_top, (const int*)tables_dev, P->out_h, P->out_w, P->ksx, P->ksy, P->fs_th, P->fs_tw,        \
+        P->fs_max_rows, P->fs_in_stride, w, b, sc, sh, reinterpret_cast<TT*>(cat)
+#define LF_FS_LAUNCH(KX, KY, TT)                                                                                                       \
+    do {                                                                                                                               \
+        if (P->format == LF_FRAME_RGB)                                                                                                 \
+            hipLaunchKernelGGL((frame_stem_kernel<KX, KY, TT>), grid, dim3(256), P->fs_lds_bytes, st, LF_FS_ARGS(TT));                 \
+        else if (P->format == LF_FRAME_BGR)                                                                                            \
+            hipLaunchKernelGGL((frame_format_stem_kernel<KX, KY, TT, LF_FRAME_BGR>), grid, dim3(256), P->fs_lds_bytes, st, LF_FS_ARGS(TT), \
+                               P->coef);                                                                                               \
+        else if (P->format == LF_FRAME_NV12)                                                                                           \
+            hipLaunchKernelGGL((frame_format_stem_kernel<KX, KY, TT, LF_FRAME_NV12>), grid, dim3(256), P->fs_lds_bytes, st, LF_FS_ARGS(TT), \
+                               P->coef);                                                                                               \
+        else                                                                                                                           \
+            hipLaunchKernelGGL((frame_format_stem_kernel<KX, KY, TT, LF_FRAME_YUYV>), grid, dim3(256), P->fs_lds_bytes, st, LF_FS_ARGS(TT), \
+                               P->coef);                                                                                               \
+    } while (0)
 #define LF_FS_TAPS(TT)                                                      \
     do {                                                                    \
         if (P->ksx == 7 && P->ksy == 7) LF_FS_LAUNCH(7, 7, TT);             \
@@ -227,6 +267,7 @@ int lf_frame_stem_fwd_infer(const lf_pipeline_plan* P, const uint8_t* frames, in
     else LF_FS_TAPS(float);
 #undef LF_FS_TAPS
 #undef LF_FS_LAUNCH
+#undef LF_FS_ARGS
     LF_CHECK_LAUNCH("frame_stem");
     return 0;
 }

@@ -78,12 +78,14 @@ void pil_nearest_table(int in_size, int out_size, std::vector<int>& tab) {
 // KSX / KSY: compile-time tap counts (table rows are zero-padded to them); 0 = generic (runtime count).
 // Staging uses aligned dword loads with a per-row byte shift; the horizontal pass keeps a column's weights in
 // registers while it walks the rows; the vertical pass walks output rows with wave-uniform (scalar) weights.
-template <int KSX, int KSY>
-__global__ __launch_bounds__(256) void resize_bilinear_kernel(const uint8_t* __restrict__ frames, size_t total_bytes, int Hin, int Win,
-                                                             int crop_top, const int* __restrict__ tables, int oh, int ow,
-                                                             int ksx, int ksy, int TILE_H, int TILE_W, int max_rows, int in_stride,
-                                                             const uint8_t* __restrict__ flip, float* __restrict__ out,
-                                                             const int64_t* __restrict__ sel, long pool_frames, int* __restrict__ bad_index) {
+// FMT: the frame format (LF_FRAME_*), which only the staging knows; cf: its YCbCr coefficients (unused for RGB / BGR).
+template <int KSX, int KSY, int FMT>
+__device__ __forceinline__ void resize_bilinear_body(const uint8_t* __restrict__ frames, size_t total_bytes, int Hin, int Win,
+                                                     int crop_top, const int* __restrict__ tables, int oh, int ow,
+                                                     int ksx, int ksy, int TILE_H, int TILE_W, int max_rows, int in_stride,
+                                                     const uint8_t* __restrict__ flip, float* __restrict__ out,
+                                                     const int64_t* __restrict__ sel, long pool_frames, int* __restrict__ bad_index,
+                                                     const lf_yuv_coef cf) {
     extern __shared__ uint8_t smem[];
     const int h_stride = TILE_W * 3;
     int* s_shift = reinterpret_cast<int*>(smem);                                  // [max_rows + 1] byte shift of each staged row
@@ -104,7 +106,10 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const uint8_t* __r
         frame = 0;
     }
     // (the gather of a cached dataset's index batch happens here, not in a separate 88 MB copy)
-    lf_stage_window(frames, total_bytes, frame, Hin, Win, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave);
+    if constexpr (FMT == LF_FRAME_RGB)
+        lf_stage_window(frames, total_bytes, frame, Hin, Win, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave);
+    else
+        lf_stage_window_format<FMT>(frames, total_bytes, frame, Hin, Win, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave, cf);
     __syncthreads();
     // horizontal pass: one (x, channel) column per thread, rows in sequence
     if ((int)threadIdx.x < tw * 3) {
@@ -155,6 +160,28 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const uint8_t* __r
             o[(size_t)y * ow] = (float)clip8(acc) / 255.0f;
         }
     }
+}
+
+// packed RGB frames: the kernel every plan ran before there were formats, the same code
+template <int KSX, int KSY>
+__global__ __launch_bounds__(256) void resize_bilinear_kernel(const uint8_t* __restrict__ frames, size_t total_bytes, int Hin, int Win,
+                                                             int crop_top, const int* __restrict__ tables, int oh, int ow,
+                                                             int ksx, int ksy, int TILE_H, int TILE_W, int max_rows, int in_stride,
+                                                             const uint8_t* __restrict__ flip, float* __restrict__ out,
+                                                             const int64_t* __restrict__ sel, long pool_frames, int* __restrict__ bad_index) {
+    resize_bilinear_body<KSX, KSY, LF_FRAME_RGB>(frames, total_bytes, Hin, Win, crop_top, tables, oh, ow, ksx, ksy, TILE_H, TILE_W, max_rows,
+                                                 in_stride, flip, out, sel, pool_frames, bad_index, lf_yuv_coef{});
+}
+// BGR, NV12 and YUYV frames: the staging converts, the passes are the same
+template <int KSX, int KSY, int FMT>
+__global__ __launch_bounds__(256) void resize_format_kernel(const uint8_t* __restrict__ frames, size_t total_bytes, int Hin, int Win,
+                                                           int crop_top, const int* __restrict__ tables, int oh, int ow,
+                                                           int ksx, int ksy, int TILE_H, int TILE_W, int max_rows, int in_stride,
+                                                           const uint8_t* __restrict__ flip, float* __restrict__ out,
+                                                           const int64_t* __restrict__ sel, long pool_frames, int* __restrict__ bad_index,
+                                                           const lf_yuv_coef cf) {
+    resize_bilinear_body<KSX, KSY, FMT>(frames, total_bytes, Hin, Win, crop_top, tables, oh, ow, ksx, ksy, TILE_H, TILE_W, max_rows,
+                                        in_stride, flip, out, sel, pool_frames, bad_index, cf);
 }
 
 // mode bits: 1 = zero classes 3 and 4 before flipping (BEV always; BP when nclasses < 3),
@@ -268,6 +295,29 @@ int lf_pipeline_frame_stem_tile(const lf_pipeline_plan* P, int* tile_h, int* til
     return 0;
 }
 
+// include/lanefit.h, "additions since 5 -- frame formats".  Host only.  The staged LDS layout is the RGB one for every format, so the
+// tiles and LDS bytes the plan chose from its geometry (and lf_pipeline_frame_stem_ok) hold for all of them.
+int lf_pipeline_plan_set_format(lf_pipeline_plan* P, int format, const int coef[6]) {
+    LF_REQUIRE(P, "lf_pipeline_plan_set_format: null plan");
+    LF_REQUIRE(format >= LF_FRAME_RGB && format <= LF_FRAME_YUYV, "lf_pipeline_plan_set_format: unknown format %d", format);
+    LF_REQUIRE(format != LF_FRAME_NV12 || !((P->Hin | P->Win) & 1), "lf_pipeline_plan_set_format: NV12 frames need an even size, got %d x %d",
+               P->Hin, P->Win);
+    LF_REQUIRE(format != LF_FRAME_YUYV || !(P->Win & 1), "lf_pipeline_plan_set_format: YUYV frames need an even width, got %d", P->Win);
+    if (coef && (format == LF_FRAME_NV12 || format == LF_FRAME_YUYV)) {
+        // |c_y y'| + the largest chroma term + the rounding constant, over Y, Cb, Cr in 0..255, must stay inside int32
+        const auto mag = [](int v) { return v < 0 ? -(long long)v : (long long)v; };
+        const long long ymax = mag(coef[0]) * (mag(coef[1]) + 255);
+        long long cmax = mag(coef[2]);
+        if (mag(coef[3]) + mag(coef[4]) > cmax) cmax = mag(coef[3]) + mag(coef[4]);
+        if (mag(coef[5]) > cmax) cmax = mag(coef[5]);
+        LF_REQUIRE(ymax + 128 * cmax + 32768 <= 0x7fffffffLL, "lf_pipeline_plan_set_format: coefficients overflow int32");
+        P->coef = lf_yuv_coef{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
+    }
+    P->format = format;
+    return 0;
+}
+size_t lf_pipeline_frame_bytes(const lf_pipeline_plan* P) { return P ? lf_plan_frame_bytes(P) : 0; }
+
 // Copy the tables (bilinear bounds + weights, nearest indices) to a device buffer of lf_pipeline_table_bytes().
 int lf_pipeline_upload(const lf_pipeline_plan* P, void* tables_dev, void* stream) {
     LF_REQUIRE(P && tables_dev, "lf_pipeline_upload: null pointer");
@@ -295,21 +345,35 @@ int lf_pipeline_tables_host(const lf_pipeline_plan* P, int* ksx, int* ksy, int* 
     return 0;
 }
 
-// frames (N, Hin, Win, 3) uint8 HWC (what the image decoder produces); flip (N) uint8 or NULL;
-// out (N, 3, out_h, out_w) fp32 in [0, 1].
+// frames (N, Hin, Win, 3) uint8 HWC (what the image decoder produces) or, on a plan with a format, N frames of
+// lf_plan_frame_bytes in it; flip (N) uint8 or NULL; out (N, 3, out_h, out_w) fp32 in [0, 1].
 static int pipeline_image(const lf_pipeline_plan* P, const uint8_t* frames, long pool_frames, const int64_t* sel, int N,
                           const void* tables_dev, const uint8_t* flip, float* out, int* bad_index, void* stream) {
     LF_REQUIRE(P && frames && tables_dev && out && N > 0 && pool_frames > 0, "lf_pipeline_image: bad arguments");
     const dim3 grid(lf_cdiv(P->out_w, P->tile_w), lf_cdiv(P->out_h, P->tile_h), N);
-    const size_t total = (size_t)pool_frames * P->Hin * P->Win * 3;
-#define LF_RESIZE_LAUNCH(KX, KY)                                                                                              \
-    hipLaunchKernelGGL((resize_bilinear_kernel<KX, KY>), grid, dim3(256), P->lds_bytes, (hipStream_t)stream, frames, total,   \
-                       P->Hin, P->Win, P->crop_top, (const int*)tables_dev, P->out_h, P->out_w, P->ksx, P->ksy, P->tile_h,    \
-                       P->tile_w, P->max_rows, P->in_stride, flip, out, sel, pool_frames, bad_index)
+    const size_t total = (size_t)pool_frames * lf_plan_frame_bytes(P);
+#define LF_RESIZE_ARGS                                                                                                           \
+    frames, total, P->Hin, P->Win, P->crop_top, (const int*)tables_dev, P->out_h, P->out_w, P->ksx, P->ksy, P->tile_h, P->tile_w, \
+        P->max_rows, P->in_stride, flip, out, sel, pool_frames, bad_index
+#define LF_RESIZE_LAUNCH(KX, KY)                                                                                                 \
+    do {                                                                                                                         \
+        if (P->format == LF_FRAME_RGB)                                                                                           \
+            hipLaunchKernelGGL((resize_bilinear_kernel<KX, KY>), grid, dim3(256), P->lds_bytes, (hipStream_t)stream, LF_RESIZE_ARGS); \
+        else if (P->format == LF_FRAME_BGR)                                                                                      \
+            hipLaunchKernelGGL((resize_format_kernel<KX, KY, LF_FRAME_BGR>), grid, dim3(256), P->lds_bytes, (hipStream_t)stream,  \
+                               LF_RESIZE_ARGS, P->coef);                                                                         \
+        else if (P->format == LF_FRAME_NV12)                                                                                     \
+            hipLaunchKernelGGL((resize_format_kernel<KX, KY, LF_FRAME_NV12>), grid, dim3(256), P->lds_bytes, (hipStream_t)stream, \
+                               LF_RESIZE_ARGS, P->coef);                                                                         \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((resize_format_kernel<KX, KY, LF_FRAME_YUYV>), grid, dim3(256), P->lds_bytes, (hipStream_t)stream, \
+                               LF_RESIZE_ARGS, P->coef);                                                                         \
+    } while (0)
     if (P->ksx == 7 && P->ksy == 7) LF_RESIZE_LAUNCH(7, 7);          // 640x1280 -> 256x512 (x2.5)
     else if (P->ksx == 5 && P->ksy == 5) LF_RESIZE_LAUNCH(5, 5);     // -> 320x640 (x2), 512x1024 (x1.25)
     else LF_RESIZE_LAUNCH(0, 0);
 #undef LF_RESIZE_LAUNCH
+#undef LF_RESIZE_ARGS
     LF_CHECK_LAUNCH("lf_pipeline_image");
     return 0;
 }

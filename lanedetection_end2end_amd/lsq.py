@@ -13,7 +13,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import erfnet, fit, geometry, ops
+from . import erfnet, fit, geometry, ops, pipeline
 from .clas import Classification, ClassificationBEV, Projections
 
 
@@ -250,6 +250,12 @@ FRAME_STEM_AUTO_MAX_BATCH = 8
 # ... in precision mode bf16 it won at all five batches in both geometries (one frame 0.523 -> 0.508 and 0.559 -> 0.544 ms; 32 frames
 # 1.872 -> 1.862 and 1.949 -> 1.898 ms)
 FRAME_STEM_AUTO_MAX_BATCH_BF16 = 32
+# ... and the frame formats (camera(pixel_format=...)) follow the two constants: a format would get one of its own if its fused form
+# were not faster than its own two-launch form beyond both min-max ranges at a batch these route to, and none is
+# (tools/detector_latency.py --frames --formats, profiles/detector_frames_formats_latency.json, 720 x 1280 -> 256 x 512, lanes).  bgr,
+# nv12 and yuyv won at 1, 2, 4, 8 in fp32 (nv12, one frame: 0.687 (0.687 - 0.687) -> 0.671 (0.670 - 0.671) ms; eight: 1.763 (1.763 -
+# 1.764) -> 1.757 (1.756 - 1.757)) and at all five batches in bf16 (nv12, 32 frames: 1.865 (1.864 - 1.865) -> 1.829 (1.828 - 1.829));
+# at 32 fp32 frames, where "auto" runs two launches, bgr won and the ranges of nv12 and yuyv overlap
 
 # what LaneDetector.lanes returns
 FrameLanes = namedtuple("FrameLanes", ["lanes", "betas", "line", "horizon", "line_flags", "horizon_row"])
@@ -309,11 +315,12 @@ class LaneDetector:
         self._cameras = weakref.WeakSet()
         self.refresh()
 
-    def camera(self, frame_hw=(720, 1280), crop=640, fused="auto"):
+    def camera(self, frame_hw=(720, 1280), crop=640, fused="auto", pixel_format="rgb", yuv="jfif"):
         """A ``CameraDetector`` on this detector: the same calls from decoded uint8 camera frames ``(batch, Hf, Wf, 3)`` -- the
         reference's ``LaneTestSet`` pixel work (crop the bottom ``crop`` rows, Pillow BILINEAR resize to the detector's
-        ``(height, width)``, ``ToTensor``) inside the one backbone C call.  RGB models only.  See ``CameraDetector``."""
-        return CameraDetector(self, frame_hw, crop, fused)
+        ``(height, width)``, ``ToTensor``) inside the one backbone C call.  RGB models only.  ``pixel_format``: ``"rgb"``, ``"bgr"``,
+        ``"nv12"`` or ``"yuyv"`` frames, ``yuv``: their YCbCr matrix (``"jfif"``, ``"bt709"`` or six ints).  See ``CameraDetector``."""
+        return CameraDetector(self, frame_hw, crop, fused, pixel_format, yuv)
 
     @torch.no_grad()
     def refresh(self):
@@ -551,9 +558,18 @@ class CameraDetector(LaneDetector):
     128 x 64) raises ``ValueError`` for ``True`` and runs as two launches for ``"auto"``.
 
     Input: a contiguous uint8 tensor ``(batch, Hf, Wf, 3)`` on the device (``ValueError`` otherwise; ``LaneFitLibraryError`` for a
-    CPU tensor).  Eval mode only, as the detector."""
+    CPU tensor).  Eval mode only, as the detector.
 
-    def __init__(self, det, frame_hw=(720, 1280), crop=640, fused="auto"):
+    ``pixel_format`` / ``yuv``: what the frames hold (``pipeline.PIXEL_FORMATS``, ``pipeline.YUV_PRESETS``) -- ``"rgb"`` (default) or
+    ``"bgr"`` ``(batch, Hf, Wf, 3)``; ``"nv12"`` ``(batch, Hf * 3 // 2, Wf)``, the Y plane and then the interleaved CbCr rows, as video
+    and JPEG decoders write it (``Hf``, ``Wf`` even); ``"yuyv"`` ``(batch, Hf, Wf, 2)``, as USB / CSI cameras deliver it (``Wf`` even).
+    ``cam.frame_shape`` is the shape expected.  The staging of the source window converts in registers: chroma replicated, YCbCr ->
+    RGB by the Q16 integers of ``yuv`` (``"jfif"``: full-range BT.601, libjpeg's decoder bit for bit; ``"bt709"``: limited-range
+    BT.709; or six ints), and EVERY result equals that of an ``"rgb"`` camera on the RGB frames this definition makes
+    (include/lanefit.h, "additions since 5 -- frame formats").  Unknown names raise ``ValueError``; ``"auto"`` routes every format
+    as ``"rgb"`` (measured per format, see ``FRAME_STEM_AUTO_MAX_BATCH``)."""
+
+    def __init__(self, det, frame_hw=(720, 1280), crop=640, fused="auto", pixel_format="rgb", yuv="jfif"):
         if type(det) is not LaneDetector:
             raise TypeError("camera() is a method of a LaneDetector")
         lib = erfnet._lib.load()
@@ -564,12 +580,15 @@ class CameraDetector(LaneDetector):
         Hf, Wf = int(frame_hw[0]), int(frame_hw[1])
         N, _, H, W = det.shape
         self._det = det
-        self.frame_shape = (N, Hf, Wf, 3)
+        self.frame_shape = pipeline.frames_shape(pixel_format, N, (Hf, Wf))
+        pipeline.yuv_coefficients(yuv)
+        self.pixel_format = pixel_format
         self.last_status = None
         self._pipe = lib.lf_pipeline_plan_create(Hf, Wf, Hf - int(crop), int(crop), H, W)
         if not self._pipe:
             raise erfnet._lib.LaneFitLibraryError("lf_pipeline_plan_create failed: %s" % lib.lf_last_error().decode())
         self._pipe = ctypes.c_void_p(self._pipe)
+        pipeline.set_plan_format(self._pipe, pixel_format, yuv)
         self.fits = bool(lib.lf_pipeline_frame_stem_ok(self._pipe))
         self.fused = fused
         self._tables = self._ws = None
@@ -648,8 +667,9 @@ class CameraDetector(LaneDetector):
         if not frames.is_cuda:
             raise erfnet._lib.LaneFitLibraryError("lanefit camera needs its frames on the MI355X; there is no CPU path")
         if frames.dtype != torch.uint8 or not frames.is_contiguous():
-            raise ValueError("camera frames are contiguous uint8 (batch, Hf, Wf, 3) tensors, got %s%s"
-                             % (frames.dtype, "" if frames.is_contiguous() else ", not contiguous"))
+            raise ValueError("camera frames are contiguous uint8 %s tensors, got %s%s"
+                             % ("(batch, Hf, Wf, 3)" if self.frame_shape[3:] == (3,) else "%s (%s)" % (self.frame_shape, self.pixel_format),
+                                frames.dtype, "" if frames.is_contiguous() else ", not contiguous"))
         return frames
 
     def _backbone(self, x):

@@ -16,22 +16,83 @@ import torch
 from . import _lib
 
 
+# Frame formats (include/lanefit.h, "additions since 5 -- frame formats"): LF_FRAME_* codes, and the YCbCr -> RGB presets
+# (c_y, y_off, c_rv, c_gu, c_gv, c_bu) of the Q16 form  R = clamp8((c_y (Y - y_off) + c_rv (Cr - 128) + 32768) >> 16), ...
+#   "jfif":  full-range BT.601 -- the integers of libjpeg's decoder, bit for bit what Image.open(jpeg).convert("RGB") holds;
+#   "bt709": limited-range BT.709, what video decoders usually emit: round(65536 x) of 1.164384, 1.792741, 0.213249, 0.532909, 2.112402.
+PIXEL_FORMATS = {"rgb": 0, "bgr": 1, "nv12": 2, "yuyv": 3}
+YUV_PRESETS = {"jfif": (65536, 0, 91881, 22554, 46802, 116130), "bt709": (76309, 16, 117489, 13975, 34925, 138438)}
+
+
+def yuv_coefficients(yuv):
+    """The six ints of a ``yuv=`` argument: a preset name or a 6-tuple of ints (``ValueError`` otherwise)."""
+    if isinstance(yuv, str):
+        if yuv not in YUV_PRESETS:
+            raise ValueError("yuv=%r: the presets are %s (or give six ints c_y, y_off, c_rv, c_gu, c_gv, c_bu)" % (yuv, sorted(YUV_PRESETS)))
+        return YUV_PRESETS[yuv]
+    try:
+        coef = tuple(yuv)
+    except TypeError:
+        raise ValueError("yuv=%r: a preset name or six ints (c_y, y_off, c_rv, c_gu, c_gv, c_bu)" % (yuv,))
+    if len(coef) != 6 or not all(isinstance(c, (int, np.integer)) and not isinstance(c, bool) for c in coef):
+        raise ValueError("yuv=%r: a preset name or six ints (c_y, y_off, c_rv, c_gu, c_gv, c_bu)" % (yuv,))
+    return tuple(int(c) for c in coef)
+
+
+def frames_shape(pixel_format, n, frame_hw):
+    """Shape of ``n`` frames of ``frame_hw`` in ``pixel_format``; ``ValueError`` for an unknown format or a size it cannot hold."""
+    if pixel_format not in PIXEL_FORMATS:
+        raise ValueError("pixel_format=%r: one of %s" % (pixel_format, sorted(PIXEL_FORMATS)))
+    H, W = int(frame_hw[0]), int(frame_hw[1])
+    if pixel_format == "nv12":
+        if H % 2 or W % 2:
+            raise ValueError("nv12 frames have an even height and width, got %d x %d" % (H, W))
+        return (n, H * 3 // 2, W)
+    if pixel_format == "yuyv":
+        if W % 2:
+            raise ValueError("yuyv frames have an even width, got %d" % W)
+        return (n, H, W, 2)
+    return (n, H, W, 3)
+
+
+def set_plan_format(handle, pixel_format, yuv):
+    """``lf_pipeline_plan_set_format`` on a plan handle, from the Python names.  Validates both before touching the plan."""
+    code = PIXEL_FORMATS.get(pixel_format)
+    if code is None:
+        raise ValueError("pixel_format=%r: one of %s" % (pixel_format, sorted(PIXEL_FORMATS)))
+    coef = yuv_coefficients(yuv)
+    if code == 0:
+        return                                   # a plan that never gets the call is an RGB plan
+    lib = _lib.load()
+    if lib.lf_pipeline_plan_set_format(handle, code, (ctypes.c_int * 6)(*coef)) != 0:
+        raise ValueError("lf_pipeline_plan_set_format failed: %s" % lib.lf_last_error().decode())
+
+
 class InputPipeline:
-    """``InputPipeline(resize, tree='bev'|'bp', nclasses=2, frame_hw=(720, 1280), crop=640)``;
+    """``InputPipeline(resize, tree='bev'|'bp', nclasses=2, frame_hw=(720, 1280), crop=640, pixel_format='rgb', yuv='jfif')``;
     ``__call__(frames_u8, labels_u8=None, flip=None) -> (image, gt, horizon)``.
 
     frames_u8 (N, H, W, 3) uint8 and labels_u8 (N, H, W) uint8 on the GPU; flip (N,) bool (the reference draws
     ``np.random.uniform() > 0.5 and flip_on`` per training sample).  image (N,3,R,2R) fp32, gt (N,1,R,2R) int64,
-    horizon (N,R) fp32 for tree='bev' (the BP tree derives its horizon from the lane coordinates on the host)."""
+    horizon (N,R) fp32 for tree='bev' (the BP tree derives its horizon from the lane coordinates on the host).
 
-    def __init__(self, resize, tree="bev", nclasses=2, frame_hw=(720, 1280), crop=640):
+    ``pixel_format``: what the frames hold -- ``'rgb'`` / ``'bgr'`` (N, H, W, 3), ``'nv12'`` (N, H * 3 // 2, W: the Y plane, then the
+    interleaved CbCr rows; H, W even) or ``'yuyv'`` (N, H, W, 2; W even), contiguous.  The image is bit for bit the ``'rgb'`` image of
+    the frames the Q16 definition above makes from them (chroma replicated; ``yuv``: ``'jfif'``, ``'bt709'`` or six ints; ignored for
+    ``'rgb'`` / ``'bgr'``).  Labels know no format."""
+
+    def __init__(self, resize, tree="bev", nclasses=2, frame_hw=(720, 1280), crop=640, pixel_format="rgb", yuv="jfif"):
         assert tree in ("bev", "bp")
-        lib = _lib.load()
         H, W = frame_hw
+        self.frames_shape = frames_shape(pixel_format, -1, (H, W))[1:]
+        yuv_coefficients(yuv)
+        lib = _lib.load()
         self.resize, self.tree, self.nclasses, self.frame_hw = resize, tree, nclasses, (H, W)
+        self.pixel_format = pixel_format
         self.handle = lib.lf_pipeline_plan_create(H, W, H - crop, crop, resize, 2 * resize)
         if not self.handle:
             raise _lib.LaneFitLibraryError("lf_pipeline_plan_create failed: %s" % lib.lf_last_error().decode())
+        set_plan_format(self.handle, pixel_format, yuv)
         self.mode = (1 if (tree == "bev" or nclasses < 3) else 0) | (2 if tree == "bp" else 0)
         self._tables = None
         self._lut = None
@@ -84,8 +145,10 @@ class InputPipeline:
         lib = _lib.load()
         if not frames_u8.is_cuda:
             raise _lib.LaneFitLibraryError("InputPipeline needs the decoded frames on the MI355X; there is no CPU path")
-        pool, H, W, C = frames_u8.shape
-        assert (H, W) == self.frame_hw and C == 3 and frames_u8.dtype == torch.uint8
+        if tuple(frames_u8.shape[1:]) != self.frames_shape or frames_u8.dtype != torch.uint8:
+            raise ValueError("this pipeline takes %s frames of shape (N,) + %s, uint8; got %s, %s"
+                             % (self.pixel_format, self.frames_shape, tuple(frames_u8.shape), frames_u8.dtype))
+        pool, (H, W) = frames_u8.shape[0], self.frame_hw
         dev = frames_u8.device
         tables, lut = self._device_state(dev)
         R = self.resize

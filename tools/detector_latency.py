@@ -42,6 +42,14 @@ frame_stem_kernel).  Geometries: -> 256 x 512 on the BP --clas recipe through ``
 ``frame_stem_auto_max_batch_by_precision``: the largest batch up to which (C) won at every batch and in both geometries (0: nowhere)
 -- lsq.FRAME_STEM_AUTO_MAX_BATCH / _BF16.
 
+    python tools/detector_latency.py --frames --formats rgb,bgr,nv12,yuyv [--out profiles/detector_frames_formats_latency.json] [--yuv bt709]
+
+--frames --formats: ``det.camera(pixel_format=F).lanes(frames)`` on 720 x 1280 -> 256 x 512 (BP --clas) per frame format, the two-launch
+and the fused form of each, all alternated in one process by the same protocol.  The yardstick is the ``rgb`` call of the same process
+(``against_rgb``, stated only beyond both min-max ranges).  ``frame_stem_auto_max_batch_by_format``: per format and precision the
+largest batch up to which its fused form beat its own two-launch form at every batch -- a format for which that is below what
+lsq.FRAME_STEM_AUTO_MAX_BATCH / _BF16 route to needs a constant of its own beside them (none does: the comment there).
+
     rocprofv3 --kernel-trace --stats -d DIR -o trace -- python tools/detector_latency.py --trace F|G
     python tools/detector_latency.py --frames-launches DB_F DB_G [--out profiles/detector_launches.md]   (appends; F fused, G two launches)
 
@@ -386,6 +394,94 @@ def run_frames(args):
     print(json.dumps({"frame_stem_auto_max_batch_by_precision": bounds}))
 
 
+def format_frames(rgb, fmt):
+    """(N, H, W, 3) uint8 RGB frames re-read as frames in format fmt: the planes of the picture stand in for B G R / Y Cb Cr (the
+    cost does not depend on the values; the chroma planes are sub-sampled by dropping, as the layout demands)"""
+    import numpy as np
+    N, H, W, _ = rgb.shape
+    if fmt in ("rgb", "bgr"):
+        return np.ascontiguousarray(rgb)
+    if fmt == "nv12":
+        return np.ascontiguousarray(np.concatenate([rgb[..., 1], rgb[:, ::2, ::2][..., [2, 0]].reshape(N, H // 2, W)], axis=1))
+    return np.ascontiguousarray(np.stack([rgb[..., 1], np.where(np.arange(W) % 2 == 0, rgb[..., 2], rgb[..., 0])], axis=-1))
+
+
+def measure_formats(precision, N, formats, yuv, warmup, calls, repeats):
+    """--frames --formats: cam.lanes(frames) per frame format, two-launch and fused, all alternated in one process"""
+    import torch
+    cfg = LANES_CFG
+    model = make_model(cfg, precision, N, clas=True)
+    det = model.detector(batch=N, height=cfg["H"], width=cfg["W"], thin="auto")
+    rgb = camera_frames(N).cpu().numpy()
+    buf = torch.empty(N, cfg["K"], 56, dtype=torch.int32, device="cuda")
+    paths, frames = {}, {}
+    for fmt in formats:
+        frames[fmt] = torch.from_numpy(format_frames(rgb, fmt)).cuda()
+        for fused in (False, True):
+            cam = det.camera(FRAMES_HW, FRAMES_CROP, fused=fused, pixel_format=fmt, yuv=yuv)
+            paths[(fmt, fused)] = (lambda c: lambda u: c.lanes(u, out=buf).lanes)(cam)
+        # the two forms of a format give the same bits (that they are the bits of the rgb call on the converted frames is the tests')
+        assert torch.equal(paths[(fmt, True)](frames[fmt]).clone(), paths[(fmt, False)](frames[fmt])), fmt
+    ev = {k: [] for k in paths}
+    wall = {k: [] for k in paths}
+    for _ in range(repeats):
+        for key, fn in paths.items():
+            for _ in range(warmup):
+                fn(frames[key[0]])
+            e, w = timed(fn, frames[key[0]], calls)
+            ev[key].append(e)
+            wall[key].append(w)
+    row = {"config": cfg["name"], "through": "lanes", "frames": "%dx%d crop %d" % (FRAMES_HW + (FRAMES_CROP,)), "yuv": yuv,
+           "precision": precision, "batch": N, "formats": {}}
+    for fmt in formats:
+        b, c = stats(ev[(fmt, False)]), stats(ev[(fmt, True)])
+        r = {"frame_bytes": int(frames[fmt][0].numel()),
+             "two_launches": {"in_stream_ms": b, "wall_ms": stats(wall[(fmt, False)])},
+             "fused": {"in_stream_ms": c, "wall_ms": stats(wall[(fmt, True)])},
+             "fused_wins": c["max"] < b["min"],
+             "fused_against_two_launches": "gain" if c["max"] < b["min"] else "loss" if c["min"] > b["max"] else "ranges overlap",
+             "median_ratio_fused_to_two_launches": round(c["median"] / b["median"], 4)}
+        row["formats"][fmt] = r
+    if "rgb" in formats:      # the yardstick: the rgb call of the same process
+        for fmt in formats:
+            for form in ("two_launches", "fused"):
+                s, y = row["formats"][fmt][form]["in_stream_ms"], row["formats"]["rgb"][form]["in_stream_ms"]
+                row["formats"][fmt][form]["against_rgb"] = "faster" if s["max"] < y["min"] else "slower" if s["min"] > y["max"] else "ranges overlap"
+                row["formats"][fmt][form]["median_ratio_to_rgb"] = round(s["median"] / y["median"], 4)
+    del model, det, paths, frames
+    torch.cuda.empty_cache()
+    return row
+
+
+def run_formats(args):
+    import torch
+    formats = args.formats.split(",")
+    precisions = args.precisions.split(",")
+    batches = [int(b) for b in args.batches.split(",")]
+    rows = []
+    for precision in precisions:
+        for N in batches:
+            rows.append(measure_formats(precision, N, formats, args.yuv, args.warmup, args.calls, args.repeats))
+            print(json.dumps(rows[-1]), flush=True)
+    bounds = {}
+    for fmt in formats:       # per format: the largest batch up to which its fused form beat its own two-launch form at every batch
+        bounds[fmt] = {}
+        for precision in precisions:
+            bounds[fmt][precision] = 0
+            for N in sorted(set(batches)):
+                at = [r for r in rows if r["precision"] == precision and r["batch"] == N]
+                if not at or not all(r["formats"][fmt]["fused_wins"] for r in at):
+                    break
+                bounds[fmt][precision] = N
+    res = {"tool": "detector_latency --frames --formats", "commit": commit_stamp(), "device": torch.cuda.get_device_name(0),
+           "warmup": args.warmup, "calls": args.calls, "repeats": args.repeats, "check_singular": False,
+           "frame_stem_auto_max_batch_by_format": bounds, "results": rows}
+    with open(args.out or os.path.join(ROOT, "profiles", "detector_frames_formats_latency.json"), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"frame_stem_auto_max_batch_by_format": bounds}))
+
+
 def trace_frames(fused):
     """ten batch-1 cam.lanes(frame) calls, 720 x 1280 -> 256 x 512 fp32, --clas (run under rocprofv3 --kernel-trace --stats)"""
     import torch
@@ -527,6 +623,8 @@ if __name__ == "__main__":
     ap.add_argument("--trace", choices=["A", "C", "L", "F", "G"])
     ap.add_argument("--lanes", action="store_true")
     ap.add_argument("--frames", action="store_true")
+    ap.add_argument("--formats", help="with --frames: frame formats to compare, e.g. rgb,bgr,nv12,yuyv")
+    ap.add_argument("--yuv", default="bt709", help="with --formats: the YCbCr preset (the cost does not depend on it)")
     ap.add_argument("--frames-launches", nargs=2, metavar=("DB_F", "DB_G"))
     ap.add_argument("--lanes-launches", metavar="DB_L")
     ap.add_argument("--launches", nargs=2, metavar=("DB_A", "DB_C"))
@@ -541,6 +639,8 @@ if __name__ == "__main__":
         frames_launches(args.frames_launches[0], args.frames_launches[1], args.out)
     elif args.lanes:
         run_lanes(args)
+    elif args.frames and args.formats:
+        run_formats(args)
     elif args.frames:
         run_frames(args)
     else:
