@@ -60,7 +60,8 @@ extern "C" {
                                  additions since 5 (camera frames): lf_pipeline_frame_stem_ok, lf_pipeline_frame_stem_lds_bytes,
                                  lf_pipeline_frame_stem_tile, lf_lane_infer_u8_workspace_bytes, lf_lane_infer_seg_u8_workspace_bytes,
                                  lf_lane_infer_folded_u8, lf_lane_infer_seg_folded_u8;
-                                 additions since 5 (frame formats): lf_pipeline_plan_set_format, lf_pipeline_frame_bytes */
+                                 additions since 5 (frame formats): lf_pipeline_plan_set_format, lf_pipeline_frame_bytes;
+                                 additions since 5 (surfaces): lf_pipeline_plan_set_layout, lf_pipeline_surface_span */
 
 /* activation applied to the backbone logits: BEV/Networks/LSQ_layer.py:43-63 */
 enum { LF_ACT_SQUARE = 0, LF_ACT_ABS = 1, LF_ACT_RELU = 2, LF_ACT_SIGMOID = 3,
@@ -799,6 +800,58 @@ int lf_lane_infer_seg_folded_u8(const lf_erfnet_plan* plan, const lf_pipeline_pl
 enum { LF_FRAME_RGB = 0, LF_FRAME_BGR = 1, LF_FRAME_NV12 = 2, LF_FRAME_YUYV = 3 };
 int lf_pipeline_plan_set_format(lf_pipeline_plan* plan, int format, const int coef[6]);
 size_t lf_pipeline_frame_bytes(const lf_pipeline_plan* plan);
+
+/* additions since 5 -- surfaces: frames as a decoder leaves them.  A hardware decoder writes NV12 with a row pitch aligned to 256
+ * bytes and the chroma plane behind an aligned height (720 -> 736 rows), often in an allocation of its own; a batch of cameras is N
+ * surfaces of a pool; software decoders give planar I420, compositors and capture cards 4-byte RGBX / BGRX.  A frame layout on the
+ * plan lifts "contiguous, pitch = width" of the block above: the staging reads the surface where it lies, no repacking pass.
+ * Planes, rows x row bytes (Hin x Win pixels):
+ *   LF_FRAME_RGB, LF_FRAME_BGR    one plane, Hin x 3 Win;
+ *   LF_FRAME_RGBX, LF_FRAME_BGRX  one plane, Hin x 4 Win: R G B X / B G R X per pixel, the fourth byte is ignored;
+ *   LF_FRAME_YUYV                 one plane, Hin x 2 Win; Win even;
+ *   LF_FRAME_NV12                 Y: Hin x Win; CbCr: Hin/2 x Win; Hin and Win even;
+ *   LF_FRAME_I420                 Y: Hin x Win; Cb: Hin/2 x Win/2; Cr: Hin/2 x Win/2; Hin and Win even.  YV12 is I420 with the
+ *                                 offsets (or the pointers) of planes 1 and 2 exchanged.
+ * The chroma of I420 pixel (y, x) is sample (y >> 1, x >> 1) of each chroma plane, replicated as for NV12; the Q16 YCbCr -> RGB form
+ * and coef are those of the block above.
+ * lf_frame_layout: pitch[p] bytes between rows of plane p (0 = the row's own bytes); plane_offset[p] bytes from a frame's base to
+ *   plane p ([0] must be 0; 0 for p > 0 = directly behind plane p - 1, its rows x its pitch); frame_stride bytes between the frames
+ *   of a contiguous batch (0 = the end of the furthest plane at full pitch).  plane_pointers = 0: `frames` is the base of a
+ *   contiguous batch, 4-byte aligned.  plane_pointers = 1: `frames` is a DEVICE array (N, planes) of plane base pointers, row n the
+ *   planes of batch element n -- separate allocations, surfaces of a pool in any order; plane_offset and frame_stride are then not
+ *   looked at, whatever they hold (nor, in either mode, the values of planes the format lacks).
+ *   Each pointer must be 4-byte aligned (2 bytes suffice for the NV12 CbCr plane): no host-only call can check a device table, it is
+ *   the caller's contract.  For a CbCr pointer that is only 2-byte aligned the staging loads the aligned dword that holds the plane's
+ *   first two bytes, i.e. it reads the 2 bytes in front of the pointer too (the same memory granule; they reach no result).
+ * lf_pipeline_plan_set_layout: sets format and layout of a plan (host only); coef as for lf_pipeline_plan_set_format (NULL: keeps the
+ *   plan's).  Returns != 0, leaves the plan untouched and sets lf_last_error for: a NULL plan or layout; an unknown format; an odd
+ *   Hin or Win for NV12 / I420, an odd Win for YUYV; a negative value; a pitch below the row's bytes; plane_offset[0] != 0;
+ *   coefficients that overflow int32; and the alignment the staging relies on --
+ *     YUYV, RGBX, BGRX: pitch, plane offset and frame stride multiples of 4 (every pixel group is one aligned dword);
+ *     NV12: CbCr pitch and offset even, and the frame stride even (it moves the CbCr plane of every frame but the first).
+ *   RGB, BGR and I420 take any pitch, offset and stride (odd ones too).  LF_FRAME_I420, _RGBX and _BGRX are reachable only through this
+ *   call: lf_pipeline_plan_set_format keeps refusing codes >= 4, and after a set_layout it resets the plan to a tight plan of its format.
+ * lf_pipeline_surface_span: plane >= 0 -- (rows_p - 1) pitch_p + row bytes_p, the bytes a plane pointer must grant (0 for a plane the
+ *   format does not have); plane < 0 -- the furthest byte of one frame, max over p of plane_offset_p + span_p.  On a plan without a
+ *   layout: those of its tight frames.
+ * lf_pipeline_frame_bytes returns the frame stride on a layout plan.
+ * Bit contract: that of the frame formats -- every result of every entry point that takes a plan and a frames pointer
+ *   (lf_pipeline_image, lf_pipeline_image_indexed, lf_lane_infer_folded_u8, lf_lane_infer_seg_folded_u8) equals the same call on a
+ *   tight LF_FRAME_RGB plan fed the RGB frames the definition makes from the surface's pixels.  No padding byte influences a result.
+ * Bounds: contiguous mode -- no load reaches past (N - 1) frame_stride + span(-1) bytes behind `frames` (N = pool_frames for the
+ *   indexed call); pointer mode -- no load for plane p of frame n reaches past span(p) bytes behind that pointer.
+ * lf_pipeline_image_indexed on a plane_pointers plan is refused at the call: it covers contiguous pools only.
+ * Tight plans run the kernels they always ran; a layout plan runs resize_surface_kernel / frame_surface_stem_kernel. */
+enum { LF_FRAME_I420 = 4, LF_FRAME_RGBX = 5, LF_FRAME_BGRX = 6 };
+typedef struct lf_frame_layout {
+    int  format;            /* any LF_FRAME_* 0..6 */
+    int  plane_pointers;    /* 0: `frames` is the base of a contiguous batch; 1: `frames` is a device array (N, planes) of plane base pointers */
+    long pitch[3];          /* bytes between rows of plane p; 0 = tight (the row's own bytes) */
+    long plane_offset[3];   /* bytes from a frame's base to plane p; [0] must be 0; 0 for p > 0 = directly behind plane p-1 (its rows x its pitch) */
+    long frame_stride;      /* bytes between frames of a contiguous batch; 0 = tight (end of the last plane at full pitch) */
+} lf_frame_layout;
+int    lf_pipeline_plan_set_layout(lf_pipeline_plan* plan, const lf_frame_layout* layout, const int coef[6]);
+size_t lf_pipeline_surface_span(const lf_pipeline_plan* plan, int plane);
 
 /* additions since 5 -- input-image gradient: d loss / d input of Net.forward, what `input.requires_grad_()` before the forward and
  * `loss.backward()` (BEV/main.py:264-266) give in the reference -- the data gradient of the stem DownsamplerBlock's

@@ -157,6 +157,8 @@ def _declare(lib):
         "lf_lane_infer_seg_folded_u8": (I, [P, P, P, P, P, P, P, P, L, P, I, I, I, D, D, I, P, P, P, P, c_size_t, I, P]),
         "lf_pipeline_plan_set_format": (I, [P, I, P]),
         "lf_pipeline_frame_bytes": (c_size_t, [P]),
+        "lf_pipeline_plan_set_layout": (I, [P, P, P]),
+        "lf_pipeline_surface_span": (c_size_t, [P, I]),
     }
     # test / tooling hooks (csrc/lf_debug.h; not part of include/lanefit.h)
     dbg = {

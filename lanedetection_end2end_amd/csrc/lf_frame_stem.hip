@@ -10,7 +10,9 @@
 //     the padding taps and the padded K-step; the pooled channels after the same permutes, bias / affine + ReLU in the same order.
 // The staging (and its guard against the end of the frames buffer) is SHARED with resize_bilinear_kernel (lf_pipeline_dev.h), and it
 // is the only stage that knows the frame format: frame_stem_kernel is the packed-RGB kernel, frame_format_stem_kernel<.., FMT> the same
-// body behind lf_stage_window_format<FMT> (BGR, NV12, YUYV -> the same RGB triples in the same LDS rows; the same LDS budget).  The
+// body behind lf_stage_window_format<FMT> (BGR, NV12, YUYV -> the same RGB triples in the same LDS rows; the same LDS budget), and
+// frame_surface_stem_kernel<.., FMT> the same body behind lf_stage_surface<FMT> for a plan with a frame layout (decoder surfaces:
+// pitch, plane offsets or pointers, frame stride; all seven formats).  The
 // two resize passes and the stem's per-tile arithmetic are LABELLED COPIES: the passes here walk a window
 // with a one-pixel zero border and write LDS, not NCHW rows, and stem_fwd_kernel interleaves its operand addressing with the MFMA
 // issue -- a common body would change the registers of both existing kernels.
@@ -44,12 +46,13 @@ inline FsLayout fs_layout(int th, int tw, int max_rows, int max_cols, int ksx, i
 
 // KSX / KSY: compile-time tap counts (table rows are zero-padded to them); 0 = generic (runtime count), as resize_bilinear_kernel
 // FMT: the frame format (LF_FRAME_*), which only the staging knows; cf: its YCbCr coefficients (unused for RGB / BGR)
-template <int KSX, int KSY, typename T, int FMT>
+// SURF: the frames are decoder surfaces laid out as S says (lf_stage_surface; total_bytes is then the end of the whole batch)
+template <int KSX, int KSY, typename T, int FMT, bool SURF = false>
 __device__ __forceinline__ void frame_stem_body(const uint8_t* __restrict__ frames, size_t total_bytes, int Hin, int Win, int crop_top,
                                                 const int* __restrict__ tables, int oh, int ow, int ksx, int ksy, int TH, int TW,
                                                 int max_rows, int in_stride, const float* __restrict__ w, const float* __restrict__ b,
                                                 const float* __restrict__ sc, const float* __restrict__ sh, T* __restrict__ cat,
-                                                const lf_yuv_coef cf) {
+                                                const lf_yuv_coef cf, const lf_surface& S = lf_surface{}) {
     constexpr int CIN = 3, Cc = 16 - CIN, KK = 9 * CIN, KS = (KK + 3) / 4;
     extern __shared__ uint8_t smem[];
     const int ncw = 2 * TW + 1, nrw = 2 * TH + 1;             // resized window: columns, rows
@@ -69,7 +72,9 @@ __device__ __forceinline__ void frame_stem_body(const uint8_t* __restrict__ fram
     const int r0 = Tb.by[2 * ya], r1 = Tb.by[2 * yb] + Tb.by[2 * yb + 1];
     const int c0 = Tb.bx[2 * xa], c1 = Tb.bx[2 * xb] + Tb.bx[2 * xb + 1];
     const int nr = r1 - r0, ncb = (c1 - c0) * 3;
-    if constexpr (FMT == LF_FRAME_RGB)
+    if constexpr (SURF)
+        lf_stage_surface<FMT>(frames, total_bytes, S, n, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave, cf);
+    else if constexpr (FMT == LF_FRAME_RGB)
         lf_stage_window(frames, total_bytes, n, Hin, Win, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave);
     else
         lf_stage_window_format<FMT>(frames, total_bytes, n, Hin, Win, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave, cf);
@@ -200,6 +205,17 @@ __global__ __launch_bounds__(256) void frame_format_stem_kernel(const uint8_t* _
     frame_stem_body<KSX, KSY, T, FMT>(frames, total_bytes, Hin, Win, crop_top, tables, oh, ow, ksx, ksy, TH, TW, max_rows, in_stride, w, b, sc, sh,
                                       cat, cf);
 }
+// decoder surfaces (a plan with a layout), every format: lf_stage_surface, everything behind it is the same
+template <int KSX, int KSY, typename T, int FMT>
+__global__ __launch_bounds__(256) void frame_surface_stem_kernel(const uint8_t* __restrict__ frames, size_t total_bytes, int Hin, int Win,
+                                                                int crop_top, const int* __restrict__ tables, int oh, int ow, int ksx, int ksy,
+                                                                int TH, int TW, int max_rows, int in_stride, const float* __restrict__ w,
+                                                                const float* __restrict__ b, const float* __restrict__ sc,
+                                                                const float* __restrict__ sh, T* __restrict__ cat, const lf_yuv_coef cf,
+                                                                const lf_surface S) {
+    frame_stem_body<KSX, KSY, T, FMT, true>(frames, total_bytes, Hin, Win, crop_top, tables, oh, ow, ksx, ksy, TH, TW, max_rows, in_stride, w, b,
+                                            sc, sh, cat, cf, S);
+}
 
 }  // namespace
 
@@ -239,6 +255,35 @@ int lf_frame_stem_fwd_infer(const lf_pipeline_plan* P, const uint8_t* frames, in
     LF_REQUIRE(P->fs_ok, "frame_stem: the source window of a tile does not fit the LDS budget (%d x %d from %d x %d)", P->out_h, P->out_w,
                P->crop_h, P->Win);
     const dim3 grid(lf_cdiv(P->out_w / 2, P->fs_tw), lf_cdiv(P->out_h / 2, P->fs_th), N);
+    if (P->has_layout) {
+        const size_t end = (size_t)(N - 1) * P->surf.stride + P->surf.frame_span;
+#define LF_FSS_LAUNCH(KX, KY, TT, F)                                                                                                         \
+    hipLaunchKernelGGL((frame_surface_stem_kernel<KX, KY, TT, F>), grid, dim3(256), P->fs_lds_bytes, st, frames, end, P->Hin, P->Win,       \
+                       P->crop_top, (const int*)tables_dev, P->out_h, P->out_w, P->ksx, P->ksy, P->fs_th, P->fs_tw, P->fs_max_rows,          \
+                       P->fs_in_stride, w, b, sc, sh, reinterpret_cast<TT*>(cat), P->coef, P->surf)
+#define LF_FSS_FORMATS(KX, KY, TT)                                               \
+    switch (P->format) {                                                         \
+        case LF_FRAME_RGB: LF_FSS_LAUNCH(KX, KY, TT, LF_FRAME_RGB); break;       \
+        case LF_FRAME_BGR: LF_FSS_LAUNCH(KX, KY, TT, LF_FRAME_BGR); break;       \
+        case LF_FRAME_NV12: LF_FSS_LAUNCH(KX, KY, TT, LF_FRAME_NV12); break;     \
+        case LF_FRAME_YUYV: LF_FSS_LAUNCH(KX, KY, TT, LF_FRAME_YUYV); break;     \
+        case LF_FRAME_I420: LF_FSS_LAUNCH(KX, KY, TT, LF_FRAME_I420); break;     \
+        case LF_FRAME_RGBX: LF_FSS_LAUNCH(KX, KY, TT, LF_FRAME_RGBX); break;     \
+        default: LF_FSS_LAUNCH(KX, KY, TT, LF_FRAME_BGRX); break;                \
+    }
+        // the camera geometry's 7 / 7 taps compiled in, every other geometry on the generic taps (lf_pipeline.hip does the same)
+        if (P->ksx == 7 && P->ksy == 7) {
+            if (s16) LF_FSS_FORMATS(7, 7, lf_bf16)
+            else LF_FSS_FORMATS(7, 7, float)
+        } else {
+            if (s16) LF_FSS_FORMATS(0, 0, lf_bf16)
+            else LF_FSS_FORMATS(0, 0, float)
+        }
+#undef LF_FSS_FORMATS
+#undef LF_FSS_LAUNCH
+        LF_CHECK_LAUNCH("frame_stem");
+        return 0;
+    }
     const size_t total = (size_t)N * lf_plan_frame_bytes(P);
 #define LF_FS_ARGS(TT)                                                                                                                 \
     frames, total, P->Hin, P->Win, P->crop_top, (const int*)tables_dev, P->out_h, P->out_w, P->ksx, P->ksy, P->fs_th, P->fs_tw,        \

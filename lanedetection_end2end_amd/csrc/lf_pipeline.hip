@@ -79,13 +79,14 @@ void pil_nearest_table(int in_size, int out_size, std::vector<int>& tab) {
 // Staging uses aligned dword loads with a per-row byte shift; the horizontal pass keeps a column's weights in
 // registers while it walks the rows; the vertical pass walks output rows with wave-uniform (scalar) weights.
 // FMT: the frame format (LF_FRAME_*), which only the staging knows; cf: its YCbCr coefficients (unused for RGB / BGR).
-template <int KSX, int KSY, int FMT>
+// SURF: the frames are decoder surfaces laid out as S says (lf_stage_surface; total_bytes is then the end of the whole batch).
+template <int KSX, int KSY, int FMT, bool SURF = false>
 __device__ __forceinline__ void resize_bilinear_body(const uint8_t* __restrict__ frames, size_t total_bytes, int Hin, int Win,
                                                      int crop_top, const int* __restrict__ tables, int oh, int ow,
                                                      int ksx, int ksy, int TILE_H, int TILE_W, int max_rows, int in_stride,
                                                      const uint8_t* __restrict__ flip, float* __restrict__ out,
                                                      const int64_t* __restrict__ sel, long pool_frames, int* __restrict__ bad_index,
-                                                     const lf_yuv_coef cf) {
+                                                     const lf_yuv_coef cf, const lf_surface& S = lf_surface{}) {
     extern __shared__ uint8_t smem[];
     const int h_stride = TILE_W * 3;
     int* s_shift = reinterpret_cast<int*>(smem);                                  // [max_rows + 1] byte shift of each staged row
@@ -106,7 +107,9 @@ __device__ __forceinline__ void resize_bilinear_body(const uint8_t* __restrict__
         frame = 0;
     }
     // (the gather of a cached dataset's index batch happens here, not in a separate 88 MB copy)
-    if constexpr (FMT == LF_FRAME_RGB)
+    if constexpr (SURF)
+        lf_stage_surface<FMT>(frames, total_bytes, S, frame, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave, cf);
+    else if constexpr (FMT == LF_FRAME_RGB)
         lf_stage_window(frames, total_bytes, frame, Hin, Win, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave);
     else
         lf_stage_window_format<FMT>(frames, total_bytes, frame, Hin, Win, crop_top + r0, c0, nr, ncb, s_in, in_stride, s_shift, lane, wave, cf);
@@ -182,6 +185,17 @@ __global__ __launch_bounds__(256) void resize_format_kernel(const uint8_t* __res
                                                            const lf_yuv_coef cf) {
     resize_bilinear_body<KSX, KSY, FMT>(frames, total_bytes, Hin, Win, crop_top, tables, oh, ow, ksx, ksy, TILE_H, TILE_W, max_rows,
                                         in_stride, flip, out, sel, pool_frames, bad_index, cf);
+}
+// decoder surfaces (a plan with a layout), every format: the staging reads pitched planes or plane pointers, the passes are the same
+template <int KSX, int KSY, int FMT>
+__global__ __launch_bounds__(256) void resize_surface_kernel(const uint8_t* __restrict__ frames, size_t total_bytes, int Hin, int Win,
+                                                            int crop_top, const int* __restrict__ tables, int oh, int ow,
+                                                            int ksx, int ksy, int TILE_H, int TILE_W, int max_rows, int in_stride,
+                                                            const uint8_t* __restrict__ flip, float* __restrict__ out,
+                                                            const int64_t* __restrict__ sel, long pool_frames, int* __restrict__ bad_index,
+                                                            const lf_yuv_coef cf, const lf_surface S) {
+    resize_bilinear_body<KSX, KSY, FMT, true>(frames, total_bytes, Hin, Win, crop_top, tables, oh, ow, ksx, ksy, TILE_H, TILE_W, max_rows,
+                                              in_stride, flip, out, sel, pool_frames, bad_index, cf, S);
 }
 
 // mode bits: 1 = zero classes 3 and 4 before flipping (BEV always; BP when nclasses < 3),
@@ -314,9 +328,47 @@ int lf_pipeline_plan_set_format(lf_pipeline_plan* P, int format, const int coef[
         P->coef = lf_yuv_coef{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
     }
     P->format = format;
+    P->has_layout = false;          // back to a tight plan of that format
     return 0;
 }
 size_t lf_pipeline_frame_bytes(const lf_pipeline_plan* P) { return P ? lf_plan_frame_bytes(P) : 0; }
+
+// include/lanefit.h, "additions since 5 -- surfaces".  Host only; every check comes before the first write to the plan.
+static_assert(LF_FRAME_RGB == LF_SURF_RGB && LF_FRAME_BGR == LF_SURF_BGR && LF_FRAME_NV12 == LF_SURF_NV12 && LF_FRAME_YUYV == LF_SURF_YUYV &&
+                  LF_FRAME_I420 == LF_SURF_I420 && LF_FRAME_RGBX == LF_SURF_RGBX && LF_FRAME_BGRX == LF_SURF_BGRX,
+              "lf_surface.h restates the format codes");
+int lf_pipeline_plan_set_layout(lf_pipeline_plan* P, const lf_frame_layout* layout, const int coef[6]) {
+    LF_REQUIRE(P && layout, "lf_pipeline_plan_set_layout: null plan or layout");
+    lf_surface S;
+    const char* why = lf_surface_resolve(layout->format, P->Hin, P->Win, layout->pitch, layout->plane_offset, layout->frame_stride,
+                                         layout->plane_pointers, &S);
+    LF_REQUIRE(!why, "lf_pipeline_plan_set_layout: %s (format %d, %d x %d)", why, layout->format, P->Hin, P->Win);
+    const bool ycc = layout->format == LF_FRAME_NV12 || layout->format == LF_FRAME_YUYV || layout->format == LF_FRAME_I420;
+    if (coef && ycc) {
+        // as lf_pipeline_plan_set_format: |c_y y'| + the largest chroma term + the rounding constant must stay inside int32
+        const auto mag = [](int v) { return v < 0 ? -(long long)v : (long long)v; };
+        const long long ymax = mag(coef[0]) * (mag(coef[1]) + 255);
+        long long cmax = mag(coef[2]);
+        if (mag(coef[3]) + mag(coef[4]) > cmax) cmax = mag(coef[3]) + mag(coef[4]);
+        if (mag(coef[5]) > cmax) cmax = mag(coef[5]);
+        LF_REQUIRE(ymax + 128 * cmax + 32768 <= 0x7fffffffLL, "lf_pipeline_plan_set_layout: coefficients overflow int32");
+        P->coef = lf_yuv_coef{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
+    }
+    P->format = layout->format;
+    P->surf = S;
+    P->has_layout = true;
+    return 0;
+}
+size_t lf_pipeline_surface_span(const lf_pipeline_plan* P, int plane) {
+    if (!P) return 0;
+    lf_surface S = P->surf;
+    if (!P->has_layout) {          // a tight plan is the layout of all defaults
+        const long zero[3] = {0, 0, 0};
+        if (lf_surface_resolve(P->format, P->Hin, P->Win, zero, zero, 0, 0, &S)) return 0;
+    }
+    if (plane < 0) return (size_t)S.frame_span;
+    return plane < S.planes ? (size_t)S.span[plane] : 0;
+}
 
 // Copy the tables (bilinear bounds + weights, nearest indices) to a device buffer of lf_pipeline_table_bytes().
 int lf_pipeline_upload(const lf_pipeline_plan* P, void* tables_dev, void* stream) {
@@ -351,6 +403,31 @@ static int pipeline_image(const lf_pipeline_plan* P, const uint8_t* frames, long
                           const void* tables_dev, const uint8_t* flip, float* out, int* bad_index, void* stream) {
     LF_REQUIRE(P && frames && tables_dev && out && N > 0 && pool_frames > 0, "lf_pipeline_image: bad arguments");
     const dim3 grid(lf_cdiv(P->out_w, P->tile_w), lf_cdiv(P->out_h, P->tile_h), N);
+    if (P->has_layout) {
+        // decoder surfaces: the end of the batch is the last frame's furthest byte (pointer mode: the kernel guards by plane span)
+        const size_t end = (size_t)(pool_frames - 1) * P->surf.stride + P->surf.frame_span;
+#define LF_SURFACE_LAUNCH(KX, KY, F)                                                                                                          \
+    hipLaunchKernelGGL((resize_surface_kernel<KX, KY, F>), grid, dim3(256), P->lds_bytes, (hipStream_t)stream, frames, end, P->Hin, P->Win,  \
+                       P->crop_top, (const int*)tables_dev, P->out_h, P->out_w, P->ksx, P->ksy, P->tile_h, P->tile_w, P->max_rows,           \
+                       P->in_stride, flip, out, sel, pool_frames, bad_index, P->coef, P->surf)
+#define LF_SURFACE_FORMATS(KX, KY)                                             \
+    switch (P->format) {                                                       \
+        case LF_FRAME_RGB: LF_SURFACE_LAUNCH(KX, KY, LF_FRAME_RGB); break;     \
+        case LF_FRAME_BGR: LF_SURFACE_LAUNCH(KX, KY, LF_FRAME_BGR); break;     \
+        case LF_FRAME_NV12: LF_SURFACE_LAUNCH(KX, KY, LF_FRAME_NV12); break;   \
+        case LF_FRAME_YUYV: LF_SURFACE_LAUNCH(KX, KY, LF_FRAME_YUYV); break;   \
+        case LF_FRAME_I420: LF_SURFACE_LAUNCH(KX, KY, LF_FRAME_I420); break;   \
+        case LF_FRAME_RGBX: LF_SURFACE_LAUNCH(KX, KY, LF_FRAME_RGBX); break;   \
+        default: LF_SURFACE_LAUNCH(KX, KY, LF_FRAME_BGRX); break;              \
+    }
+        // the 2.5x taps of the camera geometry (720 x 1280 -> 256 x 512) compiled in, every other geometry on the generic taps
+        if (P->ksx == 7 && P->ksy == 7) LF_SURFACE_FORMATS(7, 7)
+        else LF_SURFACE_FORMATS(0, 0)
+#undef LF_SURFACE_FORMATS
+#undef LF_SURFACE_LAUNCH
+        LF_CHECK_LAUNCH("lf_pipeline_image");
+        return 0;
+    }
     const size_t total = (size_t)pool_frames * lf_plan_frame_bytes(P);
 #define LF_RESIZE_ARGS                                                                                                           \
     frames, total, P->Hin, P->Win, P->crop_top, (const int*)tables_dev, P->out_h, P->out_w, P->ksx, P->ksy, P->tile_h, P->tile_w, \
@@ -403,6 +480,7 @@ int lf_pipeline_image(const lf_pipeline_plan* P, const uint8_t* frames, int N, c
 int lf_pipeline_image_indexed(const lf_pipeline_plan* P, const uint8_t* pool, long pool_frames, const int64_t* sel, int N,
                               const void* tables_dev, const uint8_t* flip, float* out, int* bad_index, void* stream) {
     LF_REQUIRE(sel, "lf_pipeline_image_indexed: null index");
+    LF_REQUIRE(!(P && P->has_layout && P->surf.ptrs), "lf_pipeline_image_indexed: a plane-pointer plan has no pool to index (contiguous pools only)");
     return pipeline_image(P, pool, pool_frames, sel, N, tables_dev, flip, out, bad_index, stream);
 }
 

@@ -8,13 +8,9 @@
 #include <vector>
 
 #include "lf_common.h"
+#include "lf_surface.h"      // lf_yuv_coef, lf_yuv_pixel; the surface layout and the staging group that knows it
 
 #define PIL_PRECISION_BITS 22
-
-// YCbCr -> RGB in Q16 (include/lanefit.h, "additions since 5 -- frame formats"); passed to the kernels by value
-struct lf_yuv_coef {
-    int c_y, y_off, c_rv, c_gu, c_gv, c_bu;
-};
 
 struct lf_pipeline_plan {
     int format = LF_FRAME_RGB;           // LF_FRAME_*: what the frames buffer holds (lf_pipeline_plan_set_format)
@@ -33,6 +29,10 @@ struct lf_pipeline_plan {
     // geometry does not fit (odd output size, or no tile whose window stays inside the LDS budget)
     int fs_ok, fs_th, fs_tw, fs_max_rows, fs_max_cols, fs_in_stride;
     size_t fs_lds_bytes;
+    // lf_pipeline_plan_set_layout: the plan reads decoder surfaces (pitch, plane offsets, frame stride, plane pointers) and runs the
+    // surface kernels (resize_surface_kernel, frame_surface_stem_kernel); false: tight frames, the kernels they always ran
+    bool has_layout = false;
+    lf_surface surf = {};
 };
 
 // fills the fs_* fields (lf_frame_stem.hip); called by lf_pipeline_plan_create
@@ -42,8 +42,10 @@ void lf_frame_stem_plan(lf_pipeline_plan* P);
 int lf_frame_stem_fwd_infer(const lf_pipeline_plan* P, const uint8_t* frames, int N, const void* tables_dev, const float* w, const float* b,
                             const float* sc, const float* sh, float* cat, int s16, hipStream_t st);
 
-// bytes of one frame in the plan's format (pitch = width): the kernels' guard is pool_frames x this
+// bytes of one frame in the plan's format (pitch = width): the kernels' guard is pool_frames x this; on a layout plan the frame
+// stride (the guard there: (pool_frames - 1) x stride + surf.frame_span)
 inline size_t lf_plan_frame_bytes(const lf_pipeline_plan* P) {
+    if (P->has_layout) return (size_t)P->surf.stride;
     const size_t px = (size_t)P->Hin * P->Win;
     return P->format == LF_FRAME_NV12 ? px / 2 * 3 : (P->format == LF_FRAME_YUYV ? px * 2 : px * 3);
 }
@@ -110,15 +112,7 @@ __device__ __forceinline__ uint64_t lf_frame_qword(const uint8_t* __restrict__ f
     return (uint64_t)lf_frame_dword(frames, total_bytes, a) | ((uint64_t)lf_frame_dword(frames, total_bytes, a + 4) << 32);
 }
 
-__device__ __forceinline__ int lf_clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-// one pixel as R | G << 8 | B << 16: the Q16 definition of include/lanefit.h, arithmetic shift (floor), int32 throughout
-__device__ __forceinline__ uint32_t lf_yuv_pixel(int Y, int Cb, int Cr, const lf_yuv_coef& k) {
-    const int yy = k.c_y * (Y - k.y_off) + 32768, u = Cb - 128, v = Cr - 128;
-    const int R = lf_clamp8((yy + k.c_rv * v) >> 16);
-    const int G = lf_clamp8((yy - k.c_gu * u - k.c_gv * v) >> 16);
-    const int B = lf_clamp8((yy + k.c_bu * u) >> 16);
-    return (uint32_t)R | ((uint32_t)G << 8) | ((uint32_t)B << 16);
-}
+// (lf_clamp8 and lf_yuv_pixel: lf_surface.h, shared with the surface staging and its host check)
 
 // lf_stage_window for FMT = LF_FRAME_BGR / _NV12 / _YUYV: the same rows x columns of frame `frame`, converted to RGB triples in
 // registers and written to s_in[r] with shift 0 -- what lf_stage_window leaves for the converted frame, up to the shift.  A lane
@@ -179,6 +173,47 @@ __device__ __forceinline__ void lf_stage_window_format(const uint8_t* __restrict
             dst[3 * g] = px[0] | (px[1] << 24);
             dst[3 * g + 1] = (px[1] >> 8) | (px[2] << 16);
             dst[3 * g + 2] = (px[2] >> 16) | (px[3] << 8);
+        }
+        if (lane == 0) s_shift[r] = 0;
+    }
+}
+
+// ---- decoder surfaces ------------------------------------------------------------------------------------------------------------
+// lf_stage_window_format for a plan with a layout (lf_pipeline_plan_set_layout), FMT = any LF_FRAME_*: the same rows x columns of
+// frame `frame`, from planes with their own pitch and offset, or from the plane pointers of row `frame` of a pointer table; the
+// same RGB triples in the same LDS rows, shift 0.  A lane takes four consecutive pixels (lf_surface_group, lf_surface.h -- the code
+// the host check runs over exact-size heap buffers); pitch, offsets, stride and the mode are runtime values of S.
+// Bounds.  Loads: every one is an aligned dword through `ld`, which knows how many bytes are left behind its address and touches
+// none beyond.  Contiguous mode: left counts to total_bytes = (pool_frames - 1) x stride + frame_span behind `frames`, whatever the
+// lane's pixels are; rounding an address down stays at or behind `frames` (4-byte aligned).  Pointer mode: left counts to span_p =
+// (rows_p - 1) pitch_p + row bytes_p behind the plane's pointer, so the last group of a plane's last row reads inside the plane or
+// takes zeros.  A 4-byte aligned pointer makes rounding down stay inside the plane.  The NV12 CbCr pointer may be 2-byte aligned:
+// its first fetch then loads the aligned dword 2 bytes IN FRONT of the plane -- the dword that also holds the plane's bytes 0 and 1,
+// so the load touches no granule the plane does not touch and cannot fault; the two foreign bytes are shifted out before use and
+// reach no result (tests: a CbCr base at + 2 on the host and on the device).  That one read is outside "inside the plane or zero".
+// A pitch is below 2^31.  In both
+// modes the up to three pixels of a row's last group beyond the window take padding bytes, bytes of the next row, or zeros; they
+// land in the row's over-read pad, which only zero weights meet -- no padding byte reaches a result.  frame < pool_frames (the
+// callers clamp an index outside the pool to 0) and rows stay below Hin, so the largest address of plane p is that of its last row.
+// Stores: as lf_stage_window_format, (ncb / 3 + 3) / 4 * 12 <= in_stride bytes of row r.
+template <int FMT>
+__device__ __forceinline__ void lf_stage_surface(const uint8_t* __restrict__ frames, size_t total_bytes, const lf_surface& S, long frame, int row0,
+                                                 int c0, int nr, int ncb, uint8_t* s_in, int in_stride, int* s_shift, int lane, int wave,
+                                                 const lf_yuv_coef cf) {
+    const int ng = (ncb / 3 + 3) >> 2;
+    lf_plane pl[3];
+    lf_surface_planes_of(S, frames, total_bytes, frame, pl);
+    // lf_frame_dword with the buffer's end `left` bytes behind the dword: whole inside, or put together from its bytes inside
+    const auto ld = [](const uint8_t* a, long left) { return left <= 0 ? 0u : lf_frame_dword(a, (size_t)left, 0); };
+    for (int r = wave; r < nr; r += 4) {
+        const int y = row0 + r;
+        uint32_t* dst = reinterpret_cast<uint32_t*>(s_in + (size_t)r * in_stride);
+        for (int g = lane; g < ng; g += 64) {
+            uint32_t o[3];
+            lf_surface_group<FMT>(ld, pl, y, c0 + 4 * g, cf, o);
+            dst[3 * g] = o[0];
+            dst[3 * g + 1] = o[1];
+            dst[3 * g + 2] = o[2];
         }
         if (lane == 0) s_shift[r] = 0;
     }

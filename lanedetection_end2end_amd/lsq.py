@@ -315,12 +315,14 @@ class LaneDetector:
         self._cameras = weakref.WeakSet()
         self.refresh()
 
-    def camera(self, frame_hw=(720, 1280), crop=640, fused="auto", pixel_format="rgb", yuv="jfif"):
+    def camera(self, frame_hw=(720, 1280), crop=640, fused="auto", pixel_format="rgb", yuv="jfif", layout=None):
         """A ``CameraDetector`` on this detector: the same calls from decoded uint8 camera frames ``(batch, Hf, Wf, 3)`` -- the
         reference's ``LaneTestSet`` pixel work (crop the bottom ``crop`` rows, Pillow BILINEAR resize to the detector's
         ``(height, width)``, ``ToTensor``) inside the one backbone C call.  RGB models only.  ``pixel_format``: ``"rgb"``, ``"bgr"``,
-        ``"nv12"`` or ``"yuyv"`` frames, ``yuv``: their YCbCr matrix (``"jfif"``, ``"bt709"`` or six ints).  See ``CameraDetector``."""
-        return CameraDetector(self, frame_hw, crop, fused, pixel_format, yuv)
+        ``"nv12"`` or ``"yuyv"`` frames, ``yuv``: their YCbCr matrix (``"jfif"``, ``"bt709"`` or six ints); ``layout``: a
+        ``pipeline.FrameLayout`` -- decoder surfaces (pitch, plane offsets, plane pointers, ``i420`` / ``rgbx`` / ``bgrx``) read where
+        they lie.  See ``CameraDetector``."""
+        return CameraDetector(self, frame_hw, crop, fused, pixel_format, yuv, layout)
 
     @torch.no_grad()
     def refresh(self):
@@ -567,9 +569,18 @@ class CameraDetector(LaneDetector):
     RGB by the Q16 integers of ``yuv`` (``"jfif"``: full-range BT.601, libjpeg's decoder bit for bit; ``"bt709"``: limited-range
     BT.709; or six ints), and EVERY result equals that of an ``"rgb"`` camera on the RGB frames this definition makes
     (include/lanefit.h, "additions since 5 -- frame formats").  Unknown names raise ``ValueError``; ``"auto"`` routes every format
-    as ``"rgb"`` (measured per format, see ``FRAME_STEM_AUTO_MAX_BATCH``)."""
+    as ``"rgb"`` (measured per format, see ``FRAME_STEM_AUTO_MAX_BATCH``).
 
-    def __init__(self, det, frame_hw=(720, 1280), crop=640, fused="auto", pixel_format="rgb", yuv="jfif"):
+    ``layout``: a ``pipeline.FrameLayout`` for ``frame_hw`` -- the frames are decoder surfaces (include/lanefit.h, "additions since 5
+    -- surfaces": pitched rows, planes at offsets or in allocations of their own, a frame stride, ``"i420"`` / ``"rgbx"`` /
+    ``"bgrx"``), read where they lie; the same bit contract.  The layout carries the format (a ``pixel_format`` other than the
+    default with it is a ``ValueError``), ``yuv`` works as above, ``cam.frame_shape`` is ``None``.  A contiguous layout takes a
+    contiguous uint8 device tensor of any shape with at least ``layout.batch_bytes(batch)`` elements (a decoder's buffer may be
+    larger).  A ``plane_pointers`` layout takes the ``SurfaceTable`` of ``cam.bind(surfaces)`` -- ``batch`` items, each a plane tensor
+    or a tuple of plane tensors, checked and uploaded ONCE (surface pools recycle): calls with the table cost nothing extra.
+    ``fused`` / ``"auto"`` behave as for ``"rgb"``."""
+
+    def __init__(self, det, frame_hw=(720, 1280), crop=640, fused="auto", pixel_format="rgb", yuv="jfif", layout=None):
         if type(det) is not LaneDetector:
             raise TypeError("camera() is a method of a LaneDetector")
         lib = erfnet._lib.load()
@@ -580,15 +591,20 @@ class CameraDetector(LaneDetector):
         Hf, Wf = int(frame_hw[0]), int(frame_hw[1])
         N, _, H, W = det.shape
         self._det = det
-        self.frame_shape = pipeline.frames_shape(pixel_format, N, (Hf, Wf))
+        self.layout = None if layout is None else pipeline._as_layout(layout, (Hf, Wf), pixel_format)
+        self.frame_hw = (Hf, Wf)
+        self.frame_shape = pipeline.frames_shape(pixel_format, N, (Hf, Wf)) if layout is None else None
         pipeline.yuv_coefficients(yuv)
-        self.pixel_format = pixel_format
+        self.pixel_format = pixel_format if layout is None else layout.pixel_format
         self.last_status = None
         self._pipe = lib.lf_pipeline_plan_create(Hf, Wf, Hf - int(crop), int(crop), H, W)
         if not self._pipe:
             raise erfnet._lib.LaneFitLibraryError("lf_pipeline_plan_create failed: %s" % lib.lf_last_error().decode())
         self._pipe = ctypes.c_void_p(self._pipe)
-        pipeline.set_plan_format(self._pipe, pixel_format, yuv)
+        if layout is None:
+            pipeline.set_plan_format(self._pipe, pixel_format, yuv)
+        else:
+            layout.apply(self._pipe, yuv)
         self.fits = bool(lib.lf_pipeline_frame_stem_ok(self._pipe))
         self.fused = fused
         self._tables = self._ws = None
@@ -618,7 +634,7 @@ class CameraDetector(LaneDetector):
             raise ValueError("camera(fused=...) takes True, False or \"auto\"")
         if value is True and not self.fits:
             raise ValueError("camera(fused=True): the source window of a tile does not fit the fused kernel's LDS budget at %s -> %s; "
-                             "use \"auto\" or False (two launches inside the call)" % (self.frame_shape[1:3], self._det.shape[2:]))
+                             "use \"auto\" or False (two launches inside the call)" % (self.frame_shape[1:3] if self.frame_shape else self.frame_hw, self._det.shape[2:]))
         self._fused = value
 
     def camera(self, *args, **kwargs):
@@ -660,8 +676,27 @@ class CameraDetector(LaneDetector):
             on = self._fused
         return det._flags | (0 if on else 2)          # LF_INFER_FRAME_TWO_LAUNCH
 
+    def bind(self, surfaces):
+        """``plane_pointers`` layouts: ``batch`` surfaces (a plane tensor or a tuple of plane tensors each) -> the ``SurfaceTable`` the
+        calls take.  Every plane is checked here (uint8, on the device, row stride = the layout's pitch, the plane's span reachable,
+        base alignment); the table keeps the tensors alive and holds their pointers on the device."""
+        if self.layout is None:
+            raise ValueError("bind() is for a camera built with layout=FrameLayout(..., plane_pointers=True)")
+        return self.layout.bind(surfaces, self._det.shape[0])
+
     def _input(self, frames):
         self._det._require_eval()
+        if self.layout is not None:
+            lay, N = self.layout, self._det.shape[0]
+            if isinstance(frames, pipeline.SurfaceTable):
+                if frames.layout is not lay or frames.n != N:
+                    raise ValueError("this SurfaceTable was bound for another layout or batch (%d surface(s), the camera's batch is %d)"
+                                     % (frames.n, N))
+                return frames
+            lay.check_batch(frames, "camera(layout=)")
+            if frames.numel() < lay.batch_bytes(N):
+                raise ValueError("camera(layout=): %d frame(s) need %d bytes, the tensor holds %d" % (N, lay.batch_bytes(N), frames.numel()))
+            return frames
         if tuple(frames.shape) != self.frame_shape:
             raise ValueError("this camera was built for frames of shape %s, got %s" % (self.frame_shape, tuple(frames.shape)))
         if not frames.is_cuda:

@@ -68,6 +68,200 @@ def set_plan_format(handle, pixel_format, yuv):
         raise ValueError("lf_pipeline_plan_set_format failed: %s" % lib.lf_last_error().decode())
 
 
+# Surfaces (include/lanefit.h, "additions since 5 -- surfaces"): the formats a FrameLayout takes -- the four above and the three that
+# exist only with a layout.  A table of its own: PIXEL_FORMATS, frames_shape and pixel_format= keep their four names.
+SURFACE_FORMATS = {"rgb": 0, "bgr": 1, "nv12": 2, "yuyv": 3, "i420": 4, "rgbx": 5, "bgrx": 6}
+
+
+class _CLayout(ctypes.Structure):
+    """``lf_frame_layout``"""
+    _fields_ = [("format", ctypes.c_int), ("plane_pointers", ctypes.c_int), ("pitch", ctypes.c_long * 3),
+                ("plane_offset", ctypes.c_long * 3), ("frame_stride", ctypes.c_long)]
+
+
+class FrameLayout:
+    """``FrameLayout(pixel_format, frame_hw, pitch=None, plane_offsets=None, frame_stride=None, plane_pointers=False)``: where the
+    pixels of a decoder surface lie (``lf_frame_layout``).  ``pixel_format``: one of ``SURFACE_FORMATS``.  ``pitch``: bytes between
+    rows, one int (plane 0) or one per plane, ``None`` / 0 = the row's own bytes; ``plane_offsets``: bytes from a frame's base to each
+    plane (``[0]`` is 0; ``None`` / 0 for a later plane = directly behind the one before, its rows x its pitch); ``frame_stride``:
+    bytes between the frames of a contiguous batch (``None`` / 0 = the end of the furthest plane at full pitch);
+    ``plane_pointers=True``: the planes are separate tensors, bound once with ``bind`` (``SurfaceTable``); ``plane_offsets`` and
+    ``frame_stride`` are then not read and not looked at.  YV12 is ``"i420"`` with
+    the offsets (or the bound tensors) of planes 1 and 2 exchanged.
+
+    Resolved attributes: ``planes``, ``plane_rows``, ``plane_row_bytes``, ``pitch``, ``plane_offsets``, ``frame_stride`` (tuples /
+    int, no zero left), ``span`` (per plane: ``(rows - 1) pitch + row bytes``), ``frame_span`` (the furthest byte of one frame),
+    ``batch_bytes(n)`` = ``(n - 1) frame_stride + frame_span``.  Raises ``ValueError`` for what ``lf_pipeline_plan_set_layout``
+    refuses (the same rules, restated here: no device, no library call): an unknown format, an odd size where the format needs an
+    even one, a negative value, a pitch below the row's bytes, ``plane_offsets[0] != 0``, pitch / offset / stride that are not
+    multiples of 4 for ``yuyv`` / ``rgbx`` / ``bgrx``, an odd chroma pitch / chroma offset / frame stride for ``nv12``."""
+
+    def __init__(self, pixel_format, frame_hw, pitch=None, plane_offsets=None, frame_stride=None, plane_pointers=False):
+        if pixel_format not in SURFACE_FORMATS:
+            raise ValueError("FrameLayout: pixel_format=%r: one of %s" % (pixel_format, sorted(SURFACE_FORMATS)))
+        H, W = int(frame_hw[0]), int(frame_hw[1])
+        fmt = pixel_format
+        if fmt in ("nv12", "i420") and (H % 2 or W % 2):
+            raise ValueError("%s frames have an even height and width, got %d x %d" % (fmt, H, W))
+        if fmt == "yuyv" and W % 2:
+            raise ValueError("yuyv frames have an even width, got %d" % W)
+        self.pixel_format, self.frame_hw, self.plane_pointers = fmt, (H, W), bool(plane_pointers)
+        self.planes = 3 if fmt == "i420" else (2 if fmt == "nv12" else 1)
+        row0 = {"rgb": 3 * W, "bgr": 3 * W, "yuyv": 2 * W, "rgbx": 4 * W, "bgrx": 4 * W}.get(fmt, W)
+        self.plane_rows = (H, H // 2, H // 2)[:self.planes]
+        self.plane_row_bytes = (row0, W if fmt == "nv12" else W // 2, W // 2)[:self.planes]
+
+        def per_plane(v, what):
+            if v is None:
+                return (0,) * self.planes
+            try:
+                v = (v,) if isinstance(v, (int, float, np.number)) else tuple(v)
+            except TypeError:
+                raise ValueError("FrameLayout: %s takes an int or up to %d ints, got %r" % (what, self.planes, v))
+            if len(v) > self.planes or not all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in v):
+                raise ValueError("FrameLayout: %s takes up to %d ints for %s, got %r" % (what, self.planes, fmt, v))
+            return tuple(int(x) for x in v) + (0,) * (self.planes - len(v))
+
+        if self.plane_pointers:      # plane pointers: offsets and stride are not read, and not looked at (as the C call)
+            plane_offsets = frame_stride = None
+        self._given = (per_plane(pitch, "pitch"), per_plane(plane_offsets, "plane_offsets"), int(frame_stride or 0))
+        gp, go, gs = self._given
+        if min(gp + go + (gs,)) < 0:
+            raise ValueError("FrameLayout: negative pitch, plane offset or frame stride")
+        if go[0] != 0:
+            raise ValueError("FrameLayout: plane_offsets[0] must be 0")
+        dword = fmt in ("yuyv", "rgbx", "bgrx")
+        res_p, res_o, span = [], [], []
+        for p in range(self.planes):
+            rows, rb = self.plane_rows[p], self.plane_row_bytes[p]
+            if gp[p] and gp[p] < rb:
+                raise ValueError("FrameLayout: pitch %d of plane %d is below the %d bytes of a row" % (gp[p], p, rb))
+            if gp[p] > 0x7fffffff:
+                raise ValueError("FrameLayout: pitch of 2^31 bytes or more")
+            res_p.append(gp[p] or rb)
+            res_o.append(0 if p == 0 else (go[p] or res_o[p - 1] + self.plane_rows[p - 1] * res_p[p - 1]))
+            span.append((rows - 1) * res_p[p] + rb)
+            if dword and (res_p[p] % 4 or (res_o[p] % 4 and not self.plane_pointers)):
+                raise ValueError("FrameLayout: %s surfaces need pitch and plane offset in multiples of 4" % fmt)
+            if fmt == "nv12" and p == 1 and (res_p[p] % 2 or (res_o[p] % 2 and not self.plane_pointers)):
+                raise ValueError("FrameLayout: the nv12 chroma plane needs an even pitch and offset")
+        self.pitch, self.plane_offsets, self.span = tuple(res_p), tuple(res_o), tuple(span)
+        self.frame_span = max(o + s for o, s in zip(res_o, span))
+        self.frame_stride = gs or max(o + r * q for o, r, q in zip(res_o, self.plane_rows, res_p))
+        if dword and self.frame_stride % 4 and not self.plane_pointers:
+            raise ValueError("FrameLayout: %s surfaces need a frame stride in multiples of 4" % fmt)
+        if fmt == "nv12" and self.frame_stride % 2 and not self.plane_pointers:
+            raise ValueError("FrameLayout: nv12 surfaces need an even frame stride")
+
+    def batch_bytes(self, n):
+        """Bytes a contiguous batch of ``n`` frames must grant behind its base."""
+        return (int(n) - 1) * self.frame_stride + self.frame_span
+
+    def plane_alignment(self, p):
+        """Bytes a plane's base pointer must be aligned to (4; 2 for the nv12 CbCr plane)."""
+        return 2 if (self.pixel_format == "nv12" and p == 1) else 4
+
+    def _c(self):
+        gp, go, gs = self._given
+        pad = (0,) * (3 - self.planes)
+        return _CLayout(SURFACE_FORMATS[self.pixel_format], int(self.plane_pointers), (ctypes.c_long * 3)(*(gp + pad)),
+                        (ctypes.c_long * 3)(*(go + pad)), gs)
+
+    def apply(self, handle, yuv):
+        """``lf_pipeline_plan_set_layout`` on a plan handle (and a cross-check of the two restatements of the arithmetic)."""
+        coef = yuv_coefficients(yuv)
+        lib = _lib.load()
+        c = self._c()
+        if lib.lf_pipeline_plan_set_layout(handle, ctypes.byref(c), (ctypes.c_int * 6)(*coef)) != 0:
+            raise ValueError("lf_pipeline_plan_set_layout failed: %s" % lib.lf_last_error().decode())
+        got = tuple(lib.lf_pipeline_surface_span(handle, p) for p in range(self.planes))
+        assert got == self.span and lib.lf_pipeline_surface_span(handle, -1) == self.frame_span \
+            and lib.lf_pipeline_frame_bytes(handle) == self.frame_stride, "internal: FrameLayout and lf_surface_resolve disagree"
+
+    def check_batch(self, frames, what):
+        """A contiguous batch: a contiguous uint8 device tensor of any shape with at least ``batch_bytes(N)`` elements, 4-byte
+        aligned; N is not known from the shape, so the caller gives it.  Returns nothing; raises ``ValueError``."""
+        if self.plane_pointers:
+            raise ValueError("%s: this layout has plane_pointers=True: bind() the surfaces once and pass the SurfaceTable" % what)
+        if not torch.is_tensor(frames):
+            raise ValueError("%s takes a uint8 tensor, got %s" % (what, type(frames).__name__))
+        if not frames.is_cuda:
+            raise _lib.LaneFitLibraryError("%s needs its frames on the MI355X; there is no CPU path" % what)
+        if frames.dtype != torch.uint8 or not frames.is_contiguous():
+            raise ValueError("%s takes a contiguous uint8 tensor, got %s%s" % (what, frames.dtype, "" if frames.is_contiguous() else ", not contiguous"))
+        if frames.data_ptr() % 4:
+            raise ValueError("%s: the surface's base must be 4-byte aligned" % what)
+
+    def bind(self, surfaces, n=None):
+        """N items, each a plane tensor or a tuple of plane tensors -> ``SurfaceTable``.  Each plane: uint8, on the device, at least
+        1-D, unit stride inside a row, row stride equal to the layout's pitch (a 1-D tensor is a flat buffer at that pitch), at least
+        the plane's span reachable from its first element, base aligned to ``plane_alignment(p)``.  ``n``: the batch it must hold."""
+        if not self.plane_pointers:
+            raise ValueError("bind() is for a layout with plane_pointers=True; a contiguous layout takes the batch tensor itself")
+        items = [tuple(s) if isinstance(s, (tuple, list)) else (s,) for s in surfaces]
+        if n is not None and len(items) != n:
+            raise ValueError("bind(): %d surface(s) for a batch of %d" % (len(items), n))
+        if not items:
+            raise ValueError("bind(): no surfaces")
+        ptrs, dev = [], None
+        for i, planes in enumerate(items):
+            if len(planes) != self.planes:
+                raise ValueError("bind(): surface %d has %d plane(s), %s has %d" % (i, len(planes), self.pixel_format, self.planes))
+            for p, t in enumerate(planes):
+                where = "bind(): surface %d plane %d" % (i, p)
+                if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() < 1:
+                    raise ValueError("%s is not a uint8 tensor" % where)
+                if not t.is_cuda:
+                    raise _lib.LaneFitLibraryError("%s is not on the MI355X; there is no CPU path" % where)
+                dev = dev or t.device
+                if t.device != dev:
+                    raise ValueError("%s is on another device" % where)
+                if t.stride(-1) != 1 and t.shape[-1] > 1:
+                    raise ValueError("%s: the bytes of a row are not adjacent (stride %d)" % (where, t.stride(-1)))
+                if t.dim() >= 2:
+                    lead = t.shape[:-2]
+                    if any(s != 1 for s in lead) or (t.shape[-2] > 1 and t.stride(-2) != self.pitch[p]):
+                        raise ValueError("%s: row stride %d is not the layout's pitch %d" % (where, t.stride(-2), self.pitch[p]))
+                    reach = (t.shape[-2] - 1) * self.pitch[p] + t.shape[-1]
+                else:
+                    reach = t.shape[0]
+                # what the tensor's storage holds behind the first element bounds the reach too
+                reach = min(reach, t.untyped_storage().nbytes() - t.storage_offset())
+                if reach < self.span[p]:
+                    raise ValueError("%s reaches %d bytes, the plane's span is %d" % (where, reach, self.span[p]))
+                if t.data_ptr() % self.plane_alignment(p):
+                    raise ValueError("%s: base %#x is not %d-byte aligned" % (where, t.data_ptr(), self.plane_alignment(p)))
+                ptrs.append(t.data_ptr())
+        return SurfaceTable(self, items, torch.tensor(ptrs, dtype=torch.int64).view(len(items), self.planes).to(dev))
+
+
+class SurfaceTable:
+    """What ``bind`` returns: the (N, planes) int64 device tensor of plane base pointers (one small upload, made once -- surface
+    pools recycle) and the plane tensors it points into, kept alive.  Pass it where a frames tensor goes."""
+
+    def __init__(self, layout, surfaces, pointers):
+        self.layout, self.surfaces, self.pointers = layout, surfaces, pointers
+        self.n, self.device, self.is_cuda = len(surfaces), pointers.device, True
+
+    def __len__(self):
+        return self.n
+
+    def data_ptr(self):
+        return self.pointers.data_ptr()
+
+
+def _as_layout(layout, frame_hw, pixel_format):
+    """Validates the layout= argument of InputPipeline / camera() against their frame_hw and pixel_format."""
+    if not isinstance(layout, FrameLayout):
+        raise ValueError("layout= takes a pipeline.FrameLayout, got %s" % type(layout).__name__)
+    if pixel_format != "rgb":
+        raise ValueError("layout= carries the format (%s): leave pixel_format at its default, got pixel_format=%r"
+                         % (layout.pixel_format, pixel_format))
+    if layout.frame_hw != (int(frame_hw[0]), int(frame_hw[1])):
+        raise ValueError("layout= is for frames of %s, frame_hw is %s" % (layout.frame_hw, tuple(frame_hw)))
+    return layout
+
+
 class InputPipeline:
     """``InputPipeline(resize, tree='bev'|'bp', nclasses=2, frame_hw=(720, 1280), crop=640, pixel_format='rgb', yuv='jfif')``;
     ``__call__(frames_u8, labels_u8=None, flip=None) -> (image, gt, horizon)``.
@@ -79,20 +273,32 @@ class InputPipeline:
     ``pixel_format``: what the frames hold -- ``'rgb'`` / ``'bgr'`` (N, H, W, 3), ``'nv12'`` (N, H * 3 // 2, W: the Y plane, then the
     interleaved CbCr rows; H, W even) or ``'yuyv'`` (N, H, W, 2; W even), contiguous.  The image is bit for bit the ``'rgb'`` image of
     the frames the Q16 definition above makes from them (chroma replicated; ``yuv``: ``'jfif'``, ``'bt709'`` or six ints; ignored for
-    ``'rgb'`` / ``'bgr'``).  Labels know no format."""
+    ``'rgb'`` / ``'bgr'``).  Labels know no format.
 
-    def __init__(self, resize, tree="bev", nclasses=2, frame_hw=(720, 1280), crop=640, pixel_format="rgb", yuv="jfif"):
+    ``layout``: a ``FrameLayout`` -- the frames are decoder surfaces (pitched rows, planes at offsets, a frame stride, ``i420`` /
+    ``rgbx`` / ``bgrx``), read where they lie.  The layout carries the format (``pixel_format`` stays at its default; ``yuv`` works
+    as above) and ``frames_shape`` is ``None``.  Contiguous layouts take a contiguous uint8 device tensor of ANY shape with at least
+    ``layout.batch_bytes(N)`` elements (a decoder's buffer may be larger); N -- with ``index=`` the pool's size -- is ``n=`` of the
+    call, else the labels' count, else (without ``index=``) the flips'; with none of them a buffer that has room for one frame only
+    is one frame, and a larger one is a ``ValueError``: slack is never taken for frames.  ``plane_pointers`` layouts take the ``SurfaceTable`` of ``pipe.bind(surfaces)``
+    (built once; ``index=`` is refused with it).  Same bits as the ``'rgb'`` pipeline on the pixels' RGB frames."""
+
+    def __init__(self, resize, tree="bev", nclasses=2, frame_hw=(720, 1280), crop=640, pixel_format="rgb", yuv="jfif", layout=None):
         assert tree in ("bev", "bp")
         H, W = frame_hw
-        self.frames_shape = frames_shape(pixel_format, -1, (H, W))[1:]
+        self.layout = None if layout is None else _as_layout(layout, (H, W), pixel_format)
+        self.frames_shape = frames_shape(pixel_format, -1, (H, W))[1:] if layout is None else None
         yuv_coefficients(yuv)
         lib = _lib.load()
         self.resize, self.tree, self.nclasses, self.frame_hw = resize, tree, nclasses, (H, W)
-        self.pixel_format = pixel_format
+        self.pixel_format = pixel_format if layout is None else layout.pixel_format
         self.handle = lib.lf_pipeline_plan_create(H, W, H - crop, crop, resize, 2 * resize)
         if not self.handle:
             raise _lib.LaneFitLibraryError("lf_pipeline_plan_create failed: %s" % lib.lf_last_error().decode())
-        set_plan_format(self.handle, pixel_format, yuv)
+        if layout is None:
+            set_plan_format(self.handle, pixel_format, yuv)
+        else:
+            layout.apply(self.handle, yuv)
         self.mode = (1 if (tree == "bev" or nclasses < 3) else 0) | (2 if tree == "bp" else 0)
         self._tables = None
         self._lut = None
@@ -139,16 +345,53 @@ class InputPipeline:
             self._lut = (v * 255).long().to(device)
         return self._tables, self._lut
 
-    def __call__(self, frames_u8, labels_u8=None, flip=None, index=None):
+    def bind(self, surfaces):
+        """``layout.bind(surfaces)``: the ``SurfaceTable`` of a ``plane_pointers`` layout, built once."""
+        if self.layout is None:
+            raise ValueError("bind() is for a pipeline built with layout=FrameLayout(..., plane_pointers=True)")
+        return self.layout.bind(surfaces)
+
+    def _surface_pool(self, frames_u8, labels_u8, flip, index, n):
+        """The checks of a layout pipeline's frames argument -> the number of frames behind it."""
+        lay = self.layout
+        if isinstance(frames_u8, SurfaceTable):
+            if frames_u8.layout is not lay:
+                raise ValueError("this SurfaceTable was bound for another layout")
+            if index is not None:
+                raise ValueError("index= gathers from a contiguous pool; a SurfaceTable is refused (bind the surfaces in the order wanted)")
+            if n is not None and n != frames_u8.n:
+                raise ValueError("n=%d, the SurfaceTable holds %d surface(s)" % (n, frames_u8.n))
+            return frames_u8.n
+        lay.check_batch(frames_u8, "InputPipeline(layout=)")
+        if n is None:
+            n = labels_u8.shape[0] if labels_u8 is not None else (flip.numel() if flip is not None and index is None else None)
+        if n is None:
+            # only ONE whole frame fits: no doubt.  A larger buffer may be frames or a decoder's slack -- the caller says which
+            if frames_u8.numel() >= lay.batch_bytes(2):
+                raise ValueError("InputPipeline(layout=): the tensor holds %d bytes, room for more than one frame (a frame stride is %d): "
+                                 "give n= (or labels), a decoder's buffer may be larger than its frames" % (frames_u8.numel(), lay.frame_stride))
+            n = 1
+        if n < 1 or frames_u8.numel() < lay.batch_bytes(n):
+            raise ValueError("InputPipeline(layout=): %d frame(s) need %d bytes, the tensor holds %d" % (max(n, 1), lay.batch_bytes(max(n, 1)), frames_u8.numel()))
+        return n
+
+    def __call__(self, frames_u8, labels_u8=None, flip=None, index=None, n=None):
         """``index`` (N,) int64 on the device: ``frames_u8`` / ``labels_u8`` are a resident POOL and batch element n is pool entry
-        ``index[n]`` -- gathered inside the kernels (``lf_pipeline_image_indexed``), no copy of the N selected frames first."""
+        ``index[n]`` -- gathered inside the kernels (``lf_pipeline_image_indexed``), no copy of the N selected frames first.
+        ``n``: layout pipelines only, the frames behind a contiguous surface buffer (see the class)."""
         lib = _lib.load()
-        if not frames_u8.is_cuda:
-            raise _lib.LaneFitLibraryError("InputPipeline needs the decoded frames on the MI355X; there is no CPU path")
-        if tuple(frames_u8.shape[1:]) != self.frames_shape or frames_u8.dtype != torch.uint8:
-            raise ValueError("this pipeline takes %s frames of shape (N,) + %s, uint8; got %s, %s"
-                             % (self.pixel_format, self.frames_shape, tuple(frames_u8.shape), frames_u8.dtype))
-        pool, (H, W) = frames_u8.shape[0], self.frame_hw
+        if self.layout is not None:
+            pool = self._surface_pool(frames_u8, labels_u8, flip, index, n)
+        else:
+            if n is not None:
+                raise ValueError("n= is for a pipeline with a layout: the frames' shape gives the count")
+            if not frames_u8.is_cuda:
+                raise _lib.LaneFitLibraryError("InputPipeline needs the decoded frames on the MI355X; there is no CPU path")
+            if tuple(frames_u8.shape[1:]) != self.frames_shape or frames_u8.dtype != torch.uint8:
+                raise ValueError("this pipeline takes %s frames of shape (N,) + %s, uint8; got %s, %s"
+                                 % (self.pixel_format, self.frames_shape, tuple(frames_u8.shape), frames_u8.dtype))
+            pool = frames_u8.shape[0]
+        (H, W) = self.frame_hw
         dev = frames_u8.device
         tables, lut = self._device_state(dev)
         R = self.resize
@@ -161,13 +404,17 @@ class InputPipeline:
             if self._bad is None or self._bad.device != dev:
                 self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
         fl = None if flip is None else flip.to(device=dev, dtype=torch.uint8).contiguous()
-        frames_u8 = frames_u8.contiguous()
+        if self.layout is None:
+            frames_u8 = frames_u8.contiguous()
+            frames_ptr = _lib.ptr(frames_u8)
+        else:
+            frames_ptr = ctypes.c_void_p(frames_u8.data_ptr())
         image = torch.empty(N, 3, R, 2 * R, dtype=torch.float32, device=dev)
         if sel is None:
-            _lib.check(lib.lf_pipeline_image(self.handle, _lib.ptr(frames_u8), N, _lib.ptr(tables), _lib.ptr(fl),
+            _lib.check(lib.lf_pipeline_image(self.handle, frames_ptr, N, _lib.ptr(tables), _lib.ptr(fl),
                                              _lib.ptr(image), _lib.stream()), "lf_pipeline_image")
         else:
-            _lib.check(lib.lf_pipeline_image_indexed(self.handle, _lib.ptr(frames_u8), pool, _lib.ptr(sel), N, _lib.ptr(tables),
+            _lib.check(lib.lf_pipeline_image_indexed(self.handle, frames_ptr, pool, _lib.ptr(sel), N, _lib.ptr(tables),
                                                      _lib.ptr(fl), _lib.ptr(image), _lib.ptr(self._bad), _lib.stream()),
                        "lf_pipeline_image_indexed")
         gt = horizon = None

@@ -43,6 +43,8 @@ frame_stem_kernel).  Geometries: -> 256 x 512 on the BP --clas recipe through ``
 -- lsq.FRAME_STEM_AUTO_MAX_BATCH / _BF16.
 
     python tools/detector_latency.py --frames --formats rgb,bgr,nv12,yuyv [--out profiles/detector_frames_formats_latency.json] [--yuv bt709]
+    python tools/detector_latency.py --frames --formats rgb,nv12,nv12@decoder,nv12@pointers,i420,rgbx --batches 1 \
+        --out profiles/detector_surfaces_latency.json      # surfaces: camera(layout=...), see SURFACE_SPECS
 
 --frames --formats: ``det.camera(pixel_format=F).lanes(frames)`` on 720 x 1280 -> 256 x 512 (BP --clas) per frame format, the two-launch
 and the fused form of each, all alternated in one process by the same protocol.  The yardstick is the ``rgb`` call of the same process
@@ -406,19 +408,60 @@ def format_frames(rgb, fmt):
     return np.ascontiguousarray(np.stack([rgb[..., 1], np.where(np.arange(W) % 2 == 0, rgb[..., 2], rgb[..., 0])], axis=-1))
 
 
+# --formats also takes surfaces (camera(layout=...)): a decoder's NV12 with pitch 1536 and the chroma plane behind 736 rows, the same
+# through a pointer table with Y and CbCr in separate allocations, and the formats that exist only with a layout
+SURFACE_SPECS = ("nv12@decoder", "nv12@pointers", "i420", "rgbx", "bgrx")
+DECODER_PITCH, DECODER_ROWS = 1536, 736
+
+
+def surface_case(det, spec, rgb, yuv):
+    """({fused: camera}, their frames argument, the bytes of one frame's pixels and padding) for a surface spec: both cameras share
+    the layout, so one bound table serves them"""
+    import numpy as np
+    import torch
+    from lanedetection_end2end_amd.pipeline import FrameLayout
+    N, H, W, _ = rgb.shape
+    if spec.startswith("nv12@"):
+        pointers = spec == "nv12@pointers"
+        lay = FrameLayout("nv12", (H, W), pitch=(DECODER_PITCH, DECODER_PITCH), plane_offsets=None if pointers else (0, DECODER_ROWS * DECODER_PITCH),
+                          plane_pointers=pointers)
+        tight = format_frames(rgb, "nv12")
+        y = np.zeros((N, DECODER_ROWS, DECODER_PITCH), np.uint8)
+        c = np.zeros((N, H // 2, DECODER_PITCH), np.uint8)
+        y[:, :H, :W], c[:, :, :W] = tight[:, :H], tight[:, H:]
+        cams = {fused: det.camera((H, W), FRAMES_CROP, fused=fused, layout=lay, yuv=yuv) for fused in (False, True)}
+        if pointers:      # Y and CbCr of every frame in allocations of their own
+            arg = cams[True].bind([(torch.from_numpy(y[n]).cuda(), torch.from_numpy(c[n]).cuda()) for n in range(N)])
+        else:
+            arg = torch.from_numpy(np.concatenate([y, c], axis=1)).cuda()
+        return cams, arg, lay.frame_stride
+    if spec == "i420":
+        planes = [rgb[..., 1].reshape(N, -1), rgb[:, ::2, ::2, 2].reshape(N, -1), rgb[:, ::2, ::2, 0].reshape(N, -1)]
+        tight = np.ascontiguousarray(np.concatenate(planes, axis=1))
+    else:
+        tight = np.ascontiguousarray(np.concatenate([rgb if spec == "rgbx" else rgb[..., ::-1], np.full((N, H, W, 1), 255, np.uint8)], axis=-1))
+    lay = FrameLayout(spec, (H, W))
+    cams = {fused: det.camera((H, W), FRAMES_CROP, fused=fused, layout=lay, yuv=yuv) for fused in (False, True)}
+    return cams, torch.from_numpy(tight).cuda(), lay.frame_stride
+
+
 def measure_formats(precision, N, formats, yuv, warmup, calls, repeats):
-    """--frames --formats: cam.lanes(frames) per frame format, two-launch and fused, all alternated in one process"""
+    """--frames --formats: cam.lanes(frames) per frame format or surface, two-launch and fused, all alternated in one process"""
     import torch
     cfg = LANES_CFG
     model = make_model(cfg, precision, N, clas=True)
     det = model.detector(batch=N, height=cfg["H"], width=cfg["W"], thin="auto")
     rgb = camera_frames(N).cpu().numpy()
     buf = torch.empty(N, cfg["K"], 56, dtype=torch.int32, device="cuda")
-    paths, frames = {}, {}
+    paths, frames, nbytes = {}, {}, {}
     for fmt in formats:
-        frames[fmt] = torch.from_numpy(format_frames(rgb, fmt)).cuda()
+        if fmt not in SURFACE_SPECS:
+            frames[fmt] = torch.from_numpy(format_frames(rgb, fmt)).cuda()
+            nbytes[fmt] = int(frames[fmt][0].numel())
+        else:
+            cams, frames[fmt], nbytes[fmt] = surface_case(det, fmt, rgb, yuv)
         for fused in (False, True):
-            cam = det.camera(FRAMES_HW, FRAMES_CROP, fused=fused, pixel_format=fmt, yuv=yuv)
+            cam = cams[fused] if fmt in SURFACE_SPECS else det.camera(FRAMES_HW, FRAMES_CROP, fused=fused, pixel_format=fmt, yuv=yuv)
             paths[(fmt, fused)] = (lambda c: lambda u: c.lanes(u, out=buf).lanes)(cam)
         # the two forms of a format give the same bits (that they are the bits of the rgb call on the converted frames is the tests')
         assert torch.equal(paths[(fmt, True)](frames[fmt]).clone(), paths[(fmt, False)](frames[fmt])), fmt
@@ -435,13 +478,20 @@ def measure_formats(precision, N, formats, yuv, warmup, calls, repeats):
            "precision": precision, "batch": N, "formats": {}}
     for fmt in formats:
         b, c = stats(ev[(fmt, False)]), stats(ev[(fmt, True)])
-        r = {"frame_bytes": int(frames[fmt][0].numel()),
+        r = {"frame_bytes": nbytes[fmt],
              "two_launches": {"in_stream_ms": b, "wall_ms": stats(wall[(fmt, False)])},
              "fused": {"in_stream_ms": c, "wall_ms": stats(wall[(fmt, True)])},
              "fused_wins": c["max"] < b["min"],
              "fused_against_two_launches": "gain" if c["max"] < b["min"] else "loss" if c["min"] > b["max"] else "ranges overlap",
              "median_ratio_fused_to_two_launches": round(c["median"] / b["median"], 4)}
         row["formats"][fmt] = r
+    for fmt in formats:       # surfaces that move NV12's bytes are held against the tight nv12 call of the same process
+        if (fmt.startswith("nv12@") or fmt == "i420") and "nv12" in formats:
+            for form in ("two_launches", "fused"):
+                s, y = row["formats"][fmt][form]["in_stream_ms"], row["formats"]["nv12"][form]["in_stream_ms"]
+                row["formats"][fmt][form]["against_nv12"] = ("inside nv12's range" if y["min"] <= s["median"] <= y["max"] else
+                                                             "faster" if s["max"] < y["min"] else "slower" if s["min"] > y["max"] else "ranges overlap")
+                row["formats"][fmt][form]["median_ratio_to_nv12"] = round(s["median"] / y["median"], 4)
     if "rgb" in formats:      # the yardstick: the rgb call of the same process
         for fmt in formats:
             for form in ("two_launches", "fused"):
@@ -623,7 +673,8 @@ if __name__ == "__main__":
     ap.add_argument("--trace", choices=["A", "C", "L", "F", "G"])
     ap.add_argument("--lanes", action="store_true")
     ap.add_argument("--frames", action="store_true")
-    ap.add_argument("--formats", help="with --frames: frame formats to compare, e.g. rgb,bgr,nv12,yuyv")
+    ap.add_argument("--formats", help="with --frames: frame formats to compare, e.g. rgb,bgr,nv12,yuyv; surfaces too: nv12@decoder (pitch 1536, "
+                    "chroma at row 736), nv12@pointers (the same, Y and CbCr in separate allocations), i420, rgbx, bgrx")
     ap.add_argument("--yuv", default="bt709", help="with --formats: the YCbCr preset (the cost does not depend on it)")
     ap.add_argument("--frames-launches", nargs=2, metavar=("DB_F", "DB_G"))
     ap.add_argument("--lanes-launches", metavar="DB_L")
